@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the Ada-MVS depth-inference hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg1|tiny] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg1|tiny] [--batch B] [--dump-outputs DIR]
 
 A "step" = one pass of the hot path (reference models/adamvs.py:586-618 minus
 FeatureNet0: hypothesis sampling, plane sweep, per-view weighting, recurrent
@@ -276,6 +276,31 @@ def rel_l1(x, ref):
     return float((x - ref).abs().mean() / ref.abs().mean().clamp_min(1e-30))
 
 
+DUMP_BYTES = 64 * 10 ** 6 - 4096        # --dump-outputs: at most 64 MB in all, .npy headers included
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, maps):
+    """--dump-outputs: the maps a caller of the timed path receives ({name: [n_tiles, H, W]}, the last timed step) ->
+    out_dir/<name>.npy, float32, plus out_dir/tile_index.npy (float64): the global tile index of every row.  Whole tiles;
+    when all of them would pass DUMP_BYTES, a fixed sample of tiles drawn with DUMP_SEED (the same for every run with the
+    same arguments, so two builds compare output for output).  Copied to the host at once: the graph's output buffers
+    are reused by what runs after the timed region.  -> {"dir", "arrays", "tiles"} for the result line."""
+    import numpy as np
+    n = next(iter(maps.values())).shape[0]
+    per_tile = sum(m[0].numel() * 4 for m in maps.values()) + 8
+    keep = min(n, DUMP_BYTES // per_tile)
+    if keep < 1:
+        raise SystemExit("bench.py: one tile's maps (%d bytes) exceed the --dump-outputs limit of %d bytes" % (per_tile, DUMP_BYTES))
+    tiles = np.arange(n) if keep == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, m in maps.items():
+        idx = torch.from_numpy(tiles).to(m.device)
+        np.save(os.path.join(out_dir, name + ".npy"), m.index_select(0, idx).float().cpu().numpy())
+    np.save(os.path.join(out_dir, "tile_index.npy"), tiles.astype(np.float64))
+    return {"dir": out_dir, "arrays": sorted(maps) + ["tile_index"], "tiles": "%d of %d" % (keep, n)}
+
+
 def source_stamp():
     """sha256 over the kernel sources and the C ABI header: profiles/*_traffic.json carry the stamp of the build they were
     measured on, and a stale file is refused instead of being quoted."""
@@ -336,7 +361,7 @@ def bench_msrednet(args):
             m.infer_from_features(maps, shapes, proj, dv, interval)
         torch.cuda.current_stream().wait_stream(side)
         with torch.cuda.graph(g):
-            m.infer_from_features(maps, shapes, proj, dv, interval)
+            o = m.infer_from_features(maps, shapes, proj, dv, interval)
         for _ in range(args.warmup):
             g.replay()
         torch.cuda.synchronize()
@@ -345,6 +370,7 @@ def bench_msrednet(args):
             g.replay()
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
+        dumped = dump_outputs(args.dump_outputs, {k: o[k] for k in ("depth", "photometric_confidence")}) if args.dump_outputs else None
     flops = B * msrednet_flops(c["views"], c["H"], c["W"], nd)
     ach = flops / dt / 1e12
     result = {"metric": "depth maps/s", "value": B / dt, "unit": "depth maps/s", "n_gpus": 1, "steps": args.steps,
@@ -358,6 +384,8 @@ def bench_msrednet(args):
                            "frac": ach / FP32_MFMA_PEAK_TFLOPS, "traffic": None,
                            "note": "%d planes x 4 levels x 7 dependent launches on maps down to %dx%d: latency-bound, see DESIGN.md"
                                    % (sum(nd), c["H"] // 32, c["W"] // 32)}}
+    if dumped:
+        result["dump_outputs"] = dumped
     if not args.no_cpu_baseline:
         from oracle import msrednet_oracle as MO       # checker / baseline only
         sd_cpu = {k: v.detach().cpu() for k, v in sd.items()}
@@ -589,7 +617,13 @@ def main():
     ap.add_argument("--red-batch", type=int, default=1, help="--model msrednet: tiles per step")
     ap.add_argument("--model", default="adamvs", choices=["adamvs", "msrednet"],
                     help="adamvs: the headline path; msrednet: the sibling model (SURVEY.md 8f row f3), --red-batch tiles per step, 1 GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the maps the last timed step computed (depth, photometric_confidence: "
+                         "[tiles, H, W], all tiles of the step) as DIR/<name>.npy in float32; at most 64 MB in all, a fixed seeded "
+                         "sample of whole tiles when the step's maps are larger (DIR/tile_index.npy names them)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.model == "msrednet":
         _lib.load()
         return bench_msrednet(args)
@@ -665,6 +699,9 @@ def main():
             rank_ms = [float(x.item()) for x in every]
 
         result = None
+        dumped = None
+        if rank == 0 and args.dump_outputs:
+            dumped = dump_outputs(args.dump_outputs, {"depth": gathered[0], "photometric_confidence": gathered[1]})
         if rank == 0:
             assert gathered[0].shape[0] == n_tiles and bool(torch.isfinite(gathered[0]).all())
             tile0 = (gathered[0][0].clone(), gathered[1][0].clone())      # the graph's output buffers are reused below
@@ -691,6 +728,8 @@ def main():
                 "feature_net_ms_per_tile": 1e3 * wl.t_feat / B,
                 "end_to_end_maps_per_s_per_gpu": B / (wl.t_feat + elapsed / args.steps),
             }
+            if dumped:
+                result["dump_outputs"] = dumped
 
         if rank == 0 and world == 1 and not args.no_roofline:
             result.update(roofline_of(wl, args, result["ms_per_step"]))

@@ -4,11 +4,15 @@
   hang   rank 1 never enters the barrier (it sleeps): the others wait in it for ever -- what a rank whose GPU stopped
          answering looks like to its peers
   fail   rank 1 writes to stderr and exits 7 while rank 0 waits in the barrier
+
+The barrier is an all_reduce of a host tensor: dist.barrier() asks the HIP runtime for the device count, which would open
+the GPU in every rank of this CPU-only world on a machine that has one.
 """
 import os
 import sys
 import time
 
+import torch
 import torch.distributed as dist
 
 
@@ -24,7 +28,7 @@ def main():
         sys.stderr.write("rank 1: simulated failure\n")
         sys.stderr.flush()
         os._exit(7)
-    dist.barrier()
+    dist.all_reduce(torch.zeros(1))          # the barrier (see above)
     if rank == 0:
         print('{"ok": true, "world": %d}' % world)
     dist.destroy_process_group()

@@ -19,6 +19,12 @@ def _free_port():
     return p
 
 
+def _barrier():
+    """A barrier of this CPU-only world: an all_reduce of a host tensor.  dist.barrier() asks the HIP runtime for the device
+    count (torch._C._get_accelerator), which opens the GPU in every rank on a machine that has one."""
+    dist.all_reduce(torch.zeros(1))
+
+
 def _worker(rank, world, port, n_tiles, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     r, w, _ = adist.init_from_env(backend="gloo")
@@ -33,7 +39,7 @@ def _worker(rank, world, port, n_tiles, q):
         q.put((depth.clone(), conf.clone()))
     else:
         assert depth is None and conf is None
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
 
 
@@ -53,7 +59,7 @@ def _worker_steps(rank, world, port, n_tiles, q):
         q.put((depth.clone(), conf.clone()))
     else:
         assert depth is None and conf is None
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
 
 
@@ -79,7 +85,7 @@ def _worker_every_step(rank, world, port, n_tiles, q):
             assert depth is None and conf is None
     if rank == 0:
         q.put((torch.stack([d for d, _ in per_step]), torch.stack([c for _, c in per_step])))
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
 
 
@@ -98,15 +104,15 @@ def _worker_views(rank, world, port, n_views, q):
             full[v] = g[r, i]
     if rank == 0:
         q.put((full.clone(), full.clone()))
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
 
 
-def _run(n_tiles, worker=None):
+def _run(n_tiles, worker=None, world=2):
     ctx = mp.get_context("spawn")
     q = ctx.SimpleQueue()
     port = _free_port()
-    procs = [ctx.Process(target=worker or _worker, args=(r, 2, port, n_tiles, q)) for r in range(2)]
+    procs = [ctx.Process(target=worker or _worker, args=(r, world, port, n_tiles, q)) for r in range(world)]
     for p in procs:
         p.start()
     depth, conf = q.get()
@@ -145,6 +151,16 @@ def test_map_gatherer_steps_even_and_uneven():
         for t in range(n_tiles):
             assert float(depth[t].min()) == float(depth[t].max()) == 200.0 + t
             assert float(conf[t, 0, 0]) == 200.25 + t
+
+
+def test_map_gatherer_steps_over_eight_ranks():
+    """BASELINE config 4's deal (32 tiles over 8 ranks, 4 per rank) through bench.py's step loop: eight gloo ranks on the
+    host, where the GPU suite runs fewer ranks on one device."""
+    depth, conf = _run(32, _worker_steps, world=8)
+    assert depth.shape == (32, 4, 6)
+    for t in range(32):
+        assert float(depth[t].min()) == float(depth[t].max()) == 200.0 + t
+        assert float(conf[t, 0, 0]) == 200.25 + t
 
 
 def test_map_gatherer_consumed_after_every_step():

@@ -351,6 +351,32 @@ def test_bench_refuses_a_world_that_is_not_gpus():
     assert r.returncode == 2 and "--gpus 2 but 1 rank" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """bench.py --dump-outputs: maps of at most 64 MB are written whole; larger ones as a sample of whole tiles that is the same
+    in every run (rows in global tile order, tile_index.npy naming them), float32 maps and float64 indices, 64 MB at most."""
+    import numpy as np
+    import bench
+    H, W = 384, 768                                            # cfg2 / cfg3 maps: 2.36 MB per tile, both maps
+    for n, sampled in ((5, False), (40, True)):
+        depth = torch.arange(n, dtype=torch.float32).view(n, 1, 1).expand(n, H, W).contiguous()
+        maps = {"depth": depth, "photometric_confidence": depth + 0.5}
+        runs = []
+        for k in ("a", "b"):
+            d = str(tmp_path / ("%d%s" % (n, k)))
+            info = bench.dump_outputs(d, maps)
+            assert sorted(os.listdir(d)) == ["depth.npy", "photometric_confidence.npy", "tile_index.npy"]
+            assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 * 10 ** 6
+            runs.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+        tiles = runs[0]["tile_index"]
+        assert tiles.dtype == np.float64 and np.array_equal(tiles, runs[1]["tile_index"])
+        assert (len(tiles) < n) == sampled and info["tiles"] == "%d of %d" % (len(tiles), n)
+        assert np.all(np.diff(tiles) > 0) and tiles[0] >= 0 and tiles[-1] < n
+        for z in runs:
+            assert z["depth"].dtype == z["photometric_confidence"].dtype == np.float32
+            assert np.array_equal(z["depth"], np.broadcast_to(tiles.astype(np.float32)[:, None, None], (len(tiles), H, W)))
+            assert np.array_equal(z["photometric_confidence"], z["depth"] + 0.5)
+
+
 def test_cost_reg_width_table_and_padded_packing():
     """packing.REG_WIDTHS is the library's table (csrc/costreg2d.hip::costreg_width); a network of D hypotheses is packed at the
     next width with zero filters and PAD_SCORE on `prob`'s pad channels, and the blob has the length the library expects."""

@@ -45,6 +45,14 @@ def test_all_ranks_succeed_and_rank0_stdout_is_relayed():
     assert out.getvalue().strip().splitlines()[-1] == '{"ok": true, "world": 2}' and data.decode() == out.getvalue()
 
 
+def test_eight_ranks_succeed():
+    """The world of `bench.py --gpus 8`: eight fresh ranks, all of them through the barrier, rank 0's line relayed."""
+    out, err = io.StringIO(), io.StringIO()
+    code, _ = launch.run_ranks(WORKER + ["ok"], 8, timeout=180, out=out, err=err)
+    assert code == 0, err.getvalue()[-3000:]
+    assert out.getvalue().strip().splitlines()[-1] == '{"ok": true, "world": 8}'
+
+
 def test_a_rank_sleeping_outside_the_barrier_trips_the_deadline():
     """Rank 1 never joins: rank 0 sits in barrier().  The deadline ends BOTH by PID, the code is 124 and every rank's last
     stderr lines are relayed with how it ended."""
