@@ -57,6 +57,12 @@ class StageDesc(ctypes.Structure):
                                                                                    ("half_span_dev", ctypes.c_void_p)]
 
 
+class FusionSource(ctypes.Structure):
+    """adamvs_fusion_source"""
+    _fields_ = [("depth", ctypes.c_void_p), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("fwd", ctypes.c_float * 12), ("back", ctypes.c_float * 12)]
+
+
 # name -> (restype, argtypes); every symbol include/adamvs_hip.h declares
 SIGNATURES = {
     "adamvs_version": (c_i, []),
@@ -116,11 +122,18 @@ SIGNATURES = {
     "adamvs_red_recur_split": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_float,
                                      ctypes.c_void_p, c_sz, c_st]),
     "adamvs_soft_argmin": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_st]),
+    "adamvs_fusion_max_sources": (c_i, []),
+    "adamvs_geo_consistency": (c_i, [c_f, c_f, c_i, c_i, ctypes.POINTER(FusionSource), c_i, ctypes.c_float, ctypes.c_float,
+                                     ctypes.c_float, c_i, ctypes.c_void_p, c_f, ctypes.c_void_p, c_st]),
+    "adamvs_fusion_scan": (c_i, [ctypes.c_void_p, ctypes.c_void_p, c_i, c_st]),
+    "adamvs_fusion_emit": (c_i, [c_f, ctypes.c_void_p, c_i, c_i, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_void_p,
+                                 ctypes.c_void_p, ctypes.c_long, c_st]),
 }
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 PRECISIONS = {"fp32": 0, "bf16x3": 1}
 PLANES_EXPLICIT, PLANES_UNIFORM, PLANES_WINDOW = 0, 1, 2
+FUSION_TILE = 256                # ADAMVS_FUSION_TILE: pixels per workgroup of the fusion kernels
 PHASE_VIEW_WEIGHTS, PHASE_AGGREGATE, PHASE_RECURRENCE, PHASE_SOFT_ARGMIN, PHASE_ALL = 1, 2, 4, 8, 15
 _lib = None
 

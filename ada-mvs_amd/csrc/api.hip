@@ -357,3 +357,45 @@ extern "C" int adamvs_bench_stage_phase(const adamvs_stage_desc* desc, const flo
   return stage_forward(desc, feat, rt, planes, prev_conf, w_reg, w_reg_floats, w_fuse, view_weight, pair_depth, depth, confidence,
                        phases, workspace, workspace_bytes, stream, true);
 }
+
+// ---- depth-map fusion (fusion.hip): every argument is checked here, before any launch
+extern "C" int adamvs_fusion_max_sources(void) { return ADAMVS_FUSION_MAX_SOURCES; }
+
+static bool finite_f(float v) { return v == v && v <= 3.402823466e38f && v >= -3.402823466e38f; }
+
+extern "C" int adamvs_geo_consistency(const float* ref_depth, const float* ref_conf, int H, int W, const adamvs_fusion_source* sources,
+                                      int N, float prob_threshold, float pix_threshold, float rel_depth_threshold, int min_consistent,
+                                      unsigned char* count, float* fused, unsigned* block_kept, void* stream) {
+  ADAMVS_CHECK_ARG(ref_depth && ref_conf && sources && count && fused && block_kept, "geo_consistency: null pointer");
+  ADAMVS_CHECK_ARG(H > 0 && W > 0 && (long)H * W < (1L << 31), "geo_consistency: bad reference size H=%d W=%d", H, W);
+  ADAMVS_CHECK_ARG(N >= 1 && N <= ADAMVS_FUSION_MAX_SOURCES, "geo_consistency: N=%d sources (1 .. %d)", N, ADAMVS_FUSION_MAX_SOURCES);
+  ADAMVS_CHECK_ARG(finite_f(prob_threshold), "geo_consistency: prob_threshold is not finite");
+  ADAMVS_CHECK_ARG(finite_f(pix_threshold) && pix_threshold > 0.f, "geo_consistency: pix_threshold must be finite and > 0");
+  ADAMVS_CHECK_ARG(finite_f(rel_depth_threshold) && rel_depth_threshold > 0.f, "geo_consistency: rel_depth_threshold must be finite and > 0");
+  ADAMVS_CHECK_ARG(min_consistent >= 0, "geo_consistency: min_consistent=%d (>= 0)", min_consistent);
+  for (int s = 0; s < N; ++s) {
+    ADAMVS_CHECK_ARG(sources[s].depth, "geo_consistency: source %d: null depth pointer", s);
+    ADAMVS_CHECK_ARG(sources[s].H > 0 && sources[s].W > 0 && (long)sources[s].H * sources[s].W < (1L << 31),
+                     "geo_consistency: source %d: bad size H=%d W=%d", s, sources[s].H, sources[s].W);
+    for (int k = 0; k < 12; ++k)
+      ADAMVS_CHECK_ARG(finite_f(sources[s].fwd[k]) && finite_f(sources[s].back[k]), "geo_consistency: source %d: transform not finite", s);
+  }
+  return launch_geo_consistency(ref_depth, ref_conf, H, W, sources, N, prob_threshold, pix_threshold, rel_depth_threshold, min_consistent,
+                                count, fused, block_kept, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_fusion_scan(const unsigned* block_kept, unsigned* offsets, int nblocks, void* stream) {
+  ADAMVS_CHECK_ARG(block_kept && offsets, "fusion_scan: null pointer");
+  ADAMVS_CHECK_ARG(nblocks > 0, "fusion_scan: nblocks=%d (> 0)", nblocks);
+  return launch_fusion_scan(block_kept, offsets, nblocks, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_fusion_emit(const float* fused, const unsigned char* rgba, int H, int W, const double* camera, const unsigned* offsets,
+                                  double* xyz, unsigned char* rgb, long capacity, void* stream) {
+  ADAMVS_CHECK_ARG(fused && rgba && camera && offsets && xyz && rgb, "fusion_emit: null pointer");
+  ADAMVS_CHECK_ARG(H > 0 && W > 0 && (long)H * W < (1L << 31), "fusion_emit: bad size H=%d W=%d", H, W);
+  ADAMVS_CHECK_ARG(capacity >= (long)H * W, "fusion_emit: capacity %ld < H W = %ld points", capacity, (long)H * W);
+  for (int k = 0; k < 21; ++k)
+    ADAMVS_CHECK_ARG(std::isfinite(camera[k]), "fusion_emit: camera[%d] is not finite", k);
+  return launch_fusion_emit(fused, rgba, H, W, camera, offsets, xyz, rgb, capacity, (hipStream_t)stream);
+}

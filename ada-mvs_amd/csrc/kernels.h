@@ -5,6 +5,7 @@
 #include "common.h"
 #include "options.h"
 #include "planes.h"
+#include "../../include/adamvs_hip.h"
 
 namespace adamvs {
 
@@ -135,5 +136,15 @@ int launch_pair_similarity(const float* feat, const float* rt, PlaneSrc planes, 
 int launch_softmax_regress(const float* score, PlaneSrc planes, float* vw, float* pd, int S, int B, int D, int h, int w,
                            hipStream_t st, int n_planes = 0);
 bool costreg_depth_supported(int D);
+
+// fusion.hip: geometric-consistency filtering and point emission (include/adamvs_hip.h, "depth-map fusion")
+constexpr int FUSION_TILE = ADAMVS_FUSION_TILE;
+constexpr int FUSION_MAX_SOURCES = ADAMVS_FUSION_MAX_SOURCES;
+int launch_geo_consistency(const float* ref_depth, const float* ref_conf, int H, int W, const adamvs_fusion_source* srcs, int N,
+                           float prob_threshold, float pix_threshold, float rel_depth_threshold, int min_consistent, uint8_t* count,
+                           float* fused, unsigned* block_kept, hipStream_t st);
+int launch_fusion_scan(const unsigned* counts, unsigned* offsets, int nblocks, hipStream_t st);
+int launch_fusion_emit(const float* fused, const uint8_t* rgba, int H, int W, const double* camera, const unsigned* offsets, double* xyz,
+                       uint8_t* rgb, long capacity, hipStream_t st);
 
 }  // namespace adamvs

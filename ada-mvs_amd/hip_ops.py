@@ -494,3 +494,76 @@ def soft_argmin(vol, planes, B, D, h, w):
     check(_lib.load().adamvs_soft_argmin(_p(vol), _p(_dev(planes, "planes")), _p(depth), _p(conf), B, D, h, w, _stream()),
           "soft_argmin")
     return depth, conf
+
+
+# ---- depth-map fusion (csrc/fusion.hip; driven per view by ada_mvs_amd/fusion.py) ----------------------------------------
+def _dev_as(t, name, dtype):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.AdaMVSHipError("%s must be a GPU tensor: the fusion path has no CPU fallback" % name)
+    if t.dtype != dtype:
+        raise _lib.AdaMVSHipError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def fusion_blocks(H, W):
+    """Workgroups of the fusion kernels for an [H, W] reference map (ADAMVS_FUSION_TILE consecutive pixels each)."""
+    return (H * W + _lib.FUSION_TILE - 1) // _lib.FUSION_TILE
+
+
+def geo_consistency(ref_depth, ref_conf, sources, prob_threshold=0.5, pix_threshold=1.0, rel_depth_threshold=0.01, min_consistent=2):
+    """adamvs_geo_consistency.  ref_depth, ref_conf [H, W] fp32; sources: list of (depth [Hs, Ws] fp32, fwd (12,), back (12,))
+    with fwd / back as include/adamvs_hip.h describes them (ada_mvs_amd/fusion.py::relative_transforms forms them in fp64).
+    -> (count [H, W] uint8, fused [H, W] fp32, block_kept [nblocks] int32 (uint32 in the C ABI))."""
+    ref_depth = _dev(ref_depth, "ref_depth")
+    ref_conf = _dev(ref_conf, "ref_conf")
+    H, W = ref_depth.shape
+    if tuple(ref_conf.shape) != (H, W):
+        raise _lib.AdaMVSHipError("ref_conf %s != ref_depth %s" % (tuple(ref_conf.shape), (H, W)))
+    arr = (_lib.FusionSource * max(len(sources), 1))()
+    keep = []
+    for i, (dep, fwd, back) in enumerate(sources):
+        dep = _dev(dep, "source depth %d" % i)
+        keep.append(dep)
+        arr[i].depth = dep.data_ptr()
+        arr[i].H, arr[i].W = dep.shape
+        arr[i].fwd[:] = [float(v) for v in fwd]
+        arr[i].back[:] = [float(v) for v in back]
+    count = torch.empty(H, W, device=ref_depth.device, dtype=torch.uint8)
+    fused = torch.empty(H, W, device=ref_depth.device, dtype=torch.float32)
+    block_kept = torch.empty(fusion_blocks(H, W), device=ref_depth.device, dtype=torch.int32)
+    check(_lib.load().adamvs_geo_consistency(_p(ref_depth), _p(ref_conf), H, W, arr, len(sources), float(prob_threshold),
+                                             float(pix_threshold), float(rel_depth_threshold), int(min_consistent), _p(count),
+                                             _p(fused), _p(block_kept), _stream()), "geo_consistency")
+    return count, fused, block_kept
+
+
+def emit_points(fused, block_kept, rgba, camera, xyz=None, rgb=None):
+    """adamvs_fusion_scan + adamvs_fusion_emit.  fused [H, W] fp32 and block_kept from geo_consistency, rgba [H, W, 4] uint8,
+    camera: 21 float64 {K^-1 (9), R_wc (9), C (3)} (host).  -> (xyz [H W, 3] float64, rgb [H W, 3] uint8, offsets [nblocks + 1]
+    int32): points 0 .. offsets[-1] are valid, in row-major pixel order.  xyz / rgb: reusable buffers of at least H W points."""
+    import numpy as np
+    fused = _dev(fused, "fused")
+    block_kept = _dev_as(block_kept, "block_kept", torch.int32)
+    rgba = _dev_as(rgba, "rgba", torch.uint8)
+    H, W = fused.shape
+    if tuple(rgba.shape) != (H, W, 4):
+        raise _lib.AdaMVSHipError("rgba %s != (%d, %d, 4)" % (tuple(rgba.shape), H, W))
+    nb = fusion_blocks(H, W)
+    if block_kept.numel() != nb:
+        raise _lib.AdaMVSHipError("block_kept holds %d counts, [%d, %d] needs %d" % (block_kept.numel(), H, W, nb))
+    cam = np.ascontiguousarray(np.asarray(camera, dtype=np.float64).reshape(-1))
+    if cam.size != 21:
+        raise _lib.AdaMVSHipError("camera: 21 doubles {K^-1, R_wc, C}, got %d" % cam.size)
+    if xyz is None:
+        xyz = torch.empty(H * W, 3, device=fused.device, dtype=torch.float64)
+    if rgb is None:
+        rgb = torch.empty(H * W, 3, device=fused.device, dtype=torch.uint8)
+    cap = min(xyz.shape[0], rgb.shape[0])
+    if xyz.dtype != torch.float64 or rgb.dtype != torch.uint8 or not (xyz.is_contiguous() and rgb.is_contiguous()):
+        raise _lib.AdaMVSHipError("xyz must be contiguous float64 [n, 3], rgb contiguous uint8 [n, 3]")
+    offsets = torch.empty(nb + 1, device=fused.device, dtype=torch.int32)
+    lib = _lib.load()
+    check(lib.adamvs_fusion_scan(_p(block_kept), _p(offsets), nb, _stream()), "fusion_scan")
+    check(lib.adamvs_fusion_emit(_p(fused), _p(rgba), H, W, cam.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _p(offsets),
+                                 _p(xyz), _p(rgb), cap, _stream()), "fusion_emit")
+    return xyz, rgb, offsets

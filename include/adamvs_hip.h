@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ADAMVS_ABI_VERSION 16
+#define ADAMVS_ABI_VERSION 17
 
 int adamvs_version(void);
 const char* adamvs_last_error_string(void);
@@ -454,6 +454,49 @@ int adamvs_red_recur_split(const float* gxr, const float* gxu, const float* cx, 
  * the stored slices: vol [B][D][h*w] = reg_cost of every plane, planes [B][D][h*w] -> depth, confidence [B][h*w]. */
 int adamvs_soft_argmin(const float* vol, const float* planes, float* depth, float* confidence, int B, int D, int h, int w,
                        void* stream);
+
+/* ---- depth-map fusion (after predict_whu.py; the reference stops at writing the maps, predict_whu.py "step1") -------------
+ * Geometric-consistency filtering of one reference view against up to ADAMVS_FUSION_MAX_SOURCES source views and the kept
+ * pixels as world points (ada-mvs_amd/fusion.py drives it per view; fuse_whu.py is the CLI).  Pixel centres sit at integer
+ * coordinates (the convention of homo_warping, models/module.py:527-568).  Three calls per view, enqueued on `stream`:
+ * _geo_consistency -> _fusion_scan -> _fusion_emit; no atomics, output bit-identical from run to run, points in row-major
+ * pixel order.  Workgroups cover ADAMVS_FUSION_TILE consecutive row-major pixels: nblocks = ceil(H W / ADAMVS_FUSION_TILE). */
+#define ADAMVS_FUSION_MAX_SOURCES 16
+#define ADAMVS_FUSION_TILE 256
+int adamvs_fusion_max_sources(void);
+
+/* One source view, host memory (copied into the kernel arguments).  depth: device pointer to its depth map [H][W] fp32.
+ * fwd = {A row-major, b}: the source's homogeneous pixel of reference pixel (x, y) at depth d is d A [x y 1]^T + b
+ * (A = K_s R_sr K_r^-1, b = K_s t_sr); back = {B, c}: the reference's homogeneous pixel of source pixel (u, v) at depth d_s
+ * is d_s B [u v 1]^T + c (B = K_r R_rs K_s^-1, c = K_r t_rs).  The third component is the depth in that camera.  Formed
+ * in fp64 by the caller and rounded to fp32: camera-frame magnitudes are depths and baselines, not world coordinates. */
+typedef struct {
+  const float* depth;
+  int H, W;
+  float fwd[12];
+  float back[12];
+} adamvs_fusion_source;
+
+/* Per reference pixel p = (x, y) with d = ref_depth[p]: a candidate iff d is finite and > 0 and ref_conf[p] >= prob_threshold
+ * (NaN is not).  Source s is consistent iff the projection has z > 0, lands in 0 <= u < W_s - 1, 0 <= v < H_s - 1, its four
+ * bilinear taps of depth_s are finite and > 0, and the bilinear depth projected back gives |(x', y') - (x, y)| < pix_threshold
+ * and |d' - d| < rel_depth_threshold d.  count[p] = number of consistent sources n (uint8); fused[p] = (d + sum d') / (1 + n)
+ * if a candidate with n >= min_consistent, else 0; block_kept[nblocks] = number of kept pixels per workgroup.
+ * ref_depth, ref_conf [H][W]; 1 <= N <= ADAMVS_FUSION_MAX_SOURCES; thresholds finite, pix / rel > 0, min_consistent >= 0. */
+int adamvs_geo_consistency(const float* ref_depth, const float* ref_conf, int H, int W, const adamvs_fusion_source* sources,
+                           int N, float prob_threshold, float pix_threshold, float rel_depth_threshold, int min_consistent,
+                           unsigned char* count, float* fused, unsigned* block_kept, void* stream);
+
+/* Exclusive scan: offsets[i] = sum of block_kept[0 .. i), offsets[nblocks] = the total (uint32, nblocks + 1 entries). */
+int adamvs_fusion_scan(const unsigned* block_kept, unsigned* offsets, int nblocks, void* stream);
+
+/* Every pixel with fused[p] > 0 becomes point offsets[block] + (its rank among the kept pixels of the block):
+ * xyz[q] = R_wc (fused[p] K^-1 [x y 1]^T) + C in fp64 (world coordinates of aerial scenes reach 1e6 m: fp32 would lose
+ * decimetres), rgb[q] = the first three bytes of rgba[p] (reference image [H][W][4] uint8).  camera: HOST pointer to 21
+ * doubles {K^-1 row-major (9), R_wc row-major (9), C (3)}, camera axes x right / y down / z forward.  xyz [capacity][3],
+ * rgb [capacity][3]; capacity >= H W is required (a view has at most H W points; none is written at or past capacity). */
+int adamvs_fusion_emit(const float* fused, const unsigned char* rgba, int H, int W, const double* camera, const unsigned* offsets,
+                       double* xyz, unsigned char* rgb, long capacity, void* stream);
 
 #ifdef __cplusplus
 }
