@@ -270,30 +270,84 @@ def test_winograd_one_and_two_workgroups_per_cu_give_the_same_bits(hip, set_opti
     assert torch.equal(outs[0], outs[1]) and float(outs[0].abs().max()) > 0
 
 
-@pytest.mark.parametrize("switch", ["winograd", "wino_softmax"])
-def test_cost_reg_net_2d_direct_kernels_behind_their_options(hip, O, set_option, switch):
-    """The A/B options of CostRegNet2D.  winograd = 0: its stride-1 layers on the direct kernel at the widths the F(2x2, 3x3) kernel
-    otherwise takes, the softmax epilogue of the direct `prob` layer included.  wino_softmax = 0: the F(2x2, 3x3) `prob` layer writes
-    its scores and k_softmax_regress reads them, as before round 4's partials + merge (test_piecewise_phase_masks runs stage 1 at
-    D = 192 through it).  The tests named below run again under the option."""
-    set_option(switch, 0)
+def _rerun(names, fixtures, keep=lambda name, case: True):
+    """Run the named tests of this module once per parametrised case (keep(name, case) may leave a case out) under whatever
+    options the caller has set; fixtures: name -> value for the non-parametrised arguments.  Returns the cases run."""
     import inspect
     me = sys.modules[__name__]
     ran = 0
-    for name in ("test_cost_reg_net_2d_widths", "test_prob_softmax_regress_fused", "test_generated_planes_equal_materialised_planes",
-                 "test_piecewise_phase_masks"):
+    for name in names:
         fn = getattr(me, name)
         marks = [mk for mk in getattr(fn, "pytestmark", []) if mk.name == "parametrize"]
-        names = inspect.signature(fn).parameters
+        params = inspect.signature(fn).parameters
         cases = [{}]
         for mk in marks:
             keys = [k.strip() for k in mk.args[0].split(",")]
             cases = [dict(c, **dict(zip(keys, v if len(keys) > 1 else (v,)))) for c in cases for v in mk.args[1]]
         for c in cases:
-            fixtures = {"hip": hip, "O": O}
-            fn(**{k: (c[k] if k in c else fixtures[k]) for k in names})
-            ran += 1
+            if keep(name, c):
+                fn(**{k: (c[k] if k in c else fixtures[k]) for k in params})
+                ran += 1
+    return ran
+
+
+_NET = ("test_cost_reg_net_2d_widths",)
+_STAGE = ("test_stage_one_at_any_hypothesis_count",)
+
+
+def _small_stage(name, case):
+    return name not in _STAGE or case["D"] <= 160          # the larger hypothesis counts take a minute of CPU oracle each
+
+
+_WINO_RERUN = _NET + ("test_prob_softmax_regress_fused", "test_generated_planes_equal_materialised_planes", "test_piecewise_phase_masks")
+_COSTREG_SWITCHES = [
+    ("winograd=0", _WINO_RERUN),
+    ("wino_softmax=0", _WINO_RERUN),
+    ("fuse_softmax=0", _NET + _STAGE + ("test_generated_planes_equal_materialised_planes", "test_piecewise_phase_masks")),
+    ("s2_pairs=0", _NET + ("test_stride_two_layer_in_the_pair_form",)),
+    ("conv_rows2=0", _NET + ("test_conv3x3_dd_winograd",)),
+    ("conv_rows2=1", _NET + ("test_conv3x3_dd_winograd",)),
+    ("t2_fused=0", _NET + ("test_cost_reg_net_2d_golden",)),
+    ("t2_fused=1", _NET + ("test_cost_reg_net_2d_golden",)),
+    ("t2_kb8=0,t2_fused=0", _NET + ("test_cost_reg_net_2d_golden",)),
+    ("costreg_defer_skips=0", _NET + _STAGE + ("test_cost_reg_net_2d_golden",)),
+    ("conv256_split=0", _NET + ("test_conv3x3_dd_winograd", "test_prob_softmax_regress_fused")),
+]
+
+
+@pytest.mark.parametrize("switch,names", [pytest.param(s, n, id=s) for s, n in _COSTREG_SWITCHES])
+def test_cost_reg_net_2d_direct_kernels_behind_their_options(hip, O, set_option, switch, names):
+    """The A/B options of CostRegNet2D (include/adamvs_hip.h "OPTIONS"); the tests named run again under each.  winograd = 0:
+    the stride-1 layers on the direct kernel at the widths the F(2x2, 3x3) kernel otherwise takes, the softmax epilogue of the
+    direct `prob` layer included.  wino_softmax = 0: the F(2x2, 3x3) `prob` layer writes its scores and k_softmax_regress reads
+    them, as before round 4's partials + merge.  fuse_softmax = 0: the direct `prob` layer writes scores for k_softmax_regress
+    too (both precisions).  conv_rows2 / t2_fused: one arm of the size rule for every layer; t2_kb8 = 0 needs the class-by-class
+    transposed kernel, which small maps reach only with t2_fused = 0.  No option of the table changes the bf16x3 network's
+    layers (test_cost_reg_net_2d_bf16x3) other than fuse_softmax, which the stage test covers at bf16x3."""
+    for kv in switch.split(","):
+        name, value = kv.split("=")
+        set_option(name, int(value))
+    ran = _rerun(names, {"hip": hip, "O": O, "set_option": set_option}, _small_stage)
     assert ran >= 8
+
+
+_CONV1_FCONV_SWITCHES = [
+    ("conv1_f23=0", ("test_aggregate_conv1",)),
+    ("conv1_f23=1", ("test_aggregate_conv1",)),
+    ("conv1_f23=2", ("test_aggregate_conv1",)),
+    ("fconv_f23=0", ("test_feature_net0_against_oracle", "test_feature_net0_golden", "test_feature_net0_in_chunks_equals_one_call")),
+]
+
+
+@pytest.mark.parametrize("switch,names", [pytest.param(s, n, id=s) for s, n in _CONV1_FCONV_SWITCHES])
+def test_conv1_and_feature_net0_behind_their_options(hip, O, set_option, switch, names):
+    """conv1_f23 = 0 / 1 / 2: conv1 of SliceCostRegNetRED on k_conv1_ksplit<32> and / or k_conv1_two_row<16 / 8> instead of the
+    F(2, 3)-along-x kernels (fp32 cases; bf16x3 has one form).  fconv_f23 = 0: FeatureNet0's stride-1 layers on k_fconv and its
+    transposed layers class by class.  The tests named run again under the option."""
+    name, value = switch.split("=")
+    set_option(name, int(value))
+    ran = _rerun(names, {"hip": hip, "O": O}, lambda name, case: case.get("precision", "fp32") == "fp32")
+    assert ran >= 5
 
 
 @pytest.mark.parametrize("D,h,w", [(32, 16, 24), (64, 8, 16), (192, 8, 16), (256, 8, 8)])

@@ -53,6 +53,32 @@ def test_every_option_is_documented_in_the_header_with_its_default():
     assert sites <= 3, sites
 
 
+def test_every_option_value_names_the_test_that_runs_it():
+    """tests/test_kernel_forms.py::FORMS (read as a literal: no import, no GPU) has one entry per option of csrc/options.h, each
+    with the header default and every other value its launchers tell apart, and every value names a test that exists."""
+    import ast
+    src = open(os.path.join(ROOT, "tests", "test_kernel_forms.py")).read()
+    node = next(n for n in ast.parse(src).body if isinstance(n, ast.Assign) and [t.id for t in n.targets] == ["FORMS"])
+    forms = ast.literal_eval(node.value)
+    names = _lib.option_names()
+    assert sorted(forms) == sorted(names), set(forms) ^ set(names)
+    lib = _lib.load()
+    special = {"wino_wps": {0, 1, 2}, "conv_small_grid": {0, 1024}, "conv1_f23": {0, 1, 2, 3}, "gru_wino": {0, 1, 2, 4, 7, 8},
+               "recur_mode": {-1, 0, 1, 3, 5}}
+    for name in names:
+        v = ctypes.c_int(0)
+        assert lib.adamvs_option_default(name.encode(), ctypes.byref(v)) == 0
+        want = special.get(name, {-1, 0, 1} if v.value == -1 else {0, 1})
+        assert v.value in forms[name] and len(forms[name]) >= 2, name
+        assert set(forms[name]) == want, (name, sorted(forms[name]), sorted(want))
+        for value, text in forms[name].items():
+            refs = re.findall(r"\b(test_\w+\.py)::(test_\w+)", text)
+            assert refs, "FORMS[%r][%d] names no test" % (name, value)
+            for fname, test in refs:
+                path = os.path.join(ROOT, "tests", fname)
+                assert os.path.exists(path) and re.search(r"^def %s\(" % test, open(path).read(), re.M), "%s::%s" % (fname, test)
+
+
 def test_argument_errors_surface_as_exceptions_without_a_gpu():
     lib = _lib.load()
     null = ctypes.c_void_p(0)
