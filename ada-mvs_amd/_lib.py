@@ -63,6 +63,12 @@ class FusionSource(ctypes.Structure):
                 ("fwd", ctypes.c_float * 12), ("back", ctypes.c_float * 12)]
 
 
+class DsmGrid(ctypes.Structure):
+    """adamvs_dsm_grid"""
+    _fields_ = [("x0", ctypes.c_double), ("y_top", ctypes.c_double), ("gsd", ctypes.c_double), ("z_ref", ctypes.c_double),
+                ("W", ctypes.c_int), ("H", ctypes.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/adamvs_hip.h declares
 SIGNATURES = {
     "adamvs_version": (c_i, []),
@@ -128,12 +134,20 @@ SIGNATURES = {
     "adamvs_fusion_scan": (c_i, [ctypes.c_void_p, ctypes.c_void_p, c_i, c_st]),
     "adamvs_fusion_emit": (c_i, [c_f, ctypes.c_void_p, c_i, c_i, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_void_p, ctypes.c_long, c_st]),
+    "adamvs_dsm_accumulate": (c_i, [ctypes.POINTER(DsmGrid), ctypes.c_void_p, ctypes.c_long, ctypes.c_long, c_i, ctypes.c_void_p,
+                                    ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_dsm_claim": (c_i, [ctypes.POINTER(DsmGrid), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_void_p,
+                               ctypes.c_void_p, c_st]),
+    "adamvs_dsm_finalize": (c_i, [ctypes.POINTER(DsmGrid), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, c_i,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
 }
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 PRECISIONS = {"fp32": 0, "bf16x3": 1}
 PLANES_EXPLICIT, PLANES_UNIFORM, PLANES_WINDOW = 0, 1, 2
 FUSION_TILE = 256                # ADAMVS_FUSION_TILE: pixels per workgroup of the fusion kernels
+DSM_MAX, DSM_MEAN = 0, 1         # ADAMVS_DSM_MAX / ADAMVS_DSM_MEAN
+DSM_MAX_CELLS = 1 << 28          # ADAMVS_DSM_MAX_CELLS
 PHASE_VIEW_WEIGHTS, PHASE_AGGREGATE, PHASE_RECURRENCE, PHASE_SOFT_ARGMIN, PHASE_ALL = 1, 2, 4, 8, 15
 _lib = None
 

@@ -399,3 +399,46 @@ extern "C" int adamvs_fusion_emit(const float* fused, const unsigned char* rgba,
     ADAMVS_CHECK_ARG(std::isfinite(camera[k]), "fusion_emit: camera[%d] is not finite", k);
   return launch_fusion_emit(fused, rgba, H, W, camera, offsets, xyz, rgb, capacity, (hipStream_t)stream);
 }
+
+// ---- DSM (dsm.hip): every argument is checked here, before any launch
+static int dsm_check_grid(const adamvs_dsm_grid* g, const char* what) {
+  ADAMVS_CHECK_ARG(g, "%s: null grid", what);
+  ADAMVS_CHECK_ARG(std::isfinite(g->gsd) && g->gsd > 0.0, "%s: gsd=%g must be finite and > 0", what, g->gsd);
+  ADAMVS_CHECK_ARG(std::isfinite(g->x0) && std::isfinite(g->y_top) && std::isfinite(g->z_ref), "%s: grid origin / z_ref not finite", what);
+  ADAMVS_CHECK_ARG(g->W > 0 && g->H > 0 && (long)g->W * g->H <= ADAMVS_DSM_MAX_CELLS, "%s: grid W=%d H=%d (W H <= %d cells)", what, g->W,
+                   g->H, ADAMVS_DSM_MAX_CELLS);
+  return 0;
+}
+
+static int dsm_check_points(long n, long seq0, const char* what) {
+  ADAMVS_CHECK_ARG(n >= 0, "%s: n=%ld (>= 0)", what, n);
+  ADAMVS_CHECK_ARG(seq0 >= 0 && seq0 <= (1L << 32) - n, "%s: seq0=%ld + n=%ld exceeds 2^32 points", what, seq0, n);
+  return 0;
+}
+
+extern "C" int adamvs_dsm_accumulate(const adamvs_dsm_grid* grid, const double* xyz, long n, long seq0, int mode, unsigned long long* key,
+                                     unsigned* count, long long* sum, void* stream) {
+  if (int rc = dsm_check_grid(grid, "dsm_accumulate")) return rc;
+  if (int rc = dsm_check_points(n, seq0, "dsm_accumulate")) return rc;
+  ADAMVS_CHECK_ARG(mode == ADAMVS_DSM_MAX || mode == ADAMVS_DSM_MEAN, "dsm_accumulate: mode=%d (0 max, 1 mean)", mode);
+  ADAMVS_CHECK_ARG(xyz && key && count && (sum || mode == ADAMVS_DSM_MAX), "dsm_accumulate: null pointer");
+  return launch_dsm_accumulate(*grid, xyz, n, seq0, mode, key, count, sum, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_dsm_claim(const adamvs_dsm_grid* grid, const double* xyz, const unsigned char* rgb, long n, long seq0,
+                                const unsigned long long* key, unsigned* color, void* stream) {
+  if (int rc = dsm_check_grid(grid, "dsm_claim")) return rc;
+  if (int rc = dsm_check_points(n, seq0, "dsm_claim")) return rc;
+  ADAMVS_CHECK_ARG(xyz && rgb && key && color, "dsm_claim: null pointer");
+  return launch_dsm_claim(*grid, xyz, rgb, n, seq0, key, color, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_dsm_finalize(const adamvs_dsm_grid* grid, const unsigned long long* key, const unsigned* count, const long long* sum,
+                                   const unsigned* color, int mode, int min_count, float* dsm, unsigned short* count16, unsigned char* rgba,
+                                   void* stream) {
+  if (int rc = dsm_check_grid(grid, "dsm_finalize")) return rc;
+  ADAMVS_CHECK_ARG(mode == ADAMVS_DSM_MAX || mode == ADAMVS_DSM_MEAN, "dsm_finalize: mode=%d (0 max, 1 mean)", mode);
+  ADAMVS_CHECK_ARG(min_count >= 1, "dsm_finalize: min_count=%d (>= 1)", min_count);
+  ADAMVS_CHECK_ARG(key && count && color && dsm && count16 && rgba && (sum || mode == ADAMVS_DSM_MAX), "dsm_finalize: null pointer");
+  return launch_dsm_finalize(*grid, key, count, sum, color, mode, min_count, dsm, count16, (unsigned*)rgba, (hipStream_t)stream);
+}

@@ -147,4 +147,13 @@ int launch_fusion_scan(const unsigned* counts, unsigned* offsets, int nblocks, h
 int launch_fusion_emit(const float* fused, const uint8_t* rgba, int H, int W, const double* camera, const unsigned* offsets, double* xyz,
                        uint8_t* rgb, long capacity, hipStream_t st);
 
+// dsm.hip: rasterisation of a point cloud into a DSM and a true orthophoto (include/adamvs_hip.h, "DSM")
+constexpr int DSM_TILE = 256;
+int launch_dsm_accumulate(const adamvs_dsm_grid& g, const double* xyz, long n, long seq0, int mode, unsigned long long* key,
+                          unsigned* count, long long* sum, hipStream_t st);
+int launch_dsm_claim(const adamvs_dsm_grid& g, const double* xyz, const uint8_t* rgb, long n, long seq0, const unsigned long long* key,
+                     unsigned* color, hipStream_t st);
+int launch_dsm_finalize(const adamvs_dsm_grid& g, const unsigned long long* key, const unsigned* count, const long long* sum,
+                        const unsigned* color, int mode, int min_count, float* dsm, uint16_t* count16, unsigned* rgba, hipStream_t st);
+
 }  // namespace adamvs

@@ -567,3 +567,75 @@ def emit_points(fused, block_kept, rgba, camera, xyz=None, rgb=None):
     check(lib.adamvs_fusion_emit(_p(fused), _p(rgba), H, W, cam.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _p(offsets),
                                  _p(xyz), _p(rgb), cap, _stream()), "fusion_emit")
     return xyz, rgb, offsets
+
+
+# ---- DSM rasterisation (csrc/dsm.hip; driven chunk by chunk by ada_mvs_amd/dsm.py::DsmBuilder) ---------------------------
+# Cell state as torch tensors of the signed type of each C type's width (key int64 = uint64, count / color int32 = uint32,
+# sum int64); dsm.py reads them back through numpy views of the unsigned types.
+def _dsm_grid(grid):
+    g = _lib.DsmGrid()
+    g.x0, g.y_top, g.gsd, g.z_ref = float(grid.x0), float(grid.y_top), float(grid.gsd), float(grid.z_ref)
+    g.W, g.H = int(grid.W), int(grid.H)
+    return g
+
+
+def _dsm_points(xyz, rgb=None):
+    xyz = _dev_as(xyz, "xyz", torch.float64)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise _lib.AdaMVSHipError("xyz must be [n, 3], got %s" % (tuple(xyz.shape),))
+    if rgb is not None:
+        rgb = _dev_as(rgb, "rgb", torch.uint8)
+        if tuple(rgb.shape) != (xyz.shape[0], 3):
+            raise _lib.AdaMVSHipError("rgb %s != (%d, 3)" % (tuple(rgb.shape), xyz.shape[0]))
+    return xyz, rgb
+
+
+def _dsm_cells(t, name, dtype, grid):
+    if _dev_as(t, name, dtype) is not t:          # the kernels write the state in place: a contiguous copy would lose it
+        raise _lib.AdaMVSHipError("%s must be contiguous" % name)
+    if t.numel() != int(grid.W) * int(grid.H):
+        raise _lib.AdaMVSHipError("%s holds %d cells, the grid has %d x %d" % (name, t.numel(), grid.H, grid.W))
+    return t
+
+
+def dsm_accumulate(grid, xyz, seq0, mode, key, count, sum_=None):
+    """adamvs_dsm_accumulate: points xyz [n, 3] float64 (device) with sequence numbers seq0 .. seq0 + n - 1 into the cell state
+    key [H W] int64, count [H W] int32 and, in mean mode, sum_ [H W] int64."""
+    xyz, _ = _dsm_points(xyz)
+    key = _dsm_cells(key, "key", torch.int64, grid)
+    count = _dsm_cells(count, "count", torch.int32, grid)
+    sp = None if sum_ is None else _p(_dsm_cells(sum_, "sum", torch.int64, grid))
+    if xyz.shape[0] == 0:                         # nothing to launch (an empty tensor has no data pointer)
+        return
+    g = _dsm_grid(grid)
+    check(_lib.load().adamvs_dsm_accumulate(ctypes.byref(g), _p(xyz), xyz.shape[0], int(seq0), int(mode), _p(key), _p(count), sp, _stream()),
+          "dsm_accumulate")
+
+
+def dsm_claim(grid, xyz, rgb, seq0, key, color):
+    """adamvs_dsm_claim: after dsm_accumulate of the same points, the max-key point of each cell writes its colour into
+    color [H W] int32 (RGBA bytes)."""
+    xyz, rgb = _dsm_points(xyz, rgb)
+    key = _dsm_cells(key, "key", torch.int64, grid)
+    color = _dsm_cells(color, "color", torch.int32, grid)
+    if xyz.shape[0] == 0:
+        return
+    g = _dsm_grid(grid)
+    check(_lib.load().adamvs_dsm_claim(ctypes.byref(g), _p(xyz), _p(rgb), xyz.shape[0], int(seq0), _p(key), _p(color), _stream()), "dsm_claim")
+
+
+def dsm_finalize(grid, key, count, sum_, color, mode, min_count):
+    """adamvs_dsm_finalize -> (dsm [H, W] float32, count16 [H, W] int16 (uint16 in the C ABI), rgba [H, W, 4] uint8), device."""
+    key = _dsm_cells(key, "key", torch.int64, grid)
+    count = _dsm_cells(count, "count", torch.int32, grid)
+    color = _dsm_cells(color, "color", torch.int32, grid)
+    sp = None if sum_ is None else _p(_dsm_cells(sum_, "sum", torch.int64, grid))
+    H, W = int(grid.H), int(grid.W)
+    dev = key.device
+    dsm = torch.empty(H, W, device=dev, dtype=torch.float32)
+    count16 = torch.empty(H, W, device=dev, dtype=torch.int16)
+    rgba = torch.empty(H, W, 4, device=dev, dtype=torch.uint8)
+    g = _dsm_grid(grid)
+    check(_lib.load().adamvs_dsm_finalize(ctypes.byref(g), _p(key), _p(count), sp, _p(color), int(mode), int(min_count), _p(dsm),
+                                          _p(count16), _p(rgba), _stream()), "dsm_finalize")
+    return dsm, count16, rgba

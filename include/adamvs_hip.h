@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ADAMVS_ABI_VERSION 17
+#define ADAMVS_ABI_VERSION 18
 
 int adamvs_version(void);
 const char* adamvs_last_error_string(void);
@@ -497,6 +497,54 @@ int adamvs_fusion_scan(const unsigned* block_kept, unsigned* offsets, int nblock
  * rgb [capacity][3]; capacity >= H W is required (a view has at most H W points; none is written at or past capacity). */
 int adamvs_fusion_emit(const float* fused, const unsigned char* rgba, int H, int W, const double* camera, const unsigned* offsets,
                        double* xyz, unsigned char* rgb, long capacity, void* stream);
+
+/* ---- DSM (after fuse_whu.py): a point cloud rasterised into a digital surface model and a true orthophoto ----------------
+ * ada-mvs_amd/dsm.py streams the points in chunks; dsm_whu.py is the CLI.  World axes: x east, y north, z up.
+ *
+ * Grid: column i, row j (row 0 is the northern edge).  A point (x, y, z) falls in  i = floor((x - x0) / gsd),
+ * j = floor((y_top - y) / gsd),  both in fp64 with exactly these operations (cell (i, j) holds x0 + i gsd <= x < x0 + (i + 1) gsd
+ * and y_top - (j + 1) gsd < y <= y_top - j gsd, up to the rounding of those operations),
+ * and is USED iff 0 <= i < W, 0 <= j < H and |z - z_ref| < 65536 (all in fp64; NaN / inf coordinates are never used).
+ * Point k of a call has the sequence number seq = seq0 + k (uint32; the stream holds fewer than 2^32 points).
+ * Per used point  h = (float)(z - z_ref),  o(h) = the order-preserving uint32 of h's bits (-0 taken as +0: equal heights, equal
+ * o), and the 64-bit key  o(h) << 32 | (0xFFFFFFFF - seq):  the highest point has the largest key, and among equal fp32 heights
+ * the earliest point.  A used point's key is never 0; key 0 marks an empty cell.
+ * Per cell: key = max over its used points, count = their number (uint32), and in ADAMVS_DSM_MEAN mode
+ * sum = the int64 sum of q = rint((z - z_ref) * 65536.0) (exact while count * max|q| < 2^63, i.e. 2^31 points at +-65536 m).
+ * Then for count >= min_count
+ *   ADAMVS_DSM_MAX:  dsm = (float)(z_ref + (double)h of the max-key point)                     (the first-surface DSM)
+ *   ADAMVS_DSM_MEAN: dsm = (float)(z_ref + ((double)sum / (double)count) / 65536.0)
+ *   rgba = the RGB of the max-key point, alpha 255 (both modes);
+ * and dsm = NaN (0x7fc00000), rgba = 0 for count < min_count.  count16 = min(count, 65535) for every cell.
+ * Every reduction is an integer max or sum: the output is bit-identical from run to run, and in mean mode (dsm, count) under
+ * any permutation or chunking of the points.
+ *
+ * Cell state (device, row-major [H][W], zeroed by the caller before the first chunk): key (uint64), count (uint32), color
+ * (uint32 RGBA, little-endian r g b a), and sum (int64, mean mode only; may be NULL in max mode): 16 bytes per cell in max
+ * mode, 24 in mean mode; the finalize outputs add 10 (dsm fp32, count16 uint16, rgba 4 x uint8).  W H <= ADAMVS_DSM_MAX_CELLS.
+ * Per chunk: _dsm_accumulate, then _dsm_claim with the same points and seq0 (the lane whose key is the cell's key writes its
+ * colour; a later chunk that wins the cell overwrites it in its own claim), in stream order; _dsm_finalize once at the end.
+ * grid: HOST pointer (copied into the kernel arguments); xyz: device [n][3] fp64; rgb: device [n][3] uint8; the finalize
+ * outputs dsm [H][W] fp32, count16 [H][W] uint16, rgba [H][W][4] uint8 (4-byte aligned: written as one uint32 per cell).
+ * Argument errors (<0, before any launch): a null pointer, n < 0, seq0 < 0 or seq0 + n > 2^32, gsd <= 0 or not finite,
+ * x0 / y_top / z_ref not finite, W or H <= 0 or W H > ADAMVS_DSM_MAX_CELLS, a mode other than the two below, min_count < 1.
+ * n = 0 is valid and launches nothing. */
+#define ADAMVS_DSM_MAX 0
+#define ADAMVS_DSM_MEAN 1
+#define ADAMVS_DSM_MAX_CELLS (1 << 28)
+
+typedef struct {
+  double x0, y_top, gsd, z_ref;
+  int W, H;
+} adamvs_dsm_grid;
+
+int adamvs_dsm_accumulate(const adamvs_dsm_grid* grid, const double* xyz, long n, long seq0, int mode, unsigned long long* key,
+                          unsigned* count, long long* sum, void* stream);
+int adamvs_dsm_claim(const adamvs_dsm_grid* grid, const double* xyz, const unsigned char* rgb, long n, long seq0,
+                     const unsigned long long* key, unsigned* color, void* stream);
+int adamvs_dsm_finalize(const adamvs_dsm_grid* grid, const unsigned long long* key, const unsigned* count, const long long* sum,
+                        const unsigned* color, int mode, int min_count, float* dsm, unsigned short* count16, unsigned char* rgba,
+                        void* stream);
 
 #ifdef __cplusplus
 }
