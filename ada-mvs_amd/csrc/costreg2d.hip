@@ -1352,12 +1352,10 @@ int launch_cost_reg_net_2d(const float* x, const float* wpk, float* ws, float* s
 }
 
 template <int NQ>
-static void launch_softmax_nq(const float* score, const PlaneSrc& planes, float* vw, float* pd, int B, int D, int hw, size_t npix, int Dp,
-                              hipStream_t st) {
-  static const int capacity = resident_blocks(k_softmax_regress<NQ>, 256, 0);     // once per instantiation
-  const size_t nblk = (npix + 15) / 16;
-  hipLaunchKernelGGL(k_softmax_regress<NQ>, dim3((unsigned)(nblk < (size_t)capacity ? nblk : (size_t)capacity)), dim3(256), 0, st, score,
-                     planes, vw, pd, B, D, hw, npix, Dp);
+static int launch_softmax_nq(const float* score, const PlaneSrc& planes, float* vw, float* pd, int B, int D, int hw, size_t npix, int Dp,
+                             hipStream_t st) {
+  return launch_resident<k_softmax_regress<NQ>>((long)((npix + 15) / 16), 0, st, "softmax_regress", score, planes, vw, pd, B, D, hw,
+                                                npix, Dp);
 }
 
 int launch_softmax_regress(const float* score, PlaneSrc planes, float* vw, float* pd, int S, int B, int D, int h, int w,
@@ -1366,16 +1364,14 @@ int launch_softmax_regress(const float* score, PlaneSrc planes, float* vw, float
   const int Dp = n_planes > 0 ? n_planes : D;
   ADAMVS_CHECK_ARG(Dp <= D, "softmax_regress: %d planes for %d score channels", Dp, D);
   switch ((D + 63) / 64) {
-    case 1: launch_softmax_nq<1>(score, planes, vw, pd, B, D, h * w, npix, Dp, st); break;
-    case 2: launch_softmax_nq<2>(score, planes, vw, pd, B, D, h * w, npix, Dp, st); break;
-    case 3: launch_softmax_nq<3>(score, planes, vw, pd, B, D, h * w, npix, Dp, st); break;
-    case 4: launch_softmax_nq<4>(score, planes, vw, pd, B, D, h * w, npix, Dp, st); break;
-    case 6: launch_softmax_nq<6>(score, planes, vw, pd, B, D, h * w, npix, Dp, st); break;
-    case 8: launch_softmax_nq<8>(score, planes, vw, pd, B, D, h * w, npix, Dp, st); break;
-    default: launch_softmax_nq<0>(score, planes, vw, pd, B, D, h * w, npix, Dp, st); break;
+    case 1: return launch_softmax_nq<1>(score, planes, vw, pd, B, D, h * w, npix, Dp, st);
+    case 2: return launch_softmax_nq<2>(score, planes, vw, pd, B, D, h * w, npix, Dp, st);
+    case 3: return launch_softmax_nq<3>(score, planes, vw, pd, B, D, h * w, npix, Dp, st);
+    case 4: return launch_softmax_nq<4>(score, planes, vw, pd, B, D, h * w, npix, Dp, st);
+    case 6: return launch_softmax_nq<6>(score, planes, vw, pd, B, D, h * w, npix, Dp, st);
+    case 8: return launch_softmax_nq<8>(score, planes, vw, pd, B, D, h * w, npix, Dp, st);
+    default: return launch_softmax_nq<0>(score, planes, vw, pd, B, D, h * w, npix, Dp, st);
   }
-  ADAMVS_CHECK_LAUNCH("softmax_regress");
-  return 0;
 }
 
 }  // namespace adamvs

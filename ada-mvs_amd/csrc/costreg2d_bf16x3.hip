@@ -13,6 +13,7 @@
 #include "common.h"
 #include "costreg_softmax.h"
 #include "kernels.h"
+#include "persistent.h"
 
 namespace adamvs {
 
@@ -231,13 +232,9 @@ __global__ __launch_bounds__(256, (MODE == BX_S2 || (MT == 4 && WM == 4)) ? 1 : 
 template <int MT, int WM, int MODE, bool SM = false>
 static int launch_bx3_mode(const ConvDDArgs16& a, dim3 grid, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * BxGeom<MODE>::LR * BxGeom<MODE>::LC * BX_PIX * sizeof(__bf16);
-  auto kern = k_conv_dd_bx3<MT, WM, MODE, SM>;
-  static bool attr_set = false;          // idempotent per-kernel attribute (not a stream operation)
-  if (lds > 64 * 1024 && !attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return set_error((int)e, "conv_dd_bf16x3: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  constexpr auto kern = k_conv_dd_bx3<MT, WM, MODE, SM>;
+  int capacity;                          // unused: the grid is the tiling, not capacity-bound; the call sets the LDS limit
+  if (int rc = resident_capacity<kern>(lds, "conv_dd_bf16x3", &capacity)) return rc;
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
   ADAMVS_CHECK_LAUNCH("conv_dd_bf16x3");
   return 0;

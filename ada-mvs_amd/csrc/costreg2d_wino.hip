@@ -377,14 +377,10 @@ __global__ __launch_bounds__(256, WPS) void k_conv_wino(WinoArgs a, TileGrid tg,
 template <int MT, int NT, int WPS, bool SM = false>
 static int launch_wino_cfg(const WinoArgs& a, int N, hipStream_t st) {
   const int groups = a.D / (16 * MT);
-  auto kern = k_conv_wino<MT, NT, WPS, SM>;
-  static const int capacity = resident_blocks(kern, 256, 0);       // once per instantiation, thread-safely (magic static)
   TileGrid tg;
   if (int rc = make_tile_grid(tg, groups * cdiv(a.w, 32), cdiv(a.h, 2 * NT), N)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, a, tg, groups, (unsigned)(((1ull << 32) + groups - 1) / groups));
-  ADAMVS_CHECK_LAUNCH("conv_wino");
-  return 0;
+  return launch_resident<k_conv_wino<MT, NT, WPS, SM>>(tg.ntiles, 0, st, "conv_wino", a, tg, groups,
+                                                       (unsigned)(((1ull << 32) + groups - 1) / groups));
 }
 
 bool wino_depth_supported(int D) { return D >= 64 && D <= 512 && D % 64 == 0; }       // channel groups of 64; 16-channel LDS chunks

@@ -433,15 +433,11 @@ __global__ __launch_bounds__(256) void k_conv0_fused(Conv0Args a, TileGrid tg) {
 struct ViewOrder { int B, V, n0; };      // how the N images of a launch are found in `imgs` (Conv0Args)
 static int launch_conv0_fused(const float* imgs, const adamvs_fconv_weights& c00, const adamvs_fconv_weights& c01, float* out, int N,
                               int H, int W, ViewOrder vo, hipStream_t st) {
-  static const int capacity = resident_blocks(k_conv0_fused, 256, 0);
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(W, 14), cdiv(H, 8), N)) return rc;
   if ((size_t)H * W * 4 * 3 >= 0x7fffffffu) return set_error(-1, "feature net conv0: image too large for 32-bit plane offsets (%d x %d)", H, W);
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
   Conv0Args a{imgs, c00.w, c00.b, c01.w, c01.b, out, H, W, vo.B, vo.V, vo.n0};
-  hipLaunchKernelGGL(k_conv0_fused, dim3(grid), dim3(256), 0, st, a, tg);
-  ADAMVS_CHECK_LAUNCH("feature net conv0 (fused)");
-  return 0;
+  return launch_resident<k_conv0_fused>(tg.ntiles, 0, st, "feature net conv0 (fused)", a, tg);
 }
 
 // deconv2.conv (reference models/module.py:506-524, DeConv2dFuse: 3x3 on cat(deconv output, skip), 16 -> 8, BN, ReLU) at full
@@ -455,15 +451,11 @@ __global__ __launch_bounds__(256) void k_fconv_pair_two_row(SmallConvArgs a, Til
 
 static int launch_pair_two_row(const float* srcA, const float* srcB, const adamvs_fconv_weights& w, float* out, int N, int h, int wd,
                                hipStream_t st) {
-  constexpr size_t lds = TwoRowPairRole<TR_BIAS_RELU>::LDS_BYTES;
-  static const int capacity = resident_blocks(k_fconv_pair_two_row, 256, lds);
   SmallConvArgs a{srcA, srcB, w.w, w.b, out, nullptr, h, wd, h, wd, 8, nullptr};
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(wd, 16), cdiv(h, 8), N)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(k_fconv_pair_two_row, dim3(grid), dim3(256), lds, st, a, tg);
-  ADAMVS_CHECK_LAUNCH("feature net deconv2.conv (two-row)");
-  return 0;
+  return launch_resident<k_fconv_pair_two_row>(tg.ntiles, TwoRowPairRole<TR_BIAS_RELU>::LDS_BYTES, st, "feature net deconv2.conv (two-row)",
+                                               a, tg);
 }
 
 // ---------------------------------------------------------------------------
@@ -642,14 +634,10 @@ static int launch_fconv_f23(const FConvArgs& a, int N, hipStream_t st, const cha
   constexpr int G = (CA + CB) / 4, NPIX = 6 * 34;
   constexpr size_t lds = (size_t)G * group_pitch(plane_pitch16(NPIX), G) * sizeof(float);
   static_assert(lds <= 64 * 1024, "tile exceeds the default dynamic LDS limit");
-  auto kern = k_fconv_f23<CA, CB, NT, EPI>;
-  static const int capacity = resident_blocks(kern, 256, lds);      // once per instantiation, thread-safely (magic static)
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(a.wo, 32), cdiv(a.ho, 4), N)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, tg);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error((int)e, "feature_net0 %s (F(2,3) along x): %s", name, hipGetErrorString(e));
+  if (int rc = launch_resident<k_fconv_f23<CA, CB, NT, EPI>>(tg.ntiles, lds, st, name, a, tg))
+    return set_error(rc, "feature_net0 %s (F(2,3) along x): %s", name, hipGetErrorString((hipError_t)rc));
   return 0;
 }
 
@@ -672,20 +660,13 @@ static int launch_fconv(const FConvArgs& a_in, int N, hipStream_t st, const char
   if (int rc = make_tile_grid(tg, cdiv(a.wo, 16), cdiv(a.ho, 4), N)) return rc;
   if constexpr (GM::T && NT == 1) {
     if (a.cout <= 8 && fconv_f23()) {      // (the same switch: ADAMVS_FCONV_F23=0 = rounds 2 - 4)
-      auto kp = k_fconv<CA, CB, NT, MODE, EPI, true>;
-      static const int cap8 = resident_blocks(kp, 256, lds);
-      hipLaunchKernelGGL(kp, dim3(tg.ntiles < cap8 ? tg.ntiles : cap8), dim3(256), lds, st, a, tg);
-      hipError_t e8 = hipGetLastError();
-      if (e8 != hipSuccess) return set_error((int)e8, "feature_net0 %s (paired classes): %s", name, hipGetErrorString(e8));
+      if (int rc = launch_resident<k_fconv<CA, CB, NT, MODE, EPI, true>>(tg.ntiles, lds, st, name, a, tg))
+        return set_error(rc, "feature_net0 %s (paired classes): %s", name, hipGetErrorString((hipError_t)rc));
       return 0;
     }
   }
-  auto kern = k_fconv<CA, CB, NT, MODE, EPI>;
-  static const int capacity = resident_blocks(kern, 256, lds);      // once per instantiation, thread-safely (magic static)
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, tg);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error((int)e, "feature_net0 %s: %s", name, hipGetErrorString(e));
+  if (int rc = launch_resident<k_fconv<CA, CB, NT, MODE, EPI>>(tg.ntiles, lds, st, name, a, tg))
+    return set_error(rc, "feature_net0 %s: %s", name, hipGetErrorString((hipError_t)rc));
   return 0;
 }
 

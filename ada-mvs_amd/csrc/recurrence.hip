@@ -116,16 +116,13 @@ template <class R0, class R1, class R2>
 static int launch_slot(const RoleUse<R0>& u0, const RoleUse<R1>& u1, const RoleUse<R2>& u2, int B, hipStream_t st, const char* name) {
   constexpr size_t lds = max3(R0::LDS_BYTES, R1::LDS_BYTES, R2::LDS_BYTES);
   static_assert(lds <= 160 * 1024, "slot exceeds the LDS of a CU");
-  auto kern = k_slot<R0, R1, R2>;
-  static const int capacity = [&] {                                  // per instantiation; once, thread-safely (magic static)
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return resident_blocks(kern, 256, lds);
-  }();
+  constexpr auto kern = k_slot<R0, R1, R2>;
+  int capacity, rc;
+  if ((rc = resident_capacity<kern>(lds, name, &capacity))) return rc;
   SlotArgs<R0, R1, R2> s;
   memset(&s, 0, sizeof(s));
   long tiles[3] = {0, 0, 0};
   double work[3] = {0, 0, 0};
-  int rc;
   auto prep = [&](auto* args, auto& dst_args, TileGrid& g, TileRange& r, float cost, float f0, float f1, int i, auto role) -> int {
     typedef decltype(role) R;
     if (!args) return 0;
@@ -147,8 +144,7 @@ static int launch_slot(const RoleUse<R0>& u0, const RoleUse<R1>& u1, const RoleU
   s.n0 = n[0];
   s.n1 = n[1];
   hipLaunchKernelGGL(kern, dim3(n[0] + n[1] + n[2]), dim3(256), lds, st, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error((int)e, "%s: %s", name, hipGetErrorString(e));
+  ADAMVS_CHECK_LAUNCH(name);
   return 0;
 }
 
@@ -181,13 +177,13 @@ static int launch_slot4(const RoleUse<R0>& u0, const RoleUse<R1>& u1, const Role
                         const char* name) {
   constexpr size_t lds = max4(R0::LDS_BYTES, R1::LDS_BYTES, R2::LDS_BYTES, R3::LDS_BYTES);
   static_assert(lds <= 64 * 1024, "slot exceeds the default dynamic LDS limit");
-  auto kern = k_slot4<R0, R1, R2, R3>;
-  static const int capacity = resident_blocks(kern, 256, lds);
+  constexpr auto kern = k_slot4<R0, R1, R2, R3>;
+  int capacity, rc;
+  if ((rc = resident_capacity<kern>(lds, name, &capacity))) return rc;
   SlotArgs4<R0, R1, R2, R3> s;
   memset(&s, 0, sizeof(s));
   long tiles[4] = {0, 0, 0, 0};
   double work[4] = {0, 0, 0, 0};
-  int rc;
   auto prep = [&](auto* args, auto& dst_args, TileGrid& g, TileRange& r, float cost, float f0, float f1, int i, auto role) -> int {
     typedef decltype(role) R;
     if (!args) return 0;
@@ -209,8 +205,7 @@ static int launch_slot4(const RoleUse<R0>& u0, const RoleUse<R1>& u1, const Role
   split_grid<4>((int)(all < capacity ? all : capacity), tiles, work, n);
   s.n0 = n[0]; s.n1 = n[1]; s.n2 = n[2];
   hipLaunchKernelGGL(kern, dim3(n[0] + n[1] + n[2] + n[3]), dim3(256), lds, st, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error((int)e, "%s: %s", name, hipGetErrorString(e));
+  ADAMVS_CHECK_LAUNCH(name);
   return 0;
 }
 

@@ -108,33 +108,17 @@ static int launch_small_shape(const SmallConvArgs& a, int B, hipStream_t st, con
   constexpr int PLANE = (STRIDE == 1) ? plane_pitch16(LR * LC) : ((LR * LC) | 1);
   constexpr size_t lds = (size_t)((CA + CB) / 4) * group_pitch(PLANE, (CA + CB) / 4) * sizeof(float);
   static_assert(lds <= 64 * 1024, "tile exceeds the default dynamic LDS limit");
-  auto kern = k_conv_small<CA, CB, NT, STRIDE, EPI, TR, RW>;
-  static const int capacity = resident_blocks(kern, 256, lds);      // once per instantiation, thread-safely (magic static)
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(a.wo, TC), cdiv(a.ho, TR), B)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, tg);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error((int)e, "%s: %s", name, hipGetErrorString(e));
-  return 0;
+  return launch_resident<k_conv_small<CA, CB, NT, STRIDE, EPI, TR, RW>>(tg.ntiles, lds, st, name, a, tg);
 }
 
 template <int CA, int CB, int NT, int EPI>
 static int launch_small_wino(const SmallConvArgs& a, int B, hipStream_t st, const char* name) {
   typedef ConvWinoRole<CA, CB, NT, EPI> Role;
-  constexpr size_t lds = Role::LDS_BYTES;
-  auto kern = k_conv_small_wino<CA, CB, NT, EPI>;
-  static const int capacity = [&] {                      // once per instantiation, thread-safely (magic static)
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return resident_blocks(kern, 256, lds);
-  }();
   TileGrid tg;
   if (int rc = make_tile_grid(tg, Role::tiles_x(a), Role::tiles_y(a), B)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, tg);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error((int)e, "%s: %s", name, hipGetErrorString(e));
-  return 0;
+  return launch_resident<k_conv_small_wino<CA, CB, NT, EPI>>(tg.ntiles, Role::LDS_BYTES, st, name, a, tg);
 }
 
 // option gru_wino: bit mask of the GRU convolutions that run in the F(2x2, 3x3) form when a role has a launch of its own
@@ -261,13 +245,9 @@ __global__ __launch_bounds__(256) void k_conv1_two_row(const float* __restrict__
 static int launch_cand1_two_row(const SmallConvArgs& a, int B, hipStream_t st) {
   constexpr int G = 4;
   constexpr size_t lds = (size_t)G * group_pitch(plane_pitch16(10 * 18), G) * sizeof(float);
-  static const int capacity = resident_blocks(k_cand1_two_row, 256, lds);      // once per instantiation, thread-safely (magic static)
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(a.wo, 16), cdiv(a.ho, 8), B)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(k_cand1_two_row, dim3(grid), dim3(256), lds, st, a, tg);
-  ADAMVS_CHECK_LAUNCH("cand1 (two-row)");
-  return 0;
+  return launch_resident<k_cand1_two_row>(tg.ntiles, lds, st, "cand1 (two-row)", a, tg);
 }
 
 // The same convolution for wide inputs (C = 32) with the contraction split over the waves.  Held in full, the
@@ -700,14 +680,9 @@ template <int C>
 static int launch_conv1_f23_rows(const float* cost, const float* w, float* c1, int N, int h, int w_, hipStream_t st) {
   constexpr int G = C / 4;
   constexpr size_t lds = (size_t)G * ((group_pitch(plane_pitch16(10 * 34), G) + 1) & ~1) * sizeof(float);
-  auto kern = k_conv1_f23_rows<C>;
-  static const int capacity = resident_blocks(kern, 256, lds);      // once per instantiation, thread-safely (magic static)
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(w_, 32), cdiv(h, 8), N)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, cost, w, c1, h, w_, tg);
-  ADAMVS_CHECK_LAUNCH("conv1 (F(2,3) along x)");
-  return 0;
+  return launch_resident<k_conv1_f23_rows<C>>(tg.ntiles, lds, st, "conv1 (F(2,3) along x)", cost, w, c1, h, w_, tg);
 }
 
 // option conv1_f23: bit 1 = C = 32 (stage 1), bit 2 = C = 16 / 8 (stages 2, 3) in the F(2, 3)-along-x form; 0 = k_conv1_ksplit /
@@ -718,54 +693,33 @@ static int launch_conv1_f23_32(const float* cost, const float* w, float* c1, int
   constexpr int C = 32;
   constexpr size_t lds = ((size_t)(C / 4) * group_pitch(plane_pitch16(10 * 34), C / 4) + 4 * 2 * 64 * 4) * sizeof(float);
   static_assert(lds <= 64 * 1024, "default dynamic LDS limit");
-  auto kern = k_conv1_f23<C>;
-  static const int capacity = resident_blocks(kern, 256, lds);      // once per instantiation, thread-safely (magic static)
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(w_, 32), cdiv(h, 8), N)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, cost, w, c1, h, w_, tg);
-  ADAMVS_CHECK_LAUNCH("conv1 (F(2,3) along x)");
-  return 0;
+  return launch_resident<k_conv1_f23<C>>(tg.ntiles, lds, st, "conv1 (F(2,3) along x)", cost, w, c1, h, w_, tg);
 }
 
 static int launch_conv1_ksplit32(const float* cost, const float* w, float* c1, int N, int h, int w_, hipStream_t st) {
   constexpr int C = 32;
   constexpr size_t lds = ((size_t)(C / 4) * group_pitch(plane_pitch16(10 * 18), C / 4) + 12 * 64 * 4) * sizeof(float);
-  auto kern = k_conv1_ksplit<C>;
-  static const int capacity = resident_blocks(kern, 256, lds);      // once per instantiation, thread-safely (magic static)
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(w_, 16), cdiv(h, 8), N)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, cost, w, c1, h, w_, tg);
-  ADAMVS_CHECK_LAUNCH("conv1");
-  return 0;
+  return launch_resident<k_conv1_ksplit<C>>(tg.ntiles, lds, st, "conv1", cost, w, c1, h, w_, tg);
 }
 
 template <int C>
 static int launch_conv1_c(const float* cost, const float* w, float* c1, int N, int h, int w_, hipStream_t st) {
   constexpr size_t lds = (size_t)(C / 4) * group_pitch(plane_pitch16(10 * 18), C / 4) * sizeof(float);
-  auto kern = k_conv1_two_row<C>;
-  static const int capacity = resident_blocks(kern, 256, lds);      // once per instantiation, thread-safely (magic static)
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(w_, 16), cdiv(h, 8), N)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, cost, w, c1, h, w_, tg);
-  ADAMVS_CHECK_LAUNCH("conv1");
-  return 0;
+  return launch_resident<k_conv1_two_row<C>>(tg.ntiles, lds, st, "conv1", cost, w, c1, h, w_, tg);
 }
 
 template <int CA, int CB, int NT>
 static int launch_small_pro(const SmallConvArgs& a, const GruPro& pro, int B, hipStream_t st) {
   typedef ConvSmallRole<CA, CB, NT, 1, EPI_LINEAR, 4, 1> Role;
-  auto kern = k_conv_small_pro<CA, CB, NT>;
-  static const int capacity = resident_blocks(kern, 256, Role::LDS_BYTES);      // once per instantiation, thread-safely
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(a.wo, 16), cdiv(a.ho, 4), B)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), Role::LDS_BYTES, st, a, tg, pro);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error((int)e, "conv_pair (folded): %s", hipGetErrorString(e));
-  return 0;
+  return launch_resident<k_conv_small_pro<CA, CB, NT>>(tg.ntiles, Role::LDS_BYTES, st, "conv_pair (folded)", a, tg, pro);
 }
 
 // out = conv3x3(cat(srcA, srcB)) + bias on compact channel-last maps (the ConvGRUCell2 convolutions of MS-REDNet's two
@@ -856,15 +810,8 @@ int launch_slice_step(const float* c1, const FuseWeights& fw, const StepBuffers&
   TileGrid tg;
   if ((rc = make_tile_grid(tg, cdiv(w, DecoderRole<true>::TCI), cdiv(h, DecoderRole<true>::TRI), B))) return rc;
   constexpr size_t dlds = DecoderRole<true>::LDS_BYTES;
-  if (in_up) {
-    static const int cap_up = resident_blocks(k_decoder<true>, 256, dlds);      // once, thread-safely (magic static)
-    hipLaunchKernelGGL((k_decoder<true>), dim3(tg.ntiles < cap_up ? tg.ntiles : cap_up), dim3(256), dlds, st, da, tg);
-  } else {
-    static const int cap_flat = resident_blocks(k_decoder<false>, 256, dlds);
-    hipLaunchKernelGGL((k_decoder<false>), dim3(tg.ntiles < cap_flat ? tg.ntiles : cap_flat), dim3(256), dlds, st, da, tg);
-  }
-  ADAMVS_CHECK_LAUNCH("decoder");
-  return 0;
+  if (in_up) return launch_resident<k_decoder<true>>(tg.ntiles, dlds, st, "decoder", da, tg);
+  return launch_resident<k_decoder<false>>(tg.ntiles, dlds, st, "decoder", da, tg);
 }
 
 int launch_soft_argmin(const float* vol, const float* planes, float* depth, float* conf, int B, int D, int h, int w,

@@ -33,15 +33,9 @@ static int launch_bx(const SmallConvArgsBx& a, int N, hipStream_t st, const char
   constexpr int LC = (STRIDE == 1) ? TC + 2 : 2 * TC + 1;
   constexpr size_t lds = (size_t)2 * LR * LC * bx_pixel_pitch(CA + CB) * sizeof(__bf16);
   static_assert(lds <= 64 * 1024, "tile exceeds the default dynamic LDS limit");
-  auto kern = k_conv_small_bx3<CA, CB, NT, STRIDE, EPI>;
-  static const int capacity = resident_blocks(kern, 256, lds);      // once per instantiation, thread-safely (magic static)
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(a.wo, TC), cdiv(a.ho, TR), N)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, tg);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error((int)e, "%s: %s", name, hipGetErrorString(e));
-  return 0;
+  return launch_resident<k_conv_small_bx3<CA, CB, NT, STRIDE, EPI>>(tg.ntiles, lds, st, name, a, tg);
 }
 
 int launch_conv1_bf16x3(const float* cost, const float* w, float* c1, int N, int C, int h, int w_, hipStream_t st) {
@@ -58,27 +52,16 @@ __global__ __launch_bounds__(256, 2) void k_gru2_fused_bx3(Gru2Args a, TileGrid 
 }
 
 static int launch_gru2_fused(const Gru2Args& a, int B, hipStream_t st) {
-  constexpr size_t lds = Gru2FusedBx3Role::LDS_BYTES;
-  static const int capacity = resident_blocks(k_gru2_fused_bx3, 256, lds);      // once per instantiation, thread-safely (magic static)
   TileGrid tg;
   if (int rc = make_tile_grid(tg, Gru2FusedBx3Role::tiles_x(a), Gru2FusedBx3Role::tiles_y(a), B)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(k_gru2_fused_bx3, dim3(grid), dim3(256), lds, st, a, tg);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error((int)e, "gru2 fused (bf16x3): %s", hipGetErrorString(e));
-  return 0;
+  return launch_resident<k_gru2_fused_bx3>(tg.ntiles, Gru2FusedBx3Role::LDS_BYTES, st, "gru2 fused (bf16x3)", a, tg);
 }
 
 static int launch_gru1_fused(const Gru1Args& a, int B, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * 12 * 34 * 32 + 10 * 32 * 32;
-  static const int capacity = resident_blocks(k_gru1_fused_bx3, 256, lds);      // once per instantiation, thread-safely (magic static)
   TileGrid tg;
   if (int rc = make_tile_grid(tg, cdiv(a.w, 30), cdiv(a.h, 8), B)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(k_gru1_fused_bx3, dim3(grid), dim3(256), lds, st, a, tg);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error((int)e, "gru1 fused (bf16x3): %s", hipGetErrorString(e));
-  return 0;
+  return launch_resident<k_gru1_fused_bx3>(tg.ntiles, lds, st, "gru1 fused (bf16x3)", a, tg);
 }
 
 // GRU level 1 (fused) / conv2 / GRU level 2 (fused) of one recurrent step (the decoder stays on the fp32 path).

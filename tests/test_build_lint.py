@@ -6,6 +6,7 @@ group on the last tile of every workgroup -- small enough to pass a loose tolera
 checked, on CPU, every time the suite runs.
 """
 import os
+import re
 import subprocess
 import sys
 
@@ -18,3 +19,20 @@ def test_no_mfma_read_after_write_hazard_in_built_library():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "mfma_hazard_lint.py"), lib], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert "0 hazards" in r.stdout
+
+
+def test_persistent_grids_are_sized_in_persistent_h_only():
+    """Persistent launches size their grid through csrc/persistent.h (resident_capacity / launch_resident), which caches the
+    resident capacity and raises the dynamic-LDS limit per device.  The raw queries appear nowhere else, and no launcher keeps
+    a per-process capacity or attribute flag of its own: one process may drive several devices (nn.DataParallel)."""
+    csrc = os.path.join(ROOT, "ada-mvs_amd", "csrc")
+    raw = ("resident_blocks(", "hipOccupancyMaxActiveBlocksPerMultiprocessor", "hipFuncSetAttribute")
+    local_static = re.compile(r"^[ \t]+static\s+(?:const\s+)?\w+\s+(\w*(?:cap|attr)\w*)", re.M)
+    bad = []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")) or f == "persistent.h":
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        bad += ["%s: %s" % (f, r) for r in raw if r in src]
+        bad += ["%s: static %s" % (f, m.group(1)) for m in local_static.finditer(src)]
+    assert not bad, "grid sizing outside persistent.h:\n" + "\n".join(bad)

@@ -586,6 +586,19 @@ def test_data_parallel_wrapper_and_module_prefixed_checkpoint(hip):
         out = dp(dev(imgs), {k: dev(v) for k, v in proj.items()}, dev(dv))
     g = load_golden("e2e_tiny")
     assert rel_l1(out["depth"], g["depth"]) < NORTH_STAR_TOL
+    # One tile per device, one thread per device, in one process: each device sizes its persistent grids and raises the
+    # dynamic-LDS limit for itself (csrc/persistent.h).  cuda:0 runs first: a per-process cache would hand its values on.
+    n = torch.cuda.device_count()
+    if n < 2:
+        return
+    imgs, proj, dv = synth.tile_inputs("tiny", batch=n, seed=1)
+    for precision in ("fp32", "bf16x3"):
+        m.set_precision(precision)
+        with torch.no_grad():
+            one = m(dev(imgs), {k: dev(v) for k, v in proj.items()}, dev(dv))
+            many = dp(dev(imgs), {k: dev(v) for k, v in proj.items()}, dev(dv))
+        for key in ("depth", "photometric_confidence"):
+            assert torch.equal(many[key], one[key]), (precision, key)
 
 
 def test_batch_of_tiles_matches_single_tiles(hip, O):
