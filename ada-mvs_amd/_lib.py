@@ -69,6 +69,13 @@ class DsmGrid(ctypes.Structure):
                 ("W", ctypes.c_int), ("H", ctypes.c_int)]
 
 
+class DsmFillStats(ctypes.Structure):
+    """adamvs_dsm_fill_stats"""
+    _fields_ = [("cycles", ctypes.c_int), ("converged", ctypes.c_int), ("residual_height", ctypes.c_double),
+                ("residual_colour", ctypes.c_double), ("cells_valid", ctypes.c_long), ("cells_filled", ctypes.c_long),
+                ("cells_empty", ctypes.c_long)]
+
+
 # name -> (restype, argtypes); every symbol include/adamvs_hip.h declares
 SIGNATURES = {
     "adamvs_version": (c_i, []),
@@ -140,14 +147,19 @@ SIGNATURES = {
                                ctypes.c_void_p, c_st]),
     "adamvs_dsm_finalize": (c_i, [ctypes.POINTER(DsmGrid), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, c_i,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_dsm_fill_workspace_bytes": (ctypes.c_long, [c_i, c_i]),
+    "adamvs_dsm_fill": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i,
+                              ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                              ctypes.POINTER(DsmFillStats), c_st]),
 }
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 PRECISIONS = {"fp32": 0, "bf16x3": 1}
 PLANES_EXPLICIT, PLANES_UNIFORM, PLANES_WINDOW = 0, 1, 2
 FUSION_TILE = 256                # ADAMVS_FUSION_TILE: pixels per workgroup of the fusion kernels
 DSM_MAX, DSM_MEAN = 0, 1         # ADAMVS_DSM_MAX / ADAMVS_DSM_MEAN
 DSM_MAX_CELLS = 1 << 28          # ADAMVS_DSM_MAX_CELLS
+DSM_FILL_MAX_RADIUS = 1024       # ADAMVS_DSM_FILL_MAX_RADIUS
 PHASE_VIEW_WEIGHTS, PHASE_AGGREGATE, PHASE_RECURRENCE, PHASE_SOFT_ARGMIN, PHASE_ALL = 1, 2, 4, 8, 15
 _lib = None
 

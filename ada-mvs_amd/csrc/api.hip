@@ -442,3 +442,31 @@ extern "C" int adamvs_dsm_finalize(const adamvs_dsm_grid* grid, const unsigned l
   ADAMVS_CHECK_ARG(key && count && color && dsm && count16 && rgba && (sum || mode == ADAMVS_DSM_MAX), "dsm_finalize: null pointer");
   return launch_dsm_finalize(*grid, key, count, sum, color, mode, min_count, dsm, count16, (unsigned*)rgba, (hipStream_t)stream);
 }
+
+// ---- DSM gap fill (dsm_fill.hip)
+static int dsm_fill_check_size(int W, int H, const char* what) {
+  ADAMVS_CHECK_ARG(W > 0 && H > 0 && (long)W * H <= ADAMVS_DSM_MAX_CELLS, "%s: grid W=%d H=%d (W H <= %d cells)", what, W, H,
+                   ADAMVS_DSM_MAX_CELLS);
+  return 0;
+}
+
+extern "C" long adamvs_dsm_fill_workspace_bytes(int W, int H) {
+  if (int rc = dsm_fill_check_size(W, H, "dsm_fill_workspace_bytes")) return rc;
+  return dsm_fill_workspace_bytes(W, H);
+}
+
+extern "C" int adamvs_dsm_fill(int W, int H, const float* dsm, const unsigned char* rgba, double r_cells, double tol_height,
+                               double tol_colour, int max_cycles, void* workspace, long workspace_bytes, float* dsm_out,
+                               unsigned char* rgba_out, int* dist2, unsigned char* filled, adamvs_dsm_fill_stats* stats, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "dsm_fill")) return rc;
+  ADAMVS_CHECK_ARG(dsm && rgba && workspace && dsm_out && rgba_out && dist2 && filled && stats, "dsm_fill: null pointer");
+  ADAMVS_CHECK_ARG(std::isfinite(r_cells) && r_cells > 0.0 && r_cells <= ADAMVS_DSM_FILL_MAX_RADIUS,
+                   "dsm_fill: r_cells=%g must be finite, > 0 and <= %d", r_cells, ADAMVS_DSM_FILL_MAX_RADIUS);
+  ADAMVS_CHECK_ARG(std::isfinite(tol_height) && tol_height > 0.0, "dsm_fill: tol_height=%g must be finite and > 0", tol_height);
+  ADAMVS_CHECK_ARG(std::isfinite(tol_colour) && tol_colour > 0.0, "dsm_fill: tol_colour=%g must be finite and > 0", tol_colour);
+  ADAMVS_CHECK_ARG(max_cycles >= 1, "dsm_fill: max_cycles=%d (>= 1)", max_cycles);
+  const long need = dsm_fill_workspace_bytes(W, H);
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "dsm_fill: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  return launch_dsm_fill(W, H, dsm, rgba, r_cells, tol_height, tol_colour, max_cycles, workspace, dsm_out, rgba_out, dist2, filled,
+                         stats, (hipStream_t)stream);
+}

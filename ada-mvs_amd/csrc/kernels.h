@@ -156,4 +156,10 @@ int launch_dsm_claim(const adamvs_dsm_grid& g, const double* xyz, const uint8_t*
 int launch_dsm_finalize(const adamvs_dsm_grid& g, const unsigned long long* key, const unsigned* count, const long long* sum,
                         const unsigned* color, int mode, int min_count, float* dsm, uint16_t* count16, unsigned* rgba, hipStream_t st);
 
+// dsm_fill.hip: bounded harmonic gap fill of a finalised DSM (include/adamvs_hip.h, "DSM gap fill")
+long dsm_fill_workspace_bytes(int W, int H);
+int launch_dsm_fill(int W, int H, const float* dsm, const uint8_t* rgba, double r_cells, double tol_height, double tol_colour,
+                    int max_cycles, void* workspace, float* dsm_out, uint8_t* rgba_out, int* dist2, uint8_t* filled,
+                    adamvs_dsm_fill_stats* stats, hipStream_t st);
+
 }  // namespace adamvs

@@ -1,13 +1,16 @@
 """Rasterisation of a fused point cloud into a digital surface model (DSM) and a true orthophoto.
 
     python dsm_whu.py --ply /out/predict/fused.ply --gsd 0.25 --out /out/predict/dsm [--mode max|mean] [--min_count 1]
-                      [--bounds XMIN YMIN XMAX YMAX] [--chunk N]
+                      [--bounds XMIN YMIN XMAX YMAX] [--chunk N] [--fill_max_dist METRES]
 
 The step after fuse_whu.py.  The PLY is streamed twice in chunks through a memory map (the cloud is never held in host
 memory): the first pass finds the bounds of the finite points on the GPU (torch aminmax; min and max are exact), the second
 scatters every chunk into the cell state on the GPU (csrc/dsm.hip; include/adamvs_hip.h "DSM" states the semantics).
 Written: `<out>_dsm.tif` (float32 heights, NaN where empty), `<out>_count.tif` (uint16 points per cell, saturating),
 `<out>_ortho.png` (RGBA, alpha 0 where empty), ESRI world files next to each image (`.tfw` / `.pgw`) and `<out>_dsm.json`.
+
+With --fill_max_dist, the empty cells within that distance of a filled one are filled on the GPU by bounded harmonic
+interpolation (fill_gaps; csrc/dsm_fill.hip, include/adamvs_hip.h "DSM gap fill"), and fill_output_paths(out) are written too.
 
 World axes are x east, y north, z up.  Row 0 of every raster is the northern edge (y_top); column 0 the western (x0).
 """
@@ -26,6 +29,8 @@ from .fusion import PLY_DTYPE
 MODES = {"max": 0, "mean": 1}                       # ADAMVS_DSM_MAX / ADAMVS_DSM_MEAN
 MAX_CELLS = 1 << 28                                 # ADAMVS_DSM_MAX_CELLS
 MAX_POINTS = (1 << 32) - 1                          # sequence numbers are uint32
+FILL_MAX_RADIUS = 1024                              # ADAMVS_DSM_FILL_MAX_RADIUS, cells
+FILL_MAX_CYCLES = 200
 # device bytes per cell: key 8 + count 4 + colour 4 (+ sum 8 in mean mode) of state, dsm 4 + count 2 + rgba 4 of output
 STATE_BYTES = {"max": 16, "mean": 24}
 OUTPUT_BYTES = 10
@@ -172,14 +177,48 @@ def point_bounds(path, chunk, device):
     return lo, hi
 
 
-def from_ply(ply, gsd, mode="max", min_count=1, bounds=None, chunk=1 << 23, device=None, out=None):
+# ---- gap fill -----------------------------------------------------------------------------------------------------------
+class FillNotConverged(RuntimeError):
+    pass
+
+
+def fill_gaps(dsm, rgba, r_cells, tol_height=1e-6, tol_colour=1e-3, max_cycles=FILL_MAX_CYCLES, device=None):
+    """Bounded harmonic fill of the empty cells of finish()'s rasters (host arrays dsm [H, W] float32, rgba [H, W, 4] uint8)
+    within r_cells of a valid cell -> dict(dsm, rgba, filled (uint8, 1 where filled), dist2 (int32), cycles, residual_height,
+    residual_colour, cells_valid, cells_filled, cells_empty, seconds).  Raises FillNotConverged if max_cycles V-cycles do not
+    bring the largest residual under the tolerances."""
+    import torch
+    from . import hip_ops
+    r = float(r_cells)
+    if not (math.isfinite(r) and 0.0 < r <= FILL_MAX_RADIUS):
+        raise ValueError("fill radius %r cells: must be finite, > 0 and <= %d" % (r_cells, FILL_MAX_RADIUS))
+    dev = torch.device(device if device is not None else "cuda")
+    d = torch.from_numpy(np.ascontiguousarray(dsm, np.float32)).to(dev)
+    c = torch.from_numpy(np.ascontiguousarray(rgba, np.uint8)).to(dev)
+    torch.cuda.synchronize(dev)
+    t0 = time.time()
+    d2, c2, dist2, filled, st = hip_ops.dsm_fill(d, c, r, tol_height, tol_colour, max_cycles)
+    seconds = time.time() - t0
+    if not st.converged:
+        raise FillNotConverged("gap fill did not converge in %d V-cycles: largest residual %.3e m (tolerance %.3e) and %.3e colour "
+                               "levels (tolerance %.3e)" % (st.cycles, st.residual_height, tol_height, st.residual_colour, tol_colour))
+    return dict(dsm=d2.cpu().numpy(), rgba=c2.cpu().numpy(), filled=filled.cpu().numpy(), dist2=dist2.cpu().numpy(), cycles=st.cycles,
+                residual_height=st.residual_height, residual_colour=st.residual_colour, cells_valid=st.cells_valid,
+                cells_filled=st.cells_filled, cells_empty=st.cells_empty, seconds=seconds)
+
+
+def from_ply(ply, gsd, mode="max", min_count=1, bounds=None, chunk=1 << 23, device=None, out=None, fill_max_dist=None):
     """Two passes over the PLY (bounds, raster) -> DsmBuilder.finish()'s dict; written to `out` (a path prefix) if given.
-    bounds: (xmin, ymin, xmax, ymax) crops the grid; z_ref = floor of the lowest finite z either way."""
+    bounds: (xmin, ymin, xmax, ymax) crops the grid; z_ref = floor of the lowest finite z either way.
+    fill_max_dist (metres): also fill_gaps() at r = fill_max_dist / gsd cells, as res["fill"] (with max_dist, gsd, r_cells),
+    written to fill_output_paths(out)."""
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("dsm: needs an MI355X (there is no CPU fallback for the DSM kernels)")
     device = torch.device(device if device is not None else "cuda")
     gsd = _check_gsd(gsd)
+    if fill_max_dist is not None:
+        fill_r = fill_radius_cells(fill_max_dist, gsd)
     if mode not in MODES:
         raise ValueError("mode %r: one of %s" % (mode, sorted(MODES)))
     if int(min_count) < 1:
@@ -202,13 +241,65 @@ def from_ply(ply, gsd, mode="max", min_count=1, bounds=None, chunk=1 << 23, devi
     res = b.finish(min_count)
     if out is not None:
         write_outputs(out, res)
+    if fill_max_dist is not None:
+        res["fill"] = fill_gaps(res["dsm"], res["rgba"], fill_r, device=device)
+        res["fill"].update(max_dist=float(fill_max_dist), gsd=gsd, r_cells=fill_r)
+        if out is not None:
+            write_fill_outputs(out, res["grid"], res["fill"])
     return res
+
+
+def fill_radius_cells(max_dist, gsd):
+    """--fill_max_dist (metres) -> r in cells (max_dist / gsd), checked against the cap."""
+    m = float(max_dist)
+    r = m / gsd
+    if not (math.isfinite(m) and m > 0.0 and r <= FILL_MAX_RADIUS):
+        raise ValueError("fill_max_dist=%r m at gsd %g is %g cells: must be > 0 and at most %d cells" % (max_dist, gsd, r, FILL_MAX_RADIUS))
+    return r
 
 
 # ---- files --------------------------------------------------------------------------------------------------------------
 def output_paths(out):
     return dict(dsm=out + "_dsm.tif", dsm_world=out + "_dsm.tfw", count=out + "_count.tif", count_world=out + "_count.tfw",
                 ortho=out + "_ortho.png", ortho_world=out + "_ortho.pgw", json=out + "_dsm.json")
+
+
+def fill_output_paths(out):
+    """The files of the gap fill (--fill_max_dist), next to output_paths(out) and disjoint from them."""
+    return dict(dsm=out + "_dsm_filled.tif", dsm_world=out + "_dsm_filled.tfw", ortho=out + "_ortho_filled.png",
+                ortho_world=out + "_ortho_filled.pgw", filled=out + "_filled.png", filled_world=out + "_filled.pgw", json=out + "_fill.json")
+
+
+def fill_summary(fill):
+    return {k: fill[k] for k in ("max_dist", "gsd", "r_cells", "cells_valid", "cells_filled", "cells_empty", "cycles", "residual_height",
+                                 "residual_colour", "seconds")}
+
+
+def write_fill_outputs(out, grid, fill):
+    """fill_gaps()'s rasters (with max_dist, gsd, r_cells added), their world files and the JSON -> fill_output_paths(out)."""
+    from PIL import Image
+    paths = fill_output_paths(out)
+    if os.path.dirname(out):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+    Image.fromarray(np.ascontiguousarray(fill["dsm"], np.float32)).save(paths["dsm"], format="TIFF")
+    Image.fromarray(np.ascontiguousarray(fill["rgba"], np.uint8)).save(paths["ortho"], format="PNG")
+    Image.fromarray(np.where(np.asarray(fill["filled"]) != 0, 255, 0).astype(np.uint8)).save(paths["filled"], format="PNG")
+    wf = world_file_text(grid)
+    for k in ("dsm_world", "ortho_world", "filled_world"):
+        with open(paths[k], "w") as f:
+            f.write(wf)
+    with open(paths["json"], "w") as f:
+        json.dump(fill_summary(fill), f, indent=1)
+        f.write("\n")
+    return paths
+
+
+def read_fill_outputs(out):
+    """-> (dsm float32, rgba uint8, filled uint8 (1 where filled)) read back from the files of write_fill_outputs."""
+    from PIL import Image
+    paths = fill_output_paths(out)
+    return (np.array(Image.open(paths["dsm"]), np.float32), np.array(Image.open(paths["ortho"]).convert("RGBA")),
+            (np.array(Image.open(paths["filled"])) == 255).astype(np.uint8))
 
 
 def summary(res):
@@ -254,6 +345,8 @@ def build_parser():
     ap.add_argument("--min_count", type=int, default=1, help="cells with fewer points are left empty (NaN, alpha 0)")
     ap.add_argument("--bounds", type=float, nargs=4, metavar=("XMIN", "YMIN", "XMAX", "YMAX"), default=None, help="crop to this area")
     ap.add_argument("--chunk", type=int, default=1 << 23, help="points per chunk streamed to the GPU")
+    ap.add_argument("--fill_max_dist", type=float, default=None, metavar="METRES",
+                    help="also fill empty cells within this distance of a filled cell by harmonic interpolation (<out>_dsm_filled.tif, ...)")
     return ap
 
 
@@ -261,10 +354,15 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     print("argv:", sys.argv[1:] if argv is None else argv)
     t0 = time.time()
-    res = from_ply(args.ply, args.gsd, args.mode, args.min_count, args.bounds, args.chunk, out=args.out)
+    res = from_ply(args.ply, args.gsd, args.mode, args.min_count, args.bounds, args.chunk, out=args.out, fill_max_dist=args.fill_max_dist)
     g = res["grid"]
     print("dsm %d x %d cells at gsd %g (x0 %.3f, y_top %.3f, z_ref %g, %s): %d of %d points used, %d cells filled, total_time = %.3f s"
           % (g.W, g.H, g.gsd, g.x0, g.y_top, g.z_ref, res["mode"], res["points_used"], res["points_read"], res["cells_filled"], time.time() - t0))
+    if "fill" in res:
+        f = res["fill"]
+        print("fill within %g m (%g cells): %d cells filled, %d left empty, %d valid; %d V-cycles, residual %.2e m / %.2e levels, %.3f s"
+              % (f["max_dist"], f["r_cells"], f["cells_filled"], f["cells_empty"], f["cells_valid"], f["cycles"], f["residual_height"],
+                 f["residual_colour"], f["seconds"]))
     return res
 
 

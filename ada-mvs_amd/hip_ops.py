@@ -639,3 +639,29 @@ def dsm_finalize(grid, key, count, sum_, color, mode, min_count):
     check(_lib.load().adamvs_dsm_finalize(ctypes.byref(g), _p(key), _p(count), sp, _p(color), int(mode), int(min_count), _p(dsm),
                                           _p(count16), _p(rgba), _stream()), "dsm_finalize")
     return dsm, count16, rgba
+
+
+def dsm_fill(dsm, rgba, r_cells, tol_height=1e-6, tol_colour=1e-3, max_cycles=200, workspace=None):
+    """adamvs_dsm_fill: bounded harmonic gap fill of a finalised DSM (dsm [H, W] float32, rgba [H, W, 4] uint8, device) ->
+    (dsm_out float32, rgba_out uint8, dist2 [H, W] int32, filled [H, W] uint8, _lib.DsmFillStats).  Blocks until done."""
+    dsm = _dev_as(dsm, "dsm", torch.float32)
+    rgba = _dev_as(rgba, "rgba", torch.uint8)
+    if dsm.dim() != 2:
+        raise _lib.AdaMVSHipError("dsm must be [H, W], got %s" % (tuple(dsm.shape),))
+    H, W = dsm.shape
+    if tuple(rgba.shape) != (H, W, 4):
+        raise _lib.AdaMVSHipError("rgba %s != (%d, %d, 4)" % (tuple(rgba.shape), H, W))
+    lib = _lib.load()
+    need = lib.adamvs_dsm_fill_workspace_bytes(W, H)
+    check(0 if need >= 0 else int(need), "dsm_fill_workspace_bytes")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=dsm.device, dtype=torch.uint8)
+    dsm_out = torch.empty_like(dsm)
+    rgba_out = torch.empty_like(rgba)
+    dist2 = torch.empty(H, W, device=dsm.device, dtype=torch.int32)
+    filled = torch.empty(H, W, device=dsm.device, dtype=torch.uint8)
+    stats = _lib.DsmFillStats()
+    check(lib.adamvs_dsm_fill(W, H, _p(dsm), _p(rgba), float(r_cells), float(tol_height), float(tol_colour), int(max_cycles), _p(workspace),
+                              workspace.numel(), _p(dsm_out), _p(rgba_out), _p(dist2), _p(filled), ctypes.byref(stats), _stream()),
+          "dsm_fill")
+    return dsm_out, rgba_out, dist2, filled, stats

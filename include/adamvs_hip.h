@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ADAMVS_ABI_VERSION 18
+#define ADAMVS_ABI_VERSION 19
 
 int adamvs_version(void);
 const char* adamvs_last_error_string(void);
@@ -545,6 +545,57 @@ int adamvs_dsm_claim(const adamvs_dsm_grid* grid, const double* xyz, const unsig
 int adamvs_dsm_finalize(const adamvs_dsm_grid* grid, const unsigned long long* key, const unsigned* count, const long long* sum,
                         const unsigned* color, int mode, int min_count, float* dsm, unsigned short* count16, unsigned char* rgba,
                         void* stream);
+
+/* ---- DSM gap fill (after _dsm_finalize): bounded harmonic interpolation of the empty cells -----------------------------
+ * ada-mvs_amd/dsm.py fill_gaps(); dsm_whu.py --fill_max_dist METRES (r = max_dist / gsd).
+ * Input: a finalised raster as _dsm_finalize writes it, dsm [H][W] fp32 (NaN where empty) and rgba [H][W][4] uint8, and a
+ * radius r in cells (fp64).  Cells (i, j) are row i, column j; N4(c) are the (up to) 4 edge neighbours of c inside the grid.
+ *   V        the valid cells: dsm finite.
+ *   dist2    int32, the exact squared Euclidean distance in cells to the nearest valid cell, min over (k, l) in V of
+ *            (i - k)^2 + (j - l)^2, wherever (double)dist2 <= r * r; INT32_MAX everywhere else (every cell when V is empty).
+ *            0 on V.
+ *   F        the fillable cells: not in V and (double)dist2 <= r * r.  Every other empty cell stays empty (dsm NaN
+ *            0x7fc00000, rgba 0).
+ *   height   for every c in F:  sum over n in N4(c) & (V | F) of (u_n - u_c) = 0,  u = dsm on V.  Neighbours outside the grid
+ *            or left empty are left out of the sum (zero flux: a Neumann boundary).  Every F cell has a 4-connected path
+ *            through F to V: take its nearest valid cell (k, l); a step from (i, j) that shrinks |i - k| or |j - l| by one
+ *            strictly lowers the squared distance to (k, l), so it lands in V or in a cell whose dist2 is smaller, hence in
+ *            F (or V); repeat.  So every connected component of F touches V (a Dirichlet boundary), the matrix of the system
+ *            (diagonal = the number of neighbours in V | F, -1 per neighbour in F) is symmetric, irreducibly diagonally
+ *            dominant with an M-matrix structure per component, hence positive definite: the solution is unique.  Solved in
+ *            fp64; dsm_out = (float)u on F, and V cells are copied bit for bit (dsm and rgba).
+ *   colour   R, G and B each solve the same equation with the colours of V as boundary values (fp32);
+ *            rgba_out = (uint8)clamp(rint(u), 0, 255) per channel and alpha 255 on F.
+ *   filled   uint8: 1 on F, 0 elsewhere.
+ * Stopping rule: the residual of a cell of F is |left side of the height (colour) equation|.  Multigrid V-cycles run until
+ * the largest residual over F is <= tol_height for the height and <= tol_colour for every colour channel (both checked
+ * after each cycle from an exact integer max reduction: the output is bit-identical from run to run), or until
+ * max_cycles cycles.  stats (a HOST pointer): cycles run, converged (0 when max_cycles ended the solve: the caller must
+ * not take the result as the solution), the largest residuals reached, and the cells in V, in F and left empty.
+ * An empty V or an empty F is valid input: the outputs equal the inputs, cells_filled = 0, converged = 1, cycles = 0.
+ * Kernels (csrc/dsm_fill.hip): the distance in two windowed passes (per column, then per row with the row segment in LDS),
+ * both bounded by R = ceil(r) per cell; multigrid V-cycles with red-black Gauss-Seidel smoothing, levels halved down to
+ * <= 8 x 8 cells (a coarse cell is Dirichlet if a child is, unknown if a child is and none is Dirichlet, excluded otherwise),
+ * the unscaled 5-point operator on every level, cell-centred bilinear prolongation over the coarse cells that are not
+ * excluded and its transpose as restriction.
+ * The call runs on `stream` and blocks: it reads the two residual maxima back once per cycle.
+ * workspace: device memory of at least _dsm_fill_workspace_bytes(W, H) bytes (about 66 bytes per cell), 256-byte aligned.
+ * dsm, rgba, dsm_out, rgba_out (4-byte aligned), dist2, filled: device [H][W]; outputs must not alias the inputs.
+ * Argument errors (<0, before any launch): a null pointer, W or H <= 0 or W H > ADAMVS_DSM_MAX_CELLS, r not finite or <= 0
+ * or > ADAMVS_DSM_FILL_MAX_RADIUS, a tolerance not finite or <= 0, max_cycles < 1, workspace_bytes below the query.
+ * _dsm_fill_workspace_bytes returns < 0 for W or H <= 0 or W H > ADAMVS_DSM_MAX_CELLS. */
+#define ADAMVS_DSM_FILL_MAX_RADIUS 1024
+
+typedef struct {
+  int cycles, converged;
+  double residual_height, residual_colour;
+  long cells_valid, cells_filled, cells_empty;
+} adamvs_dsm_fill_stats;
+
+long adamvs_dsm_fill_workspace_bytes(int W, int H);
+int adamvs_dsm_fill(int W, int H, const float* dsm, const unsigned char* rgba, double r_cells, double tol_height, double tol_colour,
+                    int max_cycles, void* workspace, long workspace_bytes, float* dsm_out, unsigned char* rgba_out, int* dist2,
+                    unsigned char* filled, adamvs_dsm_fill_stats* stats, void* stream);
 
 #ifdef __cplusplus
 }
