@@ -76,6 +76,18 @@ class DsmFillStats(ctypes.Structure):
                 ("cells_empty", ctypes.c_long)]
 
 
+class MeshView(ctypes.Structure):
+    """adamvs_mesh_view"""
+    _fields_ = [("K", ctypes.c_float * 9), ("R", ctypes.c_float * 9), ("c", ctypes.c_float * 3), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("depth", ctypes.c_void_p), ("rgba", ctypes.c_void_p)]
+
+
+class MeshBrick(ctypes.Structure):
+    """adamvs_mesh_brick"""
+    _fields_ = [("origin", ctypes.c_double * 3), ("voxel", ctypes.c_double), ("mu", ctypes.c_double), ("B", ctypes.c_int),
+                ("bx", ctypes.c_int), ("by", ctypes.c_int), ("bz", ctypes.c_int), ("min_weight", ctypes.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/adamvs_hip.h declares
 SIGNATURES = {
     "adamvs_version": (c_i, []),
@@ -151,15 +163,27 @@ SIGNATURES = {
     "adamvs_dsm_fill": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i,
                               ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                               ctypes.POINTER(DsmFillStats), c_st]),
+    "adamvs_mesh_check_views": (c_i, [ctypes.POINTER(MeshView), c_i]),
+    "adamvs_tsdf_integrate": (c_i, [ctypes.POINTER(MeshBrick), ctypes.c_void_p, c_i, ctypes.c_void_p, c_i, c_f, ctypes.c_void_p,
+                                    ctypes.c_void_p, c_st]),
+    "adamvs_mesh_classify": (c_i, [ctypes.POINTER(MeshBrick), c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_mesh_count_vertices": (c_i, [ctypes.POINTER(MeshBrick), c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_mesh_emit": (c_i, [ctypes.POINTER(MeshBrick), c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                               ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
+                               ctypes.c_void_p, ctypes.c_long, c_st]),
 }
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 PRECISIONS = {"fp32": 0, "bf16x3": 1}
 PLANES_EXPLICIT, PLANES_UNIFORM, PLANES_WINDOW = 0, 1, 2
 FUSION_TILE = 256                # ADAMVS_FUSION_TILE: pixels per workgroup of the fusion kernels
 DSM_MAX, DSM_MEAN = 0, 1         # ADAMVS_DSM_MAX / ADAMVS_DSM_MEAN
 DSM_MAX_CELLS = 1 << 28          # ADAMVS_DSM_MAX_CELLS
 DSM_FILL_MAX_RADIUS = 1024       # ADAMVS_DSM_FILL_MAX_RADIUS
+MESH_TILE = 256                  # ADAMVS_MESH_TILE: samples / cubes per workgroup of the mesh kernels
+MESH_BRICKS = (32, 64, 128)      # the brick sizes B
+MESH_MAX_VIEWS = 65535           # ADAMVS_MESH_MAX_VIEWS
+MESH_MAX_EXTENT = 16384.0        # ADAMVS_MESH_MAX_EXTENT, metres from the volume origin
 PHASE_VIEW_WEIGHTS, PHASE_AGGREGATE, PHASE_RECURRENCE, PHASE_SOFT_ARGMIN, PHASE_ALL = 1, 2, 4, 8, 15
 _lib = None
 

@@ -470,3 +470,74 @@ extern "C" int adamvs_dsm_fill(int W, int H, const float* dsm, const unsigned ch
   return launch_dsm_fill(W, H, dsm, rgba, r_cells, tol_height, tol_colour, max_cycles, workspace, dsm_out, rgba_out, dist2, filled,
                          stats, (hipStream_t)stream);
 }
+
+// ---- TSDF mesh (mesh.hip): every argument is checked here, before any launch
+static int mesh_check_brick(const adamvs_mesh_brick* b, const char* what) {
+  ADAMVS_CHECK_ARG(b, "%s: null brick", what);
+  ADAMVS_CHECK_ARG(b->B == 32 || b->B == 64 || b->B == 128, "%s: B=%d (32, 64 or 128)", what, b->B);
+  ADAMVS_CHECK_ARG(std::isfinite(b->voxel) && b->voxel > 0.0, "%s: voxel=%g must be finite and > 0", what, b->voxel);
+  ADAMVS_CHECK_ARG(std::isfinite(b->mu) && b->mu > 0.0, "%s: mu=%g must be finite and > 0", what, b->mu);
+  ADAMVS_CHECK_ARG(std::isfinite(b->origin[0]) && std::isfinite(b->origin[1]) && std::isfinite(b->origin[2]), "%s: origin not finite",
+                   what);
+  ADAMVS_CHECK_ARG(b->bx >= 0 && b->by >= 0 && b->bz >= 0, "%s: brick index (%d, %d, %d) < 0", what, b->bx, b->by, b->bz);
+  const int bmax = b->bx > b->by ? (b->bx > b->bz ? b->bx : b->bz) : (b->by > b->bz ? b->by : b->bz);
+  const double far = ((double)bmax + 1.0) * b->B * b->voxel;
+  ADAMVS_CHECK_ARG(far <= ADAMVS_MESH_MAX_EXTENT, "%s: brick (%d, %d, %d) reaches %g m from the origin (at most %g)", what, b->bx, b->by,
+                   b->bz, far, ADAMVS_MESH_MAX_EXTENT);
+  ADAMVS_CHECK_ARG(b->min_weight >= 1 && b->min_weight <= 65535, "%s: min_weight=%d (1 .. 65535)", what, b->min_weight);
+  return 0;
+}
+
+extern "C" int adamvs_mesh_check_views(const adamvs_mesh_view* views, int nviews) {
+  ADAMVS_CHECK_ARG(views, "mesh_check_views: null pointer");
+  ADAMVS_CHECK_ARG(nviews >= 1 && nviews <= ADAMVS_MESH_MAX_VIEWS, "mesh_check_views: nviews=%d (1 .. %d)", nviews, ADAMVS_MESH_MAX_VIEWS);
+  for (int i = 0; i < nviews; ++i) {
+    const adamvs_mesh_view& v = views[i];
+    ADAMVS_CHECK_ARG(v.depth && v.rgba, "mesh_check_views: view %d has a null pointer", i);
+    ADAMVS_CHECK_ARG(v.H >= 1 && v.W >= 1, "mesh_check_views: view %d is %d x %d", i, v.H, v.W);
+    for (int k = 0; k < 9; ++k)
+      ADAMVS_CHECK_ARG(std::isfinite(v.K[k]) && std::isfinite(v.R[k]), "mesh_check_views: view %d: K or R_cw not finite", i);
+    ADAMVS_CHECK_ARG(v.K[6] == 0.f && v.K[7] == 0.f && v.K[8] == 1.f, "mesh_check_views: view %d: K's last row is not 0 0 1", i);
+    for (int k = 0; k < 3; ++k)
+      ADAMVS_CHECK_ARG(std::isfinite(v.c[k]) && std::fabs(v.c[k]) <= ADAMVS_MESH_MAX_EXTENT,
+                       "mesh_check_views: view %d: camera %g m from the origin along axis %d (at most %g)", i, (double)v.c[k], k,
+                       ADAMVS_MESH_MAX_EXTENT);
+  }
+  return 0;
+}
+
+extern "C" int adamvs_tsdf_integrate(const adamvs_mesh_brick* brick, const adamvs_mesh_view* views, int nviews, const int* view_list,
+                                     int nlist, float* tsdf, unsigned short* weight, unsigned* rgba, void* stream) {
+  if (int rc = mesh_check_brick(brick, "tsdf_integrate")) return rc;
+  ADAMVS_CHECK_ARG(nviews >= 1 && nviews <= ADAMVS_MESH_MAX_VIEWS, "tsdf_integrate: nviews=%d (1 .. %d)", nviews, ADAMVS_MESH_MAX_VIEWS);
+  ADAMVS_CHECK_ARG(nlist >= 0 && nlist <= nviews, "tsdf_integrate: nlist=%d (0 .. nviews=%d)", nlist, nviews);
+  ADAMVS_CHECK_ARG(views && (view_list || nlist == 0) && tsdf && weight && rgba, "tsdf_integrate: null pointer");
+  return launch_tsdf_integrate(*brick, views, nviews, view_list, nlist, tsdf, weight, rgba, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_mesh_classify(const adamvs_mesh_brick* brick, const float* tsdf, const unsigned short* weight, unsigned* cube_code,
+                                    unsigned* block_tris, void* stream) {
+  if (int rc = mesh_check_brick(brick, "mesh_classify")) return rc;
+  ADAMVS_CHECK_ARG(tsdf && weight && cube_code && block_tris, "mesh_classify: null pointer");
+  return launch_mesh_classify(*brick, tsdf, weight, cube_code, block_tris, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_mesh_count_vertices(const adamvs_mesh_brick* brick, const float* tsdf, const unsigned* cube_code,
+                                          unsigned char* edge_mask, unsigned* block_verts, void* stream) {
+  if (int rc = mesh_check_brick(brick, "mesh_count_vertices")) return rc;
+  ADAMVS_CHECK_ARG(tsdf && cube_code && edge_mask && block_verts, "mesh_count_vertices: null pointer");
+  return launch_mesh_count_vertices(*brick, tsdf, cube_code, edge_mask, block_verts, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_mesh_emit(const adamvs_mesh_brick* brick, const float* tsdf, const unsigned* rgba, const unsigned* cube_code,
+                                const unsigned char* edge_mask, const unsigned* vert_offsets, const unsigned* tri_offsets,
+                                unsigned vertex_base, double* xyz, unsigned char* rgb, unsigned* first_vertex, long vert_capacity,
+                                unsigned* faces, long tri_capacity, void* stream) {
+  if (int rc = mesh_check_brick(brick, "mesh_emit")) return rc;
+  ADAMVS_CHECK_ARG(tsdf && rgba && cube_code && edge_mask && vert_offsets && tri_offsets && first_vertex, "mesh_emit: null pointer");
+  ADAMVS_CHECK_ARG(vert_capacity >= 0 && tri_capacity >= 0, "mesh_emit: capacity < 0");
+  ADAMVS_CHECK_ARG((xyz && rgb) || vert_capacity == 0, "mesh_emit: null vertex output");
+  ADAMVS_CHECK_ARG(faces || tri_capacity == 0, "mesh_emit: null face output");
+  return launch_mesh_emit(*brick, tsdf, rgba, cube_code, edge_mask, vert_offsets, tri_offsets, vertex_base, xyz, rgb, first_vertex,
+                          vert_capacity, faces, tri_capacity, (hipStream_t)stream);
+}

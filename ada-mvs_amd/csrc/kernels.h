@@ -162,4 +162,16 @@ int launch_dsm_fill(int W, int H, const float* dsm, const uint8_t* rgba, double 
                     int max_cycles, void* workspace, float* dsm_out, uint8_t* rgba_out, int* dist2, uint8_t* filled,
                     adamvs_dsm_fill_stats* stats, hipStream_t st);
 
+// mesh.hip: TSDF integration and marching-tetrahedra extraction per brick (include/adamvs_hip.h, "TSDF mesh")
+constexpr int MESH_TILE = ADAMVS_MESH_TILE;
+int launch_tsdf_integrate(const adamvs_mesh_brick& b, const adamvs_mesh_view* views, int nviews, const int* list, int nlist, float* tsdf,
+                          uint16_t* weight, unsigned* rgba, hipStream_t st);
+int launch_mesh_classify(const adamvs_mesh_brick& b, const float* tsdf, const uint16_t* weight, unsigned* cube_code, unsigned* block_tris,
+                         hipStream_t st);
+int launch_mesh_count_vertices(const adamvs_mesh_brick& b, const float* tsdf, const unsigned* cube_code, uint8_t* edge_mask,
+                               unsigned* block_verts, hipStream_t st);
+int launch_mesh_emit(const adamvs_mesh_brick& b, const float* tsdf, const unsigned* rgba, const unsigned* cube_code, const uint8_t* edge_mask,
+                     const unsigned* vert_offsets, const unsigned* tri_offsets, unsigned vertex_base, double* xyz, uint8_t* rgb,
+                     unsigned* first_vertex, long vert_capacity, unsigned* faces, long tri_capacity, hipStream_t st);
+
 }  // namespace adamvs

@@ -665,3 +665,91 @@ def dsm_fill(dsm, rgba, r_cells, tol_height=1e-6, tol_colour=1e-3, max_cycles=20
                               workspace.numel(), _p(dsm_out), _p(rgba_out), _p(dist2), _p(filled), ctypes.byref(stats), _stream()),
           "dsm_fill")
     return dsm_out, rgba_out, dist2, filled, stats
+
+
+# ---- TSDF mesh (csrc/mesh.hip; driven brick by brick by ada_mvs_amd/mesh.py) ------------------------------------------------
+# Per-sample state as torch tensors of the signed type of each C type's width: weight int16 = uint16, rgba int32 = uint32
+# (little-endian r g b a), cube_code int32 = uint32, faces int32 = uint32.
+def mesh_brick(origin, voxel, mu, B, b, min_weight=1):
+    """-> _lib.MeshBrick (adamvs_mesh_brick) of brick b = (bx, by, bz)."""
+    mb = _lib.MeshBrick()
+    mb.origin[:] = [float(v) for v in origin]
+    mb.voxel, mb.mu, mb.B, mb.min_weight = float(voxel), float(mu), int(B), int(min_weight)
+    mb.bx, mb.by, mb.bz = (int(v) for v in b)
+    return mb
+
+
+def mesh_views(views, device):
+    """views: list of (K [3, 3], R_cw [3, 3], c = C - O [3] (fp64, rounded here to fp32), depth [H, W] fp32, rgba [H, W, 4] uint8
+    (device tensors)) -> the device array of adamvs_mesh_view (a uint8 tensor), checked by adamvs_mesh_check_views.  The depth and
+    image tensors must outlive it."""
+    arr = (_lib.MeshView * max(len(views), 1))()
+    for i, (K, R, c, depth, rgba) in enumerate(views):
+        depth = _dev_as(depth, "view %d depth" % i, torch.float32)
+        rgba = _dev_as(rgba, "view %d rgba" % i, torch.uint8)
+        if depth.dim() != 2 or tuple(rgba.shape) != tuple(depth.shape) + (4,):
+            raise _lib.AdaMVSHipError("view %d: depth %s, rgba %s" % (i, tuple(depth.shape), tuple(rgba.shape)))
+        arr[i].K[:] = [float(v) for v in K.reshape(-1)]
+        arr[i].R[:] = [float(v) for v in R.reshape(-1)]
+        arr[i].c[:] = [float(v) for v in c]
+        arr[i].H, arr[i].W = depth.shape
+        arr[i].depth, arr[i].rgba = depth.data_ptr(), rgba.data_ptr()
+    check(_lib.load().adamvs_mesh_check_views(arr, len(views)), "mesh_check_views")
+    host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+    return host.to(device)
+
+
+def _mesh_sizes(B):
+    S = (B + 1) ** 3
+    return S, (S + _lib.MESH_TILE - 1) // _lib.MESH_TILE, B ** 3 // _lib.MESH_TILE
+
+
+def tsdf_integrate(brick, views_dev, nviews, view_list):
+    """adamvs_tsdf_integrate.  brick: _lib.MeshBrick; views_dev from mesh_views; view_list: device int32 [n] (sorted, conservative).
+    -> (tsdf [(B+1)^3] float32, weight int16 (uint16), rgba int32 (uint32 r g b a))."""
+    views_dev = _dev_as(views_dev, "views", torch.uint8)
+    view_list = _dev_as(view_list, "view_list", torch.int32)
+    S, _, _ = _mesh_sizes(brick.B)
+    dev = views_dev.device
+    tsdf = torch.empty(S, device=dev, dtype=torch.float32)
+    weight = torch.empty(S, device=dev, dtype=torch.int16)
+    rgba = torch.empty(S, device=dev, dtype=torch.int32)
+    check(_lib.load().adamvs_tsdf_integrate(ctypes.byref(brick), _p(views_dev), int(nviews), _p(view_list), view_list.numel(), _p(tsdf),
+                                            _p(weight), _p(rgba), _stream()), "tsdf_integrate")
+    return tsdf, weight, rgba
+
+
+def mesh_extract(brick, tsdf, weight, rgba, vertex_base=0):
+    """adamvs_mesh_classify + _count_vertices + two adamvs_fusion_scan + adamvs_mesh_emit on one brick's volume.  Reads the two
+    totals back (one synchronisation).  -> (xyz [nv, 3] float64, rgb [nv, 3] uint8, faces [nt, 3] int32 (uint32: vertex_base +
+    brick-local index)), device tensors."""
+    tsdf = _dev(tsdf, "tsdf")
+    weight = _dev_as(weight, "weight", torch.int16)
+    rgba = _dev_as(rgba, "rgba", torch.int32)
+    B = brick.B
+    S, nbs, nbc = _mesh_sizes(B)
+    if tsdf.numel() != S or weight.numel() != S or rgba.numel() != S:
+        raise _lib.AdaMVSHipError("B=%d needs %d samples: tsdf %d, weight %d, rgba %d" % (B, S, tsdf.numel(), weight.numel(), rgba.numel()))
+    dev = tsdf.device
+    lib = _lib.load()
+    code = torch.empty(B ** 3, device=dev, dtype=torch.int32)
+    mask = torch.empty(S, device=dev, dtype=torch.uint8)
+    counts = torch.empty(nbc + nbs, device=dev, dtype=torch.int32)
+    offs = torch.empty(nbc + 1 + nbs + 1, device=dev, dtype=torch.int32)
+    block_tris, block_verts = counts[:nbc], counts[nbc:]
+    tri_off, vert_off = offs[:nbc + 1], offs[nbc + 1:]
+    st = _stream()
+    check(lib.adamvs_mesh_classify(ctypes.byref(brick), _p(tsdf), _p(weight), _p(code), _p(block_tris), st), "mesh_classify")
+    check(lib.adamvs_mesh_count_vertices(ctypes.byref(brick), _p(tsdf), _p(code), _p(mask), _p(block_verts), st), "mesh_count_vertices")
+    check(lib.adamvs_fusion_scan(_p(block_tris), _p(tri_off), nbc, st), "fusion_scan")
+    check(lib.adamvs_fusion_scan(_p(block_verts), _p(vert_off), nbs, st), "fusion_scan")
+    nt, nv = (int(v) & 0xFFFFFFFF for v in torch.stack([tri_off[-1], vert_off[-1]]).cpu().tolist())
+    if int(vertex_base) + nv > 0xFFFFFFFF:
+        raise _lib.AdaMVSHipError("mesh: more than 2^32 - 1 vertices")
+    xyz = torch.empty(max(nv, 1), 3, device=dev, dtype=torch.float64)
+    rgb = torch.empty(max(nv, 1), 3, device=dev, dtype=torch.uint8)
+    faces = torch.empty(max(nt, 1), 3, device=dev, dtype=torch.int32)
+    first = torch.empty(S, device=dev, dtype=torch.int32)
+    check(lib.adamvs_mesh_emit(ctypes.byref(brick), _p(tsdf), _p(rgba), _p(code), _p(mask), _p(vert_off), _p(tri_off), int(vertex_base),
+                               _p(xyz), _p(rgb), _p(first), nv, _p(faces), nt, st), "mesh_emit")
+    return xyz[:nv], rgb[:nv], faces[:nt]

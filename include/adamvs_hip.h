@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ADAMVS_ABI_VERSION 19
+#define ADAMVS_ABI_VERSION 20
 
 int adamvs_version(void);
 const char* adamvs_last_error_string(void);
@@ -596,6 +596,111 @@ long adamvs_dsm_fill_workspace_bytes(int W, int H);
 int adamvs_dsm_fill(int W, int H, const float* dsm, const unsigned char* rgba, double r_cells, double tol_height, double tol_colour,
                     int max_cycles, void* workspace, long workspace_bytes, float* dsm_out, unsigned char* rgba_out, int* dist2,
                     unsigned char* filled, adamvs_dsm_fill_stats* stats, void* stream);
+
+/* ---- TSDF mesh (after fuse_whu.py): the depth maps of all views integrated into a truncated signed-distance field on a voxel
+ * grid, brick by brick, and its zero level set extracted as a coloured triangle mesh ---------------------------------------
+ * ada-mvs_amd/mesh.py drives it per brick; mesh_whu.py is the CLI.  World axes: x east, y north, z up.
+ *
+ * Volume.  Origin O (fp64, the min corner), voxel size s (fp64).  Sample g = (i, j, k) (integers >= 0) sits at O + g s.  The
+ * volume is cut into bricks of B^3 cubes, B in {32, 64, 128}: brick b = (bx, by, bz) owns the cubes b B .. b B + B - 1 along
+ * each axis and holds the samples b B .. b B + B (one layer shared with each upper neighbour), so every cube belongs to
+ * exactly one brick.  Inside a brick, sample l = g - b B (0 <= l <= B per axis) is entry n = (l.z (B+1) + l.y)(B+1) + l.x of
+ * the per-sample arrays ([(B+1)^3], "sample row-major"), and cube l (0 <= l < B) is entry (l.z B + l.y) B + l.x of the
+ * per-cube arrays ([B^3], "cube row-major").  The brick: a HOST pointer to an adamvs_mesh_brick, copied into the arguments.
+ *
+ * Views.  One DEVICE array of adamvs_mesh_view, built once per scene from a host array that adamvs_mesh_check_views
+ * accepted: K (fp32, row-major, last row 0 0 1), R_cw (fp32, row-major: world -> camera x right / y down / z forward) and
+ * c = C - O (formed in fp64 by the caller, rounded to fp32), the depth map [H][W] fp32 (device) and the image [H][W][4]
+ * uint8 RGBA (device).  Per brick the caller passes a DEVICE list of view indices, sorted ascending, no repeats, and
+ * CONSERVATIVE: every view that projects a sample of the closed brick box (grown by mu) into its image is in it.  An index
+ * outside [0, nviews) is skipped.
+ * Precision: all camera-frame arithmetic is fp32 relative to O.  Cameras (|c| per axis) and bricks ((b + 1) B s per axis)
+ * farther than ADAMVS_MESH_MAX_EXTENT = 16384 m from O are refused (fp32 spacing <= 2^-10 m there).  With L = |g s| + |c|
+ * (Euclidean, <= 2 sqrt(3) 16384 m), each view's sdf is within 16 2^-24 L of the fp64 value of the same fp32 inputs, hence
+ * |tsdf - tsdf_fp64| <= 16 2^-24 L / mu + 2^-24 (weight + 2)  (<= 0.055 m / mu + 2^-24 (weight + 2) at the limit),
+ * wherever the pixel choices and the tests below decide alike (a pixel coordinate within that error of a half integer,
+ * z, sdf + mu or |sdf| - mu within it of 0, may go either way).
+ *
+ * Integration (adamvs_tsdf_integrate): every sample g of the brick independently, the views of the list in list order, no
+ * atomics.  sf = (float)s, muf = (float)mu; per view:
+ *   x = (float)g sf - c (fp32),  p = R_cw x,  z = p.z;  skip the view unless z > 0;
+ *   u = (K00 p.x + K01 p.y + K02 z) / z,  v = (K10 p.x + K11 p.y + K12 z) / z  (pixel centres at integer coordinates);
+ *   the nearest pixel (floor(u + 0.5), floor(v + 0.5)): skip unless it lies inside the image and its depth d is finite and
+ *   > 0 (depth 0 marks a pixel fusion rejected: unknown, not free space);
+ *   sdf = d - z (fp32); skip if sdf < -muf;
+ *   T += min(1, sdf / muf) (fp32, in list order), weight += 1;
+ *   if |sdf| <= muf: the pixel's R, G, B are added to integer sums and 1 to a colour count n.
+ * Outputs [(B+1)^3]: tsdf = T / (float)weight (0 where weight = 0), weight uint16 saturating at 65535, rgba uint32
+ * (little-endian r g b a): per channel (sum + n / 2) / n in integers and alpha 255, 0 where n = 0.  Every step is integer or
+ * in a fixed order, so a sample's value does not depend on the brick that computed it as long as the view lists are
+ * conservative: the shared layers of neighbouring bricks are bit-identical.
+ *
+ * Extraction: marching tetrahedra on the Kuhn split.  A cube is PROCESSED iff its 8 corners have weight >= min_weight.  It
+ * splits into 6 tetrahedra along its main diagonal, tet t for the axis permutation (a, b, c) =
+ *   t = 0 (x y z), 1 (x z y), 2 (y x z), 3 (y z x), 4 (z x y), 5 (z y x),
+ * with vertices v0 = 000, v1 = e_a, v2 = e_a + e_b, v3 = 111.  Every lattice edge a tet uses runs from a sample g in one of 7
+ * positive directions, numbered  0 +x, 1 +y, 2 +z, 3 +xy, 4 +xz, 5 +yz, 6 +xyz;  a vertex is "edge e of sample g".
+ * A corner is INSIDE iff tsdf < 0; the tet case is sum over k of inside(v_k) << k.  A vertex exists on an edge (g, g + e) iff
+ * its two samples differ in that sign and a processed cube of the brick uses the edge.  With a = g, b = g + e:
+ *   lambda = t_a / (t_a - t_b)  (fp32),  position = O + ((double)g + (double)lambda e) s  per axis, fp64, no contraction;
+ *   colour = per channel rint(c_a + lambda (c_b - c_a)) in fp32 (no contraction), clamped to 0 .. 255 (a corner without
+ *   colour counts as 0).
+ * Triangles per tet: cases 0 and 15 give none.  A lone vertex i (one inside or one outside) gives the triangle on its edges
+ * to the other three, in ascending order of those.  A 2-2 split, inside {i < j}, outside {k < l}, gives the quad
+ * q0 = (i,k), q1 = (i,l), q2 = (j,l), q3 = (j,k), cut along q0 - q2 into (q0 q1 q2) and (q0 q2 q3).  Each triangle is then
+ * oriented so that its right-hand normal, at lambda = 1/2 on every edge, points along (centroid of the outside corners -
+ * centroid of the inside corners), i.e. toward increasing tsdf (out of the solid); if not, its last two vertices swap.
+ * Output order: vertices in sample row-major order, then edge direction; triangles in cube row-major order, then tet order,
+ * then the order above.  Indices are brick-local (uint32) plus a caller-given vertex_base.  A vertex on a face, edge or
+ * corner layer shared with a neighbouring brick is written by each brick that uses it, at bit-identical coordinates and
+ * colour: welding by exact position (mesh.py weld) merges them.
+ *
+ * Calls, per brick, in stream order (no inter-workgroup waits, no atomics: bit-identical from run to run).  Workgroups cover
+ * ADAMVS_MESH_TILE consecutive entries: nblocks_cubes = B^3 / 256, nblocks_samples = ceil((B+1)^3 / 256).
+ *   _tsdf_integrate       tsdf [(B+1)^3] fp32, weight [(B+1)^3] uint16, rgba [(B+1)^3] uint32;
+ *   _mesh_classify        cube_code [B^3] uint32: bit 0 processed, bits 1 + 4 t .. 4 + 4 t the case of tet t (0 for a cube
+ *                         not processed), bits 25 .. 28 its triangle count; block_tris [nblocks_cubes] uint32;
+ *   _mesh_count_vertices  edge_mask [(B+1)^3] uint8 (bit e: the vertex on edge e of the sample exists); block_verts
+ *                         [nblocks_samples] uint32;
+ *   adamvs_fusion_scan of block_verts -> vert_offsets [nblocks_samples + 1] and of block_tris -> tri_offsets [nblocks_cubes + 1];
+ *   _mesh_emit            xyz [nv][3] fp64, rgb [nv][3] uint8, first_vertex [(B+1)^3] uint32 (the brick-local index of the
+ *                         sample's first vertex; its vertex on edge e is first_vertex + popcount(edge_mask & ((1 << e) - 1))),
+ *                         then faces [nt][3] uint32.  Nothing is written at or past vert_capacity / tri_capacity.
+ * Argument errors (<0, before any launch): a null pointer (the view list may be null when nlist = 0), B not in the set, s or
+ * mu not finite or <= 0, a brick index < 0, O not finite, (b + 1) B s > ADAMVS_MESH_MAX_EXTENT, min_weight < 1 or > 65535,
+ * nviews < 1 or > ADAMVS_MESH_MAX_VIEWS, nlist < 0 or > nviews, a capacity < 0, and in _mesh_check_views (host array) a view
+ * with a null pointer, H or W < 1, a non-finite K / R_cw / c, K's last row not 0 0 1, or |c| > ADAMVS_MESH_MAX_EXTENT. */
+#define ADAMVS_MESH_TILE 256
+#define ADAMVS_MESH_MAX_VIEWS 65535
+#define ADAMVS_MESH_MAX_EXTENT 16384.0
+
+typedef struct {
+  float K[9];
+  float R[9];
+  float c[3];
+  int H, W;
+  const float* depth;
+  const unsigned char* rgba;
+} adamvs_mesh_view;
+
+typedef struct {
+  double origin[3];
+  double voxel, mu;
+  int B, bx, by, bz;
+  int min_weight;
+} adamvs_mesh_brick;
+
+int adamvs_mesh_check_views(const adamvs_mesh_view* views, int nviews);
+int adamvs_tsdf_integrate(const adamvs_mesh_brick* brick, const adamvs_mesh_view* views, int nviews, const int* view_list, int nlist,
+                          float* tsdf, unsigned short* weight, unsigned* rgba, void* stream);
+int adamvs_mesh_classify(const adamvs_mesh_brick* brick, const float* tsdf, const unsigned short* weight, unsigned* cube_code,
+                         unsigned* block_tris, void* stream);
+int adamvs_mesh_count_vertices(const adamvs_mesh_brick* brick, const float* tsdf, const unsigned* cube_code, unsigned char* edge_mask,
+                               unsigned* block_verts, void* stream);
+int adamvs_mesh_emit(const adamvs_mesh_brick* brick, const float* tsdf, const unsigned* rgba, const unsigned* cube_code,
+                     const unsigned char* edge_mask, const unsigned* vert_offsets, const unsigned* tri_offsets, unsigned vertex_base,
+                     double* xyz, unsigned char* rgb, unsigned* first_vertex, long vert_capacity, unsigned* faces, long tri_capacity,
+                     void* stream);
 
 #ifdef __cplusplus
 }
