@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the Ada-MVS depth-inference hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg1|tiny] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg1|tiny] [--batch B] [--dump-outputs DIR] [--full]
 
 A "step" = one pass of the hot path (reference models/adamvs.py:586-618 minus
 FeatureNet0: hypothesis sampling, plane sweep, per-view weighting, recurrent
@@ -10,15 +10,20 @@ GPU, feature maps already resident in HBM.  N > 1: one process per GPU
 (torchrun), tiles sharded over ranks, one RCCL gather of the finished maps per
 step.  Rank 0 prints ONE JSON line (contract: see the task description).
 
-Also measured by rank 0 at N = 1 (after the timed region, same shapes):
+A plain run does only what the headline needs: set up, warm up, time the steps,
+write --dump-outputs, print the line.  With --full, rank 0 at N = 1 also
+measures, after the timed region (each part can be left out with its --no-* option):
   roofline      per-kernel HIP-event timing of the stage run phase by phase through the C ABI
-  cpu_baseline  the CPU oracle ("port") on one tile of the same workload
+  cpu_baseline  the CPU oracle ("port") on one tile of the same workload, and parity_rel_l1 of the
+                timed run's tile 0 against it (exit 3 above 1e-3)
+  cascade       the cfg3 / cfg4-share / cfg5 configurations in both precisions (default cfg2 workload only)
 """
 import argparse
 import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 
 def _argv_value(name, default):
@@ -386,7 +391,7 @@ def bench_msrednet(args):
                                    % (sum(nd), c["H"] // 32, c["W"] // 32)}}
     if dumped:
         result["dump_outputs"] = dumped
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import msrednet_oracle as MO       # checker / baseline only
         sd_cpu = {k: v.detach().cpu() for k, v in sd.items()}
         threads = min(os.cpu_count() or 1, 32)
@@ -401,6 +406,21 @@ def bench_msrednet(args):
     print(json.dumps(result))
 
 
+def tile_images(cfg, tiles, dev, threads=None):
+    """The images of `tiles` ([len(tiles), V, 3, H, W] float32 on dev): tile t's are synth.tile_inputs(cfg, 1, seed=t)'s, drawn
+    on host threads (one generator per tile, so the values do not depend on the thread count) and copied into the device
+    tensor a few tiles at a time, without a host copy of the whole batch."""
+    c = synth.CONFIGS[cfg]
+    out = torch.empty(len(tiles), c["views"], 3, c["H"], c["W"], dtype=torch.float32, device=dev)
+    threads = threads or max(1, min(torch.get_num_threads(), 16))
+    chunk = 2 * threads
+    with ThreadPoolExecutor(threads) as ex:
+        for s in range(0, len(tiles), chunk):
+            for i, x in enumerate(ex.map(lambda t: synth.tile_inputs(cfg, 1, seed=t)[0], tiles[s:s + chunk]), s):
+                out[i].copy_(x[0])
+    return out
+
+
 class Workload:
     """One configuration of the hot path set up for timing on this rank: the model, this rank's tiles (images seeded by
     their GLOBAL tile index; rig b of the batch for slot b), FeatureNet0 outputs resident in HBM (upstream
@@ -413,10 +433,11 @@ class Workload:
         assert B > 0 and B % groups == 0, "tiles per GPU must be a positive multiple of --groups"
         self.Bg = Bg = B // groups
         self.model, self.sd = build_model(cfg, dev, precision)
-        imgs = torch.cat([synth.tile_inputs(cfg, 1, seed=t)[0] for t in self.tiles], 0).to(dev)
-        _, proj, dv = synth.tile_inputs(cfg, batch=B, seed=0, baseline=baseline)
+        imgs = tile_images(cfg, self.tiles, dev)
+        # the rig and depth range of synth.tile_inputs(cfg, B, seed=0, baseline), without drawing its B image sets
+        proj = synth.rig_projections(self.c["views"], self.c["H"], self.c["W"], batch=B, baseline=baseline)
         proj = {k: v.to(dev) for k, v in proj.items()}
-        dv = dv.to(dev)
+        dv = torch.tensor([list(synth.DEPTH_RANGE)] * B, dtype=torch.float32).to(dev)
         self.interval = (synth.DEPTH_RANGE[1] - synth.DEPTH_RANGE[0]) / self.c["num_depth"]
         G = groups
         with torch.no_grad():
@@ -607,10 +628,14 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3"],
                     help="fp32: fp32 MFMA, stride-1 CostRegNet2D layers in the F(2x2,3x3) form (the cfg2 headline); bf16x3: split-bf16 MFMA for the convolutions (~1e-5 of fp32)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline and phase tables, the CPU baseline with the parity check "
+                         "of the timed run, and the cfg3 / cfg4-share / cfg5 cascade configurations (N = 1); a plain run "
+                         "measures the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline and phase tables")
     ap.add_argument("--no-cascade", action="store_true",
-                    help="skip the cfg3 / cfg4-share measurements that follow the headline (N = 1, default workload only)")
+                    help="--full: skip the cfg3 / cfg4-share measurements that follow the headline (N = 1, default workload only)")
     ap.add_argument("--launch-timeout", type=float, default=900.0,
                     help="self-launched N > 1 runs: seconds after which every rank is ended by PID and the launcher exits 124 "
                          "(a rank hanging in a collective); read by the launcher before argparse, listed here for --help")
@@ -731,14 +756,14 @@ def main():
             if dumped:
                 result["dump_outputs"] = dumped
 
-        if rank == 0 and world == 1 and not args.no_roofline:
+        if rank == 0 and world == 1 and args.full and not args.no_roofline:
             result.update(roofline_of(wl, args, result["ms_per_step"]))
         if rank == 0 and world > 1:
             result["roofline"] = result["cpu_baseline"] = None
-            result["note"] = "roofline, cpu_baseline, parity_rel_l1 and cascade are measured by the N = 1 line only (per-kernel timing and the oracle run on rank 0's GPU / host cores)"
+            result["note"] = "roofline, cpu_baseline, parity_rel_l1 and cascade are measured by the N = 1 line with --full only (per-kernel timing and the oracle run on rank 0's GPU / host cores)"
         parity_ok = True
         sd = wl.sd
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             # the oracle runs tile 0 of this very workload: its maps are the parity check of the timed run
             result["cpu_baseline"], ref = cpu_baseline(cfg, sd, args.baseline)
             result["parity_rel_l1"] = parity_of(tile0, ref, c, wl.interval)
@@ -748,7 +773,7 @@ def main():
 
         # BASELINE.json's cascade configurations beside the headline: cfg3 (configs[2]) and one GPU's share of cfg4
         # (configs[3]), each with parity against ONE oracle pass of cfg3's tile 0
-        if rank == 0 and world == 1 and cfg == "cfg2" and not strong and not args.no_cascade:
+        if rank == 0 and world == 1 and cfg == "cfg2" and not strong and args.full and not args.no_cascade:
             cas, tiles0, sd3 = bench_cascade(dev, max(3, min(args.steps, 10)), max(1, min(args.warmup, 3)), args.baseline,
                                              use_graph=not args.no_graph)
             if not args.no_cpu_baseline:

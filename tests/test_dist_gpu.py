@@ -197,3 +197,29 @@ def test_bench_dump_outputs_are_the_maps_of_the_last_timed_step(tmp_path):
     for name, want in (("depth", depth), ("photometric_confidence", conf)):
         a = np.load(str(out / (name + ".npy")))
         assert a.dtype == np.float32 and np.array_equal(a, want), name
+
+
+def test_bench_plain_line_is_the_headline_and_full_adds_the_rest(tmp_path):
+    """`python bench.py --gpus 1` measures the headline alone; `--full` adds the roofline and phase tables, the CPU baseline and
+    the parity of the timed run's tile 0 against it, at the same headline fields."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "cfg1",
+               "--batch", "2"] + extra
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[name] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for d in (plain, full):
+        assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["unit"] == "depth maps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert plain["metric"] == full["metric"]
+    for key in ("roofline", "phase_ms_per_step", "cpu_baseline", "parity_rel_l1", "cascade"):
+        assert key not in plain, key
+    assert full["roofline"]["achieved"] > 0 and full["phase_ms_per_step"] and full["cpu_baseline"]["value"] > 0
+    assert max(full["parity_rel_l1"]["depth"], full["parity_rel_l1"]["photometric_confidence"]) <= 1e-3
+    assert "cascade" not in full                                 # cfg2's companions only

@@ -403,6 +403,22 @@ def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
             assert np.array_equal(z["photometric_confidence"], z["depth"] + 0.5)
 
 
+def test_bench_tile_images_are_the_seeded_draws_of_their_tiles():
+    """bench.py draws a rank's images on host threads: tile t's are synth.tile_inputs(cfg, 1, seed=t)'s whatever the thread
+    count, in the order of the rank's tiles, and the batch's rig and depth range are those of tile_inputs(cfg, B, seed=0)."""
+    import bench
+    tiles = [7, 0, 3, 12, 5]                                   # a rank's share in any order, more tiles than one chunk of threads
+    want = torch.cat([synth.tile_inputs("tiny", 1, seed=t)[0] for t in tiles], 0)
+    for threads in (1, 2):
+        got = bench.tile_images("tiny", tiles, "cpu", threads=threads)
+        assert got.dtype == torch.float32 and torch.equal(got, want)
+    c = synth.CONFIGS["tiny"]
+    _, proj, dv = synth.tile_inputs("tiny", batch=len(tiles), seed=0, baseline=32.0)
+    rig = synth.rig_projections(c["views"], c["H"], c["W"], batch=len(tiles), baseline=32.0)
+    assert sorted(rig) == sorted(proj) and all(torch.equal(rig[k], proj[k]) for k in proj)
+    assert torch.equal(torch.tensor([list(synth.DEPTH_RANGE)] * len(tiles), dtype=torch.float32), dv)
+
+
 def test_cost_reg_width_table_and_padded_packing():
     """packing.REG_WIDTHS is the library's table (csrc/costreg2d.hip::costreg_width); a network of D hypotheses is packed at the
     next width with zero filters and PAD_SCORE on `prob`'s pad channels, and the blob has the length the library expects."""

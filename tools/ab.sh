@@ -21,7 +21,7 @@ for v in "${VARS[@]}"; do
     name=${case%%=*}; args=${case#*=}
     out=gpurun_out/${tag}_${name}_${vname}
     echo "== $name [$v]"
-    env $v timeout 900 python3 bench.py --no-cpu-baseline --no-cascade --steps 5 --warmup 2 $EXTRA $args > $out.json 2> $out.err || tail -3 $out.err
+    env $v timeout 900 python3 bench.py --full --no-cpu-baseline --no-cascade --steps 5 --warmup 2 $EXTRA $args > $out.json 2> $out.err || tail -3 $out.err
     python3 tools/show_bench.py $out.json | head -${SHOW:-3}
   done
 done

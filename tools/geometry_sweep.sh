@@ -9,7 +9,7 @@ tab=gpurun_out/${tag}_geometry.txt
 : > $tab
 for X in ${BASELINES:-8 32 128 512}; do
   out=gpurun_out/${tag}_baseline$X
-  timeout 900 python3 bench.py --no-cascade --baseline $X "$@" > $out.json 2> $out.err || tail -3 $out.err
+  timeout 900 python3 bench.py --full --no-cascade --baseline $X "$@" > $out.json 2> $out.err || tail -3 $out.err
   python3 - $out.json $X >> $tab <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

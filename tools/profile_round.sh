@@ -1,5 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box): tools/profile_round.sh <tag> [bench.py args...]
+#   (--full among the args: the unprofiled bench line carries the roofline and phase tables; the profiled runs leave out
+#   the roofline and the CPU baseline either way)
 #   -> gpurun_out/<tag>_kernel_stats.csv   rocprofv3 --kernel-trace --stats summary of `bench.py <args>`
 #   -> gpurun_out/<tag>_traffic.json/.txt  FETCH_SIZE / WRITE_SIZE per launch (separate --pmc passes, no trace domains)
 #   -> gpurun_out/<tag>_bench.json         the bench line of an unprofiled run
