@@ -88,6 +88,18 @@ class MeshBrick(ctypes.Structure):
                 ("bx", ctypes.c_int), ("by", ctypes.c_int), ("bz", ctypes.c_int), ("min_weight", ctypes.c_int)]
 
 
+class OrthoGrid(ctypes.Structure):
+    """adamvs_ortho_grid"""
+    _fields_ = [("x0", ctypes.c_double), ("y_top", ctypes.c_double), ("gsd", ctypes.c_double), ("W", ctypes.c_int), ("H", ctypes.c_int),
+                ("K", ctypes.c_int)]
+
+
+class OrthoView(ctypes.Structure):
+    """adamvs_ortho_view"""
+    _fields_ = [("C", ctypes.c_double * 3), ("R", ctypes.c_float * 9), ("K", ctypes.c_float * 9), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("rgba", ctypes.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/adamvs_hip.h declares
 SIGNATURES = {
     "adamvs_version": (c_i, []),
@@ -171,9 +183,16 @@ SIGNATURES = {
     "adamvs_mesh_emit": (c_i, [ctypes.POINTER(MeshBrick), c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
                                ctypes.c_void_p, ctypes.c_long, c_st]),
+    "adamvs_ortho_surface": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_ortho_zbuf": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.POINTER(OrthoView), ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_void_p, ctypes.c_long, c_st]),
+    "adamvs_ortho_compose": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.POINTER(OrthoView), c_i, ctypes.c_void_p, ctypes.c_void_p, c_i,
+                                   ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_ortho_finalize": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_void_p, ctypes.c_void_p, c_st]),
 }
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 PRECISIONS = {"fp32": 0, "bf16x3": 1}
 PLANES_EXPLICIT, PLANES_UNIFORM, PLANES_WINDOW = 0, 1, 2
 FUSION_TILE = 256                # ADAMVS_FUSION_TILE: pixels per workgroup of the fusion kernels
@@ -184,6 +203,9 @@ MESH_TILE = 256                  # ADAMVS_MESH_TILE: samples / cubes per workgro
 MESH_BRICKS = (32, 64, 128)      # the brick sizes B
 MESH_MAX_VIEWS = 65535           # ADAMVS_MESH_MAX_VIEWS
 MESH_MAX_EXTENT = 16384.0        # ADAMVS_MESH_MAX_EXTENT, metres from the volume origin
+ORTHO_BEST, ORTHO_FEATHER = 0, 1 # ADAMVS_ORTHO_BEST / ADAMVS_ORTHO_FEATHER
+ORTHO_MAX_CELLS = 1 << 28        # ADAMVS_ORTHO_MAX_CELLS
+ORTHO_MAX_UPSAMPLE = 8           # ADAMVS_ORTHO_MAX_UPSAMPLE
 PHASE_VIEW_WEIGHTS, PHASE_AGGREGATE, PHASE_RECURRENCE, PHASE_SOFT_ARGMIN, PHASE_ALL = 1, 2, 4, 8, 15
 _lib = None
 

@@ -541,3 +541,63 @@ extern "C" int adamvs_mesh_emit(const adamvs_mesh_brick* brick, const float* tsd
   return launch_mesh_emit(*brick, tsdf, rgba, cube_code, edge_mask, vert_offsets, tri_offsets, vertex_base, xyz, rgb, first_vertex,
                           vert_capacity, faces, tri_capacity, (hipStream_t)stream);
 }
+
+// ---- image orthophoto (ortho.hip): every argument is checked here, before any launch
+static int ortho_check_grid(const adamvs_ortho_grid* g, const char* what) {
+  ADAMVS_CHECK_ARG(g, "%s: null grid", what);
+  ADAMVS_CHECK_ARG(g->W >= 1 && g->H >= 1, "%s: grid %d x %d", what, g->W, g->H);
+  ADAMVS_CHECK_ARG(g->K >= 1 && g->K <= ADAMVS_ORTHO_MAX_UPSAMPLE, "%s: upsample K=%d (1 .. %d)", what, g->K, ADAMVS_ORTHO_MAX_UPSAMPLE);
+  ADAMVS_CHECK_ARG((long)g->W * g->K * (long)g->H * g->K <= ADAMVS_ORTHO_MAX_CELLS, "%s: %d x %d cells at K=%d exceed %ld", what, g->W,
+                   g->H, g->K, (long)ADAMVS_ORTHO_MAX_CELLS);
+  ADAMVS_CHECK_ARG(std::isfinite(g->x0) && std::isfinite(g->y_top) && std::isfinite(g->gsd) && g->gsd > 0.0,
+                   "%s: x0 %g, y_top %g, gsd %g (finite, gsd > 0)", what, g->x0, g->y_top, g->gsd);
+  return 0;
+}
+
+static int ortho_check_view(const adamvs_ortho_view* v, const char* what) {
+  ADAMVS_CHECK_ARG(v && v->rgba, "%s: null view or image", what);
+  ADAMVS_CHECK_ARG(v->H >= 1 && v->W >= 1, "%s: image %d x %d", what, v->H, v->W);
+  for (int k = 0; k < 9; ++k)
+    ADAMVS_CHECK_ARG(std::isfinite(v->K[k]) && std::isfinite(v->R[k]), "%s: K or R_cw not finite", what);
+  for (int k = 0; k < 3; ++k) ADAMVS_CHECK_ARG(std::isfinite(v->C[k]), "%s: C not finite", what);
+  ADAMVS_CHECK_ARG(v->K[6] == 0.f && v->K[7] == 0.f && v->K[8] == 1.f, "%s: K's last row is not 0 0 1", what);
+  return 0;
+}
+
+extern "C" int adamvs_ortho_surface(const adamvs_ortho_grid* grid, const float* dsm, double* height, void* stream) {
+  if (int rc = ortho_check_grid(grid, "ortho_surface")) return rc;
+  ADAMVS_CHECK_ARG(dsm && height, "ortho_surface: null pointer");
+  return launch_ortho_surface(*grid, dsm, height, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_ortho_zbuf(const adamvs_ortho_grid* grid, const float* dsm, const adamvs_ortho_view* view, unsigned* zbuf,
+                                 unsigned* big_count, unsigned* big_list, long big_capacity, void* stream) {
+  if (int rc = ortho_check_grid(grid, "ortho_zbuf")) return rc;
+  if (int rc = ortho_check_view(view, "ortho_zbuf")) return rc;
+  ADAMVS_CHECK_ARG(dsm && zbuf && big_count && big_list, "ortho_zbuf: null pointer");
+  const long need = 2L * (grid->W - 1) * (grid->H - 1);
+  ADAMVS_CHECK_ARG(big_capacity >= need, "ortho_zbuf: big_capacity %ld < 2 (W-1)(H-1) = %ld", big_capacity, need);
+  return launch_ortho_zbuf(*grid, dsm, *view, zbuf, big_count, big_list, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_ortho_compose(const adamvs_ortho_grid* grid, const adamvs_ortho_view* view, int view_id, const double* height,
+                                    const unsigned* zbuf, int mode, float border, float feather_px, float occlusion_tol, float* acc,
+                                    float* wmax, int* view_state, int* nvis, void* stream) {
+  if (int rc = ortho_check_grid(grid, "ortho_compose")) return rc;
+  if (int rc = ortho_check_view(view, "ortho_compose")) return rc;
+  ADAMVS_CHECK_ARG(height && zbuf && acc && wmax && view_state && nvis, "ortho_compose: null pointer");
+  ADAMVS_CHECK_ARG(mode == ADAMVS_ORTHO_BEST || mode == ADAMVS_ORTHO_FEATHER, "ortho_compose: mode=%d", mode);
+  ADAMVS_CHECK_ARG(std::isfinite(border) && border >= 0.f, "ortho_compose: border=%g (finite, >= 0)", (double)border);
+  ADAMVS_CHECK_ARG(std::isfinite(feather_px) && feather_px > 0.f, "ortho_compose: feather_px=%g (finite, > 0)", (double)feather_px);
+  ADAMVS_CHECK_ARG(std::isfinite(occlusion_tol) && occlusion_tol >= 0.f, "ortho_compose: occlusion_tol=%g (finite, >= 0)",
+                   (double)occlusion_tol);
+  return launch_ortho_compose(*grid, *view, view_id, height, zbuf, mode, border, feather_px, occlusion_tol, acc, wmax, view_state, nvis,
+                              (hipStream_t)stream);
+}
+
+extern "C" int adamvs_ortho_finalize(const adamvs_ortho_grid* grid, const float* acc, const int* view_state, const int* nvis,
+                                     unsigned char* rgba, int* view_out, unsigned short* nvis_out, void* stream) {
+  if (int rc = ortho_check_grid(grid, "ortho_finalize")) return rc;
+  ADAMVS_CHECK_ARG(acc && view_state && nvis && rgba && view_out && nvis_out, "ortho_finalize: null pointer");
+  return launch_ortho_finalize(*grid, acc, view_state, nvis, rgba, view_out, nvis_out, (hipStream_t)stream);
+}

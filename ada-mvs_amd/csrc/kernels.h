@@ -174,4 +174,17 @@ int launch_mesh_emit(const adamvs_mesh_brick& b, const float* tsdf, const unsign
                      const unsigned* vert_offsets, const unsigned* tri_offsets, unsigned vertex_base, double* xyz, uint8_t* rgb,
                      unsigned* first_vertex, long vert_capacity, unsigned* faces, long tri_capacity, hipStream_t st);
 
+
+// ortho.hip: image orthophoto over a DSM, z-buffered per view (include/adamvs_hip.h, "Image orthophoto")
+constexpr int ORTHO_TILE = ADAMVS_ORTHO_TILE;
+constexpr int ORTHO_SMALL_PX = ADAMVS_ORTHO_SMALL_PX;
+constexpr float ORTHO_NEAR = ADAMVS_ORTHO_NEAR;
+int launch_ortho_surface(const adamvs_ortho_grid& g, const float* dsm, double* height, hipStream_t st);
+int launch_ortho_zbuf(const adamvs_ortho_grid& g, const float* dsm, const adamvs_ortho_view& v, unsigned* zbuf, unsigned* big_count,
+                      unsigned* big_list, hipStream_t st);
+int launch_ortho_compose(const adamvs_ortho_grid& g, const adamvs_ortho_view& v, int view_id, const double* height, const unsigned* zbuf,
+                         int mode, float border, float feather_px, float tol, float* acc, float* wmax, int* view, int* nvis, hipStream_t st);
+int launch_ortho_finalize(const adamvs_ortho_grid& g, const float* acc, const int* view, const int* nvis, uint8_t* rgba, int* view_out,
+                          uint16_t* nvis_out, hipStream_t st);
+
 }  // namespace adamvs

@@ -1,0 +1,321 @@
+// Image orthophoto: the source images mosaicked over a DSM into a true orthophoto (the step after dsm_whu.py;
+// include/adamvs_hip.h "Image orthophoto" states every operation).  Per scene, then per view in ascending image id:
+//
+//   k_ortho_surface      once: one lane per orthophoto cell, the height of the triangulated DSM at its centre (fp64)
+//   k_ortho_zbuf_clear   per view: the depth buffer to +inf
+//   k_ortho_zbuf_small   per view: one lane per DSM quad, its two triangles; a triangle whose pixel box holds at most
+//                        ORTHO_SMALL_PX pixel centres is rasterised by the lane, a larger one is appended to a list
+//   k_ortho_zbuf_large   per view: one wave per listed triangle, the lanes stride over its pixel box
+//   k_ortho_compose      per view: one lane per cell, visibility against the depth buffer and the cell's state update
+//   k_ortho_finalize     once: RGBA, chosen view and visible-view count
+//
+// The only atomics are the depth buffer's 32-bit unsigned min on the bits of positive floats (order-independent) and the
+// large-triangle list counter (its order only decides which wave writes which min).  Every cell's state is owned by one lane
+// across the views, so the output is bit-identical from run to run.
+#include "common.h"
+#include "kernels.h"
+#include "persistent.h"
+
+// The header states the arithmetic operation by operation: no contraction into fma in this file.
+#pragma clang fp contract(off)
+
+namespace adamvs {
+
+static_assert(ORTHO_TILE == 256, "kernels below assume workgroups of four waves");
+
+constexpr unsigned ZBUF_EMPTY = 0x7F800000u;     // +inf
+
+struct OrthoArgs {
+  double x0, y_top, gsd;        // the DSM grid
+  int W, H, K;                  // DSM cells, upsample
+};
+
+struct OrthoCam {
+  double C[3];
+  float R[9], Kc[6];            // R_cw, the first two rows of K
+  int H, W;
+};
+
+static OrthoArgs ortho_args(const adamvs_ortho_grid& g) { return OrthoArgs{g.x0, g.y_top, g.gsd, g.W, g.H, g.K}; }
+
+static OrthoCam ortho_cam(const adamvs_ortho_view& v) {
+  OrthoCam c;
+  for (int k = 0; k < 3; ++k) c.C[k] = v.C[k];
+  for (int k = 0; k < 9; ++k) c.R[k] = v.R[k];
+  for (int k = 0; k < 6; ++k) c.Kc[k] = v.K[k];
+  c.H = v.H;
+  c.W = v.W;
+  return c;
+}
+
+// World point (fp64) -> d = (float)(X - C), camera-frame p = R_cw d, pixel (u, v) and depth z (fp32).
+struct Proj {
+  float dx, dy, dz, u, v, z;
+};
+
+__device__ __forceinline__ Proj project(const OrthoCam& c, double X, double Y, double Z) {
+  Proj r;
+  r.dx = (float)(X - c.C[0]);
+  r.dy = (float)(Y - c.C[1]);
+  r.dz = (float)(Z - c.C[2]);
+  const float px = c.R[0] * r.dx + c.R[1] * r.dy + c.R[2] * r.dz;
+  const float py = c.R[3] * r.dx + c.R[4] * r.dy + c.R[5] * r.dz;
+  r.z = c.R[6] * r.dx + c.R[7] * r.dy + c.R[8] * r.dz;
+  r.u = (c.Kc[0] * px + c.Kc[1] * py + c.Kc[2] * r.z) / r.z;
+  r.v = (c.Kc[3] * px + c.Kc[4] * py + c.Kc[5] * r.z) / r.z;
+  return r;
+}
+
+// ---- surface --------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ortho_surface(const OrthoArgs a, const float* __restrict__ dsm, double* __restrict__ height) {
+  const int Wo = a.W * a.K, Ho = a.H * a.K;
+  const long n = (long)blockIdx.x * ORTHO_TILE + threadIdx.x;
+  if (n >= (long)Wo * Ho) return;
+  const int i = (int)(n % Wo), j = (int)(n / Wo);
+  double s = ((double)i + 0.5) / (double)a.K - 0.5, t = ((double)j + 0.5) / (double)a.K - 0.5;
+  s = fmin(fmax(s, 0.0), (double)(a.W - 1));
+  t = fmin(fmax(t, 0.0), (double)(a.H - 1));
+  const int ia = (int)floor(s), ib = (int)floor(t);
+  const double fs = s - (double)ia, ft = t - (double)ib;
+  int va[3], vb[3];
+  double w[3];
+  va[0] = ia, vb[0] = ib, va[2] = ia + 1, vb[2] = ib + 1;
+  if (fs >= ft) {
+    va[1] = ia + 1, vb[1] = ib;
+    w[0] = 1.0 - fs, w[1] = fs - ft, w[2] = ft;
+  } else {
+    va[1] = ia, vb[1] = ib + 1;
+    w[0] = 1.0 - ft, w[1] = ft - fs, w[2] = fs;
+  }
+  double h = 0.0;
+  bool ok = true;
+  for (int k = 0; k < 3; ++k) {
+    if (!(w[k] > 0.0)) continue;                       // a vertex of weight 0 is not read (it may lie past the grid)
+    const float z = dsm[(long)vb[k] * a.W + va[k]];
+    ok = ok && isfinite(z);
+    h = h + w[k] * (double)z;
+  }
+  height[n] = ok ? h : __longlong_as_double(0x7FF8000000000000ll);
+}
+
+// ---- z-buffer -------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ortho_zbuf_clear(unsigned* __restrict__ zbuf, long n) {
+  const long k = (long)blockIdx.x * ORTHO_TILE + threadIdx.x;
+  if (k < n) zbuf[k] = ZBUF_EMPTY;
+}
+
+// One triangle in screen space, oriented (area > 0), with its clamped pixel box.
+struct Tri {
+  float u[3], v[3], iz[3], area;
+  int u0, u1, v0, v1;       // inclusive pixel-centre box; empty if u0 > u1 or v0 > v1
+};
+
+// Vertex q of triangle `half` of quad (qa, qb): half 0 = (a,b) (a+1,b) (a+1,b+1), half 1 = (a,b) (a,b+1) (a+1,b+1).
+__device__ __forceinline__ bool setup_tri(const OrthoArgs& a, const OrthoCam& c, const float* __restrict__ dsm, int qa, int qb,
+                                          int half, Tri& t) {
+  const int da[3] = {0, half == 0 ? 1 : 0, 1}, db[3] = {0, half == 0 ? 0 : 1, 1};
+  for (int k = 0; k < 3; ++k) {
+    const int va = qa + da[k], vb = qb + db[k];
+    const float zw = dsm[(long)vb * a.W + va];
+    if (!isfinite(zw)) return false;
+    const Proj p = project(c, a.x0 + ((double)va + 0.5) * a.gsd, a.y_top - ((double)vb + 0.5) * a.gsd, (double)zw);
+    if (!(p.z > ORTHO_NEAR) || !isfinite(p.u) || !isfinite(p.v) || !isfinite(p.z)) return false;
+    t.u[k] = p.u;
+    t.v[k] = p.v;
+    t.iz[k] = 1.f / p.z;
+  }
+  float area = (t.u[1] - t.u[0]) * (t.v[2] - t.v[0]) - (t.v[1] - t.v[0]) * (t.u[2] - t.u[0]);
+  if (!(area != 0.f) || !isfinite(area)) return false;
+  if (area < 0.f) {
+    float x = t.u[1]; t.u[1] = t.u[2]; t.u[2] = x;
+    x = t.v[1]; t.v[1] = t.v[2]; t.v[2] = x;
+    x = t.iz[1]; t.iz[1] = t.iz[2]; t.iz[2] = x;
+    area = -area;
+  }
+  t.area = area;
+  const float umn = fminf(fminf(t.u[0], t.u[1]), t.u[2]), umx = fmaxf(fmaxf(t.u[0], t.u[1]), t.u[2]);
+  const float vmn = fminf(fminf(t.v[0], t.v[1]), t.v[2]), vmx = fmaxf(fmaxf(t.v[0], t.v[1]), t.v[2]);
+  // clamp in float before the conversion: a vertex near the camera plane projects far outside the image
+  t.u0 = (int)fminf(fmaxf(ceilf(umn), 0.f), (float)c.W);
+  t.u1 = (int)fmaxf(fminf(floorf(umx), (float)(c.W - 1)), -1.f);
+  t.v0 = (int)fminf(fmaxf(ceilf(vmn), 0.f), (float)c.H);
+  t.v1 = (int)fmaxf(fminf(floorf(vmx), (float)(c.H - 1)), -1.f);
+  return t.u0 <= t.u1 && t.v0 <= t.v1;
+}
+
+__device__ __forceinline__ void raster_pixel(const Tri& t, int pu, int pv, int W, unsigned* __restrict__ zbuf) {
+  const float x = (float)pu, y = (float)pv;
+  const float e0 = (t.u[2] - t.u[1]) * (y - t.v[1]) - (t.v[2] - t.v[1]) * (x - t.u[1]);
+  const float e1 = (t.u[0] - t.u[2]) * (y - t.v[2]) - (t.v[0] - t.v[2]) * (x - t.u[2]);
+  const float e2 = (t.u[1] - t.u[0]) * (y - t.v[0]) - (t.v[1] - t.v[0]) * (x - t.u[0]);
+  if (!(e0 >= 0.f && e1 >= 0.f && e2 >= 0.f)) return;
+  const float z = t.area / (e0 * t.iz[0] + e1 * t.iz[1] + e2 * t.iz[2]);
+  if (!(z > 0.f) || !isfinite(z)) return;
+  atomicMin(zbuf + (long)pv * W + pu, __float_as_uint(z));
+}
+
+__global__ __launch_bounds__(256) void k_ortho_zbuf_small(const OrthoArgs a, const OrthoCam c, const float* __restrict__ dsm,
+                                                          unsigned* __restrict__ zbuf, unsigned* __restrict__ big_count,
+                                                          unsigned* __restrict__ big_list) {
+  const long nq = (long)(a.W - 1) * (a.H - 1);
+  const long q = (long)blockIdx.x * ORTHO_TILE + threadIdx.x;
+  if (q >= nq) return;
+  const int qa = (int)(q % (a.W - 1)), qb = (int)(q / (a.W - 1));
+  for (int half = 0; half < 2; ++half) {
+    Tri t;
+    if (!setup_tri(a, c, dsm, qa, qb, half, t)) continue;
+    const int bw = t.u1 - t.u0 + 1, bh = t.v1 - t.v0 + 1;
+    if ((long)bw * bh > ORTHO_SMALL_PX) {
+      const unsigned slot = atomicAdd(big_count, 1u);        // slot < 2 nq: every triangle is appended at most once
+      big_list[slot] = (unsigned)(2 * q + half);
+      continue;
+    }
+    for (int pv = t.v0; pv <= t.v1; ++pv)
+      for (int pu = t.u0; pu <= t.u1; ++pu) raster_pixel(t, pu, pv, c.W, zbuf);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ortho_zbuf_large(const OrthoArgs a, const OrthoCam c, const float* __restrict__ dsm,
+                                                          unsigned* __restrict__ zbuf, const unsigned* __restrict__ big_count,
+                                                          const unsigned* __restrict__ big_list) {
+  const unsigned n = *big_count;
+  const int lane = threadIdx.x & 63;
+  const unsigned waves = gridDim.x * (ORTHO_TILE / 64);
+  for (unsigned e = blockIdx.x * (ORTHO_TILE / 64) + (threadIdx.x >> 6); e < n; e += waves) {
+    const unsigned id = big_list[e];
+    const long q = (long)(id >> 1);
+    Tri t;
+    if (!setup_tri(a, c, dsm, (int)(q % (a.W - 1)), (int)(q / (a.W - 1)), (int)(id & 1u), t)) continue;
+    const int bw = t.u1 - t.u0 + 1;
+    const long npx = (long)bw * (t.v1 - t.v0 + 1);
+    for (long k = lane; k < npx; k += 64) raster_pixel(t, t.u0 + (int)(k % bw), t.v0 + (int)(k / bw), c.W, zbuf);
+  }
+}
+
+// ---- compose and finalize -------------------------------------------------------------------------------------------
+template <bool FEATHER>
+__global__ __launch_bounds__(256) void k_ortho_compose(const OrthoArgs a, const OrthoCam c, const uint8_t* __restrict__ rgba, int view_id,
+                                                       const double* __restrict__ height, const unsigned* __restrict__ zbuf, float border,
+                                                       float feather_px, float tol, f32x4* __restrict__ acc, float* __restrict__ wmax,
+                                                       int* __restrict__ view, int* __restrict__ nvis) {
+  const int Wo = a.W * a.K, Ho = a.H * a.K;
+  const long n = (long)blockIdx.x * ORTHO_TILE + threadIdx.x;
+  if (n >= (long)Wo * Ho) return;
+  const double h = height[n];
+  if (isnan(h)) return;
+  const int i = (int)(n % Wo), j = (int)(n / Wo);
+  const double g = a.gsd / (double)a.K;
+  const Proj p = project(c, a.x0 + ((double)i + 0.5) * g, a.y_top - ((double)j + 0.5) * g, h);
+  if (!(p.z > 0.f)) return;
+  const float umax = (float)(c.W - 1) - border, vmax = (float)(c.H - 1) - border;
+  if (!(p.u >= border && p.u <= umax && p.v >= border && p.v <= vmax)) return;       // NaN fails too
+  const int pu = (int)floorf(p.u + 0.5f), pv = (int)floorf(p.v + 0.5f);
+  const float zb = __uint_as_float(zbuf[(long)pv * c.W + pu]);
+  if (!(p.z <= zb + tol)) return;
+  const float s = -p.dz / sqrtf(p.dx * p.dx + p.dy * p.dy + p.dz * p.dz);
+  // bilinear sample
+  const int xa = (int)floorf(p.u), ya = (int)floorf(p.v);
+  const float fx = p.u - (float)xa, fy = p.v - (float)ya;
+  const int xb = xa + 1 < c.W ? xa + 1 : c.W - 1, yb = ya + 1 < c.H ? ya + 1 : c.H - 1;
+  const unsigned p00 = *(const unsigned*)(rgba + 4 * ((long)ya * c.W + xa)), p10 = *(const unsigned*)(rgba + 4 * ((long)ya * c.W + xb));
+  const unsigned p01 = *(const unsigned*)(rgba + 4 * ((long)yb * c.W + xa)), p11 = *(const unsigned*)(rgba + 4 * ((long)yb * c.W + xb));
+  float col[3];
+  for (int ch = 0; ch < 3; ++ch) {
+    const float c00 = (float)((p00 >> (8 * ch)) & 255u), c10 = (float)((p10 >> (8 * ch)) & 255u);
+    const float c01 = (float)((p01 >> (8 * ch)) & 255u), c11 = (float)((p11 >> (8 * ch)) & 255u);
+    col[ch] = (1.f - fy) * ((1.f - fx) * c00 + fx * c10) + fy * ((1.f - fx) * c01 + fx * c11);
+  }
+  nvis[n] = nvis[n] + 1;
+  if (FEATHER) {
+    const float e = fminf(fminf(p.u, (float)(c.W - 1) - p.u), fminf(p.v, (float)(c.H - 1) - p.v));
+    const float s2 = s * s;
+    const float w = s2 * s2 * fminf(1.f, (e - border) / feather_px);
+    f32x4 A = acc[n];
+    A[0] = A[0] + w;
+    A[1] = A[1] + w * col[0];
+    A[2] = A[2] + w * col[1];
+    A[3] = A[3] + w * col[2];
+    acc[n] = A;
+    if (w > wmax[n]) {
+      wmax[n] = w;
+      view[n] = view_id;
+    }
+  } else if (s > wmax[n]) {
+    wmax[n] = s;
+    view[n] = view_id;
+    acc[n] = f32x4{1.f, col[0], col[1], col[2]};
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ortho_finalize(long ncell, const f32x4* __restrict__ acc, const int* __restrict__ view,
+                                                        const int* __restrict__ nvis, unsigned* __restrict__ rgba_out,
+                                                        int* __restrict__ view_out, uint16_t* __restrict__ nvis_out) {
+  const long n = (long)blockIdx.x * ORTHO_TILE + threadIdx.x;
+  if (n >= ncell) return;
+  const f32x4 A = acc[n];
+  const int vw = view[n];
+  unsigned px = 0u;
+  if (vw >= 0 && A[0] > 0.f) {
+    px = 255u << 24;
+    for (int ch = 0; ch < 3; ++ch) {
+      const float q = floorf(A[1 + ch] / A[0] + 0.5f);
+      px |= (unsigned)fminf(fmaxf(q, 0.f), 255.f) << (8 * ch);
+    }
+  }
+  rgba_out[n] = px;
+  view_out[n] = px ? vw : -1;
+  const int k = nvis[n];
+  nvis_out[n] = (uint16_t)(k < 65535 ? k : 65535);
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------------------
+static unsigned ortho_blocks(long n) { return (unsigned)((n + ORTHO_TILE - 1) / ORTHO_TILE); }
+
+int launch_ortho_surface(const adamvs_ortho_grid& g, const float* dsm, double* height, hipStream_t st) {
+  const long n = (long)g.W * g.K * g.H * g.K;
+  hipLaunchKernelGGL(k_ortho_surface, dim3(ortho_blocks(n)), dim3(ORTHO_TILE), 0, st, ortho_args(g), dsm, height);
+  ADAMVS_CHECK_LAUNCH("ortho_surface");
+  return 0;
+}
+
+int launch_ortho_zbuf(const adamvs_ortho_grid& g, const float* dsm, const adamvs_ortho_view& v, unsigned* zbuf, unsigned* big_count,
+                      unsigned* big_list, hipStream_t st) {
+  const OrthoArgs a = ortho_args(g);
+  const OrthoCam c = ortho_cam(v);
+  const long npx = (long)v.W * v.H;
+  hipLaunchKernelGGL(k_ortho_zbuf_clear, dim3(ortho_blocks(npx)), dim3(ORTHO_TILE), 0, st, zbuf, npx);
+  ADAMVS_CHECK_LAUNCH("ortho_zbuf_clear");
+  const long nq = (long)(g.W - 1) * (g.H - 1);
+  if (nq == 0) return 0;
+  hipError_t e = hipMemsetAsync(big_count, 0, sizeof(unsigned), st);
+  if (e != hipSuccess) return set_error((int)e, "ortho_zbuf: hipMemsetAsync: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(k_ortho_zbuf_small, dim3(ortho_blocks(nq)), dim3(ORTHO_TILE), 0, st, a, c, dsm, zbuf, big_count, big_list);
+  ADAMVS_CHECK_LAUNCH("ortho_zbuf_small");
+  // the list length is known on the device only: a resident grid strides over it, one wave per triangle
+  return launch_resident<k_ortho_zbuf_large>((nq * 2 + 3) / 4, 0, st, "ortho_zbuf_large", a, c, dsm, zbuf, (const unsigned*)big_count,
+                                             (const unsigned*)big_list);
+}
+
+int launch_ortho_compose(const adamvs_ortho_grid& g, const adamvs_ortho_view& v, int view_id, const double* height, const unsigned* zbuf,
+                         int mode, float border, float feather_px, float tol, float* acc, float* wmax, int* view, int* nvis, hipStream_t st) {
+  const long n = (long)g.W * g.K * g.H * g.K;
+  if (mode == ADAMVS_ORTHO_FEATHER)
+    hipLaunchKernelGGL(k_ortho_compose<true>, dim3(ortho_blocks(n)), dim3(ORTHO_TILE), 0, st, ortho_args(g), ortho_cam(v), v.rgba,
+                       view_id, height, zbuf, border, feather_px, tol, (f32x4*)acc, wmax, view, nvis);
+  else
+    hipLaunchKernelGGL(k_ortho_compose<false>, dim3(ortho_blocks(n)), dim3(ORTHO_TILE), 0, st, ortho_args(g), ortho_cam(v), v.rgba,
+                       view_id, height, zbuf, border, feather_px, tol, (f32x4*)acc, wmax, view, nvis);
+  ADAMVS_CHECK_LAUNCH("ortho_compose");
+  return 0;
+}
+
+int launch_ortho_finalize(const adamvs_ortho_grid& g, const float* acc, const int* view, const int* nvis, uint8_t* rgba, int* view_out,
+                          uint16_t* nvis_out, hipStream_t st) {
+  const long n = (long)g.W * g.K * g.H * g.K;
+  hipLaunchKernelGGL(k_ortho_finalize, dim3(ortho_blocks(n)), dim3(ORTHO_TILE), 0, st, n, (const f32x4*)acc, view, nvis, (unsigned*)rgba,
+                     view_out, nvis_out);
+  ADAMVS_CHECK_LAUNCH("ortho_finalize");
+  return 0;
+}
+
+}  // namespace adamvs

@@ -6,6 +6,7 @@ computation below happens in libadamvs_hip.so.  All functions require CUDA
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -753,3 +754,81 @@ def mesh_extract(brick, tsdf, weight, rgba, vertex_base=0):
     check(lib.adamvs_mesh_emit(ctypes.byref(brick), _p(tsdf), _p(rgba), _p(code), _p(mask), _p(vert_off), _p(tri_off), int(vertex_base),
                                _p(xyz), _p(rgb), _p(first), nv, _p(faces), nt, st), "mesh_emit")
     return xyz[:nv], rgb[:nv], faces[:nt]
+
+
+# ---- image orthophoto (csrc/ortho.hip; driven view by view by ada_mvs_amd/ortho.py) ------------------------------------------
+# The depth buffer is int32 holding uint32 float bits; acc is float32 [N, 4]; view and nvis int32; nvis_out int16 (uint16).
+def ortho_grid(x0, y_top, gsd, W, H, K):
+    """-> _lib.OrthoGrid (adamvs_ortho_grid)."""
+    g = _lib.OrthoGrid()
+    g.x0, g.y_top, g.gsd, g.W, g.H, g.K = float(x0), float(y_top), float(gsd), int(W), int(H), int(K)
+    return g
+
+
+def ortho_view(K, R_cw, C, rgba):
+    """K [3, 3], R_cw [3, 3] (rounded here to fp32), C [3] fp64, rgba device [H, W, 4] uint8 -> _lib.OrthoView.  The image
+    tensor must outlive it."""
+    rgba = _dev_as(rgba, "rgba", torch.uint8)
+    if rgba.dim() != 3 or rgba.shape[2] != 4:
+        raise _lib.AdaMVSHipError("rgba must be [H, W, 4], got %s" % (tuple(rgba.shape),))
+    v = _lib.OrthoView()
+    v.C[:] = [float(c) for c in np.asarray(C, np.float64).reshape(-1)]
+    v.R[:] = [float(r) for r in np.asarray(R_cw, np.float64).reshape(-1)]
+    v.K[:] = [float(k) for k in np.asarray(K, np.float64).reshape(-1)]
+    v.H, v.W = int(rgba.shape[0]), int(rgba.shape[1])
+    v.rgba = rgba.data_ptr()
+    return v
+
+
+def ortho_surface(grid, dsm):
+    """adamvs_ortho_surface: dsm device [H, W] float32 -> height [H K, W K] float64 (NaN: no surface)."""
+    dsm = _dev(dsm, "dsm")
+    if tuple(dsm.shape) != (grid.H, grid.W):
+        raise _lib.AdaMVSHipError("dsm %s, grid %d x %d" % (tuple(dsm.shape), grid.H, grid.W))
+    height = torch.empty(grid.H * grid.K, grid.W * grid.K, device=dsm.device, dtype=torch.float64)
+    check(_lib.load().adamvs_ortho_surface(ctypes.byref(grid), _p(dsm), _p(height), _stream()), "ortho_surface")
+    return height
+
+
+def ortho_zbuf(grid, dsm, view, zbuf, big):
+    """adamvs_ortho_zbuf into zbuf (device int32 [H_img, W_img], uint32 float bits); big: device int32 [1 + 2 (W-1)(H-1)]
+    (the large-triangle counter, then the list)."""
+    dsm = _dev(dsm, "dsm")
+    zbuf = _dev_as(zbuf, "zbuf", torch.int32)
+    big = _dev_as(big, "big", torch.int32)
+    if tuple(zbuf.shape) != (view.H, view.W):
+        raise _lib.AdaMVSHipError("zbuf %s, image %d x %d" % (tuple(zbuf.shape), view.H, view.W))
+    if tuple(dsm.shape) != (grid.H, grid.W) or big.numel() < 1:
+        raise _lib.AdaMVSHipError("dsm %s, grid %d x %d, big %d" % (tuple(dsm.shape), grid.H, grid.W, big.numel()))
+    check(_lib.load().adamvs_ortho_zbuf(ctypes.byref(grid), _p(dsm), ctypes.byref(view), _p(zbuf), _p(big),
+                                        ctypes.c_void_p(big.data_ptr() + 4), big.numel() - 1, _stream()), "ortho_zbuf")
+
+
+def ortho_compose(grid, view, view_id, height, zbuf, mode, border, feather_px, occlusion_tol, acc, wmax, vstate, nvis):
+    """adamvs_ortho_compose: one view into the cell state (acc float32 [N, 4], wmax float32 [N], vstate int32 [N], nvis int32 [N])."""
+    height = _dev_as(height, "height", torch.float64)
+    zbuf = _dev_as(zbuf, "zbuf", torch.int32)
+    n = grid.W * grid.K * grid.H * grid.K
+    tensors = (_dev(acc, "acc"), _dev(wmax, "wmax"), _dev_as(vstate, "view", torch.int32), _dev_as(nvis, "nvis", torch.int32))
+    if height.numel() != n or tensors[0].numel() != 4 * n or any(t.numel() != n for t in tensors[1:]) or zbuf.numel() != view.H * view.W:
+        raise _lib.AdaMVSHipError("ortho_compose: state sizes do not match %d cells" % n)
+    if any(not t.is_contiguous() for t in (acc, wmax, vstate, nvis)):
+        raise _lib.AdaMVSHipError("ortho_compose: the state must be contiguous (it is updated in place)")
+    check(_lib.load().adamvs_ortho_compose(ctypes.byref(grid), ctypes.byref(view), int(view_id), _p(height), _p(zbuf), int(mode),
+                                           float(border), float(feather_px), float(occlusion_tol), *(_p(t) for t in tensors), _stream()),
+          "ortho_compose")
+
+
+def ortho_finalize(grid, acc, vstate, nvis):
+    """adamvs_ortho_finalize -> (rgba [H_o, W_o, 4] uint8, view int32 [H_o, W_o], nvis int16 (uint16) [H_o, W_o])."""
+    Ho, Wo = grid.H * grid.K, grid.W * grid.K
+    acc, vstate, nvis = _dev(acc, "acc"), _dev_as(vstate, "view", torch.int32), _dev_as(nvis, "nvis", torch.int32)
+    if acc.numel() != 4 * Ho * Wo or vstate.numel() != Ho * Wo or nvis.numel() != Ho * Wo:
+        raise _lib.AdaMVSHipError("ortho_finalize: state sizes do not match %d cells" % (Ho * Wo))
+    dev = acc.device
+    rgba = torch.empty(Ho, Wo, 4, device=dev, dtype=torch.uint8)
+    view_out = torch.empty(Ho, Wo, device=dev, dtype=torch.int32)
+    nvis_out = torch.empty(Ho, Wo, device=dev, dtype=torch.int16)
+    check(_lib.load().adamvs_ortho_finalize(ctypes.byref(grid), _p(acc), _p(vstate), _p(nvis), _p(rgba), _p(view_out), _p(nvis_out),
+                                            _stream()), "ortho_finalize")
+    return rgba, view_out, nvis_out

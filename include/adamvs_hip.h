@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ADAMVS_ABI_VERSION 20
+#define ADAMVS_ABI_VERSION 21
 
 int adamvs_version(void);
 const char* adamvs_last_error_string(void);
@@ -701,6 +701,87 @@ int adamvs_mesh_emit(const adamvs_mesh_brick* brick, const float* tsdf, const un
                      const unsigned char* edge_mask, const unsigned* vert_offsets, const unsigned* tri_offsets, unsigned vertex_base,
                      double* xyz, unsigned char* rgb, unsigned* first_vertex, long vert_capacity, unsigned* faces, long tri_capacity,
                      void* stream);
+
+/* ---- Image orthophoto (after dsm_whu.py): the source images mosaicked over a DSM into a true orthophoto -------------------
+ * ada-mvs_amd/ortho.py drives it; ortho_whu.py is the CLI.  World axes: x east, y north, z up; rows run south.
+ *
+ * Grid.  The DSM grid (x0, y_top, gsd fp64; W x H cells, row 0 north) and K = upsample, an integer 1 .. 8.  The orthophoto
+ * has W_o = W K by H_o = H K cells of size g = gsd / K (fp64), at most ADAMVS_ORTHO_MAX_CELLS = 2^28; cell (i, j) (column i,
+ * row j) is entry j W_o + i and has its centre at x = x0 + (i + 1/2) g, y = y_top - (j + 1/2) g.
+ *
+ * Surface (adamvs_ortho_surface).  The DSM dsm [H][W] fp32 (NaN: no surface) is a triangulated height field: its vertices are
+ * the cell centres (a, b), world (x0 + (a + 1/2) gsd, y_top - (b + 1/2) gsd, dsm[b][a]) in fp64, and each quad
+ * (a, b) - (a+1, b+1) is split along that diagonal into (a,b) (a+1,b) (a+1,b+1) and (a,b) (a,b+1) (a+1,b+1).  For cell (i, j),
+ * in fp64:  s = (i + 1/2) / K - 1/2,  t = (j + 1/2) / K - 1/2,  clamped to [0, W-1] x [0, H-1];  a = floor(s), fs = s - a,
+ * b = floor(t), ft = t - b;  if fs >= ft the vertices (a,b) (a+1,b) (a+1,b+1) have weights (1-fs, fs-ft, ft), otherwise
+ * (a,b) (a,b+1) (a+1,b+1) have (1-ft, ft-fs, fs).  height = sum of w z over the vertices with w > 0, in that order (fp64);
+ * NaN unless every such vertex is finite.  Vertices of weight 0 are not read, so K = 1 gives the DSM cell for cell.
+ *
+ * Views.  A HOST pointer to an adamvs_ortho_view, copied into the arguments: C (camera centre, world, fp64), R = R_cw (fp32,
+ * row-major, world -> camera x right / y down / z forward), K (fp32, row-major, last row 0 0 1), the image [H][W][4] uint8
+ * RGBA (device; alpha ignored).  Projection of a world point X (fp64):  d = (float)(X - C) per axis (the difference in fp64,
+ * so 10^6 m coordinates lose nothing), p = R d, z = p.z, u = (K00 p.x + K01 p.y + K02 z) / z, v = (K10 p.x + K11 p.y + K12 z) / z,
+ * fp32, left to right, no contraction.  Pixel centres are integer (u, v).
+ *
+ * Z-buffer (adamvs_ortho_zbuf), per view: zbuf [H][W] uint32, the bits of a positive float, cleared to +inf (0x7F800000) by the
+ * call.  Every triangle of the split whose three vertices are finite, project with z > ADAMVS_ORTHO_NEAR = 0.1 m and finite
+ * (u, v), is rasterised:  area = (u1-u0)(v2-v0) - (v1-v0)(u2-u0); skipped if 0 or not finite; if < 0, vertices 1 and 2 swap and
+ * area = -area.  For a pixel centre (x, y) inside the image:  e0 = (u2-u1)(y-v1) - (v2-v1)(x-u1),
+ * e1 = (u0-u2)(y-v2) - (v0-v2)(x-u2),  e2 = (u1-u0)(y-v0) - (v1-v0)(x-u0);  covered iff e0, e1, e2 >= 0 (inclusive);
+ * depth = area / (e0 / z0 + e1 / z1 + e2 / z2) (1/z linear in screen space; the reciprocals 1/z_k taken first, fp32), and
+ * zbuf = atomicMin(zbuf, bits(depth)) (order-independent: bit-identical from run to run).  Triangles whose box of pixel
+ * centres holds more than ADAMVS_ORTHO_SMALL_PX are rasterised one wave per triangle from a list (big_list, at least
+ * 2 (W-1)(H-1) entries; big_count one uint32), so long triangles do not stall a wave of short ones; the result is the same.
+ *
+ * Visibility of the sample P = (x, y, height) of cell (i, j) in a view: height is not NaN; z > 0; border <= u <= W-1-border and
+ * border <= v <= H-1-border (fp32); and z <= zbuf[floor(v + 1/2)][floor(u + 1/2)] + occlusion_tol (fp32).
+ * Score s = -d.z / sqrt(d.x d.x + d.y d.y + d.z d.z) (fp32: the cosine of the ray's off-nadir angle).  Colour c = a bilinear
+ * sample at (u, v): x_a = floor(u), f_x = u - x_a, x_b = min(x_a + 1, W - 1) (likewise y),
+ * c = (1 - f_y)((1 - f_x) c(x_a,y_a) + f_x c(x_b,y_a)) + f_y((1 - f_x) c(x_a,y_b) + f_x c(x_b,y_b)) per channel, fp32.
+ *
+ * Compose (adamvs_ortho_compose), one call per view in ascending image id, one lane per cell (the cell's state is owned by
+ * that lane: no atomics).  State: acc [N][4] fp32, wmax [N] fp32, view [N] int32, nvis [N] int32; the caller initialises
+ * acc = 0, view = -1, nvis = 0 and wmax = -inf (best) or 0 (feather).  A visible view adds 1 to nvis and:
+ *   ADAMVS_ORTHO_BEST:    if s > wmax:  wmax = s, view = view_id, acc = (1, c)  (an equal score keeps the earlier view);
+ *   ADAMVS_ORTHO_FEATHER: e = min(u, W-1-u, v, H-1-v),  w = (s s)(s s) min(1, (e - border) / feather_px);
+ *                         acc += (w, w c) in fp32;  if w > wmax:  wmax = w, view = view_id.
+ * Finalize (adamvs_ortho_finalize): where view >= 0 and acc.0 > 0, rgba = (floor(acc.k / acc.0 + 1/2) clamped to 0 .. 255,
+ * k = 1..3, alpha 255) and view_out = view; elsewhere rgba = 0 and view_out = -1.  nvis_out = min(nvis, 65535) uint16.
+ * rgba [N][4] uint8, view_out [N] int32, nvis_out [N] uint16.
+ *
+ * Argument errors (<0, before any launch): a null pointer, W or H < 1, K not in 1 .. 8, W_o H_o > ADAMVS_ORTHO_MAX_CELLS,
+ * x0 / y_top / gsd not finite or gsd <= 0, a view of H or W < 1 or with a non-finite C, R or K or K's last row not 0 0 1,
+ * big_capacity < 2 (W-1)(H-1), an unknown mode, border < 0 or not finite, feather_px <= 0 or not finite, occlusion_tol < 0 or
+ * not finite. */
+#define ADAMVS_ORTHO_TILE 256
+#define ADAMVS_ORTHO_MAX_CELLS (1L << 28)
+#define ADAMVS_ORTHO_MAX_UPSAMPLE 8
+#define ADAMVS_ORTHO_NEAR 0.1f
+#define ADAMVS_ORTHO_SMALL_PX 16
+#define ADAMVS_ORTHO_BEST 0
+#define ADAMVS_ORTHO_FEATHER 1
+
+typedef struct {
+  double x0, y_top, gsd;
+  int W, H, K;
+} adamvs_ortho_grid;
+
+typedef struct {
+  double C[3];
+  float R[9];
+  float K[9];
+  int H, W;
+  const unsigned char* rgba;
+} adamvs_ortho_view;
+
+int adamvs_ortho_surface(const adamvs_ortho_grid* grid, const float* dsm, double* height, void* stream);
+int adamvs_ortho_zbuf(const adamvs_ortho_grid* grid, const float* dsm, const adamvs_ortho_view* view, unsigned* zbuf, unsigned* big_count,
+                      unsigned* big_list, long big_capacity, void* stream);
+int adamvs_ortho_compose(const adamvs_ortho_grid* grid, const adamvs_ortho_view* view, int view_id, const double* height,
+                         const unsigned* zbuf, int mode, float border, float feather_px, float occlusion_tol, float* acc, float* wmax,
+                         int* view_state, int* nvis, void* stream);
+int adamvs_ortho_finalize(const adamvs_ortho_grid* grid, const float* acc, const int* view_state, const int* nvis, unsigned char* rgba,
+                          int* view_out, unsigned short* nvis_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,105 @@
+"""Image orthophoto timing (csrc/ortho.hip): z-buffers and compose for the 5-view scene over an analytic DSM.
+    python tools/ortho_bench.py [--H 2752 --W 1856] [--gsd 0.16] [--steps 3] [--crop 192]
+The 5-view scene of tools/fusion_bench.py (ada_mvs_amd/fusion_synth.py: one nadir and four 40-degree obliques) with images
+textured by world position and face class (tests/ortho_scene.py), and its DSM cast analytically at gsd (the DSM is this
+step's input).  Per (K, mode) in {1, 2} x {best, feather}: one warm-up run, then `steps` timed runs of OrthoBuilder over all
+views; device events around each view's z-buffer and compose (the medians of their sums are reported), and the host round
+trip of ortho.from_dsm (host DSM in, host rasters out).  The byte model below is priced against 6.3 TB/s.  The CPU baseline is
+the numpy restatement (tests/ortho_ref.py) on a crop of crop x crop DSM cells, scaled to the whole grid.  One JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+
+import ada_mvs_amd  # noqa: E402,F401
+
+HBM_GBS = 6300.0               # the bandwidth the estimate was priced against
+TARGET_MS = 25.0               # device-side, all 5 views at K = 1
+
+
+def model_bytes(W, H, K, img_px, covered_px):
+    """Algorithmic bytes of one run: per view the z-buffer reads every DSM height once (4 B), clears and min-writes its buffer
+    (4 B per pixel and 4 B per covered pixel); compose reads the cell's height (8 B) and its state (acc 16 + wmax 4 + view 4 +
+    nvis 4 B), writes the state back, reads one z-buffer entry (4 B) and four image texels (16 B); finalize reads the state and
+    writes 10 B per cell; the surface pass reads the DSM and writes 8 B per cell."""
+    n = W * H * K * K
+    per_view = [4 * W * H + 4 * p + 4 * c + n * (8 + 2 * 28 + 4 + 16) for p, c in zip(img_px, covered_px)]
+    return sum(per_view) + n * (28 + 10) + 4 * W * H + 8 * n
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--H", type=int, default=2752)
+    ap.add_argument("--W", type=int, default=1856)
+    ap.add_argument("--gsd", type=float, default=0.16)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--crop", type=int, default=192)
+    args = ap.parse_args()
+    import torch
+    from ada_mvs_amd import ortho
+    import ortho_ref
+    import ortho_scene as S
+    if not torch.cuda.is_available():
+        raise SystemExit("ortho_bench: needs an MI355X")
+    dev = torch.device("cuda")
+    t0 = time.time()
+    cams = S.cameras(args.H, args.W)
+    views = S.views(cams, device=dev)
+    W, H = int(round(340.0 / args.gsd)), int(round(480.0 / args.gsd))
+    z, g = S.dsm_grid(args.gsd, -170.0, 240.0, W, H)
+    setup_s = time.time() - t0
+    res = dict(bench="ortho", H=args.H, W=args.W, views=len(views), gsd=args.gsd, dsm_cells=W * H, setup_s=round(setup_s, 1), runs=[])
+    worst_k1 = 0.0
+    for K in (1, 2):
+        for mode in ("best", "feather"):
+            zs, cs, rts = [], [], []
+            for step in range(args.steps + 1):
+                b = ortho.OrthoBuilder(g, K, mode, z, keep_zbufs=(step == 0))
+                for v in views:
+                    b.add_view(v)
+                r = b.finish()
+                if step == 0:
+                    covered = [int(np.isfinite(zb.cpu().numpy().view(np.float32)).sum()) for zb in b.zbufs.values()]
+                    coloured = r["cells_coloured"]
+                    continue
+                zs.append(r["zbuf_seconds"] * 1e3)
+                cs.append(r["compose_seconds"] * 1e3)
+                torch.cuda.synchronize()
+                t1 = time.time()
+                ortho.from_dsm(z, g, views, K, mode)
+                torch.cuda.synchronize()
+                rts.append((time.time() - t1) * 1e3)
+            zms, cms = float(np.median(zs)), float(np.median(cs))
+            nbytes = model_bytes(W, H, K, [c["H"] * c["W"] for c in cams], covered)
+            dev_ms = zms + cms
+            if K == 1:
+                worst_k1 = max(worst_k1, dev_ms)
+            res["runs"].append(dict(K=K, mode=mode, cells=W * H * K * K, zbuf_ms=round(zms, 3), compose_ms=round(cms, 3),
+                                    device_ms=round(dev_ms, 3), roundtrip_ms=round(float(np.median(rts)), 1),
+                                    model_mb=round(nbytes / 1e6, 1), model_ms_at_hbm=round(nbytes / (HBM_GBS * 1e6), 3),
+                                    cells_coloured=coloured))
+    # CPU baseline: the restatement on a crop, scaled by cells
+    c = args.crop
+    zc = np.ascontiguousarray(z[H // 2 - c // 2:H // 2 + c // 2, W // 2 - c // 2:W // 2 + c // 2])
+    gc = g._replace(x0=g.x0 + (W // 2 - c // 2) * g.gsd, y_top=g.y_top - (H // 2 - c // 2) * g.gsd, W=c, H=c)
+    hv = [dict(iid=v["iid"], K=v["K"], R=v["R"], C=v["C"], rgba=v["rgba_h"]) for v in views]
+    t1 = time.time()
+    ortho_ref.compose(gc, zc, 1, hv, "best")
+    cpu_s = time.time() - t1
+    res["cpu_ref"] = dict(crop_cells=c * c, seconds=round(cpu_s, 2), scaled_to_grid_s=round(cpu_s * W * H / (c * c), 1))
+    res["target_ms_k1"] = TARGET_MS
+    res["device_ms_k1_worst"] = round(worst_k1, 3)
+    res["target_met"] = worst_k1 <= TARGET_MS
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
