@@ -285,18 +285,19 @@ def infer_depth_stage(features, proj_matrices, depth_values, sd, pre, in_up, con
         weights = [F.interpolate(c, [h, w], mode="bilinear", align_corners=False)
                    for c in confidence_map[:len(src_feas)]]
 
-    state1 = torch.zeros(B, 8, h, w)
-    state2 = torch.zeros(B, 16, h // 2, w // 2)
+    dt = ref_fea.dtype                                           # fp32 as the reference; float64 for the tests' exact bars
+    state1 = torch.zeros(B, 8, h, w, dtype=dt)
+    state2 = torch.zeros(B, 16, h // 2, w // 2, dtype=dt)
     Ho, Wo = (2 * h, 2 * w) if in_up else (h, w)
-    exp_sum = torch.zeros(B, 1, Ho, Wo)
-    depth_image = torch.zeros(B, 1, Ho, Wo)
-    max_prob = torch.zeros(B, 1, Ho, Wo)
+    exp_sum = torch.zeros(B, 1, Ho, Wo, dtype=dt)
+    depth_image = torch.zeros(B, 1, Ho, Wo, dtype=dt)
+    max_prob = torch.zeros(B, 1, Ho, Wo, dtype=dt)
     for d in range(D):                                           # adamvs.py:495-527
         plane = depth_values[:, d:d + 1]
         sim = aggregate_similarity(ref_fea, src_feas, Rs, ts, plane[:, 0], weights)
         reg, state1, state2 = slice_reg_step(sim, state1, state2, sd, pre + "reg_fuse.", in_up)
         prob = reg.exp()                                         # no max-subtraction (Q5)
-        flag = (max_prob < prob).float()
+        flag = (max_prob < prob).to(prob.dtype)
         max_prob = flag * prob + (1 - flag) * max_prob
         if in_up:
             plane = F.interpolate(plane, [Ho, Wo], mode="bilinear", align_corners=False)

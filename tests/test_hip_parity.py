@@ -13,6 +13,8 @@ import pytest
 import torch
 
 from conftest import load_golden, rel_l1
+from fp64_bars import (FEATNET, PAIR_SIM, STAGE_CONF, STAGE_CONF_BX3, STAGE_DEPTH, STAGE_DEPTH_BX3, STEP, STEP_BX3, SWEEP, SWEEP_4K,
+                       SWEEP_BX3, check, double_sd)
 import ada_mvs_amd  # noqa: F401
 from ada_mvs_amd import synth
 
@@ -121,16 +123,20 @@ def test_pack_unpack_roundtrip(hip):
 
 
 # --------------------------------------------------------------------------- FeatureNet0
-@pytest.mark.parametrize("N,H,W", [(2, 64, 96), (3, 128, 160), (1, 96, 224)])
+@pytest.mark.parametrize("N,H,W", [(2, 64, 96), (3, 128, 160), (1, 96, 224),
+                                   (1, 32, 32), (2, 32, 160), (2, 160, 32), (5, 64, 96)])
 def test_feature_net0_against_oracle(hip, O, N, H, W):
     """adamvs_feature_net0 (MFMA convolutions, folded BatchNorm, context branches applied at pooled resolution)
-    against the CPU restatement of FeatureNet0.forward, stage by stage; also the NCHW dict of the mirror's forward()."""
+    against the CPU restatement of FeatureNet0.forward, stage by stage; also the NCHW dict of the mirror's forward().
+    Every stage map per element against the oracle in float64 too, at sizes that cut every tile: the minimum 32 x 32 (stage 1
+    is 8 x 8, its context pooled by 8 is 1 x 1), one tile row or column (32 x 160, 160 x 32), five images."""
     from ada_mvs_amd.models.adamvs import FeatureNet0
     net = FeatureNet0(8)
     sd = synth.seeded_state_dict(net, seed=2)
     net.load_state_dict(sd)
     x = torch.randn(N, 3, H, W, generator=torch.Generator().manual_seed(H))
     ref = O.feature_net(x, sd, "")
+    ref64 = O.feature_net(x.double(), double_sd(sd), "")
     net = net.cuda().eval()
     assert net.hip_supported(dev(x))
     maps = net.forward_cl(dev(x))
@@ -138,6 +144,7 @@ def test_feature_net0_against_oracle(hip, O, N, H, W):
         got = hip.unpack_features(maps[k], H // scale, W // scale)
         assert got.shape == ref["stage%d" % (k + 1)].shape
         assert rel_l1(got, ref["stage%d" % (k + 1)]) < OP_TOL, "stage%d" % (k + 1)
+        check(got, ref64["stage%d" % (k + 1)], *FEATNET, what="stage%d" % (k + 1))
     out = net(dev(x))
     assert rel_l1(out["stage2"], ref["stage2"]) < OP_TOL
     net.workspace_limit_bytes = hip.feature_net0_workspace_bytes(1, H, W)          # one image per call: same maps
@@ -191,19 +198,31 @@ def test_feature_net0_golden(hip):
 
 
 # --------------------------------------------------------------------------- pass A
-@pytest.mark.parametrize("C", [32, 16, 8])
-def test_pair_similarity(hip, O, C):
-    B, S, D, h, w = 2, 2, 12, 24, 40
+@pytest.mark.parametrize("C,D,h,w,baseline", [pytest.param(C, 12, 24, 40, 60.0, id=str(C)) for C in (32, 16, 8)] +
+                         [pytest.param(C, D, h, w, bl, id="%d-D%d-%dx%d-baseline%g" % (C, D, h, w, bl)) for C in (32, 16, 8)
+                          for D, h, w, bl in ((2, 24, 40, 60.0), (13, 24, 40, 60.0), (48, 24, 40, 60.0), (12, 17, 23, 60.0),
+                                              (12, 24, 40, 200.0))])
+def test_pair_similarity(hip, O, C, D, h, w, baseline):
+    """k_pair_similarity against the oracle, and every plane per element against it in float64: 2, 12, 13 and 48 planes, a
+    17 x 23 map (h*w no multiple of a block's 256 / G pixels), a baseline that sends taps out of the image."""
+    B, S = 2, 2
     feats = [synth.smooth_features(B, C, h, w, seed=v) for v in range(S + 1)]
-    proj = synth.rig_projections(S + 1, 4 * h, 4 * w, batch=B, baseline=60.0)["stage1"]
+    proj = synth.rig_projections(S + 1, 4 * h, 4 * w, batch=B, baseline=baseline)["stage1"]
     planes = O.depth_range_samples(torch.tensor([[400.0, 600.0]] * B), D, 0.0, [B, h, w])
     feat_cl = hip.pack_features(dev(torch.stack(feats, 0).reshape(-1, C, h, w)))
     rt = hip.relative_transforms(dev(proj))
     sim = hip.pair_similarity(feat_cl, rt, dev(planes), B, S, C, D, h, w).cpu().reshape(S, B, h, w, D)
+    zero = 0.0
     for s in range(S):
         R, t = O.relative_transform(proj[:, s + 1], proj[:, 0])
         ref = O.pair_similarity_volume(feats[0], feats[s + 1], R, t, planes)        # [B,D,h,w]
         assert rel_l1(sim[s].permute(0, 3, 1, 2), ref) < OP_TOL
+        R64, t64 = O.relative_transform(proj[:, s + 1].double(), proj[:, 0].double())
+        ref64 = O.pair_similarity_volume(feats[0].double(), feats[s + 1].double(), R64, t64, planes.double())
+        check(sim[s].permute(0, 3, 1, 2), ref64, *PAIR_SIM, what="source view %d" % s, dims="ndyx")
+        zero += float((ref64 == 0).double().mean()) / S
+    if baseline > 100.0:
+        assert zero > 0.1, "case must send taps out of the image (%g)" % zero
 
 
 def test_cost_reg_net_2d_golden(hip):
@@ -439,6 +458,33 @@ def test_slice_reg_step_ragged_shapes(hip, O, precision, k, h, w):
     assert rel_l1(n1, r1) < tol and rel_l1(n2, r2) < tol and rel_l1(reg, ref) < tol
 
 
+@pytest.mark.parametrize("k,h,w", [(0, 22, 38), (1, 30, 18), (2, 26, 50), (0, 4, 6)])
+@pytest.mark.parametrize("form", ["gru_wino=0", "gru_wino=7", "gru_wino=15", "bf16x3"])
+def test_slice_reg_step_every_form_against_float64(hip, O, set_option, form, k, h, w):
+    """One recurrent step (launch_slice_step: conv1, gates and candidate of both ConvGRU levels, conv2, the decoder) per element
+    against the oracle in float64, in every form: fp32 with the GRU convolutions direct (gru_wino = 0), the default mix (7) and
+    all four roles in F(2x2, 3x3) (15; each role's form is one bit), and bf16x3; the three stage variants (C = 32 / 16 / 8,
+    transposed or flat last layer) on the ragged sizes above; three consecutive steps, each fed the states the kernels left."""
+    m, sd = _model("tiny")
+    net = m.DepthNet[k].reg_fuse
+    if form == "bf16x3":
+        net.precision = "bf16x3"
+    else:
+        set_option("gru_wino", int(form.split("=")[1]))
+    B, C = 3, net.in_channels
+    g = torch.Generator().manual_seed(100 * k + h)
+    costs = [torch.randn(B, C, h, w, generator=g) for _ in range(3)]
+    s1 = torch.randn(B, 8, h, w, generator=g) * 0.5
+    s2 = torch.randn(B, 16, h // 2, w // 2, generator=g) * 0.5
+    sd64 = double_sd(sd)
+    r1, r2, n1, n2 = s1.double(), s2.double(), dev(s1), dev(s2)
+    for step, cost in enumerate(costs):
+        ref, r1, r2 = O.slice_reg_step(cost.double(), r1, r2, sd64, "DepthNet.%d.reg_fuse." % k, in_up=(k < 2))
+        reg, n1, n2 = net(dev(cost), n1, n2)
+        for got, want, name in ((reg, ref, "reg"), (n1, r1, "state1"), (n2, r2, "state2")):
+            check(got, want, *(STEP_BX3 if form == "bf16x3" else STEP), what="step %d %s" % (step, name))
+
+
 @pytest.mark.parametrize("k", [0, 1, 2])
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
 def test_slice_reg_step_many_tiles(hip, precision, k):
@@ -460,13 +506,39 @@ def test_slice_reg_step_many_tiles(hip, precision, k):
         assert torch.equal(many, one.expand_as(many)), name
 
 
+def _sweep_reference64(O, feats, proj, planes, vw, w1):
+    """The aggregated similarity of every plane (oracle.aggregate_similarity) and conv1 of it, in float64:
+    ([D,B,C,h,w], [D,B,8,h,w])."""
+    import torch.nn.functional as F
+    S, D = len(feats) - 1, planes.shape[1]
+    B, C, h, w = feats[0].shape
+    f64 = [f.double() for f in feats]
+    Rs, ts = zip(*[O.relative_transform(proj[:, s + 1].double(), proj[:, 0].double()) for s in range(S)])
+    sim = torch.stack([O.aggregate_similarity(f64[0], f64[1:], Rs, ts, planes[:, d].double(), [vw[s].unsqueeze(1).double() for s in range(S)])
+                       for d in range(D)])
+    return sim, F.relu(F.conv2d(sim.reshape(D * B, C, h, w), w1.double(), None, 1, 1)).reshape(D, B, 8, h, w)
+
+
+def _check_sweep(sim, c1, sim64, c164, c1_bars=SWEEP):
+    """aggregate_conv1's similarity [D,B,hw,C] (None: not returned) and c1 [D,B,hw,8] against _sweep_reference64, every
+    plane per element."""
+    D, B, C, h, w = sim64.shape
+    dims = ("plane", "n", "c", "y", "x")
+    if sim is not None:
+        check(sim.reshape(D, B, h, w, C).permute(0, 1, 4, 2, 3), sim64, *SWEEP, what="aggregated similarity", dims=dims)
+    check(c1.reshape(D, B, h, w, 8).permute(0, 1, 4, 2, 3), c164, *c1_bars, what="c1", dims=dims)
+
+
 @pytest.mark.parametrize("C,h,w,D,baseline", [(32, 16, 40, 3, 80.0), (16, 20, 36, 3, 80.0), (8, 24, 70, 3, 80.0),
                                               (32, 24, 40, 24, 8.0),        # narrow sweep: one LDS-resident chunk
                                               (32, 24, 40, 16, 400.0),      # wide sweep: chunks split, patches leave the image
-                                              (16, 40, 24, 10, 2500.0)])    # extreme: per-plane patches / global fallback
+                                              (16, 40, 24, 10, 2500.0),     # extreme: per-plane patches / global fallback
+                                              (32, 16, 40, 33, 8.0), (8, 24, 70, 40, 80.0)])    # two chunks of 32 planes
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
 def test_aggregate_conv1(hip, O, C, h, w, D, baseline, precision):
-    """Weighted aggregation (register-resident taps, arbitrary planes) + two-row conv1 (fp32 and split-bf16 MFMA)."""
+    """Weighted aggregation (register-resident taps, arbitrary planes) + two-row conv1 (fp32 and split-bf16 MFMA).  Every plane
+    of c1, and of the aggregated similarity where it fits one chunk (D <= 32), per element against the oracle in float64; two
+    chunks of planes in launch_sweep_conv1 (D = 33, 40); pixels whose view weights are all zero."""
     import torch.nn.functional as F
     B, S = 2, 3
     feats = [synth.smooth_features(B, C, h, w, seed=10 + v) for v in range(S + 1)]
@@ -479,12 +551,15 @@ def test_aggregate_conv1(hip, O, C, h, w, D, baseline, precision):
         step = (200 + 40 * torch.rand(B, 1, h, w, generator=g)) / (D - 1)
         planes = lo + step * torch.arange(D, dtype=torch.float32).reshape(1, D, 1, 1)
     vw = torch.rand(S, B, h, w, generator=g)
+    vw[:, 0, 5, 3] = 0.0                                 # every view weight 0: similarity 0 / 1e-5
+    vw[:, 1, h - 1, w - 1] = 0.0
     w1 = torch.randn(8, C, 3, 3, generator=g) * 0.1
     from ada_mvs_amd import packing
-    c1 = hip.aggregate_conv1(hip.pack_features(dev(torch.stack(feats, 0).reshape(-1, C, h, w))),
-                             hip.relative_transforms(dev(proj)), dev(planes), dev(vw),
-                             (packing.pack_conv1_two_row(w1) if precision == "fp32" else packing.pack_conv1_two_row_bf16x3(w1)).cuda(),
-                             B, S, C, D, h, w, precision=0 if precision == "fp32" else 1).cpu()      # [D,B,hw,8]
+    out = hip.aggregate_conv1(hip.pack_features(dev(torch.stack(feats, 0).reshape(-1, C, h, w))),
+                              hip.relative_transforms(dev(proj)), dev(planes), dev(vw),
+                              (packing.pack_conv1_two_row(w1) if precision == "fp32" else packing.pack_conv1_two_row_bf16x3(w1)).cuda(),
+                              B, S, C, D, h, w, precision=0 if precision == "fp32" else 1, return_similarity=D <= 32)
+    c1, sim_ws = (out[0].cpu(), out[1].cpu()) if D <= 32 else (out.cpu(), None)      # [D,B,hw,8], [D,B,hw,C]
     Rs, ts = zip(*[O.relative_transform(proj[:, s + 1], proj[:, 0]) for s in range(S)])
     zero_frac = 0.0
     for d in range(D):
@@ -494,6 +569,8 @@ def test_aggregate_conv1(hip, O, C, h, w, D, baseline, precision):
         assert rel_l1(c1[d].reshape(B, h, w, 8).permute(0, 3, 1, 2), ref) < (OP_TOL if precision == "fp32" else 2e-4), "plane %d" % d
     if baseline >= 400.0:
         assert zero_frac > 0.02, "case must include pixels whose every view projects outside (%g)" % zero_frac
+    sim64, c164 = _sweep_reference64(O, feats, proj, planes, vw, w1)
+    _check_sweep(sim_ws, c1, sim64, c164, SWEEP if precision == "fp32" else SWEEP_BX3)
 
 
 # --------------------------------------------------------------------------- stages / end to end
@@ -689,6 +766,20 @@ def test_train_test_twin_golden(hip):
         m(dev(g["imgs"]), proj, dev(dv3))
 
 
+def _check_stage64(O, got, feats, proj, planes, sd, stage, in_up, prev, interval, precision):
+    """One stage per pixel against the oracle in float64: depth and (first stage) pair depths in hypothesis intervals,
+    photometric and pair confidence absolute."""
+    ref = O.infer_depth_stage([f.double() for f in feats], proj.double(), planes.double(), double_sd(sd), "DepthNet.%d." % stage, in_up,
+                              None if prev is None else [c.double() for c in prev])
+    depth_bar, conf_bar = (STAGE_DEPTH, STAGE_CONF) if precision == "fp32" else (STAGE_DEPTH_BX3, STAGE_CONF_BX3)
+    check(got["depth"], ref["depth"], depth_bar, scale=interval, what="depth (hypothesis intervals)")
+    check(got["photometric_confidence"], ref["photometric_confidence"], conf_bar, scale=1.0, what="photometric confidence")
+    for i, want in enumerate(ref["pair_confidence"]):
+        check(got["pair_confidence"][i].reshape(want.shape), want, conf_bar, scale=1.0, what="pair confidence %d" % i)
+    for i, want in enumerate(ref["pair_result"]):
+        check(got["pair_result"][i], want, depth_bar, scale=interval, what="pair depth %d (hypothesis intervals)" % i)
+
+
 # --------------------------------------------------------------------------- software-pipelined recurrence
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
 @pytest.mark.parametrize("cfg,batch", [("tiny", 3), ("cfg1", 2)])
@@ -724,7 +815,7 @@ def test_pipelined_recurrence_on_ragged_stage_sizes(hip, O, set_option, precisio
     """One cascade stage (InferDepthNet0.forward, reference adamvs.py:433-533) on maps no tile size of any role divides
     (level-2 maps 11 x 19, 13 x 25, 2 x 3; the end-to-end model only meets multiples of 8) and 40 hypotheses = one
     full chunk of 32 plus a ragged one.  Every schedule of the recurrence -- the two-launch one runs conv2 inside the
-    level-2 gate tiles -- must equal the sequential launches bit for bit, and those the CPU oracle."""
+    level-2 gate tiles -- must equal the sequential launches bit for bit, and those the CPU oracle, per pixel in float64."""
     from ada_mvs_amd.models.adamvs import Infer_AdaMVSNet
     B, V, D = 2, 3, 40
     m = Infer_AdaMVSNet(48, [48, 32, 8], synth.DEPTH_INTERVALS_RATIO, False, [8, 8, 8], precision=precision)
@@ -755,13 +846,15 @@ def test_pipelined_recurrence_on_ragged_stage_sizes(hip, O, set_option, precisio
     for key in ("depth", "photometric_confidence"):
         assert outs["0"][key].shape == ref[key].shape
         assert rel_l1(outs["0"][key], ref[key]) < tol, key
+    _check_stage64(O, outs["0"], feats, proj, planes, sd, stage, net.in_up, prev, 4.0, precision)
 
 
 @pytest.mark.parametrize("seed", list(range(8)))
 def test_stage_on_random_shapes_against_oracle(hip, O, seed):
     """InferDepthNet0.forward (reference adamvs.py:433-533) on shapes drawn at random -- stage (first stage with
     CostRegNet2D, or a later one with resampled view weights), batch, number of source views, map size (even, down to
-    4 x 4), number of hypotheses, precision -- against the CPU oracle.  Seeds are fixed: the cases are reproducible."""
+    4 x 4), number of hypotheses, precision -- against the CPU oracle, and per pixel against it in float64.  Seeds are fixed: the
+    cases are reproducible."""
     from ada_mvs_amd.models.adamvs import Infer_AdaMVSNet
     rng = np.random.default_rng(1000 + seed)
     stage = int(rng.integers(0, 3))
@@ -796,6 +889,7 @@ def test_stage_on_random_shapes_against_oracle(hip, O, seed):
         assert rel_l1(got[key], ref[key]) < tol, (key,) + case
     for a, b in zip(got["pair_confidence"][:V - 1], ref["pair_confidence"]):
         assert rel_l1(a, b) < tol, ("pair_confidence",) + case
+    _check_stage64(O, got, feats, proj, planes, sd, stage, net.in_up, prev, 160.0 / max(D, 2), precision)
 
 
 def test_soft_argmin_op(hip):
@@ -945,7 +1039,8 @@ def test_sweep_blend_views_and_widths(hip, O, C, S):
     """The aggregation sweep (k_sweep_blend, reference adamvs.py:495-512) for every channel width and 1 ... 8 source views
     (lane q of a quad projects views q, q + 4; with C = 8 a quad holds two pixels and a lane projects up to four views),
     on a map whose width is no multiple of the pixels a workgroup takes, 19 planes (two full groups of 8 and a ragged one)
-    with per-pixel spacing, a baseline that sends the far views out of bounds: against the oracle."""
+    with per-pixel spacing, a baseline that sends the far views out of bounds: against the oracle; every plane of the
+    aggregated similarity and of c1 per element against it in float64."""
     import torch.nn.functional as F
     from ada_mvs_amd import packing
     B, D, h, w = 2, 19, 14, 42
@@ -959,12 +1054,14 @@ def test_sweep_blend_views_and_widths(hip, O, C, S):
     w1 = torch.randn(8, C, 3, 3, generator=g) * 0.1
     args = (hip.pack_features(dev(torch.stack(feats, 0).reshape(-1, C, h, w))), hip.relative_transforms(dev(proj)), dev(planes), dev(vw),
             packing.pack_conv1_two_row(w1).cuda(), B, S, C, D, h, w)
-    c1 = hip.aggregate_conv1(*args).cpu()
+    c1, sim_ws = hip.aggregate_conv1(*args, return_similarity=True)
+    c1 = c1.cpu()
     Rs, ts = zip(*[O.relative_transform(proj[:, s + 1], proj[:, 0]) for s in range(S)])
     for d in (0, 7, 8, 18):
         sim = O.aggregate_similarity(feats[0], feats[1:], Rs, ts, planes[:, d], [vw[s].unsqueeze(1) for s in range(S)])
         ref = F.relu(F.conv2d(sim, w1, None, 1, 1))
         assert rel_l1(c1[d].reshape(B, h, w, 8).permute(0, 3, 1, 2), ref) < OP_TOL, "plane %d" % d
+    _check_sweep(sim_ws.cpu(), c1, *_sweep_reference64(O, feats, proj, planes, vw, w1))
 
 
 def test_feature_net0_reads_views_in_place(hip):
@@ -1213,7 +1310,8 @@ def test_cost_reg_weights_of_another_layout_are_refused(hip):
 @pytest.mark.parametrize("C,S", [(32, 10), (16, 9), (8, 13), (8, 17)])
 def test_sweep_with_more_than_eight_source_views(hip, O, C, S):
     """The reference loops over any number of source views (adamvs.py:501); the sweep takes them in groups of eight, the later
-    groups adding to the first one's sums (csrc/sweep.hip).  Aggregated similarity and conv1 against the oracle."""
+    groups adding to the first one's sums (csrc/sweep.hip).  Aggregated similarity and conv1 against the oracle; every plane
+    per element against it in float64."""
     import torch.nn.functional as F
     from ada_mvs_amd import packing
     B, D, h, w = 2, 11, 12, 30
@@ -1233,6 +1331,86 @@ def test_sweep_with_more_than_eight_source_views(hip, O, C, S):
         ref = O.aggregate_similarity(feats[0], feats[1:], Rs, ts, planes[:, d], [vw[s].unsqueeze(1) for s in range(S)])
         assert rel_l1(sim[d].reshape(B, h, w, C).permute(0, 3, 1, 2), ref) < OP_TOL, "plane %d" % d
         assert rel_l1(c1[d].reshape(B, h, w, 8).permute(0, 3, 1, 2), F.relu(F.conv2d(ref, w1, None, 1, 1))) < OP_TOL, "plane %d" % d
+    _check_sweep(sim, c1, *_sweep_reference64(O, feats, proj, planes, vw, w1))
+
+
+def _sim_rows64(feat, rts, planes, vw, B, S, h, w, b, rows, d):
+    """oracle.aggregate_similarity in float64 for plane d at rows `rows` of batch item b, with oracle.warp_plane's gather
+    written out for those pixels; features, planes and view weights are read from the device tensors -> [len(rows), w, C]."""
+    ys = torch.tensor(rows, dtype=torch.float64).repeat_interleave(w)
+    xs = torch.arange(w, dtype=torch.float64).repeat(len(rows))
+    pix = (ys * w + xs).long().cuda()
+    take = lambda m, idx: feat[m].index_select(0, idx.long().cuda()).cpu().double()
+    ref = take(b, pix)
+    depth = planes[b, d].reshape(-1).index_select(0, pix).cpu().double()
+    num, wsum = 0.0, 1e-5
+    for s in range(S):
+        R, t = rts[s][0][b], rts[s][1][b]
+        p = R @ torch.stack((xs, ys, torch.ones_like(xs))) * depth + t.reshape(3, 1)
+        ix = ((p[0] / p[2] / ((w - 1) / 2) - 1 + 1) / 2) * (w - 1)
+        iy = ((p[1] / p[2] / ((h - 1) / 2) - 1 + 1) / 2) * (h - 1)
+        x0, y0 = ix.floor(), iy.floor()
+        warped = 0.0
+        for xx, yy, wt in ((x0, y0, (x0 + 1 - ix) * (y0 + 1 - iy)), (x0 + 1, y0, (ix - x0) * (y0 + 1 - iy)),
+                           (x0, y0 + 1, (x0 + 1 - ix) * (iy - y0)), (x0 + 1, y0 + 1, (ix - x0) * (iy - y0))):
+            ok = (xx >= 0) & (xx <= w - 1) & (yy >= 0) & (yy <= h - 1)
+            idx = torch.where(ok, yy.clamp(0, h - 1) * w + xx.clamp(0, w - 1), torch.zeros_like(xx))
+            warped = warped + take((s + 1) * B + b, idx) * (wt * ok).unsqueeze(1)
+        ws = vw[s, b].reshape(-1).index_select(0, pix).cpu().double()
+        num = num + warped * ref * ws.unsqueeze(1)
+        wsum = wsum + ws
+    return (num / wsum.unsqueeze(1)).reshape(len(rows), w, -1)
+
+
+@pytest.mark.parametrize("C,B,S", [(8, 4, 2), (8, 4, 5), (32, 1, 2), (32, 1, 5)])
+def test_sweep_of_feature_maps_of_two_gib_per_view(hip, O, C, B, S):
+    """Feature maps of 2 GiB and more per view (cfg3 stage 3 from 228 tiles a step, the reference's predict size from 14 samples
+    a batch): launch_sweep_c (csrc/sweep.hip) leaves the blend sweep, whose lane offsets are 32-bit, for
+    k_sweep_aggregate<C, 4 | 8>, and conv1 reads a similarity chunk of more than 4 GiB.  Band-limited features made on the device
+    (a bicubic upsample of a coarse random tensor); the float64 reference at the rows that matter, with the neighbours conv1
+    reads: the first row, the rows either side of the 2^31-byte offset inside a view, the last row of the last batch item.  The bar
+    is fp64_bars.SWEEP_4K: fp32 tap positions at 4096-pixel coordinates; a wrong offset past 2 GiB would be off by O(1)."""
+    h, w, D = 4096, 4112, 2
+    assert B * h * w * C * 4 >= 0x7fffffff           # launch_sweep_c's test: not the blend sweep
+    try:                                             # about 24 GB (C = 8) / 19 GB (C = 32), all of it freed before the next case
+        _two_gib_sweep(hip, O, C, B, S, D, h, w)
+        failure = None
+    except AssertionError as e:
+        failure = str(e)
+    torch.cuda.empty_cache()
+    assert failure is None, failure
+
+
+def _two_gib_sweep(hip, O, C, B, S, D, h, w):
+    import torch.nn.functional as F
+    from ada_mvs_amd import packing
+    gen = torch.Generator(device="cuda").manual_seed(C + S)
+    feat = torch.empty((S + 1) * B, h * w, C, device="cuda")
+    for v in range(S + 1):
+        coarse = torch.randn(B, C, h // 16, w // 16, device="cuda", generator=gen)
+        hip.pack_features(F.interpolate(coarse, size=(h, w), mode="bicubic", align_corners=False), out=feat[v * B:(v + 1) * B])
+    proj = synth.rig_projections(S + 1, 4 * h, 4 * w, batch=B)["stage1"]
+    planes = (420.0 + 40.0 * torch.rand(B, 1, h, w, device="cuda", generator=gen)
+              + 80.0 * torch.arange(D, device="cuda", dtype=torch.float32).view(1, D, 1, 1)).contiguous()
+    vw = torch.rand(S, B, h, w, device="cuda", generator=gen)
+    vw[:, B - 1, h - 1, :5] = 0.0                    # every view weight 0
+    w1 = torch.randn(8, C, 3, 3, generator=torch.Generator().manual_seed(C)) * 0.1
+    c1, sim = hip.aggregate_conv1(feat, hip.relative_transforms(dev(proj)), planes, vw, packing.pack_conv1_two_row(w1).cuda(),
+                                  B, S, C, D, h, w, return_similarity=True)
+    torch.cuda.synchronize()
+    rts = [O.relative_transform(proj[:, s + 1].double(), proj[:, 0].double()) for s in range(S)]
+    edge = (1 << 31) // (C * 4)                      # the first pixel past 2^31 bytes of a view (channel-last, batch-major)
+    be, ye = edge // (h * w), edge % (h * w) // w
+    for b, y in ((0, 0), (be, ye - 1), (be, ye), (be, ye + 1), (B - 1, h - 1)):
+        rows = [r for r in (y - 1, y, y + 1) if 0 <= r < h]
+        for d in range(D):
+            s64 = _sim_rows64(feat, rts, planes, vw, B, S, h, w, b, rows, d)
+            check(sim[d, b].view(h, w, C)[rows[0]:rows[-1] + 1], s64, *SWEEP_4K, what="similarity b %d rows %s plane %d" % (b, rows, d),
+                  dims=("row", "x", "c"))
+            pad = torch.zeros(3, w, C, dtype=torch.float64)
+            pad[[r - y + 1 for r in rows]] = s64
+            ref = F.relu(F.conv2d(pad.permute(2, 0, 1).unsqueeze(0), w1.double(), None, 1, (0, 1)))[0, :, 0].t()     # [w, 8]
+            check(c1[d, b].view(h, w, 8)[y], ref, *SWEEP_4K, what="c1 b %d row %d plane %d" % (b, y, d), dims=("x", "c"))
 
 
 def test_eleven_views_end_to_end(hip, O):
@@ -1319,7 +1497,8 @@ def test_drop_in_forward_with_one_role_per_launch(hip, set_option):
 @pytest.mark.parametrize("stage,h,w", [(1, 22, 38), (2, 26, 50), (0, 8, 40), (1, 4, 6), (2, 70, 34)])
 def test_minimal_filtering_roles_on_ragged_stage_sizes(hip, O, set_option, recur, stage, h, w):
     """The F(2x2, 3x3) roles (8 x 32 tiles of 2 x 2 output tiles) on maps no tile divides -- level-2 maps of 11 x 19, 13 x 25, 2 x 3,
-    35 x 17 pixels: odd sizes cut through the 2 x 2 tiles --, as their own launches and sharing launches, against the CPU oracle."""
+    35 x 17 pixels: odd sizes cut through the 2 x 2 tiles --, as their own launches and sharing launches, against the CPU oracle
+    (per pixel in float64 too)."""
     from ada_mvs_amd.models.adamvs import Infer_AdaMVSNet
     B, V, D = 2, 3, 34
     m = Infer_AdaMVSNet(48, [48, 32, 8], synth.DEPTH_INTERVALS_RATIO, False, [8, 8, 8])
@@ -1343,6 +1522,7 @@ def test_minimal_filtering_roles_on_ragged_stage_sizes(hip, O, set_option, recur
     for key in ("depth", "photometric_confidence"):
         assert got[key].shape == ref[key].shape
         assert rel_l1(got[key], ref[key]) < E2E_TOL, (key, stage, h, w, recur)
+    _check_stage64(O, got, feats, proj, planes, sd, stage, net.in_up, prev, 4.0, "fp32")
 
 
 # --------------------------------------------------------------------------- stride-2 layers, minimal filtering along x (adamvs.py:206-211)

@@ -77,26 +77,37 @@ FORMS = {
         1: "folded into the next layer (what -1 takes at one sample) -- test_msrednet.py::test_end_to_end_against_reference_golden_and_oracle",
     },
     "conv1_f23": {
-        3: "F(2, 3) along x at C = 32 and C = 16 / 8 -- test_hip_parity.py::test_aggregate_conv1",
-        2: "k_conv1_ksplit<32>, F(2, 3) at C = 16 / 8 -- test_hip_parity.py::test_conv1_and_feature_net0_behind_their_options",
-        1: "F(2, 3) at C = 32, k_conv1_two_row<16 / 8> -- test_hip_parity.py::test_conv1_and_feature_net0_behind_their_options",
-        0: "k_conv1_ksplit<32>, k_conv1_two_row<16 / 8> -- test_hip_parity.py::test_conv1_and_feature_net0_behind_their_options",
+        3: "F(2, 3) along x at C = 32 and C = 16 / 8, per element against float64 -- test_hip_parity.py::test_aggregate_conv1",
+        2: "k_conv1_ksplit<32>, F(2, 3) at C = 16 / 8 -- test_hip_parity.py::test_conv1_and_feature_net0_behind_their_options "
+           "(test_aggregate_conv1 per element)",
+        1: "F(2, 3) at C = 32, k_conv1_two_row<16 / 8> -- test_hip_parity.py::test_conv1_and_feature_net0_behind_their_options "
+           "(test_aggregate_conv1 per element)",
+        0: "k_conv1_ksplit<32>, k_conv1_two_row<16 / 8> -- test_hip_parity.py::test_conv1_and_feature_net0_behind_their_options "
+           "(test_aggregate_conv1 per element)",
     },
     "fconv_f23": {
-        1: "k_fconv_f23 on FeatureNet0's stride-1 layers -- test_hip_parity.py::test_feature_net0_against_oracle",
-        0: "k_fconv there, class-by-class transposed layers -- test_hip_parity.py::test_conv1_and_feature_net0_behind_their_options",
+        1: "k_fconv_f23 on FeatureNet0's stride-1 layers, per element against float64 -- test_hip_parity.py::test_feature_net0_against_oracle",
+        0: "k_fconv there, class-by-class transposed layers -- test_hip_parity.py::test_conv1_and_feature_net0_behind_their_options "
+           "(test_feature_net0_against_oracle per element)",
     },
     "gru_wino": {
-        7: "gates1, gates2, cand2 in F(2x2, 3x3) -- test_hip_parity.py::test_gru_convolutions_in_the_minimal_filtering_form",
-        0: "direct GRU convolutions -- test_hip_parity.py::test_pipelined_recurrence_is_bit_identical_to_sequential",
-        1: "gates1 only -- test_hip_parity.py::test_gru_convolutions_in_the_minimal_filtering_form",
-        2: "gates2 only -- test_hip_parity.py::test_gru_convolutions_in_the_minimal_filtering_form",
-        4: "cand2 only -- test_hip_parity.py::test_gru_convolutions_in_the_minimal_filtering_form",
-        8: "cand1 only -- test_hip_parity.py::test_gru_convolutions_in_the_minimal_filtering_form",
+        7: "gates1, gates2, cand2 in F(2x2, 3x3) -- test_hip_parity.py::test_gru_convolutions_in_the_minimal_filtering_form, "
+           "per element against float64: test_hip_parity.py::test_slice_reg_step_every_form_against_float64",
+        0: "direct GRU convolutions -- test_hip_parity.py::test_pipelined_recurrence_is_bit_identical_to_sequential, "
+           "per element against float64: test_hip_parity.py::test_slice_reg_step_every_form_against_float64",
+        1: "gates1 only -- test_hip_parity.py::test_gru_convolutions_in_the_minimal_filtering_form; the role in F(2x2, 3x3) per "
+           "element (gru_wino = 15): test_hip_parity.py::test_slice_reg_step_every_form_against_float64",
+        2: "gates2 only -- test_hip_parity.py::test_gru_convolutions_in_the_minimal_filtering_form; the role in F(2x2, 3x3) per "
+           "element (gru_wino = 15): test_hip_parity.py::test_slice_reg_step_every_form_against_float64",
+        4: "cand2 only -- test_hip_parity.py::test_gru_convolutions_in_the_minimal_filtering_form; the role in F(2x2, 3x3) per "
+           "element (gru_wino = 15): test_hip_parity.py::test_slice_reg_step_every_form_against_float64",
+        8: "cand1 only -- test_hip_parity.py::test_gru_convolutions_in_the_minimal_filtering_form; the role in F(2x2, 3x3) per "
+           "element (gru_wino = 15): test_hip_parity.py::test_slice_reg_step_every_form_against_float64",
     },
     "recur_mode": {
-        -1: "by stage size -- test_hip_parity.py::test_stage_on_random_shapes_against_oracle",
-        0: "one role per launch -- test_hip_parity.py::test_pipelined_recurrence_is_bit_identical_to_sequential",
+        -1: "by stage size -- test_hip_parity.py::test_stage_on_random_shapes_against_oracle (per pixel against float64)",
+        0: "one role per launch -- test_hip_parity.py::test_pipelined_recurrence_is_bit_identical_to_sequential, per pixel against "
+           "float64: test_hip_parity.py::test_pipelined_recurrence_on_ragged_stage_sizes",
         1: "three launches per hypothesis -- test_hip_parity.py::test_pipelined_recurrence_is_bit_identical_to_sequential",
         3: "two launches per hypothesis -- test_hip_parity.py::test_pipelined_recurrence_is_bit_identical_to_sequential",
         5: "one launch per hypothesis -- test_hip_parity.py::test_pipelined_recurrence_is_bit_identical_to_sequential",
