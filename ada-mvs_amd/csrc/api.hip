@@ -601,3 +601,92 @@ extern "C" int adamvs_ortho_finalize(const adamvs_ortho_grid* grid, const float*
   ADAMVS_CHECK_ARG(acc && view_state && nvis && rgba && view_out && nvis_out, "ortho_finalize: null pointer");
   return launch_ortho_finalize(*grid, acc, view_state, nvis, rgba, view_out, nvis_out, (hipStream_t)stream);
 }
+
+// ---- mesh texturing (texture.hip): every argument is checked here, before any launch
+static int texture_check_mesh(long nv, long nf, const char* what) {
+  ADAMVS_CHECK_ARG(nv >= 1, "%s: nv=%ld (>= 1)", what, nv);
+  ADAMVS_CHECK_ARG(nf >= 0 && nf <= ADAMVS_TEXTURE_MAX_FACES, "%s: nf=%ld (0 .. %ld)", what, nf, (long)ADAMVS_TEXTURE_MAX_FACES);
+  return 0;
+}
+
+static int texture_check_page(int P, long npages, const char* what) {
+  ADAMVS_CHECK_ARG(P >= ADAMVS_TEXTURE_MIN_PAGE && P <= ADAMVS_TEXTURE_MAX_PAGE && (P & (P - 1)) == 0, "%s: page %d (a power of two %d .. %d)",
+                   what, P, ADAMVS_TEXTURE_MIN_PAGE, ADAMVS_TEXTURE_MAX_PAGE);
+  ADAMVS_CHECK_ARG(npages >= 1, "%s: npages=%ld (>= 1)", what, npages);
+  return 0;
+}
+
+extern "C" int adamvs_texture_project(const adamvs_ortho_view* view, const double* xyz, long nv, float* uvz, void* stream) {
+  if (int rc = ortho_check_view(view, "texture_project")) return rc;
+  if (int rc = texture_check_mesh(nv, 0, "texture_project")) return rc;
+  ADAMVS_CHECK_ARG(xyz && uvz, "texture_project: null pointer");
+  return launch_tex_project(*view, xyz, nv, uvz, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_zbuf(const adamvs_ortho_view* view, const float* uvz, long nv, const unsigned* faces, long nf, unsigned* zbuf,
+                                   unsigned* big_count, unsigned* big_list, long big_capacity, void* stream) {
+  if (int rc = ortho_check_view(view, "texture_zbuf")) return rc;
+  if (int rc = texture_check_mesh(nv, nf, "texture_zbuf")) return rc;
+  ADAMVS_CHECK_ARG(uvz && faces && zbuf && big_count && big_list, "texture_zbuf: null pointer");
+  ADAMVS_CHECK_ARG(big_capacity >= nf, "texture_zbuf: big_capacity %ld < nf = %ld", big_capacity, nf);
+  return launch_tex_zbuf(view->W, view->H, uvz, nv, faces, nf, zbuf, big_count, big_list, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_score(const adamvs_ortho_view* view, int view_index, const float* uvz, long nv, const unsigned* faces, long nf,
+                                    const unsigned* zbuf, float border, float tol, float* best, int* label, int* nvis, float* uv,
+                                    void* stream) {
+  if (int rc = ortho_check_view(view, "texture_score")) return rc;
+  if (int rc = texture_check_mesh(nv, nf, "texture_score")) return rc;
+  ADAMVS_CHECK_ARG(uvz && faces && zbuf && best && label && nvis && uv, "texture_score: null pointer");
+  ADAMVS_CHECK_ARG(view_index >= 0, "texture_score: view_index=%d (>= 0)", view_index);
+  ADAMVS_CHECK_ARG(std::isfinite(border) && border >= 0.f, "texture_score: border=%g (finite, >= 0)", (double)border);
+  ADAMVS_CHECK_ARG(std::isfinite(tol) && tol >= 0.f, "texture_score: tol=%g (finite, >= 0)", (double)tol);
+  return launch_tex_score(view->W, view->H, view_index, uvz, nv, faces, nf, zbuf, border, tol, best, label, nvis, uv, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_edge_keys(const unsigned* faces, long nf, long long* keys, void* stream) {
+  if (int rc = texture_check_mesh(1, nf, "texture_edge_keys")) return rc;
+  ADAMVS_CHECK_ARG(faces && keys, "texture_edge_keys: null pointer");
+  return launch_tex_edge_keys(faces, nf, keys, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_components(const long long* keys_sorted, const long long* entry, long nf, const int* label, int* parent,
+                                         unsigned* changed, void* stream) {
+  if (int rc = texture_check_mesh(1, nf, "texture_components")) return rc;
+  ADAMVS_CHECK_ARG(keys_sorted && entry && label && parent && changed, "texture_components: null pointer");
+  return launch_tex_components_round(keys_sorted, entry, 3 * nf, label, parent, nf, changed, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_rank(const int* label, const int* parent, long nf, unsigned* block_roots, unsigned* block_untex,
+                                   unsigned* root_off, unsigned* untex_off, int* root_chart, int* pal, void* stream) {
+  if (int rc = texture_check_mesh(1, nf, "texture_rank")) return rc;
+  ADAMVS_CHECK_ARG(label && parent && block_roots && block_untex && root_off && untex_off && root_chart && pal, "texture_rank: null pointer");
+  return launch_tex_rank(label, parent, nf, block_roots, block_untex, root_off, untex_off, root_chart, pal, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_boxes(const int* label, const int* parent, const int* root_chart, const float* uv, long nf, int* chart, int* box,
+                                    void* stream) {
+  if (int rc = texture_check_mesh(1, nf, "texture_boxes")) return rc;
+  ADAMVS_CHECK_ARG(label && parent && root_chart && uv && chart && box, "texture_boxes: null pointer");
+  return launch_tex_boxes(label, parent, root_chart, uv, nf, chart, box, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_fill(const adamvs_ortho_view* view, const int* items, const long long* prefix, int n, long texels, int P,
+                                   long npages, unsigned char* atlas, void* stream) {
+  if (int rc = ortho_check_view(view, "texture_fill")) return rc;
+  if (int rc = texture_check_page(P, npages, "texture_fill")) return rc;
+  ADAMVS_CHECK_ARG(n >= 0 && texels >= 0, "texture_fill: n=%d, texels=%ld (>= 0)", n, texels);
+  ADAMVS_CHECK_ARG((items && prefix && atlas) || n == 0, "texture_fill: null pointer");
+  return launch_tex_fill(*view, items, prefix, n, texels, P, npages, atlas, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_coords(const int* label, const int* chart, const int* pal, const float* uv, long nf, const int* charts,
+                                     int pal_ox, int pal_oy, int pal_page, int P, long npages, const unsigned* faces, long nv,
+                                     const unsigned char* vrgb, unsigned char* atlas, float* tc, int* texnum, void* stream) {
+  if (int rc = texture_check_mesh(nv, nf, "texture_coords")) return rc;
+  if (int rc = texture_check_page(P, npages, "texture_coords")) return rc;
+  ADAMVS_CHECK_ARG(label && chart && pal && uv && faces && vrgb && atlas && tc && texnum, "texture_coords: null pointer");
+  ADAMVS_CHECK_ARG(pal_ox >= 0 && pal_oy >= 0 && pal_page >= 0, "texture_coords: palette at (%d, %d) of page %d", pal_ox, pal_oy, pal_page);
+  return launch_tex_coords(label, chart, pal, uv, nf, charts, pal_ox, pal_oy, pal_page, P, npages, faces, nv, vrgb, atlas, tc, texnum,
+                           (hipStream_t)stream);
+}

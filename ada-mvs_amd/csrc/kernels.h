@@ -187,4 +187,25 @@ int launch_ortho_compose(const adamvs_ortho_grid& g, const adamvs_ortho_view& v,
 int launch_ortho_finalize(const adamvs_ortho_grid& g, const float* acc, const int* view, const int* nvis, uint8_t* rgba, int* view_out,
                           uint16_t* nvis_out, hipStream_t st);
 
+// texture.hip: mesh texture from the source views (include/adamvs_hip.h, "Mesh texturing"; raster.h holds the rasteriser it
+// shares with ortho.hip)
+constexpr int TEX_TILE = ADAMVS_TEXTURE_TILE;
+int launch_tex_project(const adamvs_ortho_view& v, const double* xyz, long nv, float* uvz, hipStream_t st);
+int launch_tex_zbuf(int W, int H, const float* uvz, long nv, const unsigned* faces, long nf, unsigned* zbuf, unsigned* big_count,
+                    unsigned* big_list, hipStream_t st);
+int launch_tex_score(int W, int H, int view, const float* uvz, long nv, const unsigned* faces, long nf, const unsigned* zbuf, float border,
+                     float tol, float* best, int* label, int* nvis, float* uv, hipStream_t st);
+int launch_tex_edge_keys(const unsigned* faces, long nf, long long* keys, hipStream_t st);
+int launch_tex_components_round(const long long* keys, const long long* entry, long n, const int* label, int* parent, long nf,
+                                unsigned* changed, hipStream_t st);
+int launch_tex_rank(const int* label, const int* parent, long nf, unsigned* block_roots, unsigned* block_untex, unsigned* root_off,
+                    unsigned* untex_off, int* root_chart, int* pal, hipStream_t st);
+int launch_tex_boxes(const int* label, const int* parent, const int* root_chart, const float* uv, long nf, int* chart, int* box,
+                     hipStream_t st);
+int launch_tex_fill(const adamvs_ortho_view& v, const int* items, const long long* prefix, int n, long texels, int P, long pages,
+                    unsigned char* atlas, hipStream_t st);
+int launch_tex_coords(const int* label, const int* chart, const int* pal, const float* uv, long nf, const int* charts, int pal_ox,
+                      int pal_oy, int pal_page, int P, long pages, const unsigned* faces, long nv, const unsigned char* vrgb,
+                      unsigned char* atlas, float* tc, int* texnum, hipStream_t st);
+
 }  // namespace adamvs

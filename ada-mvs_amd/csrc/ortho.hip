@@ -15,6 +15,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "persistent.h"
+#include "raster.h"
 
 // The header states the arithmetic operation by operation: no contraction into fma in this file.
 #pragma clang fp contract(off)
@@ -23,48 +24,12 @@ namespace adamvs {
 
 static_assert(ORTHO_TILE == 256, "kernels below assume workgroups of four waves");
 
-constexpr unsigned ZBUF_EMPTY = 0x7F800000u;     // +inf
-
 struct OrthoArgs {
   double x0, y_top, gsd;        // the DSM grid
   int W, H, K;                  // DSM cells, upsample
 };
 
-struct OrthoCam {
-  double C[3];
-  float R[9], Kc[6];            // R_cw, the first two rows of K
-  int H, W;
-};
-
 static OrthoArgs ortho_args(const adamvs_ortho_grid& g) { return OrthoArgs{g.x0, g.y_top, g.gsd, g.W, g.H, g.K}; }
-
-static OrthoCam ortho_cam(const adamvs_ortho_view& v) {
-  OrthoCam c;
-  for (int k = 0; k < 3; ++k) c.C[k] = v.C[k];
-  for (int k = 0; k < 9; ++k) c.R[k] = v.R[k];
-  for (int k = 0; k < 6; ++k) c.Kc[k] = v.K[k];
-  c.H = v.H;
-  c.W = v.W;
-  return c;
-}
-
-// World point (fp64) -> d = (float)(X - C), camera-frame p = R_cw d, pixel (u, v) and depth z (fp32).
-struct Proj {
-  float dx, dy, dz, u, v, z;
-};
-
-__device__ __forceinline__ Proj project(const OrthoCam& c, double X, double Y, double Z) {
-  Proj r;
-  r.dx = (float)(X - c.C[0]);
-  r.dy = (float)(Y - c.C[1]);
-  r.dz = (float)(Z - c.C[2]);
-  const float px = c.R[0] * r.dx + c.R[1] * r.dy + c.R[2] * r.dz;
-  const float py = c.R[3] * r.dx + c.R[4] * r.dy + c.R[5] * r.dz;
-  r.z = c.R[6] * r.dx + c.R[7] * r.dy + c.R[8] * r.dz;
-  r.u = (c.Kc[0] * px + c.Kc[1] * py + c.Kc[2] * r.z) / r.z;
-  r.v = (c.Kc[3] * px + c.Kc[4] * py + c.Kc[5] * r.z) / r.z;
-  return r;
-}
 
 // ---- surface --------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_ortho_surface(const OrthoArgs a, const float* __restrict__ dsm, double* __restrict__ height) {
@@ -104,14 +69,8 @@ __global__ __launch_bounds__(256) void k_ortho_zbuf_clear(unsigned* __restrict__
   if (k < n) zbuf[k] = ZBUF_EMPTY;
 }
 
-// One triangle in screen space, oriented (area > 0), with its clamped pixel box.
-struct Tri {
-  float u[3], v[3], iz[3], area;
-  int u0, u1, v0, v1;       // inclusive pixel-centre box; empty if u0 > u1 or v0 > v1
-};
-
 // Vertex q of triangle `half` of quad (qa, qb): half 0 = (a,b) (a+1,b) (a+1,b+1), half 1 = (a,b) (a,b+1) (a+1,b+1).
-__device__ __forceinline__ bool setup_tri(const OrthoArgs& a, const OrthoCam& c, const float* __restrict__ dsm, int qa, int qb,
+__device__ __forceinline__ bool setup_tri(const OrthoArgs& a, const ViewCam& c, const float* __restrict__ dsm, int qa, int qb,
                                           int half, Tri& t) {
   const int da[3] = {0, half == 0 ? 1 : 0, 1}, db[3] = {0, half == 0 ? 0 : 1, 1};
   for (int k = 0; k < 3; ++k) {
@@ -119,42 +78,12 @@ __device__ __forceinline__ bool setup_tri(const OrthoArgs& a, const OrthoCam& c,
     const float zw = dsm[(long)vb * a.W + va];
     if (!isfinite(zw)) return false;
     const Proj p = project(c, a.x0 + ((double)va + 0.5) * a.gsd, a.y_top - ((double)vb + 0.5) * a.gsd, (double)zw);
-    if (!(p.z > ORTHO_NEAR) || !isfinite(p.u) || !isfinite(p.v) || !isfinite(p.z)) return false;
-    t.u[k] = p.u;
-    t.v[k] = p.v;
-    t.iz[k] = 1.f / p.z;
+    if (!tri_vertex(p.u, p.v, p.z, k, t)) return false;
   }
-  float area = (t.u[1] - t.u[0]) * (t.v[2] - t.v[0]) - (t.v[1] - t.v[0]) * (t.u[2] - t.u[0]);
-  if (!(area != 0.f) || !isfinite(area)) return false;
-  if (area < 0.f) {
-    float x = t.u[1]; t.u[1] = t.u[2]; t.u[2] = x;
-    x = t.v[1]; t.v[1] = t.v[2]; t.v[2] = x;
-    x = t.iz[1]; t.iz[1] = t.iz[2]; t.iz[2] = x;
-    area = -area;
-  }
-  t.area = area;
-  const float umn = fminf(fminf(t.u[0], t.u[1]), t.u[2]), umx = fmaxf(fmaxf(t.u[0], t.u[1]), t.u[2]);
-  const float vmn = fminf(fminf(t.v[0], t.v[1]), t.v[2]), vmx = fmaxf(fmaxf(t.v[0], t.v[1]), t.v[2]);
-  // clamp in float before the conversion: a vertex near the camera plane projects far outside the image
-  t.u0 = (int)fminf(fmaxf(ceilf(umn), 0.f), (float)c.W);
-  t.u1 = (int)fmaxf(fminf(floorf(umx), (float)(c.W - 1)), -1.f);
-  t.v0 = (int)fminf(fmaxf(ceilf(vmn), 0.f), (float)c.H);
-  t.v1 = (int)fmaxf(fminf(floorf(vmx), (float)(c.H - 1)), -1.f);
-  return t.u0 <= t.u1 && t.v0 <= t.v1;
+  return tri_setup(t, c.W, c.H);
 }
 
-__device__ __forceinline__ void raster_pixel(const Tri& t, int pu, int pv, int W, unsigned* __restrict__ zbuf) {
-  const float x = (float)pu, y = (float)pv;
-  const float e0 = (t.u[2] - t.u[1]) * (y - t.v[1]) - (t.v[2] - t.v[1]) * (x - t.u[1]);
-  const float e1 = (t.u[0] - t.u[2]) * (y - t.v[2]) - (t.v[0] - t.v[2]) * (x - t.u[2]);
-  const float e2 = (t.u[1] - t.u[0]) * (y - t.v[0]) - (t.v[1] - t.v[0]) * (x - t.u[0]);
-  if (!(e0 >= 0.f && e1 >= 0.f && e2 >= 0.f)) return;
-  const float z = t.area / (e0 * t.iz[0] + e1 * t.iz[1] + e2 * t.iz[2]);
-  if (!(z > 0.f) || !isfinite(z)) return;
-  atomicMin(zbuf + (long)pv * W + pu, __float_as_uint(z));
-}
-
-__global__ __launch_bounds__(256) void k_ortho_zbuf_small(const OrthoArgs a, const OrthoCam c, const float* __restrict__ dsm,
+__global__ __launch_bounds__(256) void k_ortho_zbuf_small(const OrthoArgs a, const ViewCam c, const float* __restrict__ dsm,
                                                           unsigned* __restrict__ zbuf, unsigned* __restrict__ big_count,
                                                           unsigned* __restrict__ big_list) {
   const long nq = (long)(a.W - 1) * (a.H - 1);
@@ -175,7 +104,7 @@ __global__ __launch_bounds__(256) void k_ortho_zbuf_small(const OrthoArgs a, con
   }
 }
 
-__global__ __launch_bounds__(256) void k_ortho_zbuf_large(const OrthoArgs a, const OrthoCam c, const float* __restrict__ dsm,
+__global__ __launch_bounds__(256) void k_ortho_zbuf_large(const OrthoArgs a, const ViewCam c, const float* __restrict__ dsm,
                                                           unsigned* __restrict__ zbuf, const unsigned* __restrict__ big_count,
                                                           const unsigned* __restrict__ big_list) {
   const unsigned n = *big_count;
@@ -194,7 +123,7 @@ __global__ __launch_bounds__(256) void k_ortho_zbuf_large(const OrthoArgs a, con
 
 // ---- compose and finalize -------------------------------------------------------------------------------------------
 template <bool FEATHER>
-__global__ __launch_bounds__(256) void k_ortho_compose(const OrthoArgs a, const OrthoCam c, const uint8_t* __restrict__ rgba, int view_id,
+__global__ __launch_bounds__(256) void k_ortho_compose(const OrthoArgs a, const ViewCam c, const uint8_t* __restrict__ rgba, int view_id,
                                                        const double* __restrict__ height, const unsigned* __restrict__ zbuf, float border,
                                                        float feather_px, float tol, f32x4* __restrict__ acc, float* __restrict__ wmax,
                                                        int* __restrict__ view, int* __restrict__ nvis) {
@@ -281,7 +210,7 @@ int launch_ortho_surface(const adamvs_ortho_grid& g, const float* dsm, double* h
 int launch_ortho_zbuf(const adamvs_ortho_grid& g, const float* dsm, const adamvs_ortho_view& v, unsigned* zbuf, unsigned* big_count,
                       unsigned* big_list, hipStream_t st) {
   const OrthoArgs a = ortho_args(g);
-  const OrthoCam c = ortho_cam(v);
+  const ViewCam c = view_cam(v);
   const long npx = (long)v.W * v.H;
   hipLaunchKernelGGL(k_ortho_zbuf_clear, dim3(ortho_blocks(npx)), dim3(ORTHO_TILE), 0, st, zbuf, npx);
   ADAMVS_CHECK_LAUNCH("ortho_zbuf_clear");
@@ -300,10 +229,10 @@ int launch_ortho_compose(const adamvs_ortho_grid& g, const adamvs_ortho_view& v,
                          int mode, float border, float feather_px, float tol, float* acc, float* wmax, int* view, int* nvis, hipStream_t st) {
   const long n = (long)g.W * g.K * g.H * g.K;
   if (mode == ADAMVS_ORTHO_FEATHER)
-    hipLaunchKernelGGL(k_ortho_compose<true>, dim3(ortho_blocks(n)), dim3(ORTHO_TILE), 0, st, ortho_args(g), ortho_cam(v), v.rgba,
+    hipLaunchKernelGGL(k_ortho_compose<true>, dim3(ortho_blocks(n)), dim3(ORTHO_TILE), 0, st, ortho_args(g), view_cam(v), v.rgba,
                        view_id, height, zbuf, border, feather_px, tol, (f32x4*)acc, wmax, view, nvis);
   else
-    hipLaunchKernelGGL(k_ortho_compose<false>, dim3(ortho_blocks(n)), dim3(ORTHO_TILE), 0, st, ortho_args(g), ortho_cam(v), v.rgba,
+    hipLaunchKernelGGL(k_ortho_compose<false>, dim3(ortho_blocks(n)), dim3(ORTHO_TILE), 0, st, ortho_args(g), view_cam(v), v.rgba,
                        view_id, height, zbuf, border, feather_px, tol, (f32x4*)acc, wmax, view, nvis);
   ADAMVS_CHECK_LAUNCH("ortho_compose");
   return 0;

@@ -832,3 +832,115 @@ def ortho_finalize(grid, acc, vstate, nvis):
     check(_lib.load().adamvs_ortho_finalize(ctypes.byref(grid), _p(acc), _p(vstate), _p(nvis), _p(rgba), _p(view_out), _p(nvis_out),
                                             _stream()), "ortho_finalize")
     return rgba, view_out, nvis_out
+
+
+# ---- mesh texturing (csrc/texture.hip; driven by ada_mvs_amd/texture.py) ------------------------------------------------------
+# Views are _lib.OrthoView (ortho_view above).  faces: device int32 [nf, 3] holding uint32 indices; the depth buffer is int32
+# holding uint32 float bits; every per-face state tensor is updated in place and must be contiguous.
+def _tex_sizes(xyz_or_nv, faces):
+    nv = xyz_or_nv if isinstance(xyz_or_nv, int) else xyz_or_nv.shape[0]
+    return int(nv), int(faces.shape[0])
+
+
+def texture_project(view, xyz, uvz=None):
+    """adamvs_texture_project: xyz device float64 [nv, 3] -> uvz float32 [nv, 4] (u, v, z, 0)."""
+    xyz = _dev_as(xyz, "xyz", torch.float64)
+    if uvz is None:
+        uvz = torch.empty(xyz.shape[0], 4, device=xyz.device, dtype=torch.float32)
+    check(_lib.load().adamvs_texture_project(ctypes.byref(view), _p(xyz), xyz.shape[0], _p(uvz), _stream()), "texture_project")
+    return uvz
+
+
+def texture_zbuf(view, uvz, faces, zbuf, big):
+    """adamvs_texture_zbuf into zbuf (int32 [H, W]); big: int32 [1 + nf] (the large-face counter, then the list)."""
+    uvz, faces = _dev(uvz, "uvz"), _dev_as(faces, "faces", torch.int32)
+    zbuf, big = _dev_as(zbuf, "zbuf", torch.int32), _dev_as(big, "big", torch.int32)
+    if tuple(zbuf.shape) != (view.H, view.W) or big.numel() < 1:
+        raise _lib.AdaMVSHipError("zbuf %s, image %d x %d, big %d" % (tuple(zbuf.shape), view.H, view.W, big.numel()))
+    nv, nf = _tex_sizes(uvz, faces)
+    check(_lib.load().adamvs_texture_zbuf(ctypes.byref(view), _p(uvz), nv, _p(faces), nf, _p(zbuf), _p(big),
+                                          ctypes.c_void_p(big.data_ptr() + 4), big.numel() - 1, _stream()), "texture_zbuf")
+
+
+def texture_score(view, view_index, uvz, faces, zbuf, border, tol, best, label, nvis, uv):
+    """adamvs_texture_score: one view into the face state (best float32 [nf], label int32 [nf], nvis int32 [nf], uv float32 [nf, 6])."""
+    uvz, faces, zbuf = _dev(uvz, "uvz"), _dev_as(faces, "faces", torch.int32), _dev_as(zbuf, "zbuf", torch.int32)
+    nv, nf = _tex_sizes(uvz, faces)
+    state = (best, label, nvis, uv)
+    if any(not (t.is_cuda and t.is_contiguous()) for t in state) or uv.numel() != 6 * nf or any(t.numel() != nf for t in state[:3]):
+        raise _lib.AdaMVSHipError("texture_score: the face state must be contiguous device tensors of %d faces" % nf)
+    check(_lib.load().adamvs_texture_score(ctypes.byref(view), int(view_index), _p(uvz), nv, _p(faces), nf, _p(zbuf), float(border), float(tol),
+                                           *(_p(t) for t in state), _stream()), "texture_score")
+
+
+def texture_edge_keys(faces):
+    """adamvs_texture_edge_keys -> keys int64 [3 nf] (entry 3 f + k: edge k of face f as min << 32 | max)."""
+    faces = _dev_as(faces, "faces", torch.int32)
+    keys = torch.empty(3 * faces.shape[0], device=faces.device, dtype=torch.int64)
+    check(_lib.load().adamvs_texture_edge_keys(_p(faces), faces.shape[0], _p(keys), _stream()), "texture_edge_keys")
+    return keys
+
+
+def texture_components_round(keys_sorted, entry, label, parent, changed):
+    """adamvs_texture_components: one hook + compress round over the sorted edge entries (parent int32 [nf] in place; changed
+    int32 [1], cleared and set by the call)."""
+    keys_sorted, entry = _dev_as(keys_sorted, "keys", torch.int64), _dev_as(entry, "entry", torch.int64)
+    label = _dev_as(label, "label", torch.int32)
+    if not (parent.is_cuda and parent.is_contiguous() and parent.dtype == torch.int32) or keys_sorted.numel() != 3 * parent.numel():
+        raise _lib.AdaMVSHipError("texture_components: parent must be contiguous int32 [nf] with 3 nf sorted entries")
+    check(_lib.load().adamvs_texture_components(_p(keys_sorted), _p(entry), parent.numel(), _p(label), _p(parent), _p(changed), _stream()),
+          "texture_components")
+
+
+def texture_rank(label, parent):
+    """adamvs_texture_rank -> (root_chart int32 [nf], pal int32 [nf], charts, untextured) (the two counts are read back)."""
+    label, parent = _dev_as(label, "label", torch.int32), _dev_as(parent, "parent", torch.int32)
+    nf = label.numel()
+    nb = max(1, (nf + _lib.TEXTURE_TILE - 1) // _lib.TEXTURE_TILE)
+    ws = torch.empty(4 * nb + 2, device=label.device, dtype=torch.int32)
+    root_chart, pal = torch.empty_like(label), torch.empty_like(label)
+    blk_r, blk_u, off_r, off_u = ws[:nb], ws[nb:2 * nb], ws[2 * nb:3 * nb + 1], ws[3 * nb + 1:]
+    check(_lib.load().adamvs_texture_rank(_p(label), _p(parent), nf, _p(blk_r), _p(blk_u), _p(off_r), _p(off_u), _p(root_chart), _p(pal),
+                                          _stream()), "texture_rank")
+    if nf == 0:
+        return root_chart, pal, 0, 0
+    tot = torch.stack((off_r[nb], off_u[nb])).cpu()
+    return root_chart, pal, int(tot[0]), int(tot[1])
+
+
+def texture_boxes(label, parent, root_chart, uv, n_charts):
+    """adamvs_texture_boxes -> (chart int32 [nf], box int32 [n_charts, 4] = min floor u, min floor v, max floor u, max floor v)."""
+    label, parent, root_chart, uv = (_dev_as(label, "label", torch.int32), _dev_as(parent, "parent", torch.int32),
+                                     _dev_as(root_chart, "root_chart", torch.int32), _dev(uv, "uv"))
+    chart = torch.empty_like(label)
+    box = torch.empty(max(n_charts, 1), 4, device=label.device, dtype=torch.int32)
+    box[:, :2] = 2 ** 31 - 1
+    box[:, 2:] = -2 ** 31
+    check(_lib.load().adamvs_texture_boxes(_p(label), _p(parent), _p(root_chart), _p(uv), label.numel(), _p(chart), _p(box), _stream()),
+          "texture_boxes")
+    return chart, box[:n_charts]
+
+
+def texture_fill(view, items, prefix, texels, P, atlas):
+    """adamvs_texture_fill: items int32 [n, 8] (x0, y0, w, h, ox, oy, page, view), prefix int64 [n + 1], atlas uint8 [pages, P, P, 4]."""
+    items, prefix = _dev_as(items, "items", torch.int32), _dev_as(prefix, "prefix", torch.int64)
+    atlas = _dev_as(atlas, "atlas", torch.uint8)
+    if tuple(atlas.shape[1:]) != (P, P, 4) or prefix.numel() != items.shape[0] + 1:
+        raise _lib.AdaMVSHipError("texture_fill: atlas %s for page %d, %d items, %d prefix" % (tuple(atlas.shape), P, items.shape[0], prefix.numel()))
+    check(_lib.load().adamvs_texture_fill(ctypes.byref(view), _p(items), _p(prefix), items.shape[0], int(texels), int(P), atlas.shape[0],
+                                          _p(atlas), _stream()), "texture_fill")
+
+
+def texture_coords(label, chart, pal, uv, charts, pal_place, P, faces, vrgb, atlas):
+    """adamvs_texture_coords -> (tc float32 [nf, 6], texnum int32 [nf]); writes the palette texels into atlas.
+    charts int32 [nc, 8]; pal_place = (ox, oy, page) of the palette block."""
+    label, chart, pal = (_dev_as(t, n, torch.int32) for t, n in ((label, "label"), (chart, "chart"), (pal, "pal")))
+    faces, vrgb, atlas = _dev_as(faces, "faces", torch.int32), _dev_as(vrgb, "rgb", torch.uint8), _dev_as(atlas, "atlas", torch.uint8)
+    charts, uv = _dev_as(charts, "charts", torch.int32), _dev(uv, "uv")
+    nf = label.numel()
+    tc = torch.empty(nf, 6, device=label.device, dtype=torch.float32)
+    texnum = torch.empty(nf, device=label.device, dtype=torch.int32)
+    check(_lib.load().adamvs_texture_coords(_p(label), _p(chart), _p(pal), _p(uv), nf, _p(charts), *(int(v) for v in pal_place), int(P),
+                                            atlas.shape[0], _p(faces), vrgb.shape[0], _p(vrgb), _p(atlas), _p(tc), _p(texnum), _stream()),
+          "texture_coords")
+    return tc, texnum

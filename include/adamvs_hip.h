@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ADAMVS_ABI_VERSION 21
+#define ADAMVS_ABI_VERSION 22
 
 int adamvs_version(void);
 const char* adamvs_last_error_string(void);
@@ -782,6 +782,76 @@ int adamvs_ortho_compose(const adamvs_ortho_grid* grid, const adamvs_ortho_view*
                          int* view_state, int* nvis, void* stream);
 int adamvs_ortho_finalize(const adamvs_ortho_grid* grid, const float* acc, const int* view_state, const int* nvis, unsigned char* rgba,
                           int* view_out, unsigned short* nvis_out, void* stream);
+
+/* ---- Mesh texturing (after mesh_whu.py): a triangle mesh textured from the source images ----------------------------------
+ * ada-mvs_amd/texture.py drives it; texture_whu.py is the CLI.  Views are adamvs_ortho_view structs (a HOST pointer, copied into the
+ * arguments; projection exactly as "Image orthophoto" states it).  Mesh: xyz [nv][3] fp64 (device), faces [nf][3] uint32,
+ * counter-clockwise about the outward normal; a face with an index >= nv is ignored by every call (no view, no chart).
+ * 1 <= nv, 0 <= nf <= 2^31 - 1.  Workgroups cover ADAMVS_TEXTURE_TILE consecutive faces (vertices, edge entries, texels).
+ *
+ * Labelling, one call of each per view in ascending image id:
+ *   _project  uvz [nv][4] fp32: (u, v, z, 0) of every vertex.
+ *   _zbuf     zbuf [H][W] uint32, cleared to +inf by the call, then every face whose three vertices have z > ADAMVS_ORTHO_NEAR
+ *             and finite (u, v, z) is rasterised by the orthophoto's rule (set-up, inclusive edge functions, 1/z interpolated in
+ *             screen space, atomicMin on the bits); faces whose box holds more than ADAMVS_ORTHO_SMALL_PX pixel centres go
+ *             through big_list (at least nf entries) one wave per face.  The result does not depend on that split.
+ *   _score    face f with vertices (u_k, v_k, z_k) is VISIBLE iff every z_k > ADAMVS_ORTHO_NEAR and
+ *             border <= u_k <= W-1-border, border <= v_k <= H-1-border (fp32); area = (u1-u0)(v2-v0) - (v1-v0)(u2-u0) < 0
+ *             (front-facing: counter-clockwise about the outward normal is clockwise in an image whose v runs down; no swap);
+ *             z_k <= zbuf[floor(v_k + 1/2)][floor(u_k + 1/2)] + tol for k = 0, 1, 2 and for the centroid
+ *             uc = (u0 + u1 + u2) / 3, vc = (v0 + v1 + v2) / 3, zc = 3 / (1/z0 + 1/z1 + 1/z2) (fp32, left to right).
+ *             Then nvis += 1 and, with score = -area / 2: if score > best, best = score, label = view, uv = (u0 v0 u1 v1 u2 v2)
+ *             (a tie keeps the earlier view).  State: best [nf] fp32 (caller: -inf), label [nf] int32 (-1), nvis [nf] int32
+ *             (0), uv [nf][6] fp32.  One lane per face owns its state: no atomics.
+ * Charts: a chart is a maximal set of faces with the same label >= 0 connected through shared edges.
+ *   _edge_keys   keys [3 nf] int64: entry e = 3 f + k is the edge (faces[f][k], faces[f][(k+1) % 3]) as min << 32 | max.
+ *                The caller sorts the entries by key, then label, then e (a stable sort by label, then a stable one by key)
+ *                into keys_sorted and entry (int64 entry ids).
+ *   _components  parent [nf] int32 (caller: parent[f] = f); one round: sorted neighbours i, i+1 with equal keys and equal labels
+ *                >= 0 and roots ra = parent[a] != rb = parent[b] do atomicMin(parent[max(ra, rb)], min(ra, rb)) and set
+ *                *changed (cleared by the call); then every face walks to its root and stores it.  The caller repeats rounds
+ *                until *changed stays 0: then parent[f] is the smallest face of f's chart.  parent[x] <= x holds throughout.
+ *   _rank        chart ids in ascending root order and palette indices of the untextured faces (label -1) in face order:
+ *                root_chart [nf] (the chart id of a root, -1 elsewhere), pal [nf] (-1 for textured faces); block_roots,
+ *                block_untex [nblocks], root_off, untex_off [nblocks + 1] uint32 workspace; root_off[nblocks] is the chart
+ *                count and untex_off[nblocks] the untextured count (adamvs_fusion_scan).
+ *   _boxes       chart [nf] int32 (-1 untextured); box [nc][4] int32 (caller: INT_MAX, INT_MAX, INT_MIN, INT_MIN) becomes
+ *                (min floor u, min floor v, max floor u, max floor v) over the chart's corners (atomic min / max).
+ * Atlas: pages [npages][P][P] of uint32 texels, byte k = channel k (alpha byte 0); the caller zeroes them.  Charts are placed by
+ * the caller: charts [nc][8] int32 = (x0, y0, w, h, ox, oy, page, view) with x0 = max(minu - pad, 0),
+ * x1 = min(maxu + 1 + pad, W - 1), w = x1 - x0 + 1 (likewise y).
+ *   _fill    per view: items [n][8] rows of charts (that view's), prefix [n + 1] int64 = exclusive sum of w h; texel t of the
+ *            concatenation is image texel (x, y) of item k (prefix[k] <= t < prefix[k+1]) copied to atlas texel
+ *            (ox + x - x0, oy + y - y0) of page `page`, alpha byte 0.  No resampling.
+ *   _coords  tc [nf][6] fp32, texnum [nf] int32: a textured face of chart c has s_k = (ox + (u_k - x0) + 1/2) / P,
+ *            t_k = 1 - (oy + (v_k - y0) + 1/2) / P (fp32, left to right) and texnum = page; the k-th untextured face has
+ *            all three corners at the centre of texel (pal_ox + k mod P, pal_oy + k div P) of page pal_page, which it writes:
+ *            per channel (c0 + c1 + c2 + 1) div 3 of its vertex colours vrgb [nv][3] uint8 (the rounded mean).
+ * Argument errors (<0, before any launch): a null pointer where data is read or written, nv < 1, nf < 0 or > 2^31 - 1, a view
+ * of H or W < 1 or with a non-finite C, R or K or K's last row not 0 0 1, border or tol < 0 or not finite, big_capacity < nf,
+ * P not a power of two in ADAMVS_TEXTURE_MIN_PAGE .. ADAMVS_TEXTURE_MAX_PAGE, npages < 1, n < 0. */
+#define ADAMVS_TEXTURE_TILE 256
+#define ADAMVS_TEXTURE_MIN_PAGE 1024
+#define ADAMVS_TEXTURE_MAX_PAGE 16384
+#define ADAMVS_TEXTURE_MAX_FACES 2147483647L
+
+int adamvs_texture_project(const adamvs_ortho_view* view, const double* xyz, long nv, float* uvz, void* stream);
+int adamvs_texture_zbuf(const adamvs_ortho_view* view, const float* uvz, long nv, const unsigned* faces, long nf, unsigned* zbuf,
+                        unsigned* big_count, unsigned* big_list, long big_capacity, void* stream);
+int adamvs_texture_score(const adamvs_ortho_view* view, int view_index, const float* uvz, long nv, const unsigned* faces, long nf,
+                         const unsigned* zbuf, float border, float tol, float* best, int* label, int* nvis, float* uv, void* stream);
+int adamvs_texture_edge_keys(const unsigned* faces, long nf, long long* keys, void* stream);
+int adamvs_texture_components(const long long* keys_sorted, const long long* entry, long nf, const int* label, int* parent,
+                              unsigned* changed, void* stream);
+int adamvs_texture_rank(const int* label, const int* parent, long nf, unsigned* block_roots, unsigned* block_untex, unsigned* root_off,
+                        unsigned* untex_off, int* root_chart, int* pal, void* stream);
+int adamvs_texture_boxes(const int* label, const int* parent, const int* root_chart, const float* uv, long nf, int* chart, int* box,
+                         void* stream);
+int adamvs_texture_fill(const adamvs_ortho_view* view, const int* items, const long long* prefix, int n, long texels, int P, long npages,
+                        unsigned char* atlas, void* stream);
+int adamvs_texture_coords(const int* label, const int* chart, const int* pal, const float* uv, long nf, const int* charts, int pal_ox,
+                          int pal_oy, int pal_page, int P, long npages, const unsigned* faces, long nv, const unsigned char* vrgb,
+                          unsigned char* atlas, float* tc, int* texnum, void* stream);
 
 #ifdef __cplusplus
 }
