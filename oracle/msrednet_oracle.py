@@ -106,15 +106,16 @@ def infer_depth_stage_red(features, proj_matrices, depth_values, sd, pre):
     B, C, h, w = ref.shape
     rel = [ao.relative_transform(proj_matrices[:, v], proj_matrices[:, 0]) for v in range(1, len(features))]
     Rs, ts = [r[0] for r in rel], [r[1] for r in rel]
-    states = [torch.zeros(B, 8 << k, h >> k, w >> k) for k in range(4)]
-    exp_sum = torch.zeros(B, 1, h, w)
-    depth_image = torch.zeros(B, 1, h, w)
-    max_prob = torch.zeros(B, 1, h, w)
+    zeros = lambda *shape: torch.zeros(*shape, dtype=ref.dtype)      # noqa: E731  (states and sums in the inputs' dtype)
+    states = [zeros(B, 8 << k, h >> k, w >> k) for k in range(4)]
+    exp_sum = zeros(B, 1, h, w)
+    depth_image = zeros(B, 1, h, w)
+    max_prob = zeros(B, 1, h, w)
     for d in range(depth_values.shape[1]):
         plane = depth_values[:, d:d + 1]
         reg, states = slice_red_step(variance_cost(ref, srcs, Rs, ts, plane), states, sd, pre)
         prob = reg.exp()
-        flag = (max_prob < prob).float()
+        flag = (max_prob < prob).to(prob.dtype)
         max_prob = flag * prob + (1 - flag) * max_prob
         depth_image = plane * prob + depth_image
         exp_sum = exp_sum + prob

@@ -67,14 +67,19 @@ FORMS = {
     },
     "conv_small_grid": {
         1024: "D = 32 / 64 stride-1 layers resident up to 1024 workgroups -- test_kernel_forms.py::test_conv3x3_dd_forms, "
-              "test_msrednet.py::test_conv3x3_dd_small_grid_form_against_torch",
+              "test_msrednet.py::test_conv3x3_dd_small_grid_form_against_torch; per element, NTR = 1 / 2 / 4 at this limit and at "
+              "lowered ones -- test_msred_forms.py::test_red_recur_split",
         0: "never resident: k_conv_dd<2, 1> / <4, 1> -- test_kernel_forms.py::test_conv3x3_dd_forms, "
-           "test_msrednet.py::test_unfolded_recurrence_paths_in_a_child_process",
+           "test_msrednet.py::test_unfolded_recurrence_paths_in_a_child_process; per element -- "
+           "test_msred_forms.py::test_red_recur_split, test_msred_forms.py::test_recurrence_paths_by_their_bits",
     },
     "red_fold_applies": {
-        -1: "by batch -- test_msrednet.py::test_end_to_end_batch_of_two_against_oracle",
-        0: "unfolded GRU applies -- test_msrednet.py::test_unfolded_recurrence_paths_in_a_child_process",
-        1: "folded into the next layer (what -1 takes at one sample) -- test_msrednet.py::test_end_to_end_against_reference_golden_and_oracle",
+        -1: "by batch -- test_msrednet.py::test_end_to_end_batch_of_two_against_oracle; bit-equal to the forced arm of its side -- "
+            "test_msred_forms.py::test_recurrence_paths_by_their_bits",
+        0: "unfolded GRU applies -- test_msrednet.py::test_unfolded_recurrence_paths_in_a_child_process; per element -- "
+           "test_msred_forms.py::test_red_recur_pair, test_msred_forms.py::test_red_recur_split",
+        1: "folded into the next layer (what -1 takes at one sample) -- test_msrednet.py::test_end_to_end_against_reference_golden_and_oracle; "
+           "per element, three samples included -- test_msred_forms.py::test_red_recur_pair, test_msred_forms.py::test_red_recur_split",
     },
     "conv1_f23": {
         3: "F(2, 3) along x at C = 32 and C = 16 / 8, per element against float64 -- test_hip_parity.py::test_aggregate_conv1",

@@ -1,5 +1,9 @@
 """MS-REDNet inference: oracle/msrednet_oracle.py against fixtures the reference's own
-models/msrednet.py produced (tools/gen_golden_msred.py), and -- on the GPU -- the HIP path against both."""
+models/msrednet.py produced (tools/gen_golden_msred.py), and -- on the GPU -- the HIP path against both.
+
+The comparisons here are means over whole maps against fp32 (rel_l1), with a per-element fp64_bars.check next to them where the
+oracle gives a float64 reference.  The per-element coverage of the recurrences in every form of their launchers, of the variance
+cost, the soft-argmin, the elementwise kernels and the copies lives in tests/test_msred_forms.py."""
 import os
 import sys
 
@@ -8,6 +12,7 @@ import pytest
 import torch
 
 import ada_mvs_amd  # noqa: F401
+import fp64_bars
 from ada_mvs_amd import synth
 from oracle import msrednet_oracle as mo
 
@@ -166,6 +171,9 @@ def test_gru_cell2_against_reference_golden():
     hip_ops.gru2_out_apply(o, part, gn[64:], u, state, out, 16)
     assert rel_l1(_nchw(state, hh, ww), g["out"]) < OP_TOL
     assert rel_l1(_nchw(out[:, :, :16].contiguous(), hh, ww), g["out"]) < OP_TOL and bool((out[:, :, 16:] == 0).all())
+    ref = mo.conv_gru_cell2(x.double(), h0.double(), fp64_bars.double_sd(sd), "")
+    fp64_bars.check(_nchw(state, hh, ww), ref, *fp64_bars.RED_CELL, what="state")
+    fp64_bars.check(_nchw(out[:, :, :16].contiguous(), hh, ww), ref, *fp64_bars.RED_CELL, what="out")
 
 
 @pytest.mark.gpu
@@ -212,12 +220,17 @@ def test_slice_red_steps_against_reference_golden(concurrent):
         X0[step * B:(step + 1) * B, :, :C] = -_cl(g["cost%d" % step])
     fin, R = net.regularize_maps(X0, B, h, w)
     torch.cuda.synchronize()
+    sd64 = fp64_bars.double_sd(slice_state_dict())
+    states64 = [torch.zeros(B, 8 << k, h >> k, w >> k, dtype=torch.float64) for k in range(4)]
     for step in range(2):
         reg = fin[step * B:(step + 1) * B, :, 0].reshape(B, 1, h, w).cpu()
         assert rel_l1(reg, g["reg%d" % step]) < OP_TOL
+        reg64, states64 = mo.slice_red_step(g["cost%d" % step].double(), states64, sd64, "")
+        fp64_bars.check(reg, reg64, *fp64_bars.RED_STEP, what="reg step %d" % step)
         for k in range(4):
             state = _nchw(R[k][step * B:(step + 1) * B, :, :net.HC[k]].contiguous(), h >> k, w >> k)
             assert rel_l1(state, g["state%d_%d" % (k + 1, step)]) < OP_TOL, "state %d step %d" % (k + 1, step)
+            fp64_bars.check(state, states64[k], *fp64_bars.RED_STEP, what="state %d step %d" % (k + 1, step))
 
 
 @pytest.mark.gpu
@@ -226,11 +239,14 @@ def test_feature_net_unet_against_oracle():
     m.load_state_dict(sd)
     m = m.cuda().eval()
     x = torch.randn(2, 3, 64, 96, generator=torch.Generator().manual_seed(4))
-    want = mo.feature_net_unet(x, {k[len("feature."):]: v for k, v in sd.items() if k.startswith("feature.")}, "")
+    fsd = {k[len("feature."):]: v for k, v in sd.items() if k.startswith("feature.")}
+    want = mo.feature_net_unet(x, fsd, "")
+    want64 = mo.feature_net_unet(x.double(), fp64_bars.double_sd(fsd), "")
     with torch.no_grad():
         got = m.feature(x.cuda())
     for k in ("stage1", "stage2", "stage3"):
         assert rel_l1(got[k].cpu(), want[k]) < 5e-5, k
+        fp64_bars.check(got[k], want64[k], *fp64_bars.FEATNET, what=k)     # the FeatureNet0 kernels with zero context branches
 
 
 @pytest.mark.gpu
@@ -334,6 +350,9 @@ def test_conv3x3_dd_small_grid_form_against_torch(D, h, w, relu):
     pk = packing.pack_reg_layer(wt, torch.ones(D), bias, False).cuda()
     got = hip_ops.conv3x3_dd(_cl(x), pk[:9 * D * D], pk[9 * D * D:], _cl(skip), N, D, h, w, 0, relu)
     assert rel_l1(_nchw(got, h, w), want) < 1e-5
+    want64 = torch.nn.functional.conv2d(x.double(), wt.double(), bias.double(), padding=1)
+    want64 = (torch.relu(want64) if relu else want64) + skip.double()
+    fp64_bars.check(_nchw(got, h, w), want64, *fp64_bars.RED_CONV, what="conv3x3_dd D=%d %dx%d" % (D, h, w))
 
 
 @pytest.mark.gpu
@@ -351,6 +370,8 @@ def test_conv3x3_pair_against_torch(CA, CB, cout, h, w):
     rows = packing.pad16(cout)
     got = hip_ops.conv3x3_pair(_cl(a), _cl(b), packing.pack_small_conv(wt).cuda(), packing.pad_bias(bias, rows).cuda(), cout, h, w)
     assert got.shape == (B, h * w, cout) and rel_l1(_nchw(got, h, w), want) < 1e-5
+    want64 = torch.nn.functional.conv2d(torch.cat((a, b), 1).double(), wt.double(), bias.double(), padding=1)
+    fp64_bars.check(_nchw(got, h, w), want64, *fp64_bars.RED_CONV, what="conv3x3_pair (%d, %d) -> %d" % (CA, CB, cout))
 
 
 @pytest.mark.gpu
