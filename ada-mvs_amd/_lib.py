@@ -208,6 +208,21 @@ SIGNATURES = {
     "adamvs_texture_coords": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_i,
                                     c_i, c_i, c_i, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_texture_level_observe": (c_i, [ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_texture_level_rhs": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                       c_st]),
+    "adamvs_texture_level_cg_init": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_texture_level_cg": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_double, c_i,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, c_st]),
+    "adamvs_texture_level_owner": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, c_i,
+                                         ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_st]),
+    "adamvs_texture_level_dilate": (c_i, [ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_texture_level_apply": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                         ctypes.c_void_p, c_i, ctypes.c_long, ctypes.c_void_p, c_i, ctypes.c_long, ctypes.c_void_p,
+                                         c_st]),
 }
 
 ABI_VERSION = 22
@@ -227,6 +242,9 @@ ORTHO_MAX_UPSAMPLE = 8           # ADAMVS_ORTHO_MAX_UPSAMPLE
 TEXTURE_TILE = 256               # ADAMVS_TEXTURE_TILE: faces per workgroup of the texture kernels
 TEXTURE_PAGES = (1024, 16384)    # ADAMVS_TEXTURE_MIN_PAGE, ADAMVS_TEXTURE_MAX_PAGE
 TEXTURE_MAX_FACES = (1 << 31) - 1 # ADAMVS_TEXTURE_MAX_FACES
+TEXTURE_LEVEL_MAX_NODES = 1 << 30 # ADAMVS_TEXTURE_LEVEL_MAX_NODES
+TEXTURE_LEVEL_BLOCKS = 2048    # ADAMVS_TEXTURE_LEVEL_BLOCKS: workgroups (and partial sums) of a dot product of the seam solve
+TEXTURE_LEVEL_BAND = 2           # ADAMVS_TEXTURE_LEVEL_BAND: dilation rounds of the owner map
 PHASE_VIEW_WEIGHTS, PHASE_AGGREGATE, PHASE_RECURRENCE, PHASE_SOFT_ARGMIN, PHASE_ALL = 1, 2, 4, 8, 15
 _lib = None
 

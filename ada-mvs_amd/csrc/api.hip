@@ -690,3 +690,80 @@ extern "C" int adamvs_texture_coords(const int* label, const int* chart, const i
   return launch_tex_coords(label, chart, pal, uv, nf, charts, pal_ox, pal_oy, pal_page, P, npages, faces, nv, vrgb, atlas, tc, texnum,
                            (hipStream_t)stream);
 }
+
+// ---- seam levelling (texture_level.hip)
+static int level_check_graph(const int* rowptr, const unsigned* col, long nnz, long n, const char* what) {
+  ADAMVS_CHECK_ARG(n >= 0 && n <= ADAMVS_TEXTURE_LEVEL_MAX_NODES, "%s: n=%ld (0 .. %ld)", what, n, (long)ADAMVS_TEXTURE_LEVEL_MAX_NODES);
+  ADAMVS_CHECK_ARG(nnz >= 0 && nnz <= 2147483647L, "%s: nnz=%ld (0 .. 2^31 - 1)", what, nnz);
+  ADAMVS_CHECK_ARG(rowptr && (col || nnz == 0), "%s: null pointer", what);
+  return 0;
+}
+
+extern "C" int adamvs_texture_level_observe(const long long* view_tab, int nviews, const int* rowptr, const unsigned* col, long nnz,
+                                            const int* node_view, const float* pos, long n, float* f, void* stream) {
+  if (int rc = level_check_graph(rowptr, col, nnz, n, "texture_level_observe")) return rc;
+  ADAMVS_CHECK_ARG(nviews >= 1, "texture_level_observe: nviews=%d (>= 1)", nviews);
+  ADAMVS_CHECK_ARG(view_tab && node_view && pos && f, "texture_level_observe: null pointer");
+  return launch_lvl_observe(view_tab, nviews, rowptr, col, nnz, node_view, pos, n, f, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_level_rhs(const int* rowptr, const unsigned* col, long nnz, const float* f, long n, double* b, void* stream) {
+  if (int rc = level_check_graph(rowptr, col, nnz, n, "texture_level_rhs")) return rc;
+  ADAMVS_CHECK_ARG(f && b, "texture_level_rhs: null pointer");
+  return launch_lvl_rhs(rowptr, col, nnz, f, n, b, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_level_cg_init(const double* b, long n, double tol, double* g, double* r, double* p, double* partials,
+                                            double* state, void* stream) {
+  ADAMVS_CHECK_ARG(n >= 0 && n <= ADAMVS_TEXTURE_LEVEL_MAX_NODES, "texture_level_cg_init: n=%ld (0 .. %ld)", n,
+                   (long)ADAMVS_TEXTURE_LEVEL_MAX_NODES);
+  ADAMVS_CHECK_ARG(std::isfinite(tol) && tol >= 0.0, "texture_level_cg_init: tol=%g (finite, >= 0)", tol);
+  ADAMVS_CHECK_ARG(b && g && r && p && partials && state, "texture_level_cg_init: null pointer");
+  return launch_lvl_cg_init(b, n, tol, g, r, p, partials, state, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_level_cg(const int* rowptr, const unsigned* col, long nnz, long n, double lambda, int iters, double* g,
+                                       double* r, double* p, double* ap, double* partials, double* state, void* stream) {
+  if (int rc = level_check_graph(rowptr, col, nnz, n, "texture_level_cg")) return rc;
+  ADAMVS_CHECK_ARG(std::isfinite(lambda) && lambda > 0.0, "texture_level_cg: lambda=%g (finite, > 0)", lambda);
+  ADAMVS_CHECK_ARG(iters >= 0, "texture_level_cg: iters=%d (>= 0)", iters);
+  ADAMVS_CHECK_ARG(g && r && p && ap && partials && state, "texture_level_cg: null pointer");
+  ADAMVS_CHECK_ARG(((uintptr_t)g | (uintptr_t)r | (uintptr_t)p | (uintptr_t)ap) % 16 == 0, "texture_level_cg: g, r, p, ap must be 16-byte aligned");
+  return launch_lvl_cg(rowptr, col, nnz, n, lambda, iters, g, r, p, ap, partials, state, (hipStream_t)stream);
+}
+
+static int level_check_charts(const int* charts, const long long* prefix, int nc, long texels, const char* what) {
+  ADAMVS_CHECK_ARG(nc >= 0 && texels >= 0, "%s: nc=%d, texels=%ld (>= 0)", what, nc, texels);
+  ADAMVS_CHECK_ARG(prefix && (charts || nc == 0), "%s: null pointer", what);
+  return 0;
+}
+
+extern "C" int adamvs_texture_level_owner(const float* uv, const int* chart, long nf, const int* charts, const long long* prefix, int nc,
+                                          long texels, int* owner, unsigned* big_count, unsigned* big_list, long big_capacity,
+                                          void* stream) {
+  if (int rc = texture_check_mesh(1, nf, "texture_level_owner")) return rc;
+  if (int rc = level_check_charts(charts, prefix, nc, texels, "texture_level_owner")) return rc;
+  ADAMVS_CHECK_ARG(uv && chart && big_count && big_list && (owner || texels == 0), "texture_level_owner: null pointer");
+  ADAMVS_CHECK_ARG(big_capacity >= nf, "texture_level_owner: big_capacity %ld < nf = %ld", big_capacity, nf);
+  return launch_lvl_owner(uv, chart, nf, charts, prefix, nc, texels, owner, big_count, big_list, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_level_dilate(const int* charts, const long long* prefix, int nc, long texels, const int* owner_in,
+                                           int* owner_out, void* stream) {
+  if (int rc = level_check_charts(charts, prefix, nc, texels, "texture_level_dilate")) return rc;
+  ADAMVS_CHECK_ARG((owner_in && owner_out) || texels == 0, "texture_level_dilate: null pointer");
+  ADAMVS_CHECK_ARG(owner_in != owner_out || texels == 0, "texture_level_dilate: the round is double-buffered (owner_in == owner_out)");
+  return launch_lvl_dilate(charts, prefix, nc, texels, owner_in, owner_out, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_texture_level_apply(const float* uv, const int* corner_node, long nf, const double* g, long n, const int* charts,
+                                          const long long* prefix, int nc, long texels, const int* owner, int P, long npages,
+                                          unsigned char* atlas, void* stream) {
+  if (int rc = texture_check_mesh(1, nf, "texture_level_apply")) return rc;
+  if (int rc = texture_check_page(P, npages, "texture_level_apply")) return rc;
+  if (int rc = level_check_charts(charts, prefix, nc, texels, "texture_level_apply")) return rc;
+  ADAMVS_CHECK_ARG(n >= 0 && n <= ADAMVS_TEXTURE_LEVEL_MAX_NODES, "texture_level_apply: n=%ld (0 .. %ld)", n,
+                   (long)ADAMVS_TEXTURE_LEVEL_MAX_NODES);
+  ADAMVS_CHECK_ARG(uv && corner_node && atlas && (g || n == 0) && (owner || texels == 0), "texture_level_apply: null pointer");
+  return launch_lvl_apply(uv, corner_node, nf, g, n, charts, prefix, nc, texels, owner, P, npages, atlas, (hipStream_t)stream);
+}

@@ -208,4 +208,20 @@ int launch_tex_coords(const int* label, const int* chart, const int* pal, const 
                       int pal_oy, int pal_page, int P, long pages, const unsigned* faces, long nv, const unsigned char* vrgb,
                       unsigned char* atlas, float* tc, int* texnum, hipStream_t st);
 
+// texture_level.hip: global seam levelling of the textured mesh (include/adamvs_hip.h, "Mesh texturing", seam levelling)
+constexpr int TEX_LEVEL_BLOCKS = ADAMVS_TEXTURE_LEVEL_BLOCKS;
+int launch_lvl_observe(const long long* view_tab, int nviews, const int* rowptr, const unsigned* col, long nnz, const int* node_view,
+                       const float* pos, long n, float* f, hipStream_t st);
+int launch_lvl_rhs(const int* rowptr, const unsigned* col, long nnz, const float* f, long n, double* b, hipStream_t st);
+int launch_lvl_cg_init(const double* b, long n, double tol, double* g, double* r, double* p, double* partials, double* state,
+                       hipStream_t st);
+int launch_lvl_cg(const int* rowptr, const unsigned* col, long nnz, long n, double lambda, int count, double* g, double* r, double* p,
+                  double* ap, double* partials, double* state, hipStream_t st);
+int launch_lvl_owner(const float* uv, const int* chart, long nf, const int* charts, const long long* prefix, int nc, long texels,
+                     int* owner, unsigned* big_count, unsigned* big_list, hipStream_t st);
+int launch_lvl_dilate(const int* charts, const long long* prefix, int nc, long texels, const int* in, int* out, hipStream_t st);
+int launch_lvl_apply(const float* uv, const int* corner_node, long nf, const double* g, long n, const int* charts,
+                     const long long* prefix, int nc, long texels, const int* owner, int P, long pages, unsigned char* atlas,
+                     hipStream_t st);
+
 }  // namespace adamvs

@@ -944,3 +944,113 @@ def texture_coords(label, chart, pal, uv, charts, pal_place, P, faces, vrgb, atl
                                             atlas.shape[0], _p(faces), vrgb.shape[0], _p(vrgb), _p(atlas), _p(tc), _p(texnum), _stream()),
           "texture_coords")
     return tc, texnum
+
+
+# ---- seam levelling (csrc/texture_level.hip; driven by ada_mvs_amd/texture.py) ------------------------------------------------
+# The node graph is a CSR built by the caller: rowptr int32 [n + 1], col int32 [nnz] holding uint32 words (bits 0 .. 29 the
+# neighbour, bit 30 a seam edge, bit 31 a data edge).
+def _level_graph(rowptr, col):
+    rowptr, col = _dev_as(rowptr, "rowptr", torch.int32), _dev_as(col, "col", torch.int32)
+    n = rowptr.numel() - 1
+    if n < 0:
+        raise _lib.AdaMVSHipError("texture_level: rowptr must hold n + 1 entries")
+    return rowptr, col, n
+
+
+def texture_level_view_table(views):
+    """[_lib.OrthoView] -> the device table int64 [nviews, 3] = (image address, W, H) _level_observe reads (the images must outlive it)."""
+    return torch.tensor([[int(v.rgba), int(v.W), int(v.H)] for v in views], dtype=torch.int64).reshape(-1, 3)
+
+
+def texture_level_observe(view_tab, rowptr, col, node_view, pos):
+    """adamvs_texture_level_observe -> f float32 [n, 3]: the colour every node's view shows at it, averaged along its seam edges."""
+    rowptr, col, n = _level_graph(rowptr, col)
+    view_tab, node_view, pos = _dev_as(view_tab, "view_tab", torch.int64), _dev_as(node_view, "node_view", torch.int32), _dev(pos, "pos")
+    if node_view.numel() != n or pos.numel() != 2 * n or view_tab.dim() != 2 or view_tab.shape[1] != 3:
+        raise _lib.AdaMVSHipError("texture_level_observe: %d nodes, node_view %d, pos %d" % (n, node_view.numel(), pos.numel()))
+    f = torch.empty(n, 3, device=rowptr.device, dtype=torch.float32)
+    check(_lib.load().adamvs_texture_level_observe(_p(view_tab), view_tab.shape[0], _p(rowptr), _p(col), col.numel(), _p(node_view), _p(pos),
+                                                   n, _p(f), _stream()), "texture_level_observe")
+    return f
+
+
+def texture_level_rhs(rowptr, col, f):
+    """adamvs_texture_level_rhs -> b float64 [n, 3] = sum over data neighbours of (f_j - f_i)."""
+    rowptr, col, n = _level_graph(rowptr, col)
+    f = _dev(f, "f")
+    if f.numel() != 3 * n:
+        raise _lib.AdaMVSHipError("texture_level_rhs: f %s for %d nodes" % (tuple(f.shape), n))
+    b = torch.empty(n, 3, device=rowptr.device, dtype=torch.float64)
+    check(_lib.load().adamvs_texture_level_rhs(_p(rowptr), _p(col), col.numel(), _p(f), n, _p(b), _stream()), "texture_level_rhs")
+    return b
+
+
+LEVEL_POLL = 16          # iterations queued per read of the stop flag
+
+
+def texture_level_solve(rowptr, col, b, lam, tol, iters):
+    """Conjugate gradients on L g = b from g = 0 (adamvs_texture_level_cg_init, then adamvs_texture_level_cg in groups of LEVEL_POLL
+    iterations with one read of the stop flag after each) -> (g float64 [n, 3], iterations, residual [3] = |r| / |b| per channel
+    (0 where b = 0), cap_hit)."""
+    rowptr, col, n = _level_graph(rowptr, col)
+    b = _dev_as(b, "b", torch.float64)
+    lam, tol, iters = float(lam), float(tol), int(iters)
+    if b.numel() != 3 * n:
+        raise _lib.AdaMVSHipError("texture_level_solve: b %s for %d nodes" % (tuple(b.shape), n))
+    dev = rowptr.device
+    g, r, p, ap = (torch.zeros(n + 1, 3, device=dev, dtype=torch.float64) for _ in range(4))      # one spare row (16-byte passes)
+    partials = torch.zeros(3 * _lib.TEXTURE_LEVEL_BLOCKS, device=dev, dtype=torch.float64)
+    state = torch.zeros(16, device=dev, dtype=torch.float64)
+    lib = _lib.load()
+    check(lib.adamvs_texture_level_cg_init(_p(b) if n else _p(g), n, tol, _p(g), _p(r), _p(p), _p(partials), _p(state), _stream()),
+          "texture_level_cg_init")
+    # the argument checks of _cg run even when nothing is queued
+    check(lib.adamvs_texture_level_cg(_p(rowptr), _p(col), col.numel(), n, lam, 0, _p(g), _p(r), _p(p), _p(ap), _p(partials), _p(state),
+                                      _stream()), "texture_level_cg")
+    queued = 0
+    while queued < iters and float(state[12].item()) == 0.0:
+        k = min(LEVEL_POLL, iters - queued)
+        check(lib.adamvs_texture_level_cg(_p(rowptr), _p(col), col.numel(), n, lam, k, _p(g), _p(r), _p(p), _p(ap), _p(partials), _p(state),
+                                          _stream()), "texture_level_cg")
+        queued += k
+    st = state.cpu().numpy()
+    res = [float(np.sqrt(st[c] / st[3 + c])) if st[3 + c] > 0 else 0.0 for c in range(3)]
+    return g[:n], int(st[13]), res, bool(st[12] == 0.0)
+
+
+def texture_level_owner(uv, chart, charts, prefix, big):
+    """adamvs_texture_level_owner -> owner int32 [texels] (2^31 - 1: unowned) over the concatenated chart boxes; prefix int64
+    [nc + 1] on the device, big int32 [1 + nf]."""
+    uv, chart, charts = _dev(uv, "uv"), _dev_as(chart, "chart", torch.int32), _dev_as(charts, "charts", torch.int32)
+    prefix, big = _dev_as(prefix, "prefix", torch.int64), _dev_as(big, "big", torch.int32)
+    nf, nc = chart.numel(), prefix.numel() - 1
+    if uv.numel() != 6 * nf or nc < 0 or (nc and tuple(charts.shape) != (nc, 8)) or big.numel() < 1:
+        raise _lib.AdaMVSHipError("texture_level_owner: %d faces, uv %d, %d charts, charts %s" % (nf, uv.numel(), nc, tuple(charts.shape)))
+    texels = int(prefix[-1].item())
+    owner = torch.empty(texels, device=chart.device, dtype=torch.int32)
+    check(_lib.load().adamvs_texture_level_owner(_p(uv), _p(chart), nf, _p(charts), _p(prefix), nc, texels, _p(owner), _p(big),
+                                                 ctypes.c_void_p(big.data_ptr() + 4), big.numel() - 1, _stream()), "texture_level_owner")
+    return owner
+
+
+def texture_level_dilate(charts, prefix, owner):
+    """adamvs_texture_level_dilate: one round -> a new owner tensor."""
+    charts, prefix, owner = _dev_as(charts, "charts", torch.int32), _dev_as(prefix, "prefix", torch.int64), _dev_as(owner, "owner", torch.int32)
+    out = torch.empty_like(owner)
+    check(_lib.load().adamvs_texture_level_dilate(_p(charts), _p(prefix), prefix.numel() - 1, owner.numel(), _p(owner), _p(out), _stream()),
+          "texture_level_dilate")
+    return out
+
+
+def texture_level_apply(uv, corner_node, g, charts, prefix, owner, P, atlas):
+    """adamvs_texture_level_apply: g float64 [n, 3] interpolated in every owned texel's owner and added to atlas (uint8
+    [pages, P, P, 4], in place)."""
+    uv, corner_node, g = _dev(uv, "uv"), _dev_as(corner_node, "corner_node", torch.int32), _dev_as(g, "g", torch.float64)
+    charts, prefix, owner = _dev_as(charts, "charts", torch.int32), _dev_as(prefix, "prefix", torch.int64), _dev_as(owner, "owner", torch.int32)
+    if not (atlas.is_cuda and atlas.is_contiguous() and atlas.dtype == torch.uint8) or tuple(atlas.shape[1:]) != (P, P, 4):
+        raise _lib.AdaMVSHipError("texture_level_apply: atlas %s for page %d (contiguous uint8 on the device)" % (tuple(atlas.shape), P))
+    nf = corner_node.shape[0]
+    if uv.numel() != 6 * nf or corner_node.numel() != 3 * nf:
+        raise _lib.AdaMVSHipError("texture_level_apply: uv %d, corner_node %d for %d faces" % (uv.numel(), corner_node.numel(), nf))
+    check(_lib.load().adamvs_texture_level_apply(_p(uv), _p(corner_node), nf, _p(g), g.shape[0], _p(charts), _p(prefix), prefix.numel() - 1,
+                                                 owner.numel(), _p(owner), int(P), atlas.shape[0], _p(atlas), _stream()), "texture_level_apply")

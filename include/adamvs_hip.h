@@ -829,11 +829,77 @@ int adamvs_ortho_finalize(const adamvs_ortho_grid* grid, const float* acc, const
  *            per channel (c0 + c1 + c2 + 1) div 3 of its vertex colours vrgb [nv][3] uint8 (the rounded mean).
  * Argument errors (<0, before any launch): a null pointer where data is read or written, nv < 1, nf < 0 or > 2^31 - 1, a view
  * of H or W < 1 or with a non-finite C, R or K or K's last row not 0 0 1, border or tol < 0 or not finite, big_capacity < nf,
- * P not a power of two in ADAMVS_TEXTURE_MIN_PAGE .. ADAMVS_TEXTURE_MAX_PAGE, npages < 1, n < 0. */
+ * P not a power of two in ADAMVS_TEXTURE_MIN_PAGE .. ADAMVS_TEXTURE_MAX_PAGE, npages < 1, n < 0.
+ *
+ * Seam levelling (csrc/texture_level.hip; opt-in, after _boxes, the packing, _fill and _coords, on their labels, charts and atlas).
+ * Every chart boundary between two views shows the views' difference in exposure; one additive correction g per node and
+ * channel, found by one global least-squares solve and interpolated over the charts, levels it (Waechter et al. 2014, the
+ * global adjustment; this definition is the project's own).
+ * Nodes.  One node per distinct pair (vertex index v, chart c) over the corners of textured faces (chart >= 0), numbered in
+ * ascending (v, c).  Untextured faces contribute nothing.  Vertices are identified by index: an unwelded mesh is levelled
+ * brick by brick.  n <= ADAMVS_TEXTURE_LEVEL_MAX_NODES = 2^30.  corner_node [nf][3] int32: the node of every corner of a
+ * textured face (anything on untextured faces: they own no texel).  pos [n][2] fp32: the node's (u, v) in its chart's view, the
+ * uv the faces of c stored at v (every such face stored the same bits); node_view [n] int32: that view's index.
+ * Edges, undirected, each once: SMOOTHNESS (weight 1 / lambda) between (v, c) and (w, c) for every distinct mesh edge {v, w},
+ * v != w, of a face of chart c; DATA (weight 1) between (v, a) and (v, b) for every vertex v and charts a < b at v.  A smoothness
+ * edge {v, w} of chart c is a SEAM edge if {v, w} is also an edge of a textured face of another chart.
+ * Graph: a CSR over the nodes with both directions of every edge, rowptr [n + 1] int32, col [nnz] uint32 sorted by neighbour
+ * within a row: bits 0 .. 29 the neighbour, bit 30 set on a seam edge, bit 31 set on a data edge.  Built by the caller.
+ *   _level_observe  f [n][3] fp32 (R G B), the colour chart c's view shows at v.  sample(x, y) is the bilinear sample "Image
+ *                   orthophoto" states, in view node_view[i] (view_tab [nviews][3] int64 on the device: the image's device
+ *                   address, W, H).  With p = pos[i]: acc = 0, wsum = 0; for every seam edge of row i in ascending neighbour j,
+ *                   d = pos[j] - p, and for (t, w) = (0, 1), (1/4, 3/4), (1/2, 1/2) in that order: acc = acc + w sample(p + t d),
+ *                   wsum = wsum + w; f = acc / wsum (fp32, left to right, no contraction).  A node without a seam edge takes
+ *                   f = sample(p).
+ *   _level_rhs      b [n][3] fp64: b_i = sum over the data neighbours j of row i, ascending, of ((double)f_j - (double)f_i).
+ * System.  Per channel, minimise  sum_data (f_i + g_i - f_j - g_j)^2 + (1 / lambda) sum_smooth (g_i - g_j)^2.  The normal
+ * equations are the weighted graph Laplacian L g = b, L = D - W.  L is singular (constants per connected component); the
+ * solution wanted is the MINIMUM-NORM one: a chart without seams keeps g = 0 exactly, a large chart moves less than a small
+ * neighbour.
+ * The solve takes any CSR of the graph: the driver renumbers the nodes for it (by chart, then along a Z-order curve of pos in
+ * quarter pixels, ties in node order), so that a row's neighbours lie near it in memory, permutes b into that order and g back.
+ * The numbering fixes the order of every sum, so it is part of what makes g reproducible bit for bit.
+ *   _level_cg_init  g = 0, r = p = b, state: r.r = b.b per channel, iterations = 0, stop = every channel has r.r <= tol^2 b.b
+ *                   (so b = 0 stops before the first iteration).
+ *   _level_cg       `iters` iterations of plain conjugate gradients (NO preconditioner: from g = 0 the iterates stay in
+ *                   range(L), so the limit is the minimum-norm solution; a Jacobi preconditioner changes that gauge), fp64
+ *                   vectors [n][3] and scalars, the three channels interleaved, sharing L, each with its own alpha and beta:
+ *                   Ap = L p;  alpha = r.r / p.Ap (0 if p.Ap <= 0);  g += alpha p;  r -= alpha Ap;  beta = r'.r' / r.r (0 if
+ *                   r.r <= 0);  iterations += 1;  stop as above;  p = r + beta p.  Once stop is set every remaining kernel of the
+ *                   call (and of later calls) returns without writing: g and the count are those of the stopping iteration, so
+ *                   the caller may queue 16 iterations per read of the flag.  Dot products: ADAMVS_TEXTURE_LEVEL_BLOCKS = 2048
+ *                   workgroups at most, each a fixed run of rows, reduced by one workgroup in a fixed order; no floating-point
+ *                   atomics, so g is bit-identical from run to run.  partials [3 ADAMVS_TEXTURE_LEVEL_BLOCKS] fp64 workspace.
+ *                   g, r, p, Ap hold [n + 1][3] fp64, 16-byte aligned: one spare row, so that the update passes may read and
+ *                   write the vectors 16 bytes per lane whatever the parity of 3 n; the spare row holds no data.
+ *                   state [16] fp64: 0..2 r.r, 3..5 b.b, 6..8 alpha, 9..11 beta, 12 stop (0 / 1), 13 iterations, 14 tol^2.
+ * Apply.  The texels of all chart boxes concatenated in chart order, row-major in each box: prefix [nc + 1] int64 = exclusive
+ * sum of w h, texels = prefix[nc]; owner [texels] int32.
+ *   _level_owner    owner = INT_MAX (unowned), then for every textured face f of chart c: its image triangle uv[f] set up as the
+ *                   z-buffer's triangles are (orientation swap, box of pixel centres, here clamped to the chart's box) and
+ *                   owner = atomicMin(owner, f) on every texel whose centre, the pixel centre (x0 + dx, y0 + dy), passes the
+ *                   inclusive edge functions: the owner is the smallest face of c that holds the centre.  Faces whose box holds
+ *                   more than ADAMVS_ORTHO_SMALL_PX centres go through big_list (at least nf entries) one wave per face.
+ *   _level_dilate   one round, owner_in -> owner_out (two buffers): an owned texel keeps its owner; an unowned one takes the
+ *                   owner of the first owned texel of its 3 x 3 neighbourhood inside the chart's box, in row-major order, of
+ *                   owner_in.  The caller runs ADAMVS_TEXTURE_LEVEL_BAND = 2 rounds (bilinear taps of a face's texture
+ *                   coordinates lie within one texel of its triangle).
+ *   _level_apply    an owned texel with centre (x, y) and owner f = (u_k, v_k), corner nodes n_k, g_k = (float)g[n_k]:
+ *                   area = (u1-u0)(v2-v0) - (v1-v0)(u2-u0),  e1 = (u0-u2)(y-v2) - (v0-v2)(x-u2),  e2 = (u1-u0)(y-v0) - (v1-v0)(x-u0),
+ *                   b1 = e1 / area, b2 = e2 / area,  gi = g0 + b1 (g1 - g0) + b2 (g2 - g0) clamped to [min g_k, max g_k] (which
+ *                   changes nothing inside the triangle and bounds the band outside it), fp32, left to right; per channel the
+ *                   texel becomes floor(texel + gi + 1/2) clamped to 0 .. 255.  Unowned texels, the palette block and the alpha
+ *                   byte are untouched.
+ * Argument errors (<0, before any launch): a null pointer where data is read or written, n < 0 or > 2^30, nnz < 0, nviews < 1,
+ * lambda <= 0 or not finite, tol < 0 or not finite, iters < 0, nc < 0, texels < 0, nf < 0, big_capacity < nf, owner_in ==
+ * owner_out, a vector of _level_cg not 16-byte aligned, P and npages as above. */
 #define ADAMVS_TEXTURE_TILE 256
 #define ADAMVS_TEXTURE_MIN_PAGE 1024
 #define ADAMVS_TEXTURE_MAX_PAGE 16384
 #define ADAMVS_TEXTURE_MAX_FACES 2147483647L
+#define ADAMVS_TEXTURE_LEVEL_MAX_NODES (1L << 30)
+#define ADAMVS_TEXTURE_LEVEL_BLOCKS 2048
+#define ADAMVS_TEXTURE_LEVEL_BAND 2
 
 int adamvs_texture_project(const adamvs_ortho_view* view, const double* xyz, long nv, float* uvz, void* stream);
 int adamvs_texture_zbuf(const adamvs_ortho_view* view, const float* uvz, long nv, const unsigned* faces, long nf, unsigned* zbuf,
@@ -852,6 +918,20 @@ int adamvs_texture_fill(const adamvs_ortho_view* view, const int* items, const l
 int adamvs_texture_coords(const int* label, const int* chart, const int* pal, const float* uv, long nf, const int* charts, int pal_ox,
                           int pal_oy, int pal_page, int P, long npages, const unsigned* faces, long nv, const unsigned char* vrgb,
                           unsigned char* atlas, float* tc, int* texnum, void* stream);
+int adamvs_texture_level_observe(const long long* view_tab, int nviews, const int* rowptr, const unsigned* col, long nnz,
+                                 const int* node_view, const float* pos, long n, float* f, void* stream);
+int adamvs_texture_level_rhs(const int* rowptr, const unsigned* col, long nnz, const float* f, long n, double* b, void* stream);
+int adamvs_texture_level_cg_init(const double* b, long n, double tol, double* g, double* r, double* p, double* partials, double* state,
+                                 void* stream);
+int adamvs_texture_level_cg(const int* rowptr, const unsigned* col, long nnz, long n, double lambda, int iters, double* g, double* r,
+                            double* p, double* ap, double* partials, double* state, void* stream);
+int adamvs_texture_level_owner(const float* uv, const int* chart, long nf, const int* charts, const long long* prefix, int nc,
+                               long texels, int* owner, unsigned* big_count, unsigned* big_list, long big_capacity, void* stream);
+int adamvs_texture_level_dilate(const int* charts, const long long* prefix, int nc, long texels, const int* owner_in, int* owner_out,
+                                void* stream);
+int adamvs_texture_level_apply(const float* uv, const int* corner_node, long nf, const double* g, long n, const int* charts,
+                               const long long* prefix, int nc, long texels, const int* owner, int P, long npages,
+                               unsigned char* atlas, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,10 +1,14 @@
 """Mesh texture timing (csrc/texture.hip): the TSDF mesh of tools/fusion_bench.py's 5-view scene textured from its 5 images.
     python tools/texture_bench.py [--H 2752 --W 1856] [--voxel 0.25] [--page 8192] [--write 1]
+                                  [--seam_level 1 [--seam_tol 1e-4] [--seam_iters 1000]]
 The scene of tools/mesh_bench.py (one nadir and four 40-degree obliques, each view fused against the other four on the GPU),
 meshed over every active brick of 128^3 at --voxel and welded on the GPU.  One warm-up texturing of a small part of the mesh,
 then one timed run of texture.texture_mesh over the whole mesh: device events per phase (project + z-buffer, score, edge sort +
 components, rank + boxes, fill + texture coordinates), host seconds for packing and (--write 1) for writing the PLY and the
-pages to a temporary folder.  One JSON line.
+pages to a temporary folder.  One JSON line.  With --seam_level 1 the same run also levels the seams (csrc/texture_level.hip): the
+line then holds the three level_* phases, `device_ms_base` (the five phases every run has: the yardstick), the node graph's
+sizes, the iterations, and the solve's traffic per iteration counted from the array sizes (the CSR once, the fp64 vectors
+as the three passes read and write them: 11 vector passes of 24 bytes per node) over the level_solve time.
 """
 import argparse
 import json
@@ -54,6 +58,9 @@ def main():
     ap.add_argument("--voxel", type=float, default=0.25)
     ap.add_argument("--page", type=int, default=8192)
     ap.add_argument("--write", type=int, default=1, help="also time writing the PLY and the pages (to a temporary folder)")
+    ap.add_argument("--seam_level", type=int, default=0, help="1: level the seams too and report the level_* phases")
+    ap.add_argument("--seam_tol", type=float, default=1e-4)
+    ap.add_argument("--seam_iters", type=int, default=1000)
     args = ap.parse_args()
     import torch
     from ada_mvs_amd import fusion, texture
@@ -67,10 +74,11 @@ def main():
     tviews = [dict(iid=i, K=v["K"], R=v["R"], C=v["C"], rgba=v["rgba"]) for i, v in enumerate(views)]
     setup_s = time.time() - t0
     tol = 2.0 * args.voxel
-    texture.texture_mesh(xyz, rgb, faces[:100000], tviews, tol, page=args.page, device=dev)         # warm-up
+    level = dict(seam_level=True, seam_tol=args.seam_tol, seam_iters=args.seam_iters) if args.seam_level else {}
+    texture.texture_mesh(xyz, rgb, faces[:100000], tviews, tol, page=args.page, device=dev, **level)         # warm-up
     torch.cuda.synchronize()
     t1 = time.time()
-    res = texture.texture_mesh(xyz, rgb, faces, tviews, tol, page=args.page, device=dev)
+    res = texture.texture_mesh(xyz, rgb, faces, tviews, tol, page=args.page, device=dev, **level)
     run_s = time.time() - t1
     out = {"workload": "texture", "H": args.H, "W": args.W, "views": len(views), "voxel": args.voxel, "vertices": int(xyz.shape[0]),
            "faces": res["faces"], "faces_textured": res["faces_textured"], "faces_untextured": res["faces_untextured"],
@@ -78,6 +86,19 @@ def main():
            "box_fraction": round(res["box_fraction"], 4), "device_ms": {k: round(v, 3) for k, v in res["device_ms"].items()},
            "device_ms_total": round(res["device_ms_total"], 3), "target_device_ms": TARGET_MS,
            "meets_target": res["device_ms_total"] <= TARGET_MS, "pack_s": round(res["pack_seconds"], 3), "texture_mesh_s": round(run_s, 3)}
+    if args.seam_level:
+        n, nnz, it = res["nodes"], res["graph_entries"], res["seam_iterations"]
+        bytes_per_iter = 4 * (n + 1) + 4 * nnz + 11 * 24 * n
+        solve_ms = res["device_ms"]["level_solve"]
+        base = sum(res["device_ms"][k] for k in texture.PHASES)
+        out.update({"device_ms_base": round(base, 3), "nodes": n, "graph_entries": nnz, "data_edges": res["data_edges"],
+                    "seam_edges": res["seam_edges"], "seam_tol": args.seam_tol, "seam_iters": args.seam_iters, "seam_iterations": it,
+                    "seam_cap_hit": res["seam_cap_hit"], "seam_residual": [float("%.3g" % r) for r in res["seam_residual"]],
+                    "seam_rms_before": round(res["seam_rms_before"], 4), "seam_rms_after": round(res["seam_rms_after"], 4),
+                    "solve_bytes_per_iteration": bytes_per_iter, "solve_ms_per_iteration": round(solve_ms / max(it, 1), 4),
+                    "solve_tb_per_s": round(bytes_per_iter * it / (solve_ms * 1e-3) / 1e12, 3) if solve_ms > 0 else None,
+                    "copy_rate_tb_per_s": 6.3, "level_over_base": round((res["device_ms_total"] - base) / base, 3)})
+        out["meets_target"] = base <= TARGET_MS
     if args.write:
         verts = np.zeros(int(xyz.shape[0]), fusion.PLY_DTYPE)
         x = xyz.cpu().numpy()
