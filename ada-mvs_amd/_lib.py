@@ -135,6 +135,7 @@ SIGNATURES = {
                                     ctypes.c_void_p, c_sz, c_st]),
     "adamvs_depth_stage_workspace_bytes": (c_sz, [ctypes.POINTER(StageDesc)]),
     "adamvs_recurrence_schedule": (c_i, [c_i, ctypes.c_longlong]),
+    "adamvs_conv_t2_form": (c_i, [c_i, c_i, c_i, c_i]),
     "adamvs_gru_wino_mask": (c_i, []),
     "adamvs_depth_stage_forward": (c_i, [ctypes.POINTER(StageDesc), c_f, c_f, c_f, c_f, c_f, c_sz, ctypes.POINTER(FuseWeights),
                                          c_f, c_f, c_f, c_f, c_i, ctypes.c_void_p, c_sz, c_st]),

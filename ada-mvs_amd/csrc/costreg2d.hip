@@ -680,7 +680,219 @@ __global__ __launch_bounds__(256, 2) void k_conv_dd_s2p(ConvDDArgs a) {
   conv_dd_s2_pairs<MT, WM>(a, lds, blockIdx.z, blockIdx.y, blockIdx.x);
 }
 
-// option s2_pairs = 0: the stride-2 layers on the direct kernel, as in rounds 1-4 (A/B)
+// Transposed layer (conv7, conv9, conv11 of the hourglass) with the same minimal-filtering form along x.  The odd output columns of a
+// row are a two-tap filter over neighbouring inputs (tap names as in conv_dd_t2_all: kx = 2 meets in[j], kx = 0 meets in[j + 1]),
+//     out[2j + 1] = W2 in[j] + W0 in[j + 1],          out[2j + 3] = W2 in[j + 1] + W0 in[j + 2]
+// and two neighbouring ones share in[j + 1]:
+//     A1 = W2 (in[j] - in[j + 1]);  A2 = (W0 + W2) in[j + 1];  A3 = W0 (in[j + 2] - in[j + 1]);  out[2j + 1] = A1 + A2,  out[2j + 3] = A3 + A2
+// -- three products per two odd outputs instead of four; the even columns (out[2j] = W1 in[j]) stay direct.  Five MFMAs per (kernel
+// row, 4 input channels, channel tile, input row) for an input PAIR = four output pixels where the class-by-class kernel issues six:
+// 15 / 18 of the layer's products.  The columns of an MFMA are 16 input pairs; a lane reads in[2p .. 2p + 2] as one 8-byte and one
+// 4-byte LDS read (row pitch 34: aligned), forms the two differences (2 vector instructions per 5 MT MFMAs) and W0 + W2 once per chunk.
+// Five accumulator sets per input row; block = NR input rows x 32 input columns (2 NR x 64 outputs) x all channels, every wave all rows of
+// its 48 channels.  The two row classes run one after the other as in conv_dd_t2_all, the next one's first chunk requested during the
+// last chunk of the current one: py = 1 (odd output rows: kernel rows 2 and 0 on input rows i, i + 1) with KB1 input channels per chunk,
+// py = 0 (kernel row 1 on row i: half the MFMAs per channel) with KB0.  What differs at the ends of a class is peeled out of its chunk
+// loop (requests inside it are unconditional).  Built as NR = 2, KB1 = KB0 = 8: 120 accumulator registers, 120 / 60 MFMAs per wave and
+// barrier pair, 256 registers with one dword of scratch outside the chunk loops.  KB0 = 16 (120 MFMAs in both classes) spills 13
+// registers, some inside the loops; NR = 3 (180 accumulator registers) spills 170 - 340 (docs/history/tried_without_gain.md).
+constexpr int T2P_COLS = 32;     // input columns per block
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__host__ __device__ constexpr int plane_pitch32(int n) { return ((n + 31) / 64) * 64 + 32; }   // >= n, 32 mod 64: the two k-rows of a 32-lane ds_read_b64 group on disjoint banks
+template <int NR> struct T2PGeom {
+  static constexpr int WCOLS = T2P_COLS + 1, LC = T2P_COLS + 2, PLANE = plane_pitch32((NR + 1) * LC);
+  static constexpr int lds_floats(int KB) { return (KB / 4) * group_pitch(PLANE, KB / 4); }
+};
+template <int MT, int NR, int KB1, int KB0>
+__device__ __forceinline__ void conv_dd_t2_pairs(const ConvDDArgs& a, float* lds, int n, int by, int bx) {
+  using G = T2PGeom<NR>;
+  constexpr int WCOLS = G::WCOLS, LC = G::LC, PLANE = G::PLANE;
+  constexpr int NI1 = ((NR + 1) * WCOLS * (KB1 / 4) + 255) / 256, NI0 = KB0 == KB1 ? NI1 : (NR * WCOLS * (KB0 / 4) + 255) / 256, NIM = NI1 > NI0 ? NI1 : NI0;
+  constexpr int NW = (6 * (KB1 / 4) > 3 * (KB0 / 4) ? 6 * (KB1 / 4) : 3 * (KB0 / 4)) * MT;
+  static_assert(192 % (2 * KB1) == 0 && 192 % (2 * KB0) == 0, "an even number of chunks per class at D = 192, 384");
+  const int tid = threadIdx.x, lane = tid & 63, wm = __builtin_amdgcn_readfirstlane(tid >> 6);    // wave = channel slice
+  const int p = lane & 15, q = lane >> 4;
+  const int D = a.D, KCT = D / 4, NTILES = D / 16;
+  const int r0 = by * NR, c0 = bx * T2P_COLS;                  // block origin: input positions (i, j)
+
+  const buf_rsrc rx = make_rsrc((const char*)a.in + (((long)n * a.hi + r0) * a.wi + c0) * (long)D * 4);
+  const bool two = a.in2 != nullptr;                           // uniform: the layer convolves in + in2
+  const buf_rsrc rx2 = make_rsrc((const char*)(two ? a.in2 : a.in) + (((long)n * a.hi + r0) * a.wi + c0) * (long)D * 4);
+  // window fill, per class: item = (pixel of the window, group of 4 channels); pixels outside the map read as zero
+  unsigned xoff1[NI1], xlds1[NI1], xoff0[NI0], xlds0[NI0];
+  auto fill_consts = [&](auto pyc, auto kbc, auto& xoff, auto& xlds) {
+    constexpr int PY = decltype(pyc)::value, NG = decltype(kbc)::value / 4, NITEMS = (NR + PY) * WCOLS * NG, GP = group_pitch(PLANE, NG);
+#pragma unroll
+    for (int it = 0; it < (NITEMS + 255) / 256; ++it) {
+      const int i = min(tid + it * 256, NITEMS - 1);           // surplus lanes repeat the last item
+      const int g = i % NG, pp = i / NG, r = pp / WCOLS, c = pp % WCOLS;
+      const bool ok = r0 + r < a.hi && c0 + c < a.wi;
+      xoff[it] = ok ? (unsigned)(((r * a.wi + c) * D + 4 * g) * 4) : BUF_OOB;
+      xlds[it] = (unsigned)((g * GP + r * LC + c) * 4);
+      pin(xoff[it]); pin(xlds[it]);
+    }
+  };
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using K0 = std::integral_constant<int, KB0>;
+  using K1 = std::integral_constant<int, KB1>;
+  constexpr bool SAME = KB0 == KB1;                            // one fill for both classes: py = 0 loads (and ignores) the row below its own
+  fill_consts(I1{}, K1{}, xoff1, xlds1);
+  if (!SAME) fill_consts(I0{}, K0{}, xoff0, xlds0);
+  const buf_rsrc rw = make_rsrc(a.wpk);
+  unsigned woff = (unsigned)(lane * 4);
+  pin(woff);
+  unsigned xb = (unsigned)((q * PLANE + 2 * p) * 4);           // the lane's k-row and the first window column of its pair
+  pin(xb);
+  // epilogue: the lane's four output pixels (columns 4 p' .. 4 p' + 3 of the block's 64) of class py = 0 in input row r, as a byte offset
+  // from the image; BUF_OOB outside the map (the width is even: a pair is inside or outside as a whole), so that EVERY lane issues every store
+  const buf_rsrc ro = make_rsrc((char*)a.out + (long)n * a.ho * a.wo * (long)D * 4);
+  const buf_rsrc rk = make_rsrc((const char*)(a.skip ? a.skip : a.out) + (long)n * a.ho * a.wo * (long)D * 4);
+  unsigned ooff[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    const int row = r0 + r, col = c0 + 2 * p;
+    ooff[r] = (row < a.hi && col < a.wi) ? (unsigned)((((2 * row) * a.wo + 2 * col) * D + wm * MT * 16 + 4 * q) * 4) : BUF_OOB;
+    pin(ooff[r]);
+  }
+
+  float wfA[NW], wfB[NW];                                      // [kernel row of the class][kx][k-step][channel tile]
+  f32x4 xs[NIM], xs2[NIM];
+  f32x4 acc[5][MT][NR];                                        // even outputs E0 | E1, then A1 | A2 | A3
+
+  auto load_x = [&](auto pyc, auto kbc, int ch) {
+    constexpr int PY = decltype(pyc)::value, NI = PY ? NI1 : NI0;
+#pragma unroll
+    for (int it = 0; it < NI; ++it) {
+      const unsigned o = PY || SAME ? xoff1[it < NI1 ? it : 0] : xoff0[it < NI0 ? it : 0];
+      xs[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, o, (unsigned)ch * 4u, 0));
+    }
+    if (two) {
+#pragma unroll
+      for (int it = 0; it < NI; ++it) {
+        const unsigned o = PY || SAME ? xoff1[it < NI1 ? it : 0] : xoff0[it < NI0 ? it : 0];
+        xs2[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx2, o, (unsigned)ch * 4u, 0));
+      }
+    }
+  };
+  auto store_x = [&](auto pyc) {
+    constexpr int PY = decltype(pyc)::value, NI = PY ? NI1 : NI0;
+#pragma unroll
+    for (int it = 0; it < NI; ++it) {
+      float* dl = (float*)((char*)lds + (PY || SAME ? xlds1[it < NI1 ? it : 0] : xlds0[it < NI0 ? it : 0]));
+      const f32x4 v = two ? xs[it] + xs2[it] : xs[it];
+      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
+    }
+  };
+  auto load_w = [&](auto pyc, auto kbc, float (&wf)[NW], int ch) {
+    constexpr int PY = decltype(pyc)::value, NG = decltype(kbc)::value / 4;
+#pragma unroll
+    for (int ty = 0; ty <= PY; ++ty)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int ky = PY ? (ty ? 0 : 2) : 1;
+#pragma unroll
+        for (int kc = 0; kc < NG; ++kc)
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            const unsigned frag = (unsigned)(((ky * 3 + kx) * KCT + ch / 4 + kc) * NTILES + wm * MT + mt) * 256u;   // uniform
+            wf[((ty * 3 + kx) * NG + kc) * MT + mt] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, woff, frag, 0));
+          }
+      }
+  };
+  auto mfma_chunk = [&](auto pyc, auto kbc, const float (&wf)[NW]) {
+    constexpr int PY = decltype(pyc)::value, NG = decltype(kbc)::value / 4, GP = group_pitch(PLANE, NG);
+#pragma unroll
+    for (int ty = 0; ty <= PY; ++ty)
+#pragma unroll
+      for (int kc = 0; kc < NG; ++kc) {
+        float w02[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) w02[mt] = wf[((ty * 3 + 0) * NG + kc) * MT + mt] + wf[((ty * 3 + 2) * NG + kc) * MT + mt];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+          const char* row = (const char*)lds + xb + (kc * GP + (r + ty) * LC) * 4;
+          const f32x2 c = *(const f32x2*)row;
+          const float c2 = *(const float*)(row + 8);
+          const float d0 = c.x - c.y, d1 = c2 - c.y;
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            acc[0][mt][r] = mfma16(wf[((ty * 3 + 1) * NG + kc) * MT + mt], c.x, acc[0][mt][r]);
+            acc[1][mt][r] = mfma16(wf[((ty * 3 + 1) * NG + kc) * MT + mt], c.y, acc[1][mt][r]);
+            acc[2][mt][r] = mfma16(wf[((ty * 3 + 2) * NG + kc) * MT + mt], d0, acc[2][mt][r]);
+            acc[3][mt][r] = mfma16(w02[mt], c.y, acc[3][mt][r]);
+            acc[4][mt][r] = mfma16(wf[((ty * 3 + 0) * NG + kc) * MT + mt], d1, acc[4][mt][r]);
+          }
+        }
+      }
+  };
+  // one chunk of a class: `cur` holds its fragments and xs its window; `req` issues the requests that follow it
+  auto half = [&](auto pyc, auto kbc, const float (&cur)[NW], auto explicit_wait, auto&& req) {
+    if (decltype(explicit_wait)::value) wait_vmem_all();
+    __syncthreads();                    // previous chunk's readers are done
+    store_x(pyc);
+    __syncthreads();
+    req();
+    mfma_chunk(pyc, kbc, cur);
+  };
+  // one class; wfA and xs hold its first chunk on entry; on exit they hold the first chunk of the next class, if any.
+  // `first`: nothing but that first chunk is in flight (block entry); otherwise the previous class's stores are, and the
+  // wait for the chunk -- requested BEFORE them, vmcnt retires in order -- is left to the compiler, which counts them.
+  auto run_class = [&](auto pyc, auto kbc, auto first, auto&& req_next) {
+    constexpr int PY = decltype(pyc)::value, KB = decltype(kbc)::value;
+#pragma unroll
+    for (int t = 0; t < 5; ++t)
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int r = 0; r < NR; ++r) acc[t][mt][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+    half(pyc, kbc, wfA, first, [&] { load_w(pyc, kbc, wfB, KB); load_x(pyc, kbc, KB); });
+    for (int ch = KB; ch < D - KB; ch += 2 * KB) {
+      half(pyc, kbc, wfB, std::true_type{}, [&] { load_w(pyc, kbc, wfA, ch + KB); load_x(pyc, kbc, ch + KB); });
+      half(pyc, kbc, wfA, std::true_type{}, [&] { load_w(pyc, kbc, wfB, ch + 2 * KB); load_x(pyc, kbc, ch + 2 * KB); });
+    }
+    half(pyc, kbc, wfB, std::true_type{}, req_next);
+#pragma unroll
+    for (int t = 0; t < 5; ++t)
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int r = 0; r < NR; ++r) drain(acc[t][mt][r]);
+    const unsigned cls = (unsigned)(PY * a.wo * D * 4);                    // uniform: the class's row offset
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      const f32x4 b = *(const f32x4*)(a.bias + (wm * MT + mt) * 16 + 4 * q);
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        f32x4 v[4] = {acc[0][mt][r] + b, (acc[2][mt][r] + acc[3][mt][r]) + b, acc[1][mt][r] + b, (acc[4][mt][r] + acc[3][mt][r]) + b};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (a.relu) { v[k].x = fmaxf(v[k].x, 0.f); v[k].y = fmaxf(v[k].y, 0.f); v[k].z = fmaxf(v[k].z, 0.f); v[k].w = fmaxf(v[k].w, 0.f); }
+          // BUF_OOB plus these terms (< 2^31) is still out of range.  The sum is a lane offset, not the scalar offset operand: a 16-byte
+          // store with a scalar offset gets no wait state before the next write of its data registers, and the last store of the
+          // class lost its fourth channel in lanes 12 - 15 to the next class's window sum
+          const unsigned o = ooff[r] + (cls + (unsigned)(mt * 64) + (unsigned)(k * D * 4));
+          if (a.skip) v[k] += buf_load4(rk, o);
+          buf_store4(ro, o, v[k]);
+        }
+      }
+    }
+  };
+  load_w(I1{}, K1{}, wfA, 0);
+  load_x(I1{}, K1{}, 0);
+  run_class(I1{}, K1{}, std::true_type{}, [&] { load_w(I0{}, K0{}, wfA, 0); load_x(I0{}, K0{}, 0); });
+  run_class(I0{}, K0{}, std::false_type{}, [] {});
+}
+
+// grid: (ceil(wi/32), ceil(hi/NR), N); block 256
+template <int MT, int NR, int KB1, int KB0>
+__global__ __launch_bounds__(256, 2) void k_conv_dd_t2p(ConvDDArgs a) {
+  constexpr int F1 = T2PGeom<NR>::lds_floats(KB1), F0 = T2PGeom<NR>::lds_floats(KB0);
+  __shared__ __attribute__((aligned(16))) float lds[F1 > F0 ? F1 : F0];
+  conv_dd_t2_pairs<MT, NR, KB1, KB0>(a, lds, blockIdx.z, blockIdx.y, blockIdx.x);
+}
+
+// option s2_pairs = 0: the stride-2 and the transposed layers on the direct kernels, as in rounds 1-4 (A/B)
 static bool s2_pairs() { return opt(OPT_S2_PAIRS) != 0; }
 
 // grid: (ceil(cols/16), ceil(rows/BR), N); block 256; OCC = waves per SIMD the register budget is held to
@@ -741,6 +953,35 @@ static bool t2_kb8() { return opt(OPT_T2_KB8) != 0; }
 // option costreg_defer_skips = 0: the skip additions in the producing layer's epilogue, as in rounds 1-2 (A/B)
 static bool costreg_deferred_skips() { return opt(OPT_COSTREG_DEFER_SKIPS) != 0; }
 
+static bool conv256_split() { return opt(OPT_CONV256_SPLIT) != 0; }
+
+// Which kernel a transposed layer takes: 0 = class by class (k_conv_dd<CONV_T2>), 1 = the four classes per chunk (k_conv_dd_t2_fused,
+// small grids), 2 = the pair form along x (k_conv_dd_t2p; option s2_pairs = 0: never).  The pair form exists for the 192-channel tiling
+// (D = 192, and 384 as two launches; D = 256 = 2 x 128 channels stays on the direct kernel) and pads a row to blocks of 32 input columns
+// where the direct kernel pads to 16: it is taken for even widths of at least one block whose padded products are fewer than the direct
+// form's, 5 * 32 * ceil(wi / 32) < 6 * 16 * ceil(wi / 16) -- cfg2 / cfg3: conv11 (96 columns) yes; conv9 (48: a block and a half, 10 > 9)
+// and conv7 (24: less than a block) no; cfg5: conv11 (192) and conv9 (96).  Odd widths would split a pair at the border.
+constexpr int T2P_NR = 2, T2P_KB1 = 8, T2P_KB0 = 8;      // input rows per block; input channels per chunk of the odd- / even-row class
+static bool t2_pairs_pay(int wi) { return wi % 2 == 0 && wi >= T2P_COLS && 5 * 2 * cdiv(wi, T2P_COLS) < 6 * cdiv(wi, 16); }
+static int t2_form(int MT, int WM, int N, int hi, int wi) {
+  if (WM >= 2 && t2_fused((long)cdiv(wi, 16) * cdiv(hi, 8) * N)) return 1;
+  if (MT == 3 && WM == 4 && s2_pairs() && t2_pairs_pay(wi)) return 2;
+  return 0;
+}
+static int conv_t2_form(int N, int D, int hi, int wi) {
+  switch (D) {
+    case 16: return t2_form(1, 1, N, hi, wi);
+    case 32: return t2_form(2, 1, N, hi, wi);
+    case 48: return t2_form(3, 1, N, hi, wi);
+    case 64: return t2_form(4, 1, N, hi, wi);
+    case 96: return t2_form(3, 2, N, hi, wi);
+    case 128: case 512: return t2_form(4, 2, N, hi, wi);
+    case 192: case 384: return t2_form(3, 4, N, hi, wi);
+    case 256: return conv256_split() ? t2_form(4, 2, N, hi, wi) : t2_form(4, 4, N, hi, wi);
+  }
+  return -1;
+}
+
 template <int MT, int WM>
 static int launch_conv_dd_cfg(const ConvDDArgs& a_, int N, int mode, hipStream_t st) {
   const ConvDDArgs& a = a_;
@@ -767,8 +1008,10 @@ static int launch_conv_dd_cfg(const ConvDDArgs& a_, int N, int mode, hipStream_t
     hipLaunchKernelGGL((k_conv_dd_s2p<MT, (WM == 4 ? 4 : 4)>), dim3(cdiv(a.wo, 32), cdiv(a.ho, S2P_ROWS), N), dim3(256), 0, st, a);
   else if (mode == CONV_S2)
     hipLaunchKernelGGL((k_conv_dd<MT, WM, CONV_S2, KB>), dim3(cdiv(a.wo, 16), cdiv(a.ho, 8), N), dim3(256), 0, st, a);
-  else if (WM >= 2 && t2_fused((long)cdiv(a.wi, 16) * cdiv(a.hi, 8) * N))      // small grids: 2-row blocks, all classes per chunk
+  else if (WM >= 2 && t2_form(MT, WM, N, a.hi, a.wi) == 1)      // small grids: 2-row blocks, all classes per chunk
     hipLaunchKernelGGL((k_conv_dd_t2_fused<MT, (WM >= 2 ? WM : 2), 4, 2, 2>), dim3(cdiv(a.wi, 16), cdiv(a.hi, 2), N), dim3(256), 0, st, a);
+  else if (MT == 3 && WM == 4 && t2_form(MT, WM, N, a.hi, a.wi) == 2)           // 15 / 18 of the products
+    hipLaunchKernelGGL((k_conv_dd_t2p<(MT == 3 ? 3 : 3), T2P_NR, T2P_KB1, T2P_KB0>), dim3(cdiv(a.wi, T2P_COLS), cdiv(a.hi, T2P_NR), N), dim3(256), 0, st, a);
   else if (WM == 4 && MT == 3 && t2_kb8())     // at most four taps per class: two k-steps per chunk fit the register budget
     hipLaunchKernelGGL((k_conv_dd<MT, WM, CONV_T2, 8>), dim3(cdiv(a.wi, 16), cdiv(a.hi, 8), N), dim3(256), 0, st, a);
   else
@@ -1011,8 +1254,6 @@ static int launch_conv_dd_resident(const ConvDDArgs& a, int N, hipStream_t st) {
   }
   return -1;
 }
-
-static bool conv256_split() { return opt(OPT_CONV256_SPLIT) != 0; }
 
 static int launch_conv_dd_z(const ConvDDArgs& a, int N, int mode, hipStream_t st);
 
@@ -1388,6 +1629,8 @@ static int check_precision(int precision, int D, const char* who) {
                    "%s: bf16x3 needs D in {32,64,96,128,192,256,384,512}, got %d", who, D);
   return 0;
 }
+
+extern "C" int adamvs_conv_t2_form(int N, int D, int hi, int wi) { return N > 0 && hi > 0 && wi > 0 ? conv_t2_form(N, D, hi, wi) : -1; }
 
 extern "C" int adamvs_cost_reg_width(int D, int precision) {
   return D < 1 ? 0 : (precision == PRECISION_BF16X3 ? costreg_width_bf16x3(D) : costreg_width(D));

@@ -15,7 +15,7 @@ namespace adamvs {
   X(OPT_WINO_SOFTMAX, "wino_softmax", 1)             /* ... `prob` carries the softmax partials (no score volume) */                 \
   X(OPT_WINO_WPS, "wino_wps", 0)                     /* ... 1 / 2 workgroups per CU; 0 = by map size */                              \
   X(OPT_FUSE_SOFTMAX, "fuse_softmax", 1)             /* direct `prob` kernel: softmax / max / regression in its epilogue */           \
-  X(OPT_S2_PAIRS, "s2_pairs", 1)                     /* CostRegNet2D: large stride-2 layers in the pair form along x */               \
+  X(OPT_S2_PAIRS, "s2_pairs", 1)                     /* CostRegNet2D: large stride-2 / transposed layers, pair forms along x */       \
   X(OPT_CONV_ROWS2, "conv_rows2", -1)                /* CostRegNet2D: 2-row blocks on small grids; -1 = by grid size */               \
   X(OPT_T2_FUSED, "t2_fused", -1)                    /* transposed layers: four classes per launch; -1 = by grid size */              \
   X(OPT_T2_KB8, "t2_kb8", 1)                         /* transposed layers at D = 192: two k-steps per chunk */                        \

@@ -47,7 +47,7 @@ const char* adamvs_last_error_string(void);
  *   wino_softmax             1     ... its `prob` layer carries the softmax partials, no score volume (stage path); 0: score volume
  *   wino_wps                 0     ... 1 / 2: one / two workgroups per CU for every map size (same bits); 0: by map size
  *   fuse_softmax             1     direct `prob` kernel: softmax / max / depth regression in its epilogue; 0: k_softmax_regress
- *   s2_pairs                 1     CostRegNet2D: large stride-2 layers in the pair form along x (15 of 18 products); 0: direct
+ *   s2_pairs                 1     CostRegNet2D: large stride-2 and transposed layers in the pair forms along x (15 of 18 products); 0: direct
  *   conv_rows2              -1     CostRegNet2D: 2-row blocks for small grids: 0 never, 1 always, -1 by grid size
  *   t2_fused                -1     transposed layers, the four parity classes in one launch: 0 / 1 / -1 by grid size
  *   t2_kb8                   1     transposed layers at D = 192: two k-steps per chunk; 0: one
@@ -346,6 +346,11 @@ size_t adamvs_depth_stage_workspace_bytes(const adamvs_stage_desc* desc);
  * (1 gates1, 2 gates2, 4 cand2, 8 cand1: 16 of the 36 products of the direct form; option gru_wino, default 7). */
 int adamvs_recurrence_schedule(int precision_fuse, long long pixels);
 int adamvs_gru_wino_mask(void);
+
+/* Which fp32 kernel a transposed CostRegNet2D layer (adamvs_conv3x3_dd, mode 2) of N maps of hi x wi inputs and D channels takes under
+ * the current options: 0 class by class, 1 the four parity classes per chunk (small grids: option t2_fused), 2 the pair form along x
+ * (15 of 18 products: D = 192 / 384, even widths whose rows fill blocks of 32 input columns; option s2_pairs).  -1: unsupported D. */
+int adamvs_conv_t2_form(int N, int D, int hi, int wi);
 
 /* phases of a stage.  VIEW_WEIGHTS may run in a call of its own: its results are the view_weight / pair_depth OUTPUT
  * tensors, which a later call reads back.  AGGREGATE, RECURRENCE and SOFT_ARGMIN form one chain over chunks of 32
