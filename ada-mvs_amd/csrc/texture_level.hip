@@ -264,7 +264,9 @@ __global__ __launch_bounds__(256) void k_lvl_reduce_beta(const double* __restric
   if (threadIdx.x != 0) return;
   for (int ch = 0; ch < 3; ++ch) {
     const double old = state[ST_RR + ch];
-    state[ST_BETA + ch] = old > 0.0 ? tot[ch] / old : 0.0;
+    // a channel whose step was refused (alpha = 0: p.Ap <= 0 or NaN) restarts from its residual: beta = r'.r' / r.r would be 1
+    // there and p = r + p would double every iteration until it overflows and 0 * inf reaches g
+    state[ST_BETA + ch] = old > 0.0 && state[ST_ALPHA + ch] != 0.0 ? tot[ch] / old : 0.0;
     state[ST_RR + ch] = tot[ch];
   }
   state[ST_ITERS] = state[ST_ITERS] + 1.0;

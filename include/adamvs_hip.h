@@ -870,9 +870,10 @@ int adamvs_ortho_finalize(const adamvs_ortho_grid* grid, const float* acc, const
  *                   range(L), so the limit is the minimum-norm solution; a Jacobi preconditioner changes that gauge), fp64
  *                   vectors [n][3] and scalars, the three channels interleaved, sharing L, each with its own alpha and beta:
  *                   Ap = L p;  alpha = r.r / p.Ap (0 if p.Ap <= 0);  g += alpha p;  r -= alpha Ap;  beta = r'.r' / r.r (0 if
- *                   r.r <= 0);  iterations += 1;  stop as above;  p = r + beta p.  Once stop is set every remaining kernel of the
- *                   call (and of later calls) returns without writing: g and the count are those of the stopping iteration, so
- *                   the caller may queue 16 iterations per read of the flag.  Dot products: ADAMVS_TEXTURE_LEVEL_BLOCKS = 2048
+ *                   r.r <= 0 or alpha = 0: a refused step restarts from r; with beta = 1 there p would double every iteration
+ *                   until it overflows and 0 * inf reaches g);  iterations += 1;  stop as above;  p = r + beta p.  Once stop is
+ *                   set every remaining kernel of the call (and of later calls) returns without writing: g and the count are
+ *                   those of the stopping iteration, so the caller may queue 16 iterations per read of the flag.  Dot products: ADAMVS_TEXTURE_LEVEL_BLOCKS = 2048
  *                   workgroups at most, each a fixed run of rows, reduced by one workgroup in a fixed order; no floating-point
  *                   atomics, so g is bit-identical from run to run.  partials [3 ADAMVS_TEXTURE_LEVEL_BLOCKS] fp64 workspace.
  *                   g, r, p, Ap hold [n + 1][3] fp64, 16-byte aligned: one spare row, so that the update passes may read and

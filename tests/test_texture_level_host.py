@@ -150,3 +150,121 @@ def test_seam_options_parser_symbols_and_abi():
         p = inspect.signature(fn).parameters
         assert p["seam_level"].default is False and p["seam_lambda"].default == 0.1 and p["seam_tol"].default == 1e-4
         assert p["seam_iters"].default == 1000
+
+
+# ---- the restatements of the single kernels (tests/level_kernels_ref.py) ------------------------------------------------------------
+import level_kernels_ref as K
+
+
+def edge_lists(g):
+    """The CSR's undirected edges among the nodes -> (smooth [ms, 2], seam [ms] bool, data [md, 2]) as texture_level_ref takes them."""
+    word = g["col"].astype(np.int64)
+    j = word & K.INDEX
+    up = (g["row"] < j) & (j < g["n"])
+    e = np.stack([g["row"][up], j[up]], 1)
+    is_data = (word[up] & K.DATA) != 0
+    return e[~is_data], (word[up][~is_data] & K.SEAM) != 0, e[is_data]
+
+
+def test_graph_generator_places_what_it_states():
+    for n in (1, 2, 3, 255, 400, 5000):
+        g = K.random_graph(n, seed=n)
+        rp, word = g["rowptr"].astype(np.int64), g["col"].astype(np.int64)
+        j = word & K.INDEX
+        assert rp[0] == 0 and rp[-1] == len(word) and len(rp) == n + 1 and (np.diff(rp) >= 0).all()
+        same = g["row"][1:] == g["row"][:-1]
+        assert (j[1:][same] > j[:-1][same]).all()                                   # sorted by neighbour, no duplicates
+        assert (j != g["row"]).all()
+        inside = j < n
+        assert 1 <= (~inside).sum() <= 5 and j.max() == (K.INDEX if n >= 2 else n)   # stray words, one of them the largest index
+        A = K.laplacian_sparse(g, 10.0)
+        assert abs(A - A.T).max() == 0 and abs(A.sum(1)).max() < 1e-9
+        if n >= 400:
+            assert tuple(K.degrees(g)[g["special"]]) == K.SPECIAL_DEGREES and g["special"][0] == 0 and g["special"][1] == n - 1
+            kinds = word[inside] >> 30
+            assert all((kinds == k).mean() > 0.2 for k in (0, 1, 2))
+    up = K.random_graph(500, seed=1, upper_only=True)
+    assert ((up["col"].astype(np.int64) & K.INDEX) > up["row"]).all()
+    eq = K.equitable_graph(7 * 40 + 3, seed=2)
+    assert (K.degrees(eq)[:280] == 6).all() and (K.degrees(eq)[280:] == 0).all()
+    # equitable: L maps a vector that is constant on the blocks to one that is constant on the blocks
+    x = np.random.default_rng(0).normal(size=8)[eq["block"]]
+    y = K.laplacian_sparse(eq, 2.0) @ x
+    assert all(np.ptp(y[eq["block"] == c]) < 1e-12 for c in range(8))
+
+
+def test_ordered_spmv_and_rhs_equal_the_dense_definition():
+    """Per row the ordered sums make deg - 1 additions of d (exact here: the weights are 1 and 10), deg products and deg - 1
+    additions for s, one product d p_i and one subtraction: at most (deg + 2) roundings, each relative to a partial sum that
+    the row's sum of |terms| bounds.  The yardstick is the dense Laplacian applied in longdouble."""
+    n = 600
+    g = K.random_graph(n, seed=11)
+    smooth, seam, data = edge_lists(g)
+    p = np.random.default_rng(3).normal(size=(n, 3))
+    Lm = L.laplacian(n, smooth, data, 0.1)
+    want = Lm.astype(np.longdouble) @ p.astype(np.longdouble)
+    terms = np.abs(Lm) @ np.abs(p)
+    got = K.spmv_ordered(g, p, 1.0 / 0.1)
+    bound = (K.degrees(g)[:, None] + 2) * K.U64 * terms
+    assert (np.abs(got - want) <= bound).all(), (np.abs(got - want) / np.maximum(bound, 1e-300)).max()
+    assert np.abs(got - Lm @ p).max() <= 2 * bound.max()
+    np.testing.assert_allclose(K.laplacian_sparse(g, 10.0).toarray(), Lm, atol=0, rtol=0)
+    assert (got[K.degrees(g) == 0] == 0).all()
+    # b: the data entries alone, (double)f_j - (double)f_i summed in order; every term is exact, the sum makes deg - 1 roundings
+    f = np.random.default_rng(4).uniform(0, 255, (n, 3)).astype(np.float32)
+    b = K.rhs_ordered(g, f)
+    ref = L.rhs(f.astype(np.float64), data, n)
+    dd = np.bincount(data.reshape(-1), minlength=n)
+    assert (np.abs(b - ref) <= (2 * dd[:, None]) * K.U64 * 2 * 255.0 * np.maximum(dd[:, None], 1)).all()
+    assert (b[dd == 0] == 0).all()
+
+
+def test_sparse_cg_equals_the_dense_cg():
+    """Two fp64 runs of conjugate gradients that differ only in the order of their sums drift apart by about (iterations x
+    condition number x 2^-53) |g|.  With lambda = 1 every weight is 1 and the condition number of a random graph of six neighbours
+    is some tens, so some tens of iterations leave the difference well below the 1e-12 max |g| asked for."""
+    n = 300
+    g = K.random_graph(n, seed=12, special=False)
+    smooth, seam, data = edge_lists(g)
+    f = np.random.default_rng(5).uniform(0, 255, (n, 3))
+    b = L.rhs(f, data, n)
+    Lm = L.laplacian(n, smooth, data, 1.0)
+    gd, itd = L.cg(Lm, b, 1e-8, 5000)
+    gs, its, hist = K.cg_sparse(K.laplacian_sparse(g, 1.0), b, 1e-8, 5000)
+    assert its == itd and 10 < its < 200 and len(hist) == its + 1 and hist[-1] <= 1e-8 < hist[-2]
+    print("sparse against dense cg: %d iterations, max |dg| = %.3g of max |g| = %.3g" % (its, np.abs(gs - gd).max(), np.abs(gd).max()))
+    assert np.abs(gs - gd).max() <= 1e-12 * np.abs(gd).max()
+
+
+def test_a_refused_step_restarts_from_the_residual():
+    """alpha = 0 with r.r unchanged gave beta = 1 and p = r + p: p doubled every iteration, overflowed after about 1024 and
+    0 * inf = NaN reached g.  The definition now takes beta = 0 there."""
+    b = np.array([[3.0, -2.0, 0.0], [1.0, 0.5, 0.0]])
+    with np.errstate(all="raise"):
+        gd, it = L.cg(np.zeros((2, 2)), b, 1e-4, 1100)
+        gs, its, _ = K.cg_sparse(K.laplacian_sparse(K.csr(2, [], [], []), 10.0), b, 1e-4, 1100)
+    assert it == its == 1100 and (gd == 0).all() and (gs == 0).all()
+
+
+def test_fp32_observed_colour_restatement_agrees_with_the_definition():
+    n, W, H = 500, 31, 24
+    rng = np.random.default_rng(6)
+    g = K.random_graph(n, seed=13)
+    smooth, seam, data = edge_lists(g)
+    images = [rng.integers(0, 256, (H, W, 4), dtype=np.uint8) for _ in range(2)]
+    view = rng.integers(0, 2, n)
+    pos = (rng.uniform(0, 1, (n, 2)) * [W - 1, H - 1]).astype(np.float32)
+    got = K.observe32(g, pos, view, images)
+    want = L.observe(pos.astype(np.float64), view, smooth, seam, images)
+    deg = np.bincount(smooth[seam].reshape(-1), minlength=n).max()
+    bound = 255.0 * 2.0 ** -24 * (4 * max(W, H) + 11 + 2 * 3 * deg + 1)                # f_bound of tests/test_texture_level_gpu.py
+    err = np.abs(got - want).max()
+    assert deg >= 10 and 0 < err <= bound, (err, bound)
+    # a view out of range gives 0; a node without a seam entry takes the single sample
+    view2 = view.copy()
+    view2[:7] = [-1, 2, -5, 2, 7, -1, 2]
+    got2 = K.observe32(g, pos, view2, images)
+    assert (got2[:7] == 0).all()
+    none = np.bincount(smooth[seam].reshape(-1), minlength=n) == 0
+    assert none.any()
+    np.testing.assert_array_equal(got[none], K.sample_views32(images, view[none], pos[none, 0], pos[none, 1]))

@@ -188,7 +188,7 @@ def cg(L, b, tol, iters):
         g += alpha * p
         r -= alpha * Ap
         new = (r * r).sum(0)
-        beta = np.where(rr > 0, new / np.where(rr > 0, rr, 1.0), 0.0)
+        beta = np.where((rr > 0) & (alpha != 0), new / np.where(rr > 0, rr, 1.0), 0.0)
         rr = new
         p = r + beta * p
         it += 1
