@@ -184,6 +184,25 @@ SIGNATURES = {
     "adamvs_mesh_emit": (c_i, [ctypes.POINTER(MeshBrick), c_f, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
                                ctypes.c_void_p, ctypes.c_long, c_st]),
+    "adamvs_simplify_keys": (c_i, [ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                   ctypes.c_void_p, c_st]),
+    "adamvs_simplify_corners": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, c_i, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, c_st]),
+    "adamvs_simplify_accumulate": (c_i, [ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_void_p, c_i, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_simplify_solve": (c_i, [ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.c_void_p, c_i,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_simplify_solve_host": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "adamvs_simplify_triples": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_simplify_first": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_simplify_mark": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_i, ctypes.c_void_p, c_st]),
+    "adamvs_simplify_count": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_simplify_emit": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
+                                   ctypes.c_void_p, ctypes.c_long, c_st]),
     "adamvs_ortho_surface": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.c_void_p, c_st]),
     "adamvs_ortho_zbuf": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.POINTER(OrthoView), ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_void_p, ctypes.c_long, c_st]),
@@ -237,6 +256,8 @@ MESH_TILE = 256                  # ADAMVS_MESH_TILE: samples / cubes per workgro
 MESH_BRICKS = (32, 64, 128)      # the brick sizes B
 MESH_MAX_VIEWS = 65535           # ADAMVS_MESH_MAX_VIEWS
 MESH_MAX_EXTENT = 16384.0        # ADAMVS_MESH_MAX_EXTENT, metres from the volume origin
+SIMPLIFY_TILE = 256              # ADAMVS_SIMPLIFY_TILE: entries per workgroup of the simplification kernels
+SIMPLIFY_KEY_BITS = 21           # ADAMVS_SIMPLIFY_KEY_BITS: bits per axis of a cell key
 ORTHO_BEST, ORTHO_FEATHER = 0, 1 # ADAMVS_ORTHO_BEST / ADAMVS_ORTHO_FEATHER
 ORTHO_MAX_CELLS = 1 << 28        # ADAMVS_ORTHO_MAX_CELLS
 ORTHO_MAX_UPSAMPLE = 8           # ADAMVS_ORTHO_MAX_UPSAMPLE

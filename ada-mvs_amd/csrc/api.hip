@@ -542,6 +542,117 @@ extern "C" int adamvs_mesh_emit(const adamvs_mesh_brick* brick, const float* tsd
                           vert_capacity, faces, tri_capacity, (hipStream_t)stream);
 }
 
+// ---- mesh simplification (mesh_simplify.hip): every argument is checked here, before any launch
+static const long SIMPLIFY_MAX = (1L << 31) - 1;
+
+static int simplify_check_lattice(const double* origin, double cell, const char* what) {
+  ADAMVS_CHECK_ARG(origin, "%s: null origin", what);
+  ADAMVS_CHECK_ARG(std::isfinite(cell) && cell > 0, "%s: cell=%g must be finite and > 0", what, cell);
+  ADAMVS_CHECK_ARG(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]), "%s: origin is not finite", what);
+  return 0;
+}
+
+static int simplify_check_count(long n, const char* name, const char* what) {
+  ADAMVS_CHECK_ARG(n >= 1 && n <= SIMPLIFY_MAX, "%s: %s=%ld (1 .. 2^31 - 1)", what, name, n);
+  return 0;
+}
+
+extern "C" int adamvs_simplify_keys(const double* origin, double cell, const double* xyz, long nv, long long* keys, unsigned char* bad,
+                                    void* stream) {
+  if (int rc = simplify_check_lattice(origin, cell, "simplify_keys")) return rc;
+  if (int rc = simplify_check_count(nv, "nv", "simplify_keys")) return rc;
+  ADAMVS_CHECK_ARG(xyz && keys && bad, "simplify_keys: null pointer");
+  return launch_simplify_keys(origin, cell, xyz, nv, keys, bad, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_simplify_corners(const unsigned* faces, long nf, const int* vcell, long nv, int nc, int* fcell, int* entry_cell,
+                                       unsigned char* survive, void* stream) {
+  if (int rc = simplify_check_count(nf, "nf", "simplify_corners")) return rc;
+  if (int rc = simplify_check_count(nv, "nv", "simplify_corners")) return rc;
+  ADAMVS_CHECK_ARG(nc >= 1 && nc <= nv, "simplify_corners: nc=%d (1 .. nv = %ld)", nc, nv);
+  ADAMVS_CHECK_ARG(faces && vcell && fcell && entry_cell && survive, "simplify_corners: null pointer");
+  return launch_simplify_corners(faces, nf, vcell, nv, nc, fcell, entry_cell, survive, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_simplify_accumulate(const double* origin, double cell, const long long* keys, int nc, const double* xyz,
+                                          const unsigned char* rgb, long nv, const unsigned* faces, long nf, const long long* entry,
+                                          const long long* fstart, const long long* vorder, const long long* vstart, double* quadric,
+                                          double* member, unsigned long long* colour, void* stream) {
+  if (int rc = simplify_check_lattice(origin, cell, "simplify_accumulate")) return rc;
+  if (int rc = simplify_check_count(nf, "nf", "simplify_accumulate")) return rc;
+  if (int rc = simplify_check_count(nv, "nv", "simplify_accumulate")) return rc;
+  ADAMVS_CHECK_ARG(nc >= 1 && nc <= nv, "simplify_accumulate: nc=%d (1 .. nv = %ld)", nc, nv);
+  ADAMVS_CHECK_ARG(keys && xyz && rgb && faces && entry && fstart && vorder && vstart && quadric && member && colour,
+                   "simplify_accumulate: null pointer");
+  return launch_simplify_accumulate(origin, cell, keys, nc, xyz, rgb, nv, faces, nf, entry, fstart, vorder, vstart, quadric, member, colour,
+                                    (hipStream_t)stream);
+}
+
+extern "C" int adamvs_simplify_solve(const double* origin, double cell, double rank_eps, const long long* keys, int nc,
+                                     const double* quadric, const double* member, const unsigned long long* colour,
+                                     const long long* vstart, double* pos, unsigned char* col, unsigned char* rank, unsigned char* fallback,
+                                     double* error, void* stream) {
+  if (int rc = simplify_check_lattice(origin, cell, "simplify_solve")) return rc;
+  if (int rc = simplify_check_count(nc, "nc", "simplify_solve")) return rc;
+  ADAMVS_CHECK_ARG(rank_eps >= 0 && rank_eps < 1, "simplify_solve: rank_eps=%g (0 <= rank_eps < 1)", rank_eps);
+  ADAMVS_CHECK_ARG(keys && quadric && member && colour && vstart && pos && col && rank && fallback && error, "simplify_solve: null pointer");
+  return launch_simplify_solve(origin, cell, rank_eps, keys, nc, quadric, member, colour, vstart, pos, col, rank, fallback, error,
+                               (hipStream_t)stream);
+}
+
+extern "C" int adamvs_simplify_solve_host(const double* quadric, const double* mean, long n, double cell, double rank_eps, double* p,
+                                          int* rank, int* fallback, double* error) {
+  if (int rc = simplify_check_count(n, "n", "simplify_solve_host")) return rc;
+  ADAMVS_CHECK_ARG(std::isfinite(cell) && cell > 0, "simplify_solve_host: cell=%g must be finite and > 0", cell);
+  ADAMVS_CHECK_ARG(rank_eps >= 0 && rank_eps < 1, "simplify_solve_host: rank_eps=%g (0 <= rank_eps < 1)", rank_eps);
+  ADAMVS_CHECK_ARG(quadric && mean && p && rank && fallback && error, "simplify_solve_host: null pointer");
+  for (long j = 0; j < n; ++j)
+    simplify_solve_host(quadric + 10 * j, mean + 3 * j, cell, rank_eps, p + 3 * j, rank + j, fallback + j, error + j);
+  return 0;
+}
+
+extern "C" int adamvs_simplify_triples(const int* fcell, long nf, const long long* surv, long ns, int* tri, void* stream) {
+  if (int rc = simplify_check_count(nf, "nf", "simplify_triples")) return rc;
+  ADAMVS_CHECK_ARG(ns >= 1 && ns <= nf, "simplify_triples: ns=%ld (1 .. nf = %ld)", ns, nf);
+  ADAMVS_CHECK_ARG(fcell && surv && tri, "simplify_triples: null pointer");
+  return launch_simplify_triples(fcell, nf, surv, ns, tri, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_simplify_first(const int* tri, const long long* surv, const long long* order, long ns, long nf, unsigned char* keep,
+                                     void* stream) {
+  if (int rc = simplify_check_count(nf, "nf", "simplify_first")) return rc;
+  ADAMVS_CHECK_ARG(ns >= 1 && ns <= nf, "simplify_first: ns=%ld (1 .. nf = %ld)", ns, nf);
+  ADAMVS_CHECK_ARG(tri && surv && order && keep, "simplify_first: null pointer");
+  return launch_simplify_first(tri, surv, order, ns, nf, keep, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_simplify_mark(const int* fcell, const unsigned char* keep, long nf, int nc, unsigned char* used, void* stream) {
+  if (int rc = simplify_check_count(nf, "nf", "simplify_mark")) return rc;
+  if (int rc = simplify_check_count(nc, "nc", "simplify_mark")) return rc;
+  ADAMVS_CHECK_ARG(fcell && keep && used, "simplify_mark: null pointer");
+  return launch_simplify_mark(fcell, keep, nf, nc, used, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_simplify_count(const unsigned char* flags, long n, unsigned* block_count, void* stream) {
+  if (int rc = simplify_check_count(n, "n", "simplify_count")) return rc;
+  ADAMVS_CHECK_ARG(flags && block_count, "simplify_count: null pointer");
+  return launch_simplify_count(flags, n, block_count, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_simplify_emit(const double* pos, const unsigned char* col, const unsigned char* used, int nc,
+                                    const unsigned* cell_offsets, const int* fcell, const unsigned char* keep, long nf,
+                                    const unsigned* face_offsets, double* xyz, unsigned char* rgb, unsigned* new_index, long vert_capacity,
+                                    unsigned* faces, long face_capacity, void* stream) {
+  if (int rc = simplify_check_count(nf, "nf", "simplify_emit")) return rc;
+  if (int rc = simplify_check_count(nc, "nc", "simplify_emit")) return rc;
+  ADAMVS_CHECK_ARG(pos && col && used && cell_offsets && fcell && keep && face_offsets && new_index, "simplify_emit: null pointer");
+  ADAMVS_CHECK_ARG(vert_capacity >= 0 && face_capacity >= 0, "simplify_emit: capacity < 0");
+  ADAMVS_CHECK_ARG((xyz && rgb) || vert_capacity == 0, "simplify_emit: null vertex output");
+  ADAMVS_CHECK_ARG(faces || face_capacity == 0, "simplify_emit: null face output");
+  return launch_simplify_emit(pos, col, used, nc, cell_offsets, fcell, keep, nf, face_offsets, xyz, rgb, new_index, vert_capacity, faces,
+                              face_capacity, (hipStream_t)stream);
+}
+
 // ---- image orthophoto (ortho.hip): every argument is checked here, before any launch
 static int ortho_check_grid(const adamvs_ortho_grid* g, const char* what) {
   ADAMVS_CHECK_ARG(g, "%s: null grid", what);

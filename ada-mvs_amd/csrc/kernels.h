@@ -174,6 +174,28 @@ int launch_mesh_emit(const adamvs_mesh_brick& b, const float* tsdf, const unsign
                      const unsigned* vert_offsets, const unsigned* tri_offsets, unsigned vertex_base, double* xyz, uint8_t* rgb,
                      unsigned* first_vertex, long vert_capacity, unsigned* faces, long tri_capacity, hipStream_t st);
 
+// mesh_simplify.hip: vertex clustering with one quadric per lattice cell (include/adamvs_hip.h, "Mesh simplification")
+constexpr int SIMPLIFY_TILE = ADAMVS_SIMPLIFY_TILE;
+int launch_simplify_keys(const double* origin, double cell, const double* xyz, long nv, long long* keys, uint8_t* bad, hipStream_t st);
+int launch_simplify_corners(const unsigned* faces, long nf, const int* vcell, long nv, int nc, int* fcell, int* entry_cell, uint8_t* survive,
+                            hipStream_t st);
+int launch_simplify_accumulate(const double* origin, double cell, const long long* keys, int nc, const double* xyz, const uint8_t* rgb,
+                               long nv, const unsigned* faces, long nf, const long long* entry, const long long* fstart,
+                               const long long* vorder, const long long* vstart, double* quadric, double* member,
+                               unsigned long long* colour, hipStream_t st);
+int launch_simplify_solve(const double* origin, double cell, double rank_eps, const long long* keys, int nc, const double* quadric,
+                          const double* member, const unsigned long long* colour, const long long* vstart, double* pos, uint8_t* col,
+                          uint8_t* rank, uint8_t* fallback, double* error, hipStream_t st);
+void simplify_solve_host(const double* quadric, const double* mean, double cell, double rank_eps, double* p, int* rank, int* fallback,
+                         double* error);
+int launch_simplify_triples(const int* fcell, long nf, const long long* surv, long ns, int* tri, hipStream_t st);
+int launch_simplify_first(const int* tri, const long long* surv, const long long* order, long ns, long nf, uint8_t* keep, hipStream_t st);
+int launch_simplify_mark(const int* fcell, const uint8_t* keep, long nf, int nc, uint8_t* used, hipStream_t st);
+int launch_simplify_count(const uint8_t* flags, long n, unsigned* block_count, hipStream_t st);
+int launch_simplify_emit(const double* pos, const uint8_t* col, const uint8_t* used, int nc, const unsigned* cell_offsets, const int* fcell,
+                         const uint8_t* keep, long nf, const unsigned* face_offsets, double* xyz, uint8_t* rgb, unsigned* new_index,
+                         long vert_capacity, unsigned* faces, long face_capacity, hipStream_t st);
+
 
 // ortho.hip: image orthophoto over a DSM, z-buffered per view (include/adamvs_hip.h, "Image orthophoto")
 constexpr int ORTHO_TILE = ADAMVS_ORTHO_TILE;

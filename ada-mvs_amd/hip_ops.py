@@ -756,6 +756,146 @@ def mesh_extract(brick, tsdf, weight, rgba, vertex_base=0):
     return xyz[:nv], rgb[:nv], faces[:nt]
 
 
+# ---- mesh simplification (csrc/mesh_simplify.hip; driven by ada_mvs_amd/simplify.py) -------------------------------------------
+# faces and new indices int32 = uint32, the colour sums int64 = uint64; flags uint8.
+def _lattice(origin, cell):
+    o = np.ascontiguousarray(np.asarray(origin, dtype=np.float64).reshape(-1))
+    if o.size != 3:
+        raise _lib.AdaMVSHipError("lattice origin: 3 doubles, got %d" % o.size)
+    return o, o.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(cell)
+
+
+def simplify_keys(xyz, cell, origin):
+    """adamvs_simplify_keys.  xyz [nv, 3] float64 -> (keys [nv] int64, bad [nv] uint8: 0 fine, 1 not finite, 2 outside the lattice)."""
+    xyz = _dev_as(xyz, "xyz", torch.float64)
+    nv = xyz.shape[0]
+    keep, o, c = _lattice(origin, cell)
+    keys = torch.empty(nv, device=xyz.device, dtype=torch.int64)
+    bad = torch.empty(nv, device=xyz.device, dtype=torch.uint8)
+    check(_lib.load().adamvs_simplify_keys(o, c, _p(xyz), nv, _p(keys), _p(bad), _stream()), "simplify_keys")
+    return keys, bad
+
+
+def simplify_corners(faces, vcell, nc):
+    """adamvs_simplify_corners.  faces [nf, 3] int32 (uint32), vcell [nv] int32 -> (fcell [nf, 3] int32, entry_cell [nf, 3] int32,
+    survive [nf] uint8)."""
+    faces = _dev_as(faces, "faces", torch.int32)
+    vcell = _dev_as(vcell, "vcell", torch.int32)
+    nf, dev = faces.shape[0], faces.device
+    fcell = torch.empty(nf, 3, device=dev, dtype=torch.int32)
+    entry_cell = torch.empty(nf, 3, device=dev, dtype=torch.int32)
+    survive = torch.empty(nf, device=dev, dtype=torch.uint8)
+    check(_lib.load().adamvs_simplify_corners(_p(faces), nf, _p(vcell), vcell.numel(), int(nc), _p(fcell), _p(entry_cell), _p(survive),
+                                              _stream()), "simplify_corners")
+    return fcell, entry_cell, survive
+
+
+def simplify_accumulate(keys, cell, origin, xyz, rgb, faces, entry, fstart, vorder, vstart):
+    """adamvs_simplify_accumulate.  keys [nc] int64 (the cells), entry [3 nf] / vorder [nv] int64 (stable sort orders), fstart / vstart
+    [nc + 1] int64 -> (quadric [nc, 10] float64, member [nc, 3] float64, colour [nc, 3] int64)."""
+    keys = _dev_as(keys, "keys", torch.int64)
+    xyz = _dev_as(xyz, "xyz", torch.float64)
+    rgb = _dev_as(rgb, "rgb", torch.uint8)
+    faces = _dev_as(faces, "faces", torch.int32)
+    entry, fstart = _dev_as(entry, "entry", torch.int64), _dev_as(fstart, "fstart", torch.int64)
+    vorder, vstart = _dev_as(vorder, "vorder", torch.int64), _dev_as(vstart, "vstart", torch.int64)
+    nc, nv, nf, dev = keys.numel(), xyz.shape[0], faces.shape[0], xyz.device
+    if rgb.shape[0] != nv or entry.numel() != 3 * nf or vorder.numel() != nv or fstart.numel() != nc + 1 or vstart.numel() != nc + 1:
+        raise _lib.AdaMVSHipError("simplify_accumulate: nv %d, nf %d, nc %d against rgb %d, entry %d, vorder %d, fstart %d, vstart %d"
+                                  % (nv, nf, nc, rgb.shape[0], entry.numel(), vorder.numel(), fstart.numel(), vstart.numel()))
+    keep, o, c = _lattice(origin, cell)
+    quadric = torch.empty(nc, 10, device=dev, dtype=torch.float64)
+    member = torch.empty(nc, 3, device=dev, dtype=torch.float64)
+    colour = torch.empty(nc, 3, device=dev, dtype=torch.int64)
+    check(_lib.load().adamvs_simplify_accumulate(o, c, _p(keys), nc, _p(xyz), _p(rgb), nv, _p(faces), nf, _p(entry), _p(fstart), _p(vorder),
+                                                 _p(vstart), _p(quadric), _p(member), _p(colour), _stream()), "simplify_accumulate")
+    return quadric, member, colour
+
+
+def simplify_solve(keys, cell, origin, rank_eps, quadric, member, colour, vstart):
+    """adamvs_simplify_solve -> (pos [nc, 3] float64, col [nc, 3] uint8, rank [nc] uint8, fallback [nc] uint8, error [nc] float64)."""
+    keys = _dev_as(keys, "keys", torch.int64)
+    quadric, member = _dev_as(quadric, "quadric", torch.float64), _dev_as(member, "member", torch.float64)
+    colour, vstart = _dev_as(colour, "colour", torch.int64), _dev_as(vstart, "vstart", torch.int64)
+    nc, dev = keys.numel(), keys.device
+    if quadric.numel() != 10 * nc or member.numel() != 3 * nc or colour.numel() != 3 * nc or vstart.numel() != nc + 1:
+        raise _lib.AdaMVSHipError("simplify_solve: nc %d against quadric %d, member %d, colour %d, vstart %d"
+                                  % (nc, quadric.numel(), member.numel(), colour.numel(), vstart.numel()))
+    keep, o, c = _lattice(origin, cell)
+    pos = torch.empty(nc, 3, device=dev, dtype=torch.float64)
+    col = torch.empty(nc, 3, device=dev, dtype=torch.uint8)
+    rank = torch.empty(nc, device=dev, dtype=torch.uint8)
+    fallback = torch.empty(nc, device=dev, dtype=torch.uint8)
+    error = torch.empty(nc, device=dev, dtype=torch.float64)
+    check(_lib.load().adamvs_simplify_solve(o, c, float(rank_eps), _p(keys), nc, _p(quadric), _p(member), _p(colour), _p(vstart), _p(pos),
+                                            _p(col), _p(rank), _p(fallback), _p(error), _stream()), "simplify_solve")
+    return pos, col, rank, fallback, error
+
+
+def simplify_solve_host(quadric, mean, cell, rank_eps=1e-3):
+    """adamvs_simplify_solve_host on numpy arrays: quadric [n, 10], mean [n, 3] -> (p [n, 3], rank [n], fallback [n], error [n])."""
+    q = np.ascontiguousarray(np.asarray(quadric, np.float64).reshape(-1, 10))
+    m = np.ascontiguousarray(np.asarray(mean, np.float64).reshape(-1, 3))
+    n = len(q)
+    if len(m) != n:
+        raise _lib.AdaMVSHipError("simplify_solve_host: %d quadrics, %d means" % (n, len(m)))
+    p, rank, fb, err = np.zeros((n, 3)), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n)
+    check(_lib.load().adamvs_simplify_solve_host(q.ctypes.data, m.ctypes.data, n, float(cell), float(rank_eps), p.ctypes.data,
+                                                 rank.ctypes.data, fb.ctypes.data, err.ctypes.data), "simplify_solve_host")
+    return p, rank, fb, err
+
+
+def simplify_triples(fcell, surv):
+    """adamvs_simplify_triples.  surv [ns] int64 (surviving faces, ascending) -> tri [3, ns] int32."""
+    fcell = _dev_as(fcell, "fcell", torch.int32)
+    surv = _dev_as(surv, "surv", torch.int64)
+    tri = torch.empty(3, surv.numel(), device=fcell.device, dtype=torch.int32)
+    check(_lib.load().adamvs_simplify_triples(_p(fcell), fcell.shape[0], _p(surv), surv.numel(), _p(tri), _stream()), "simplify_triples")
+    return tri
+
+
+def simplify_first(tri, surv, order, nf):
+    """adamvs_simplify_first -> keep [nf] uint8 (zero outside the surviving faces)."""
+    tri = _dev_as(tri, "tri", torch.int32)
+    surv, order = _dev_as(surv, "surv", torch.int64), _dev_as(order, "order", torch.int64)
+    ns = surv.numel()
+    if tri.numel() != 3 * ns or order.numel() != ns:
+        raise _lib.AdaMVSHipError("simplify_first: ns %d against tri %d, order %d" % (ns, tri.numel(), order.numel()))
+    keep = torch.zeros(int(nf), device=tri.device, dtype=torch.uint8)
+    check(_lib.load().adamvs_simplify_first(_p(tri), _p(surv), _p(order), ns, int(nf), _p(keep), _stream()), "simplify_first")
+    return keep
+
+
+def simplify_emit(pos, col, fcell, keep):
+    """adamvs_simplify_mark + two adamvs_simplify_count + two adamvs_fusion_scan + adamvs_simplify_emit.  Reads the two totals back
+    (one synchronisation).  -> (xyz [nu, 3] float64, rgb [nu, 3] uint8, faces [nk, 3] int32 (uint32), used [nc] uint8)."""
+    pos, col = _dev_as(pos, "pos", torch.float64), _dev_as(col, "col", torch.uint8)
+    fcell, keep = _dev_as(fcell, "fcell", torch.int32), _dev_as(keep, "keep", torch.uint8)
+    nc, nf, dev = pos.shape[0], fcell.shape[0], pos.device
+    if col.shape[0] != nc or keep.numel() != nf:
+        raise _lib.AdaMVSHipError("simplify_emit: nc %d, nf %d against col %d, keep %d" % (nc, nf, col.shape[0], keep.numel()))
+    T = _lib.SIMPLIFY_TILE
+    nbc, nbf = (nc + T - 1) // T, (nf + T - 1) // T
+    lib, st = _lib.load(), _stream()
+    used = torch.zeros(nc, device=dev, dtype=torch.uint8)
+    counts = torch.empty(nbc + nbf, device=dev, dtype=torch.int32)
+    offs = torch.empty(nbc + 1 + nbf + 1, device=dev, dtype=torch.int32)
+    cell_off, face_off = offs[:nbc + 1], offs[nbc + 1:]
+    check(lib.adamvs_simplify_mark(_p(fcell), _p(keep), nf, nc, _p(used), st), "simplify_mark")
+    check(lib.adamvs_simplify_count(_p(used), nc, _p(counts[:nbc]), st), "simplify_count")
+    check(lib.adamvs_simplify_count(_p(keep), nf, _p(counts[nbc:]), st), "simplify_count")
+    check(lib.adamvs_fusion_scan(_p(counts[:nbc]), _p(cell_off), nbc, st), "fusion_scan")
+    check(lib.adamvs_fusion_scan(_p(counts[nbc:]), _p(face_off), nbf, st), "fusion_scan")
+    nu, nk = (int(v) & 0xFFFFFFFF for v in torch.stack([cell_off[-1], face_off[-1]]).cpu().tolist())
+    xyz = torch.empty(max(nu, 1), 3, device=dev, dtype=torch.float64)
+    rgb = torch.empty(max(nu, 1), 3, device=dev, dtype=torch.uint8)
+    faces = torch.empty(max(nk, 1), 3, device=dev, dtype=torch.int32)
+    new_index = torch.empty(nc, device=dev, dtype=torch.int32)
+    check(lib.adamvs_simplify_emit(_p(pos), _p(col), _p(used), nc, _p(cell_off), _p(fcell), _p(keep), nf, _p(face_off), _p(xyz), _p(rgb),
+                                   _p(new_index), nu, _p(faces), nk, st), "simplify_emit")
+    return xyz[:nu], rgb[:nu], faces[:nk], used
+
+
 # ---- image orthophoto (csrc/ortho.hip; driven view by view by ada_mvs_amd/ortho.py) ------------------------------------------
 # The depth buffer is int32 holding uint32 float bits; acc is float32 [N, 4]; view and nvis int32; nvis_out int16 (uint16).
 def ortho_grid(x0, y_top, gsd, W, H, K):

@@ -707,6 +707,87 @@ int adamvs_mesh_emit(const adamvs_mesh_brick* brick, const float* tsdf, const un
                      double* xyz, unsigned char* rgb, unsigned* first_vertex, long vert_capacity, unsigned* faces, long tri_capacity,
                      void* stream);
 
+/* ---- Mesh simplification (after mesh_whu.py): vertex clustering on a lattice, one Garland-Heckbert quadric per cell ---------
+ * (Lindstrom's out-of-core simplification.)  ada-mvs_amd/simplify.py drives it; simplify_whu.py is the CLI.  It welds the mesh
+ * by exact position first (mesh.py weld), always, so the result does not depend on the brick size or on --weld.
+ *
+ * Inputs: vertices xyz [nv][3] fp64 world, rgb [nv][3] uint8, faces [nf][3] uint32, the cell size c > 0 in metres, the lattice
+ * origin O (fp64, O <= min xyz per axis) and rank_eps (default 1e-3).  All arithmetic below is fp64 without contraction.
+ *
+ * 1. Cell of a vertex.  Per axis i = floor((x - O) / c); key = iz << 42 | iy << 21 | ix (ADAMVS_SIMPLIFY_KEY_BITS = 21 bits per
+ *    axis).  A non-finite coordinate is error code 1, an index < 0 or >= 2^21 error code 2 (never a clamp); the key of such a
+ *    vertex is -1.  The distinct keys in ascending order are the CELLS 0 .. nc - 1; the centre of a cell is O + (i + 0.5) c.
+ * 2. Quadric of a cell: over every face with at least one corner in the cell, once per face and cell even where two or three
+ *    corners share it, and whether or not the face survives step 5.  With the face's corners relative to the cell centre,
+ *    p0, p1, p2:  u = p1 - p0, w = p2 - p0, n = u x w = (u1 w2 - u2 w1, u2 w0 - u0 w2, u0 w1 - u1 w0)  (not normalised: a face
+ *    weighs its area squared),  d = -(n0 p0.x + n1 p0.y + n2 p0.z);  A += n n^T, b += d n, and sum d^2 for the reported error.
+ *    The sums do not feel the sign of n, so the order of a face's corners is free: the driver takes them ascending by welded
+ *    vertex number (a function of the positions alone) and the faces ascending by those triples, the CANONICAL face list.  The
+ *    rounding of every sum is then a function of the mesh as a set, not of the order its faces were written in.
+ * 3. Members: every input vertex of the cell, including one that no face references.  m = the mean of their positions relative
+ *    to the centre; colour = per channel (sum + count / 2) / count in integers (half rounds up, as the tsdf's colours do).
+ * 4. Representative.  lambda_k, v_k = the eigen-decomposition of the symmetric A; eigenvalue k is KEPT iff
+ *    lambda_k > rank_eps lambda_max.  p = m + sum over the kept k of v_k (v_k . g) / lambda_k,  g = -(b + A m):  the minimiser of
+ *    the quadric nearest to m, the same whatever basis the solver returns.  If nothing is kept, or some |p_k| > c / 2, or p is
+ *    not finite, then p = m (FALLBACK): a representative always lies in its own cell.  Position = centre + p; rank = the
+ *    number kept (0 .. 3); error = p.A p + 2 b.p + sum d^2.
+ * 5. Faces.  A face SURVIVES iff its three corners lie in three distinct cells.  Of the surviving faces with the same set of
+ *    three cells the first in input order is KEPT (thin double sheets fold onto each other); kept faces stay in input order
+ *    with their orientation.
+ * 6. Vertices out: the cells USED by a kept face, in ascending key order, and the kept faces with their corners renumbered.
+ *    Cells that no kept face uses disappear.
+ *
+ * Calls, in stream order.  The caller numbers the cells (unique of the keys, ascending, with the inverse -> vcell [nv] int32),
+ * runs _simplify_corners on the faces as given (fcell and survive, for steps 5 and 6) and on the canonical face list (entry_cell,
+ * for step 2; _simplify_accumulate then takes that list as its faces), sorts entry_cell STABLY (-> entry [3 nf]: the indices 3 f + k in sorted order; fstart [nc + 1]: where each cell's run
+ * starts, fstart[nc] = the first sentinel) and sorts the vertices stably by cell (-> vorder [nv], vstart [nc + 1]).  No atomics
+ * and no inter-workgroup waits: the order of every sum is a function of these sorted inputs only, so the output is
+ * bit-identical from run to run.  Workgroups cover ADAMVS_SIMPLIFY_TILE consecutive entries.
+ *   _simplify_keys        keys [nv] int64, bad [nv] uint8 (the error code, 0 = fine);  origin: HOST pointer to 3 doubles;
+ *   _simplify_corners     fcell [nf][3] int32 (the cells of the corners), entry_cell [nf][3] int32 (the same, with the sentinel nc
+ *                         where the corner repeats an earlier corner's cell: it sorts to the end), survive [nf] uint8.  A face
+ *                         with an index >= nv gets nc thrice and does not survive;
+ *   _simplify_accumulate  one wave per cell: lane l takes entries l, l + 64, .. of the run in order and the 64 partial sums meet
+ *                         in a fixed butterfly (xor 32, 16, .. 1).  quadric [nc][10] fp64 = A00 A01 A02 A11 A12 A22, b, sum d^2;
+ *                         member [nc][3] fp64 (the sum of step 3, not yet divided), colour [nc][3] uint64 (the channel sums);
+ *   _simplify_solve       one lane per cell: cyclic Jacobi, 8 sweeps of the rotations (0,1) (0,2) (1,2), then steps 3 and 4:
+ *                         pos [nc][3] fp64, col [nc][3] uint8, rank [nc] uint8, fallback [nc] uint8, error [nc] fp64;
+ *   _simplify_solve_host  step 4 for n cells on the HOST (host pointers, the same inline function the kernel runs; mean = m):
+ *                         p [n][3] relative to the centre.  For checks of the solve on a machine without a device;
+ *   _simplify_triples     surv [ns] int64: the surviving faces in ascending order -> tri [3][ns] int32, the three cells of each in
+ *                         ascending order, one row per rank.  The caller sorts the faces stably and lexicographically by them
+ *                         (-> order [ns] int64, indices into surv);
+ *   _simplify_first       keep [nf] uint8 (zeroed by the caller): 1 for the first face of each run of equal triples;
+ *   _simplify_mark        used [nc] uint8 (zeroed by the caller): plain stores of 1 at the cells of the kept faces;
+ *   _simplify_count       block_count [ceil(n / 256)] uint32 of any flag array [n] uint8; adamvs_fusion_scan makes the offsets;
+ *   _simplify_emit        xyz [nu][3] fp64, rgb [nu][3] uint8, new_index [nc] uint32 (written at used cells), then faces
+ *                         [nk][3] uint32.  Nothing is written at or past vert_capacity / face_capacity.
+ * Argument errors (<0, before any launch): a null pointer, nv, nf, nc or ns < 1 or > 2^31 - 1, nc > nv, c not finite or <= 0,
+ * O not finite, rank_eps not in [0, 1), a capacity < 0. */
+#define ADAMVS_SIMPLIFY_TILE 256
+#define ADAMVS_SIMPLIFY_KEY_BITS 21
+
+int adamvs_simplify_keys(const double* origin, double cell, const double* xyz, long nv, long long* keys, unsigned char* bad, void* stream);
+int adamvs_simplify_corners(const unsigned* faces, long nf, const int* vcell, long nv, int nc, int* fcell, int* entry_cell,
+                            unsigned char* survive, void* stream);
+int adamvs_simplify_accumulate(const double* origin, double cell, const long long* keys, int nc, const double* xyz,
+                               const unsigned char* rgb, long nv, const unsigned* faces, long nf, const long long* entry,
+                               const long long* fstart, const long long* vorder, const long long* vstart, double* quadric,
+                               double* member, unsigned long long* colour, void* stream);
+int adamvs_simplify_solve(const double* origin, double cell, double rank_eps, const long long* keys, int nc, const double* quadric,
+                          const double* member, const unsigned long long* colour, const long long* vstart, double* pos,
+                          unsigned char* col, unsigned char* rank, unsigned char* fallback, double* error, void* stream);
+int adamvs_simplify_solve_host(const double* quadric, const double* mean, long n, double cell, double rank_eps, double* p, int* rank,
+                               int* fallback, double* error);
+int adamvs_simplify_triples(const int* fcell, long nf, const long long* surv, long ns, int* tri, void* stream);
+int adamvs_simplify_first(const int* tri, const long long* surv, const long long* order, long ns, long nf, unsigned char* keep,
+                          void* stream);
+int adamvs_simplify_mark(const int* fcell, const unsigned char* keep, long nf, int nc, unsigned char* used, void* stream);
+int adamvs_simplify_count(const unsigned char* flags, long n, unsigned* block_count, void* stream);
+int adamvs_simplify_emit(const double* pos, const unsigned char* col, const unsigned char* used, int nc, const unsigned* cell_offsets,
+                         const int* fcell, const unsigned char* keep, long nf, const unsigned* face_offsets, double* xyz,
+                         unsigned char* rgb, unsigned* new_index, long vert_capacity, unsigned* faces, long face_capacity, void* stream);
+
 /* ---- Image orthophoto (after dsm_whu.py): the source images mosaicked over a DSM into a true orthophoto -------------------
  * ada-mvs_amd/ortho.py drives it; ortho_whu.py is the CLI.  World axes: x east, y north, z up; rows run south.
  *
