@@ -203,6 +203,15 @@ SIGNATURES = {
     "adamvs_simplify_emit": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                    ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
                                    ctypes.c_void_p, ctypes.c_long, c_st]),
+    "adamvs_smooth_faces": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_smooth_edge_keys": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_smooth_boundary": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_smooth_filter": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long,
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, c_st]),
+    "adamvs_smooth_centroids": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_smooth_update": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                   c_st]),
     "adamvs_ortho_surface": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.c_void_p, c_st]),
     "adamvs_ortho_zbuf": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.POINTER(OrthoView), ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_void_p, ctypes.c_long, c_st]),
@@ -258,6 +267,7 @@ MESH_MAX_VIEWS = 65535           # ADAMVS_MESH_MAX_VIEWS
 MESH_MAX_EXTENT = 16384.0        # ADAMVS_MESH_MAX_EXTENT, metres from the volume origin
 SIMPLIFY_TILE = 256              # ADAMVS_SIMPLIFY_TILE: entries per workgroup of the simplification kernels
 SIMPLIFY_KEY_BITS = 21           # ADAMVS_SIMPLIFY_KEY_BITS: bits per axis of a cell key
+SMOOTH_TILE = 256                # ADAMVS_SMOOTH_TILE: elements per workgroup of the smoothing kernels
 ORTHO_BEST, ORTHO_FEATHER = 0, 1 # ADAMVS_ORTHO_BEST / ADAMVS_ORTHO_FEATHER
 ORTHO_MAX_CELLS = 1 << 28        # ADAMVS_ORTHO_MAX_CELLS
 ORTHO_MAX_UPSAMPLE = 8           # ADAMVS_ORTHO_MAX_UPSAMPLE

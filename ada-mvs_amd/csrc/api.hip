@@ -653,6 +653,62 @@ extern "C" int adamvs_simplify_emit(const double* pos, const unsigned char* col,
                               face_capacity, (hipStream_t)stream);
 }
 
+// ---- mesh smoothing (mesh_smooth.hip): every argument is checked here, before any launch
+static const long SMOOTH_MAX_FACES = ((1L << 31) - 1) / 3;      // the 3 nf (vertex, face) entries are counted in 31 bits
+
+static int smooth_check_counts(long nv, long nf, const char* what) {
+  ADAMVS_CHECK_ARG(nv >= 1 && nv <= SIMPLIFY_MAX, "%s: nv=%ld (1 .. 2^31 - 1)", what, nv);
+  ADAMVS_CHECK_ARG(nf >= 1 && nf <= SMOOTH_MAX_FACES, "%s: nf=%ld (1 .. (2^31 - 1) / 3)", what, nf);
+  return 0;
+}
+
+extern "C" int adamvs_smooth_faces(const double* p, long nv, const unsigned* faces, long nf, double* rec, void* stream) {
+  if (int rc = smooth_check_counts(nv, nf, "smooth_faces")) return rc;
+  ADAMVS_CHECK_ARG(p && faces && rec, "smooth_faces: null pointer");
+  ADAMVS_CHECK_ARG(((uintptr_t)rec & 63) == 0, "smooth_faces: rec is not aligned to 64 bytes");
+  return launch_smooth_faces(p, nv, faces, nf, rec, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_smooth_edge_keys(const unsigned* faces, long nf, long long* keys, void* stream) {
+  if (int rc = smooth_check_counts(1, nf, "smooth_edge_keys")) return rc;
+  ADAMVS_CHECK_ARG(faces && keys, "smooth_edge_keys: null pointer");
+  return launch_smooth_edge_keys(faces, nf, keys, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_smooth_boundary(const long long* keys, long n, long nv, unsigned char* fixed, void* stream) {
+  ADAMVS_CHECK_ARG(n >= 1 && n <= SIMPLIFY_MAX, "smooth_boundary: n=%ld (1 .. 2^31 - 1)", n);
+  ADAMVS_CHECK_ARG(nv >= 1 && nv <= SIMPLIFY_MAX, "smooth_boundary: nv=%ld (1 .. 2^31 - 1)", nv);
+  ADAMVS_CHECK_ARG(keys && fixed, "smooth_boundary: null pointer");
+  return launch_smooth_boundary(keys, n, nv, fixed, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_smooth_filter(const double* rec, const double* nin, double* nout, const unsigned* faces, long nf, long nv,
+                                    const int* vface, const long long* vstart, double sigma_s, double sigma_r, void* stream) {
+  if (int rc = smooth_check_counts(nv, nf, "smooth_filter")) return rc;
+  ADAMVS_CHECK_ARG(std::isfinite(sigma_s) && sigma_s > 0, "smooth_filter: sigma_s=%g must be finite and > 0", sigma_s);
+  ADAMVS_CHECK_ARG(std::isfinite(sigma_r) && sigma_r > 0, "smooth_filter: sigma_r=%g must be finite and > 0", sigma_r);
+  ADAMVS_CHECK_ARG(rec && nin && nout && faces && vface && vstart, "smooth_filter: null pointer");
+  ADAMVS_CHECK_ARG(nin != nout, "smooth_filter: the normals are double-buffered, nin == nout");
+  ADAMVS_CHECK_ARG(((uintptr_t)rec & 63) == 0, "smooth_filter: rec is not aligned to 64 bytes");
+  return launch_smooth_filter(rec, nin, nout, faces, nf, nv, vface, vstart, sigma_s, sigma_r, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_smooth_centroids(const double* p, long nv, const unsigned* faces, long nf, double* cen, void* stream) {
+  if (int rc = smooth_check_counts(nv, nf, "smooth_centroids")) return rc;
+  ADAMVS_CHECK_ARG(p && faces && cen, "smooth_centroids: null pointer");
+  return launch_smooth_centroids(p, nv, faces, nf, cen, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_smooth_update(const double* p0, const double* p, double* pout, long nv, const double* nrm, const double* cen,
+                                    long nf, const int* vface, const long long* vstart, const unsigned char* fixed, double cap,
+                                    unsigned char* clamped, void* stream) {
+  if (int rc = smooth_check_counts(nv, nf, "smooth_update")) return rc;
+  ADAMVS_CHECK_ARG(std::isfinite(cap) && cap > 0, "smooth_update: cap=%g must be finite and > 0", cap);
+  ADAMVS_CHECK_ARG(p0 && p && pout && nrm && cen && vface && vstart && fixed && clamped, "smooth_update: null pointer");
+  ADAMVS_CHECK_ARG(p != pout && p0 != pout, "smooth_update: the positions are double-buffered, pout aliases an input");
+  return launch_smooth_update(p0, p, pout, nv, nrm, cen, nf, vface, vstart, fixed, cap, clamped, (hipStream_t)stream);
+}
+
 // ---- image orthophoto (ortho.hip): every argument is checked here, before any launch
 static int ortho_check_grid(const adamvs_ortho_grid* g, const char* what) {
   ADAMVS_CHECK_ARG(g, "%s: null grid", what);

@@ -196,6 +196,17 @@ int launch_simplify_emit(const double* pos, const uint8_t* col, const uint8_t* u
                          const uint8_t* keep, long nf, const unsigned* face_offsets, double* xyz, uint8_t* rgb, unsigned* new_index,
                          long vert_capacity, unsigned* faces, long face_capacity, hipStream_t st);
 
+// mesh_smooth.hip: bilateral normal filtering of the mesh (include/adamvs_hip.h, "Mesh smoothing")
+constexpr int SMOOTH_TILE = ADAMVS_SMOOTH_TILE;
+int launch_smooth_faces(const double* p, long nv, const unsigned* faces, long nf, double* rec, hipStream_t st);
+int launch_smooth_edge_keys(const unsigned* faces, long nf, long long* keys, hipStream_t st);
+int launch_smooth_boundary(const long long* keys, long n, long nv, uint8_t* fixed, hipStream_t st);
+int launch_smooth_filter(const double* rec, const double* nin, double* nout, const unsigned* faces, long nf, long nv, const int* vface,
+                         const long long* vstart, double sigma_s, double sigma_r, hipStream_t st);
+int launch_smooth_centroids(const double* p, long nv, const unsigned* faces, long nf, double* cen, hipStream_t st);
+int launch_smooth_update(const double* p0, const double* p, double* pout, long nv, const double* nrm, const double* cen, long nf,
+                         const int* vface, const long long* vstart, const uint8_t* fixed, double cap, uint8_t* clamped, hipStream_t st);
+
 
 // ortho.hip: image orthophoto over a DSM, z-buffered per view (include/adamvs_hip.h, "Image orthophoto")
 constexpr int ORTHO_TILE = ADAMVS_ORTHO_TILE;

@@ -896,6 +896,90 @@ def simplify_emit(pos, col, fcell, keep):
     return xyz[:nu], rgb[:nu], faces[:nk], used
 
 
+# ---- mesh smoothing (csrc/mesh_smooth.hip; driven by ada_mvs_amd/smooth.py) ---------------------------------------------------
+# positions are relative to the origin (p = xyz - O); faces int32 = uint32; flags uint8.
+def _smooth_mesh(p, faces):
+    p = _dev_as(p, "p", torch.float64)
+    faces = _dev_as(faces, "faces", torch.int32)
+    if p.dim() != 2 or p.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.AdaMVSHipError("p [nv, 3], faces [nf, 3]: got %s, %s" % (tuple(p.shape), tuple(faces.shape)))
+    return p, faces
+
+
+def _smooth_runs(vface, vstart, nv, nf):
+    vface, vstart = _dev_as(vface, "vface", torch.int32), _dev_as(vstart, "vstart", torch.int64)
+    if vface.numel() != 3 * nf or vstart.numel() != nv + 1:
+        raise _lib.AdaMVSHipError("nv %d, nf %d against vface %d, vstart %d" % (nv, nf, vface.numel(), vstart.numel()))
+    return vface, vstart
+
+
+def smooth_faces(p, faces):
+    """adamvs_smooth_faces.  p [nv, 3] float64, faces [nf, 3] int32 (uint32) -> rec [nf, 8] float64: centroid, area, normal, 0."""
+    p, faces = _smooth_mesh(p, faces)
+    rec = torch.empty(faces.shape[0], 8, device=p.device, dtype=torch.float64)
+    check(_lib.load().adamvs_smooth_faces(_p(p), p.shape[0], _p(faces), faces.shape[0], _p(rec), _stream()), "smooth_faces")
+    return rec
+
+
+def smooth_boundary(faces, nv):
+    """adamvs_smooth_edge_keys, a sort of the keys, adamvs_smooth_boundary -> fixed [nv] uint8: the ends of every edge that occurs once."""
+    faces = _dev_as(faces, "faces", torch.int32)
+    nf = faces.shape[0]
+    keys = torch.empty(3 * nf, device=faces.device, dtype=torch.int64)
+    fixed = torch.zeros(int(nv), device=faces.device, dtype=torch.uint8)
+    lib, st = _lib.load(), _stream()
+    check(lib.adamvs_smooth_edge_keys(_p(faces), nf, _p(keys), st), "smooth_edge_keys")
+    keys = torch.sort(keys, stable=True).values
+    check(lib.adamvs_smooth_boundary(_p(keys), 3 * nf, int(nv), _p(fixed), st), "smooth_boundary")
+    return fixed
+
+
+def smooth_filter(rec, nin, faces, nv, vface, vstart, sigma_s, sigma_r, out=None):
+    """adamvs_smooth_filter: one pass.  rec [nf, 8], nin [nf, 3] float64 -> nout [nf, 3] (`out`, a buffer other than nin, is reused)."""
+    rec, nin = _dev_as(rec, "rec", torch.float64), _dev_as(nin, "nin", torch.float64)
+    faces = _dev_as(faces, "faces", torch.int32)
+    nf = faces.shape[0]
+    vface, vstart = _smooth_runs(vface, vstart, int(nv), nf)
+    if rec.numel() != 8 * nf or nin.numel() != 3 * nf:
+        raise _lib.AdaMVSHipError("smooth_filter: nf %d against rec %d, nin %d" % (nf, rec.numel(), nin.numel()))
+    nout = torch.empty_like(nin) if out is None else _dev_as(out, "out", torch.float64)
+    if nout.numel() != 3 * nf or nout.data_ptr() == nin.data_ptr() or not nout.is_contiguous():
+        raise _lib.AdaMVSHipError("smooth_filter: out must be a contiguous [nf, 3] buffer other than nin")
+    check(_lib.load().adamvs_smooth_filter(_p(rec), _p(nin), _p(nout), _p(faces), nf, int(nv), _p(vface), _p(vstart), float(sigma_s),
+                                           float(sigma_r), _stream()), "smooth_filter")
+    return nout
+
+
+def smooth_centroids(p, faces, out=None):
+    """adamvs_smooth_centroids -> cen [nf, 3] float64 of the positions p."""
+    p, faces = _smooth_mesh(p, faces)
+    cen = torch.empty(faces.shape[0], 3, device=p.device, dtype=torch.float64) if out is None else _dev_as(out, "out", torch.float64)
+    if cen.numel() != 3 * faces.shape[0]:
+        raise _lib.AdaMVSHipError("smooth_centroids: out %d against nf %d" % (cen.numel(), faces.shape[0]))
+    check(_lib.load().adamvs_smooth_centroids(_p(p), p.shape[0], _p(faces), faces.shape[0], _p(cen), _stream()), "smooth_centroids")
+    return cen
+
+
+def smooth_update(p0, p, normals, cen, vface, vstart, fixed, cap, out=None, clamped=None):
+    """adamvs_smooth_update: one pass.  p0, p [nv, 3], normals, cen [nf, 3] float64, fixed [nv] uint8 -> (pout [nv, 3], clamped [nv] uint8)."""
+    p0, p = _dev_as(p0, "p0", torch.float64), _dev_as(p, "p", torch.float64)
+    normals, cen = _dev_as(normals, "normals", torch.float64), _dev_as(cen, "cen", torch.float64)
+    fixed = _dev_as(fixed, "fixed", torch.uint8)
+    nv, nf = p0.shape[0], normals.shape[0]
+    vface, vstart = _smooth_runs(vface, vstart, nv, nf)
+    if p.numel() != 3 * nv or p0.numel() != 3 * nv or cen.numel() != 3 * nf or normals.numel() != 3 * nf or fixed.numel() != nv:
+        raise _lib.AdaMVSHipError("smooth_update: nv %d, nf %d against p %d, cen %d, fixed %d" % (nv, nf, p.numel(), cen.numel(), fixed.numel()))
+    pout = torch.empty_like(p0) if out is None else _dev_as(out, "out", torch.float64)
+    if pout.numel() != 3 * nv or pout.data_ptr() in (p.data_ptr(), p0.data_ptr()) or not pout.is_contiguous():
+        raise _lib.AdaMVSHipError("smooth_update: out must be a contiguous [nv, 3] buffer other than p and p0")
+    cl = torch.empty(nv, device=p0.device, dtype=torch.uint8) if clamped is None else _dev_as(clamped, "clamped", torch.uint8)
+    if cl.numel() != nv:
+        raise _lib.AdaMVSHipError("smooth_update: clamped %d against nv %d" % (cl.numel(), nv))
+    check(_lib.load().adamvs_smooth_update(_p(p0), _p(p), _p(pout), nv, _p(normals), _p(cen), nf, _p(vface), _p(vstart), _p(fixed),
+                                           float(cap), _p(cl), _stream()), "smooth_update")
+    return pout, cl
+
+
 # ---- image orthophoto (csrc/ortho.hip; driven view by view by ada_mvs_amd/ortho.py) ------------------------------------------
 # The depth buffer is int32 holding uint32 float bits; acc is float32 [N, 4]; view and nvis int32; nvis_out int16 (uint16).
 def ortho_grid(x0, y_top, gsd, W, H, K):

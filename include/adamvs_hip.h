@@ -788,6 +788,68 @@ int adamvs_simplify_emit(const double* pos, const unsigned char* col, const unsi
                          const int* fcell, const unsigned char* keep, long nf, const unsigned* face_offsets, double* xyz,
                          unsigned char* rgb, unsigned* new_index, long vert_capacity, unsigned* faces, long face_capacity, void* stream);
 
+/* ---- Mesh smoothing (after mesh_whu.py, before simplify_whu.py): bilateral normal filtering ---------------------------------
+ * (Zheng, Fu, Au, Tai, "Bilateral normal filtering for mesh denoising", the local iterative scheme.)  ada-mvs_amd/smooth.py
+ * drives it; smooth_whu.py is the CLI.  It welds the mesh by exact position first (mesh.py weld), always.  Flat ground and
+ * roofs flatten, creases stay; the topology is untouched.
+ *
+ * Inputs: vertices xyz [nv][3] fp64 world, rgb [nv][3] uint8, faces [nf][3] uint32, the origin O (fp64: the volume origin of
+ * <mesh>.json, else the per-axis vertex minimum), sigma_s > 0 (metres), sigma_r > 0, normal_iters and vertex_iters in 0 .. 1000,
+ * the cap > 0 (metres) and fix_boundary.  All arithmetic below is fp64 without contraction, on p = xyz - O; sqrt and the
+ * divisions round correctly, exp is the device library's.  |a|^2 of a 3-vector is (a0 a0 + a1 a1) + a2 a2 everywhere.  Faces,
+ * their order and the colours leave unchanged; only positions move.
+ *
+ * 1. Face records, from the input positions.  With the corners a, b, c:  u = b - a, w = c - a,
+ *    m = u x w = (u1 w2 - u2 w1, u2 w0 - u0 w2, u0 w1 - u1 w0),  area A = |m| / 2,  normal n = m / |m|, or the zero vector when
+ *    |m| = 0 (a DEGENERATE face),  centroid c = ((a + b) + c) / 3.
+ * 2. Incidence.  F(v): the faces with a corner at vertex v, ascending by face number, each once.  N(f): f itself, then the
+ *    faces of F(corner 0), then those of F(corner 1), then those of F(corner 2), each in order, leaving out every face that
+ *    already appeared (f included; a corner that repeats an earlier corner of f adds nothing).  That order is the summation
+ *    order of step 3.
+ * 3. Normal filter, normal_iters times, double-buffered (every read is of the previous pass):
+ *      s_f = sum over g in N(f) of  A_g exp(-(|c_f - c_g|^2 / (2 sigma_s^2) + |n_f - n_g|^2 / (2 sigma_r^2))) n_g
+ *    (the product of the spatial and the range weight, as one exponential), added term by term from zero;
+ *    n_f <- s_f / |s_f| if |s_f| > 1e-12, else n_f stays.  Areas and centroids stay those of step 1 throughout.
+ * 4. Fixed vertices.  The edges of a face are its corner pairs (0, 1), (1, 2), (2, 0), unordered.  With fix_boundary a vertex
+ *    is FIXED iff it is an end of an edge that occurs exactly once among the 3 nf edges.  An edge that occurs three or more
+ *    times gets no special treatment.
+ * 5. Vertex update, vertex_iters times, Jacobi (every read is of pass t, writes go to pass t + 1).  c_f^t = the centroids of
+ *    the current positions.  For a vertex that is not fixed and has faces:
+ *      s = sum over f in F(v), in order, of  n_f t_f,   t_f = (n_f.x e.x + n_f.y e.y) + n_f.z e.z,   e = c_f^t - x_v
+ *      x' = x_v + s / |F(v)|,   d = x' - x0_v,   x_v <- x0_v + d k,   k = cap / |d| if |d| > cap (the vertex is CLAMPED), else 1.
+ *    Fixed vertices and vertices without faces keep x0.
+ * Output: O + p for every vertex step 5 updated; the input bits for fixed vertices, vertices without faces and every vertex when
+ * vertex_iters = 0.
+ *
+ * Calls, in stream order.  The caller forms p, sorts the 3 nf (vertex, face) entries STABLY by vertex, entry 3 f + k carrying
+ * corner k of face f, or the sentinel nv where that corner repeats an earlier corner of f (-> vface [3 nf] int32: the faces
+ * in sorted order; vstart [nv + 1] int64: where each vertex's run starts, vstart[nv] = the first sentinel), and sorts the edge
+ * keys.  No atomics and no inter-workgroup waits: every lane writes its own element only, the order of every sum is a function
+ * of the sorted input, so the output is bit-identical from run to run.  Workgroups cover ADAMVS_SMOOTH_TILE consecutive
+ * elements, one lane each.
+ *   _smooth_faces       rec [nf][8] fp64, 64-byte aligned: centroid, area, normal, 0 (a face with an index >= nv: all zero);
+ *   _smooth_edge_keys   keys [3 nf] int64: min << 32 | max of the corner pairs (0, 1), (1, 2), (2, 0);
+ *   _smooth_boundary    keys [n] int64 SORTED; fixed [nv] uint8 (zeroed by the caller): plain stores of 1 at both ends of every
+ *                       key that differs from both its neighbours;
+ *   _smooth_filter      one pass of step 3: nin [nf][3] -> nout [nf][3] (nin != nout).  Whether a face already appeared is
+ *                       decided by comparing its three vertex numbers with the earlier corners of f;
+ *   _smooth_centroids   cen [nf][3] fp64 of the positions p [nv][3];
+ *   _smooth_update      one pass of step 5: p0 (the input), p -> pout [nv][3] (distinct buffers), clamped [nv] uint8 (written
+ *                       for every vertex).
+ * Argument errors (<0, before any launch): a null pointer, nv < 1 or > 2^31 - 1, nf < 1 or > (2^31 - 1) / 3, a sigma or the cap
+ * not finite or <= 0, rec not aligned to 64 bytes, aliased buffers. */
+#define ADAMVS_SMOOTH_TILE 256
+
+int adamvs_smooth_faces(const double* p, long nv, const unsigned* faces, long nf, double* rec, void* stream);
+int adamvs_smooth_edge_keys(const unsigned* faces, long nf, long long* keys, void* stream);
+int adamvs_smooth_boundary(const long long* keys, long n, long nv, unsigned char* fixed, void* stream);
+int adamvs_smooth_filter(const double* rec, const double* nin, double* nout, const unsigned* faces, long nf, long nv, const int* vface,
+                         const long long* vstart, double sigma_s, double sigma_r, void* stream);
+int adamvs_smooth_centroids(const double* p, long nv, const unsigned* faces, long nf, double* cen, void* stream);
+int adamvs_smooth_update(const double* p0, const double* p, double* pout, long nv, const double* nrm, const double* cen, long nf,
+                         const int* vface, const long long* vstart, const unsigned char* fixed, double cap, unsigned char* clamped,
+                         void* stream);
+
 /* ---- Image orthophoto (after dsm_whu.py): the source images mosaicked over a DSM into a true orthophoto -------------------
  * ada-mvs_amd/ortho.py drives it; ortho_whu.py is the CLI.  World axes: x east, y north, z up; rows run south.
  *
