@@ -212,6 +212,16 @@ SIGNATURES = {
     "adamvs_smooth_update": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
                                    ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
                                    c_st]),
+    "adamvs_cloud_nearest": (c_i, [ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long,
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p, c_st]),
+    "adamvs_cloud_nearest_host": (c_i, [ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                        ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "adamvs_cloud_sample_count": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_double, ctypes.c_void_p,
+                                        c_st]),
+    "adamvs_cloud_sample_emit": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_long, c_st]),
     "adamvs_ortho_surface": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.c_void_p, c_st]),
     "adamvs_ortho_zbuf": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.POINTER(OrthoView), ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_void_p, ctypes.c_long, c_st]),
@@ -268,6 +278,8 @@ MESH_MAX_EXTENT = 16384.0        # ADAMVS_MESH_MAX_EXTENT, metres from the volum
 SIMPLIFY_TILE = 256              # ADAMVS_SIMPLIFY_TILE: entries per workgroup of the simplification kernels
 SIMPLIFY_KEY_BITS = 21           # ADAMVS_SIMPLIFY_KEY_BITS: bits per axis of a cell key
 SMOOTH_TILE = 256                # ADAMVS_SMOOTH_TILE: elements per workgroup of the smoothing kernels
+CLOUD_TILE = 256                 # ADAMVS_CLOUD_TILE: queries per work item and candidates per tile of the cloud distance
+CLOUD_MAX_SUBDIV = 1024          # ADAMVS_CLOUD_MAX_SUBDIV: largest n of a face of the surface sampler
 ORTHO_BEST, ORTHO_FEATHER = 0, 1 # ADAMVS_ORTHO_BEST / ADAMVS_ORTHO_FEATHER
 ORTHO_MAX_CELLS = 1 << 28        # ADAMVS_ORTHO_MAX_CELLS
 ORTHO_MAX_UPSAMPLE = 8           # ADAMVS_ORTHO_MAX_UPSAMPLE

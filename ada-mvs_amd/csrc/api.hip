@@ -709,6 +709,52 @@ extern "C" int adamvs_smooth_update(const double* p0, const double* p, double* p
   return launch_smooth_update(p0, p, pout, nv, nrm, cen, nf, vface, vstart, fixed, cap, clamped, (hipStream_t)stream);
 }
 
+// ---- cloud distance (cloud_dist.hip): every argument is checked here, before any launch
+extern "C" int adamvs_cloud_nearest(const double* origin, double D, const long long* ukeys, const long long* tstart, int nc,
+                                    const double* targets, const int* tindex, long nt, const double* queries, long nq,
+                                    const long long* qorder, long nqs, const long long* item_key, const long long* item_first,
+                                    const int* item_count, long ni, float* d2, int* index, unsigned long long* pairs, void* stream) {
+  if (int rc = simplify_check_lattice(origin, D, "cloud_nearest")) return rc;
+  if (int rc = simplify_check_count(nt, "nt", "cloud_nearest")) return rc;
+  if (int rc = simplify_check_count(nq, "nq", "cloud_nearest")) return rc;
+  if (int rc = simplify_check_count(nqs, "nqs", "cloud_nearest")) return rc;
+  if (int rc = simplify_check_count(ni, "ni", "cloud_nearest")) return rc;
+  ADAMVS_CHECK_ARG(nc >= 1 && nc <= nt, "cloud_nearest: nc=%d (1 .. nt = %ld)", nc, nt);
+  ADAMVS_CHECK_ARG(nqs <= nq && ni <= nqs, "cloud_nearest: nqs=%ld, ni=%ld (ni <= nqs <= nq = %ld)", nqs, ni, nq);
+  ADAMVS_CHECK_ARG(ukeys && tstart && targets && tindex && queries && qorder && item_key && item_first && item_count && d2 && index && pairs,
+                   "cloud_nearest: null pointer");
+  return launch_cloud_nearest(origin, D, ukeys, tstart, nc, targets, tindex, nt, queries, nq, qorder, nqs, item_key, item_first, item_count,
+                              ni, d2, index, pairs, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_cloud_nearest_host(const double* origin, double D, const double* targets, long nt, const double* queries, long nq,
+                                         float* d2, int* index, unsigned long long* pairs) {
+  if (int rc = simplify_check_lattice(origin, D, "cloud_nearest_host")) return rc;
+  if (int rc = simplify_check_count(nt, "nt", "cloud_nearest_host")) return rc;
+  if (int rc = simplify_check_count(nq, "nq", "cloud_nearest_host")) return rc;
+  ADAMVS_CHECK_ARG(targets && queries && d2 && index, "cloud_nearest_host: null pointer");
+  return cloud_nearest_host(origin, D, targets, nt, queries, nq, d2, index, pairs);
+}
+
+extern "C" int adamvs_cloud_sample_count(const double* xyz, long nv, const unsigned* faces, long nf, double spacing, int* subdiv,
+                                         void* stream) {
+  if (int rc = simplify_check_count(nv, "nv", "cloud_sample_count")) return rc;
+  if (int rc = simplify_check_count(nf, "nf", "cloud_sample_count")) return rc;
+  ADAMVS_CHECK_ARG(std::isfinite(spacing) && spacing > 0, "cloud_sample_count: spacing=%g must be finite and > 0", spacing);
+  ADAMVS_CHECK_ARG(xyz && faces && subdiv, "cloud_sample_count: null pointer");
+  return launch_cloud_sample_count(xyz, nv, faces, nf, spacing, subdiv, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_cloud_sample_emit(const double* xyz, long nv, const unsigned* faces, long nf, const int* subdiv,
+                                        const long long* offsets, double* points, long capacity, void* stream) {
+  if (int rc = simplify_check_count(nv, "nv", "cloud_sample_emit")) return rc;
+  if (int rc = simplify_check_count(nf, "nf", "cloud_sample_emit")) return rc;
+  ADAMVS_CHECK_ARG(nf <= SIMPLIFY_MAX / 64, "cloud_sample_emit: nf=%ld (one wave per face: at most (2^31 - 1) / 64)", nf);
+  ADAMVS_CHECK_ARG(capacity >= 0, "cloud_sample_emit: capacity < 0");
+  ADAMVS_CHECK_ARG(xyz && faces && subdiv && offsets && (points || capacity == 0), "cloud_sample_emit: null pointer");
+  return launch_cloud_sample_emit(xyz, nv, faces, nf, subdiv, offsets, points, capacity, (hipStream_t)stream);
+}
+
 // ---- image orthophoto (ortho.hip): every argument is checked here, before any launch
 static int ortho_check_grid(const adamvs_ortho_grid* g, const char* what) {
   ADAMVS_CHECK_ARG(g, "%s: null grid", what);

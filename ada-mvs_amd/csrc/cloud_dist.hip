@@ -1,0 +1,341 @@
+// Cloud distance: the bounded nearest neighbour of every query among the targets, and a deterministic surface sampler, so that
+// clouds and meshes can be scored against a truth (include/adamvs_hip.h "Cloud distance" states every operation).  The caller
+// (ada-mvs_amd/accuracy.py) keys both clouds on the lattice of side c = D (adamvs_simplify_keys), sorts them stably, numbers the
+// occupied target cells (unique) and cuts the sorted queries into work items of one cell and at most 256 queries; here:
+//
+//   k_cloud_nearest       one 256-lane workgroup per work item: nine lanes find the nine (dy, dz) rows of the 27 cells (two binary
+//                         searches each: with x in the low key bits the three x-neighbours are one run of the sorted targets),
+//                         the workgroup walks the nine runs packed into tiles of 256 candidates through the LDS; the lanes
+//                         split into slices of one lane per query, each slice sweeps its share of a tile with reads of one
+//                         address per slice and keeps (d2, index) under the lexicographic rule, and the slices meet in a tree
+//   k_cloud_sample_count  one lane per face: n = max(1, ceil(longest edge / s))
+//   k_cloud_sample_emit   one wave per face: the (n + 1)(n + 2) / 2 barycentric lattice points, i ascending, then j
+//
+// No atomics and no inter-workgroup waits: every lane writes its own element only, and the result of a query is a function of
+// the targets as a set, so the output is bit-identical from run to run and under any permutation of either cloud.
+#include <math.h>
+
+#include <algorithm>
+#include <numeric>
+#include <vector>
+
+#include "common.h"
+#include "kernels.h"
+
+// The header states the arithmetic as separate roundings: no fused multiply-add anywhere in this file.
+#pragma clang fp contract(off)
+
+namespace adamvs {
+
+static_assert(CLOUD_TILE == 256, "the tile, the work item and the workgroup are 256 wide");
+constexpr int CKEY_BITS = ADAMVS_SIMPLIFY_KEY_BITS;
+constexpr long long CKEY_MASK = (1LL << CKEY_BITS) - 1;
+
+struct CloudLattice {
+  double o[3], c;
+};
+
+// key (>= 0) -> the centre of its cell, as mesh_simplify.hip's cell_centre
+__host__ __device__ __forceinline__ void cloud_centre(const CloudLattice& L, long long key, double* ctr) {
+  ctr[0] = L.o[0] + ((double)(key & CKEY_MASK) + 0.5) * L.c;
+  ctr[1] = L.o[1] + ((double)((key >> CKEY_BITS) & CKEY_MASK) + 0.5) * L.c;
+  ctr[2] = L.o[2] + ((double)(key >> (2 * CKEY_BITS)) + 0.5) * L.c;
+}
+
+// first position in the ascending keys [0, n) whose key is >= k (past = false) or > k (past = true)
+__host__ __device__ __forceinline__ int cloud_bound(const long long* keys, int n, long long k, bool past) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    const long long v = keys[mid];
+    if (v < k || (past && v == k)) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// Row (dy, dz) of the neighbourhood of the cell `key`: the occupied cells (iy + dy, iz + dz, ix - 1 .. ix + 1), clipped to the
+// lattice, as positions [*a, *b) of the ascending unique keys.  A row outside the lattice and an empty row give a = b.
+__host__ __device__ __forceinline__ void cloud_row_range(const long long* ukeys, int nc, long long key, int dy, int dz, int* a, int* b) {
+  const long long ix = key & CKEY_MASK, jy = ((key >> CKEY_BITS) & CKEY_MASK) + dy, jz = (key >> (2 * CKEY_BITS)) + dz;
+  *a = *b = 0;
+  if (key < 0 || jy < 0 || jy > CKEY_MASK || jz < 0 || jz > CKEY_MASK) return;
+  const long long x0 = ix > 0 ? ix - 1 : 0, x1 = ix < CKEY_MASK ? ix + 1 : CKEY_MASK;
+  const long long base = (jz << (2 * CKEY_BITS)) | (jy << CKEY_BITS);
+  *a = cloud_bound(ukeys, nc, base | x0, false);
+  *b = cloud_bound(ukeys, nc, base | x1, true);         // not (base | x1) + 1: the lattice's last key is the largest int64
+  if (*b < *a) *b = *a;
+}
+
+// (d2, idx) against the best so far: the nearer wins, and among equal d2 the lower index.  A lexicographic minimum, so the order
+// in which candidates or partial results meet does not matter.  best starts at +inf.  Selects, not branches: the sweep stays
+// straight-line and its LDS reads run ahead of their use.
+__host__ __device__ __forceinline__ void cloud_keep(float d2, int idx, float& best, int& best_idx) {
+  const bool take = (d2 < best) | ((d2 == best) & (idx < best_idx));
+  best = take ? d2 : best;
+  best_idx = take ? idx : best_idx;
+}
+
+// One (query, candidate) pair in fp32, both relative to the centre of the query's cell.
+__host__ __device__ __forceinline__ void cloud_pair_update(float qx, float qy, float qz, float px, float py, float pz, int idx, float& best,
+                                                           int& best_idx) {
+  const float dx = qx - px, dy = qy - py, dz = qz - pz;
+  cloud_keep((dx * dx + dy * dy) + dz * dz, idx, best, best_idx);
+}
+
+// the truncation: d2 stays iff d2 <= fp32(D D)
+__host__ __device__ __forceinline__ void cloud_truncate(float limit, float& best, int& best_idx) {
+  if (!(best <= limit)) best = INFINITY, best_idx = -1;
+}
+
+struct CloudEntry {      // one candidate in the LDS: 16 bytes, read as one ds_read_b128 at an address a slice's lanes share
+  float x, y, z;
+  int idx;
+};
+
+__global__ __launch_bounds__(256) void k_cloud_nearest(const CloudLattice L, float limit, const long long* __restrict__ ukeys,
+                                                       const long long* __restrict__ tstart, int nc, const double* __restrict__ targets,
+                                                       const int* __restrict__ tindex, long nt, const double* __restrict__ queries, long nq,
+                                                       const long long* __restrict__ qorder, long nqs,
+                                                       const long long* __restrict__ item_key, const long long* __restrict__ item_first,
+                                                       const int* __restrict__ item_count, float* __restrict__ d2, int* __restrict__ index,
+                                                       unsigned long long* __restrict__ pairs) {
+  __shared__ __attribute__((aligned(16))) CloudEntry tile[CLOUD_TILE];
+  __shared__ long long row_start[9];
+  __shared__ int row_off[10], row_len[9];
+  const int lane = threadIdx.x;
+  const long item = blockIdx.x;
+  const long long key = item_key[item];
+  const long long first = item_first[item];
+  int count = item_count[item];
+  count = count < 0 ? 0 : (count > CLOUD_TILE ? CLOUD_TILE : count);
+  double ctr[3];
+  cloud_centre(L, key < 0 ? 0 : key, ctr);
+  if (lane < 9) {
+    int a, b;
+    cloud_row_range(ukeys, nc, key, lane % 3 - 1, lane / 3 - 1, &a, &b);
+    long long s = tstart[a], e = tstart[b];
+    s = s < 0 ? 0 : (s > nt ? nt : s);
+    e = e < s ? s : (e > nt ? nt : e);
+    row_start[lane] = s;
+    row_len[lane] = (int)(e - s);
+  }
+  __syncthreads();
+  if (lane == 0) {
+    int acc = 0;
+    for (int r = 0; r < 9; ++r) {
+      row_off[r] = acc;
+      const int len = row_len[r];
+      acc = len > 0x7fffffff - acc ? 0x7fffffff : acc + len;
+    }
+    row_off[9] = acc;
+  }
+  // The item's queries take P lanes, P the smallest power of two >= count, and the workgroup splits into S = 256 / P SLICES: lane l
+  // serves query l mod P and sweeps candidates slice, slice + S, .. of every tile.  A cell of a fused cloud holds ten queries, not
+  // 256: with one lane per query the other lanes would idle through the sweep.
+  int P = 1;
+  while (P < count) P <<= 1;
+  const int S = CLOUD_TILE / P;
+  const int ql = lane & (P - 1), slice = lane / P;
+  const long long slot = first + ql;
+  long long qi = -1;
+  if (ql < count && slot >= 0 && slot < nqs) qi = qorder[slot];
+  const bool live = qi >= 0 && qi < nq;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (live) {
+    qx = (float)(queries[3 * qi] - ctr[0]);
+    qy = (float)(queries[3 * qi + 1] - ctr[1]);
+    qz = (float)(queries[3 * qi + 2] - ctr[2]);
+  }
+  float best = INFINITY;
+  int best_idx = 0x7fffffff;
+  __syncthreads();
+  const int total = row_off[9];
+  for (long long base = 0; base < total; base += CLOUD_TILE) {
+    const long long g = base + lane;
+    long long src = -1;
+#pragma unroll
+    for (int r = 0; r < 9; ++r) {
+      const int lo = row_off[r], hi = row_off[r + 1];
+      if (g >= lo && g < hi) src = row_start[r] + (g - lo);
+    }
+    CloudEntry e = {0.f, 0.f, 0.f, 0x7fffffff};
+    if (src >= 0 && src < nt) {
+      e.x = (float)(targets[3 * src] - ctr[0]);
+      e.y = (float)(targets[3 * src + 1] - ctr[1]);
+      e.z = (float)(targets[3 * src + 2] - ctr[2]);
+      e.idx = tindex[src];
+    }
+    tile[lane] = e;
+    __syncthreads();
+    const int n = total - base < CLOUD_TILE ? (int)(total - base) : CLOUD_TILE;
+#pragma unroll 8
+    for (int k = slice; k < n; k += S) {
+      const CloudEntry p = tile[k];
+      cloud_pair_update(qx, qy, qz, p.x, p.y, p.z, p.idx, best, best_idx);
+    }
+    __syncthreads();
+  }
+  // the S partial results of a query meet in a tree through the LDS (the tile is free after the last barrier); S is uniform
+  for (int h = S >> 1; h >= 1; h >>= 1) {
+    tile[lane].x = best;
+    tile[lane].idx = best_idx;
+    __syncthreads();
+    if (slice < h) cloud_keep(tile[lane + h * P].x, tile[lane + h * P].idx, best, best_idx);
+    __syncthreads();
+  }
+  if (live && slice == 0) {
+    cloud_truncate(limit, best, best_idx);
+    d2[qi] = best;
+    index[qi] = best_idx;
+  }
+  if (lane == 0) pairs[item] = (unsigned long long)total * (unsigned long long)count;
+}
+
+// ---- the surface sampler ------------------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ double cloud_edge2(const double* a, const double* b) {
+  const double x = b[0] - a[0], y = b[1] - a[1], z = b[2] - a[2];
+  return (x * x + y * y) + z * z;
+}
+
+// n of a face: max(1, ceil(longest edge / s)); ADAMVS_CLOUD_MAX_SUBDIV + 1 stands for anything larger or not finite
+__host__ __device__ __forceinline__ int cloud_face_n(const double* v0, const double* v1, const double* v2, double s) {
+  const double e = fmax(fmax(cloud_edge2(v0, v1), cloud_edge2(v1, v2)), cloud_edge2(v2, v0));
+  const double t = ceil(sqrt(e) / s);
+  if (!(t <= (double)ADAMVS_CLOUD_MAX_SUBDIV)) return ADAMVS_CLOUD_MAX_SUBDIV + 1;
+  return t < 1.0 ? 1 : (int)t;
+}
+
+__global__ __launch_bounds__(256) void k_cloud_sample_count(const double* __restrict__ xyz, long nv, const unsigned* __restrict__ faces,
+                                                            long nf, double s, int* __restrict__ subdiv) {
+  const long f = (long)blockIdx.x * CLOUD_TILE + threadIdx.x;
+  if (f >= nf) return;
+  const unsigned a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+  int n = 0;                                   // a face with an index >= nv has no samples
+  if ((long)a < nv && (long)b < nv && (long)c < nv) n = cloud_face_n(xyz + 3 * (long)a, xyz + 3 * (long)b, xyz + 3 * (long)c, s);
+  subdiv[f] = n;
+}
+
+__global__ __launch_bounds__(256) void k_cloud_sample_emit(const double* __restrict__ xyz, long nv, const unsigned* __restrict__ faces,
+                                                           long nf, const int* __restrict__ subdiv, const long long* __restrict__ offsets,
+                                                           double* __restrict__ points, long capacity) {
+  const int lane = threadIdx.x & 63;
+  const long f = (long)blockIdx.x * (CLOUD_TILE / 64) + (threadIdx.x >> 6);      // the wave's face
+  if (f >= nf) return;
+  const int n = subdiv[f];
+  const unsigned a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
+  if (n < 1 || n > ADAMVS_CLOUD_MAX_SUBDIV || (long)a >= nv || (long)b >= nv || (long)c >= nv) return;
+  const long long off = offsets[f];
+  double v0[3], u[3], w[3];
+  for (int k = 0; k < 3; ++k) {
+    v0[k] = xyz[3 * (long)a + k];
+    u[k] = xyz[3 * (long)b + k] - v0[k];
+    w[k] = xyz[3 * (long)c + k] - v0[k];
+  }
+  const double dn = (double)n;
+  for (int i = 0; i <= n; ++i) {
+    const long long row = off + (long long)i * (n + 1) - (long long)i * (i - 1) / 2;      // rows 0 .. i - 1 hold n + 1 - i' samples each
+    const double s = (double)i / dn;
+    for (int j = lane; j <= n - i; j += 64) {
+      const long long q = row + j;
+      if (q < 0 || q >= capacity) continue;
+      const double t = (double)j / dn;
+      for (int k = 0; k < 3; ++k) points[3 * q + k] = (v0[k] + s * u[k]) + t * w[k];
+    }
+  }
+}
+
+// ---- launches -------------------------------------------------------------------------------------------------------------------
+static CloudLattice cloud_lattice(const double* origin, double cell) {
+  CloudLattice L;
+  for (int i = 0; i < 3; ++i) L.o[i] = origin[i];
+  L.c = cell;
+  return L;
+}
+
+static unsigned cloud_tiles(long n) { return (unsigned)((n + CLOUD_TILE - 1) / CLOUD_TILE); }
+
+int launch_cloud_nearest(const double* origin, double D, const long long* ukeys, const long long* tstart, int nc, const double* targets,
+                         const int* tindex, long nt, const double* queries, long nq, const long long* qorder, long nqs,
+                         const long long* item_key, const long long* item_first, const int* item_count, long ni, float* d2, int* index,
+                         unsigned long long* pairs, hipStream_t st) {
+  hipLaunchKernelGGL(k_cloud_nearest, dim3((unsigned)ni), dim3(CLOUD_TILE), 0, st, cloud_lattice(origin, D), (float)(D * D), ukeys, tstart, nc,
+                     targets, tindex, nt, queries, nq, qorder, nqs, item_key, item_first, item_count, d2, index, pairs);
+  ADAMVS_CHECK_LAUNCH("cloud_nearest");
+  return 0;
+}
+
+int launch_cloud_sample_count(const double* xyz, long nv, const unsigned* faces, long nf, double spacing, int* subdiv, hipStream_t st) {
+  hipLaunchKernelGGL(k_cloud_sample_count, dim3(cloud_tiles(nf)), dim3(CLOUD_TILE), 0, st, xyz, nv, faces, nf, spacing, subdiv);
+  ADAMVS_CHECK_LAUNCH("cloud_sample_count");
+  return 0;
+}
+
+int launch_cloud_sample_emit(const double* xyz, long nv, const unsigned* faces, long nf, const int* subdiv, const long long* offsets,
+                             double* points, long capacity, hipStream_t st) {
+  hipLaunchKernelGGL(k_cloud_sample_emit, dim3(cloud_tiles(nf * 64)), dim3(CLOUD_TILE), 0, st, xyz, nv, faces, nf, subdiv, offsets, points,
+                     capacity);
+  ADAMVS_CHECK_LAUNCH("cloud_sample_emit");
+  return 0;
+}
+
+// ---- the same search on the host, for checks of the rule without a device ------------------------------------------------------
+// key of step 1 of "Mesh simplification" (k_simplify_keys' arithmetic), -1 for a point that is not finite or outside the lattice
+static long long cloud_key_host(const CloudLattice& L, const double* p, int* err) {
+  long long key = 0;
+  *err = 0;
+  for (int ax = 0; ax < 3; ++ax) {
+    const double x = p[ax];
+    const double t = (x - L.o[ax]) / L.c;
+    if (!(fabs(x) <= 1.7976931348623157e308)) *err = *err ? *err : 1;
+    else if (!(t >= 0.0 && t < (double)(1 << CKEY_BITS))) *err = *err ? *err : 2;
+    else key |= (long long)floor(t) << (ax * CKEY_BITS);
+  }
+  return *err ? -1 : key;
+}
+
+int cloud_nearest_host(const double* origin, double D, const double* targets, long nt, const double* queries, long nq, float* d2, int* index,
+                       unsigned long long* pairs) {
+  const CloudLattice L = cloud_lattice(origin, D);
+  const float limit = (float)(D * D);
+  std::vector<long long> tkey(nt);
+  for (long i = 0; i < nt; ++i) {
+    int err;
+    tkey[i] = cloud_key_host(L, targets + 3 * i, &err);
+    if (err) return set_error(-1, "cloud_nearest_host: target %ld is %s", i, err == 1 ? "not finite" : "outside the lattice of 2^21 cells per axis");
+  }
+  std::vector<long> order(nt);
+  std::iota(order.begin(), order.end(), 0L);
+  std::stable_sort(order.begin(), order.end(), [&](long a, long b) { return tkey[a] < tkey[b]; });
+  std::vector<long long> ukeys, tstart;
+  for (long i = 0; i < nt; ++i)
+    if (i == 0 || tkey[order[i]] != tkey[order[i - 1]]) ukeys.push_back(tkey[order[i]]), tstart.push_back(i);
+  tstart.push_back(nt);
+  const int nc = (int)ukeys.size();
+  unsigned long long evaluated = 0;
+  for (long q = 0; q < nq; ++q) {
+    int err;
+    const long long key = cloud_key_host(L, queries + 3 * q, &err);
+    float best = INFINITY;
+    int best_idx = 0x7fffffff;
+    if (!err) {
+      double ctr[3];
+      cloud_centre(L, key, ctr);
+      const float qx = (float)(queries[3 * q] - ctr[0]), qy = (float)(queries[3 * q + 1] - ctr[1]), qz = (float)(queries[3 * q + 2] - ctr[2]);
+      for (int r = 0; r < 9; ++r) {
+        int a, b;
+        cloud_row_range(ukeys.data(), nc, key, r % 3 - 1, r / 3 - 1, &a, &b);
+        for (long long s = tstart[a]; s < tstart[b]; ++s, ++evaluated) {
+          const double* p = targets + 3 * order[s];
+          cloud_pair_update(qx, qy, qz, (float)(p[0] - ctr[0]), (float)(p[1] - ctr[1]), (float)(p[2] - ctr[2]), (int)order[s], best, best_idx);
+        }
+      }
+    }
+    cloud_truncate(limit, best, best_idx);
+    d2[q] = best, index[q] = best_idx;
+  }
+  if (pairs) *pairs = evaluated;
+  return 0;
+}
+
+}  // namespace adamvs

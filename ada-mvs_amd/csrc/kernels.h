@@ -208,6 +208,18 @@ int launch_smooth_update(const double* p0, const double* p, double* pout, long n
                          const int* vface, const long long* vstart, const uint8_t* fixed, double cap, uint8_t* clamped, hipStream_t st);
 
 
+// cloud_dist.hip: bounded nearest neighbour between two clouds and the surface sampler (include/adamvs_hip.h, "Cloud distance")
+constexpr int CLOUD_TILE = ADAMVS_CLOUD_TILE;
+int launch_cloud_nearest(const double* origin, double D, const long long* ukeys, const long long* tstart, int nc, const double* targets,
+                         const int* tindex, long nt, const double* queries, long nq, const long long* qorder, long nqs,
+                         const long long* item_key, const long long* item_first, const int* item_count, long ni, float* d2, int* index,
+                         unsigned long long* pairs, hipStream_t st);
+int cloud_nearest_host(const double* origin, double D, const double* targets, long nt, const double* queries, long nq, float* d2, int* index,
+                       unsigned long long* pairs);
+int launch_cloud_sample_count(const double* xyz, long nv, const unsigned* faces, long nf, double spacing, int* subdiv, hipStream_t st);
+int launch_cloud_sample_emit(const double* xyz, long nv, const unsigned* faces, long nf, const int* subdiv, const long long* offsets,
+                             double* points, long capacity, hipStream_t st);
+
 // ortho.hip: image orthophoto over a DSM, z-buffered per view (include/adamvs_hip.h, "Image orthophoto")
 constexpr int ORTHO_TILE = ADAMVS_ORTHO_TILE;
 constexpr int ORTHO_SMALL_PX = ADAMVS_ORTHO_SMALL_PX;

@@ -896,6 +896,70 @@ def simplify_emit(pos, col, fcell, keep):
     return xyz[:nu], rgb[:nu], faces[:nk], used
 
 
+# ---- cloud distance (csrc/cloud_dist.hip; driven by ada_mvs_amd/accuracy.py) -----------------------------------------------------
+# keys and orders int64, target numbers int32, d2 float32, index int32, pair counts int64 = uint64.
+def cloud_nearest(origin, D, ukeys, tstart, targets_sorted, tindex, queries, qorder, item_key, item_first, item_count):
+    """adamvs_cloud_nearest.  ukeys [nc] / tstart [nc + 1] int64 (the occupied target cells and their runs), targets_sorted [nt, 3]
+    float64 with tindex [nt] int32 (their numbers in the caller's order), queries [nq, 3] float64, qorder [nqs] int64, the work items
+    (item_key, item_first int64, item_count int32) -> (d2 [nq] float32, index [nq] int32, pairs [ni] int64); +inf and -1 where no
+    target lies within D."""
+    ukeys, tstart = _dev_as(ukeys, "ukeys", torch.int64), _dev_as(tstart, "tstart", torch.int64)
+    targets_sorted, tindex = _dev_as(targets_sorted, "targets_sorted", torch.float64), _dev_as(tindex, "tindex", torch.int32)
+    queries, qorder = _dev_as(queries, "queries", torch.float64), _dev_as(qorder, "qorder", torch.int64)
+    item_key, item_first = _dev_as(item_key, "item_key", torch.int64), _dev_as(item_first, "item_first", torch.int64)
+    item_count = _dev_as(item_count, "item_count", torch.int32)
+    nc, nt, nq, nqs, ni, dev = ukeys.numel(), targets_sorted.shape[0], queries.shape[0], qorder.numel(), item_key.numel(), queries.device
+    if (targets_sorted.dim() != 2 or targets_sorted.shape[1] != 3 or queries.dim() != 2 or queries.shape[1] != 3 or tstart.numel() != nc + 1
+            or tindex.numel() != nt or item_first.numel() != ni or item_count.numel() != ni):
+        raise _lib.AdaMVSHipError("cloud_nearest: nc %d, nt %d, ni %d against targets %s, queries %s, tstart %d, tindex %d, item_first %d, "
+                                  "item_count %d" % (nc, nt, ni, tuple(targets_sorted.shape), tuple(queries.shape), tstart.numel(),
+                                                     tindex.numel(), item_first.numel(), item_count.numel()))
+    keep, o, d = _lattice(origin, D)
+    d2 = torch.full((nq,), float("inf"), device=dev, dtype=torch.float32)
+    index = torch.full((nq,), -1, device=dev, dtype=torch.int32)
+    pairs = torch.zeros(ni, device=dev, dtype=torch.int64)
+    check(_lib.load().adamvs_cloud_nearest(o, d, _p(ukeys), _p(tstart), nc, _p(targets_sorted), _p(tindex), nt, _p(queries), nq, _p(qorder),
+                                           nqs, _p(item_key), _p(item_first), _p(item_count), ni, _p(d2), _p(index), _p(pairs), _stream()),
+          "cloud_nearest")
+    return d2, index, pairs
+
+
+def cloud_nearest_host(targets, queries, D, origin):
+    """adamvs_cloud_nearest_host on numpy arrays: targets [nt, 3], queries [nq, 3] -> (d2 [nq] float32, index [nq] int32, pairs)."""
+    t = np.ascontiguousarray(np.asarray(targets, np.float64).reshape(-1, 3))
+    q = np.ascontiguousarray(np.asarray(queries, np.float64).reshape(-1, 3))
+    keep, o, d = _lattice(origin, D)
+    d2, index, pairs = np.zeros(len(q), np.float32), np.zeros(len(q), np.int32), ctypes.c_ulonglong(0)
+    check(_lib.load().adamvs_cloud_nearest_host(o, d, t.ctypes.data, len(t), q.ctypes.data, len(q), d2.ctypes.data, index.ctypes.data,
+                                                ctypes.addressof(pairs)), "cloud_nearest_host")
+    return d2, index, int(pairs.value)
+
+
+def cloud_sample_count(xyz, faces, spacing):
+    """adamvs_cloud_sample_count.  xyz [nv, 3] float64, faces [nf, 3] int32 (uint32) -> subdiv [nf] int32 (n per face; 1025: too fine)."""
+    xyz, faces = _dev_as(xyz, "xyz", torch.float64), _dev_as(faces, "faces", torch.int32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise _lib.AdaMVSHipError("xyz [nv, 3], faces [nf, 3]: got %s, %s" % (tuple(xyz.shape), tuple(faces.shape)))
+    subdiv = torch.empty(faces.shape[0], device=xyz.device, dtype=torch.int32)
+    check(_lib.load().adamvs_cloud_sample_count(_p(xyz), xyz.shape[0], _p(faces), faces.shape[0], float(spacing), _p(subdiv), _stream()),
+          "cloud_sample_count")
+    return subdiv
+
+
+def cloud_sample_emit(xyz, faces, subdiv, offsets, total):
+    """adamvs_cloud_sample_emit.  offsets [nf + 1] int64 (exclusive sum of the samples per face), total = offsets[nf] -> points
+    [total, 3] float64."""
+    xyz, faces = _dev_as(xyz, "xyz", torch.float64), _dev_as(faces, "faces", torch.int32)
+    subdiv, offsets = _dev_as(subdiv, "subdiv", torch.int32), _dev_as(offsets, "offsets", torch.int64)
+    nf = faces.shape[0]
+    if subdiv.numel() != nf or offsets.numel() != nf + 1:
+        raise _lib.AdaMVSHipError("cloud_sample_emit: nf %d against subdiv %d, offsets %d" % (nf, subdiv.numel(), offsets.numel()))
+    points = torch.empty(max(int(total), 1), 3, device=xyz.device, dtype=torch.float64)
+    check(_lib.load().adamvs_cloud_sample_emit(_p(xyz), xyz.shape[0], _p(faces), nf, _p(subdiv), _p(offsets), _p(points), int(total),
+                                               _stream()), "cloud_sample_emit")
+    return points[:int(total)]
+
+
 # ---- mesh smoothing (csrc/mesh_smooth.hip; driven by ada_mvs_amd/smooth.py) ---------------------------------------------------
 # positions are relative to the origin (p = xyz - O); faces int32 = uint32; flags uint8.
 def _smooth_mesh(p, faces):

@@ -850,6 +850,89 @@ int adamvs_smooth_update(const double* p0, const double* p, double* pout, long n
                          const int* vface, const long long* vstart, const unsigned char* fixed, double cap, unsigned char* clamped,
                          void* stream);
 
+/* ---- Cloud distance (scoring a cloud or a mesh against a truth): bounded nearest neighbour and a surface sampler ---------------
+ * ada-mvs_amd/accuracy.py drives it; accuracy_whu.py is the CLI.  Accuracy is the distance from every point of a reconstruction
+ * to its nearest point of the truth, completeness the same the other way round (the DTU and Tanks-and-Temples measures); both
+ * are one search: for every QUERY the nearest TARGET within the truncation distance D.
+ *
+ * Inputs: targets T [nt][3] and queries Q [nq][3], fp64 world; D > 0 in metres; the lattice origin O (fp64).
+ *
+ * 1. Lattice.  Cell side c = D.  The driver's default origin is, per axis, (min of the targets) - c / 3 - c: the third keeps
+ *    a plane at a round height off a cell boundary, the whole cell keeps every target's lower neighbour inside the lattice.
+ *    Cells, keys (x in the low bits) and cell centres are those of step 1 of "Mesh simplification", computed by
+ *    _simplify_keys for both clouds.  A target that is not finite or lies outside the 2^21 cells of an axis is an error of
+ *    the driver.  A query that is not finite or outside the lattice is no error: it has no candidates.
+ * 2. Candidates of a query in cell (ix, iy, iz): the targets of the 27 cells (ix - 1 .. ix + 1, iy - 1 .. iy + 1,
+ *    iz - 1 .. iz + 1) that exist in the lattice.  Every target within D of the query is among them, since c = D.
+ * 3. Distance.  With the centre C (fp64) of the QUERY's cell:  qf = fp32(q - C),  pf = fp32(p - C), both subtractions in fp64,
+ *    each component rounded once;  then in fp32, every operation rounded:  e = qf - pf,  d2 = (e.x e.x + e.y e.y) + e.z e.z.
+ *    |q - C| <= c / 2 and |p - C| <= 3 c / 2 per component, whatever the world offset.
+ * 4. Choice.  Over the candidates the least (d2, original index) in lexicographic order: among equal d2 the target with the
+ *    lowest number in the CALLER's order wins, so the result is a function of the targets as a set.  The candidate is KEPT iff
+ *    d2 <= fp32(D D) (the product in fp64, rounded once).  Output per query, at its original position:  d2 fp32 and index int32
+ *    of the kept candidate, else +inf and -1.  The driver reports dist = sqrt(d2) in fp32.
+ *
+ * Bound, with u = 2^-24 (half an ulp of fp32, relative).  Rounding q - C (at most c / 2) costs u c / 2, rounding p - C (at most
+ * 3 c / 2) costs 3 u c / 2, rounding the difference e (at most c wherever d <= D matters) costs u c: at most 3 u c = 1.8e-7 c
+ * per component (2.4e-7 c with ulps counted whole in places), at most sqrt(3) times that, 3.1e-7 c, on d when all three
+ * components err the same way.  The fp64 subtractions share one C and round relative 2^-53: nothing at this scale.  A square
+ * and two sums put at most 3 u on d2, the root halves that and adds its own u: 2.5 u d <= 1.5e-7 c for d <= D.  Hence
+ *      | d - d_fp64 | <= 1e-6 c
+ * with a factor two to spare; the tests hold the kernel to it.  A target within 1e-6 c of D, or two candidates within 2e-6 c
+ * of each other, may fall either way; nothing else may.
+ *
+ * Calls, in stream order.  The caller sorts the target keys STABLY (-> the sorted targets [nt][3] fp64, gathered, and tindex
+ * [nt] int32, their numbers in the caller's order), takes the distinct keys ascending (ukeys [nc] int64) with the start of each
+ * cell's run (tstart [nc + 1] int64, tstart[nc] = nt), sorts the query keys stably (qorder [nqs] int64: the queries with a
+ * key >= 0 in sorted order, as numbers in the caller's order) and cuts every run of equal query keys into WORK ITEMS of at most
+ * ADAMVS_CLOUD_TILE queries (item_key, item_first [ni] int64: the cell and the position in qorder; item_count [ni] int32).
+ *   _cloud_nearest        one workgroup of 256 lanes per work item.  Nine lanes find the nine rows (dy, dz) of step 2: with x in
+ *                         the low key bits the cells ix - 1 .. ix + 1 of a row are one run of the sorted targets, found by two
+ *                         binary searches in ukeys; a row outside the lattice and an empty row give an empty run.  The nine
+ *                         runs, row (dy, dz) = (-1, -1), (0, -1), (1, -1), (-1, 0), .. in that order, are walked as one sequence
+ *                         in tiles of 256 candidates: each lane forms pf of one candidate and stores (pf, index) as one 16-byte
+ *                         LDS entry.  With P the smallest power of two >= the item's queries the 256 lanes form S = 256 / P
+ *                         SLICES: lane l serves query l mod P in slice l / P, and after the barrier sweeps candidates
+ *                         slice, slice + S, .. of the tile, the lanes of a slice reading one shared address (a broadcast; the
+ *                         slices of a wave read consecutive entries, which lie in different banks).  The S partial results
+ *                         of a query meet in a tree under the rule of step 4, a minimum, so the result does not depend on
+ *                         how the candidates were split.  d2 and index must be pre-filled with +inf and -1 by the caller: queries
+ *                         outside every work item are not written.  pairs [ni] uint64: the (query, candidate) pairs each
+ *                         workgroup evaluated (candidates of the item times its queries).  No atomics, no waits between
+ *                         workgroups: bit-identical from run to run and under any permutation of T or of Q;
+ *   _cloud_nearest_host   steps 1 to 4 on the HOST for small nt, nq (host pointers, the same inline functions for the row
+ *                         search, the pair update and the truncation as the kernel; the keys are recomputed here);
+ *                         pairs: one uint64 or null.  For checks of the rule on a machine without a device.
+ *
+ * Surface sampler: a mesh (xyz [nv][3] fp64, faces [nf][3] uint32) is scored through points on its faces.  With the spacing
+ * s > 0 and the corners v0, v1, v2 of a face, all in fp64 without contraction:
+ *      n = max(1, ceil(L / s)),   L = sqrt(max over the edges (v0 v1), (v1 v2), (v2 v0) of (dx dx + dy dy) + dz dz);
+ *      sample (i, j), i + j <= n:   (v0 + (i / n) (v1 - v0)) + (j / n) (v2 - v0)   per component, in exactly this order.
+ * Faces ascending; within a face i ascending, then j: (n + 1)(n + 2) / 2 samples, the corners included, so samples shared by
+ * neighbouring faces stay duplicated.  n > ADAMVS_CLOUD_MAX_SUBDIV = 1024 (or L not finite) is an error of the driver, which
+ * names the face.  Covering: the samples split the face into n^2 congruent triangles with edges <= L / n <= s, and every point
+ * of a triangle with edges <= s lies within s / sqrt(3) of a corner (the circumradius of the equilateral case is the worst
+ * that can hold a point away from all three corners).  Hence every point of a face lies within s / sqrt(3) of a sample, and
+ * for any point x:  d_samples(x)^2 <= d_surface(x)^2 + s^2 / 3.
+ *   _cloud_sample_count   subdiv [nf] int32: n per face; 1025 for n > 1024 or L not finite; 0 for a face with an index >= nv;
+ *   _cloud_sample_emit    offsets [nf + 1] int64: the exclusive sum of (n + 1)(n + 2) / 2 over the faces (the caller's); points
+ *                         [total][3] fp64.  One wave per face.  Nothing is written at or past capacity.  Bit-identical to the
+ *                         restatement of the formula above.
+ * Argument errors (<0, before any launch): a null pointer, a count < 1 or > 2^31 - 1, nc > nt, D or s not finite or <= 0, O not
+ * finite, a capacity < 0. */
+#define ADAMVS_CLOUD_TILE 256
+#define ADAMVS_CLOUD_MAX_SUBDIV 1024
+
+int adamvs_cloud_nearest(const double* origin, double D, const long long* ukeys, const long long* tstart, int nc, const double* targets,
+                         const int* tindex, long nt, const double* queries, long nq, const long long* qorder, long nqs,
+                         const long long* item_key, const long long* item_first, const int* item_count, long ni, float* d2, int* index,
+                         unsigned long long* pairs, void* stream);
+int adamvs_cloud_nearest_host(const double* origin, double D, const double* targets, long nt, const double* queries, long nq, float* d2,
+                              int* index, unsigned long long* pairs);
+int adamvs_cloud_sample_count(const double* xyz, long nv, const unsigned* faces, long nf, double spacing, int* subdiv, void* stream);
+int adamvs_cloud_sample_emit(const double* xyz, long nv, const unsigned* faces, long nf, const int* subdiv, const long long* offsets,
+                             double* points, long capacity, void* stream);
+
 /* ---- Image orthophoto (after dsm_whu.py): the source images mosaicked over a DSM into a true orthophoto -------------------
  * ada-mvs_amd/ortho.py drives it; ortho_whu.py is the CLI.  World axes: x east, y north, z up; rows run south.
  *
