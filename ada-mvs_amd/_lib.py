@@ -212,6 +212,22 @@ SIGNATURES = {
     "adamvs_smooth_update": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
                                    ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
                                    c_st]),
+    "adamvs_clean_components": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_clean_area": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
+                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_clean_boundary": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_clean_successor": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_clean_double": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_clean_validate": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_i, ctypes.c_void_p,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_clean_accumulate": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                      ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
+                                      ctypes.c_void_p, c_st]),
+    "adamvs_clean_emit": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
+                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_long,
+                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
     "adamvs_cloud_nearest": (c_i, [ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p,
                                    ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
@@ -278,6 +294,10 @@ MESH_MAX_EXTENT = 16384.0        # ADAMVS_MESH_MAX_EXTENT, metres from the volum
 SIMPLIFY_TILE = 256              # ADAMVS_SIMPLIFY_TILE: entries per workgroup of the simplification kernels
 SIMPLIFY_KEY_BITS = 21           # ADAMVS_SIMPLIFY_KEY_BITS: bits per axis of a cell key
 SMOOTH_TILE = 256                # ADAMVS_SMOOTH_TILE: elements per workgroup of the smoothing kernels
+CLEAN_TILE = 256                 # ADAMVS_CLEAN_TILE: elements per workgroup of the cleaning kernels
+CLEAN_CHUNK = 1024               # ADAMVS_CLEAN_CHUNK: sorted faces per piece of a component's area
+CLEAN_MAX_HOLE_EDGES = 4096      # ADAMVS_CLEAN_MAX_HOLE_EDGES
+CLEAN_MAX_ROUNDS = 64            # ADAMVS_CLEAN_MAX_ROUNDS: cap on the rounds of the component labels
 CLOUD_TILE = 256                 # ADAMVS_CLOUD_TILE: queries per work item and candidates per tile of the cloud distance
 CLOUD_MAX_SUBDIV = 1024          # ADAMVS_CLOUD_MAX_SUBDIV: largest n of a face of the surface sampler
 ORTHO_BEST, ORTHO_FEATHER = 0, 1 # ADAMVS_ORTHO_BEST / ADAMVS_ORTHO_FEATHER

@@ -709,6 +709,87 @@ extern "C" int adamvs_smooth_update(const double* p0, const double* p, double* p
   return launch_smooth_update(p0, p, pout, nv, nrm, cen, nf, vface, vstart, fixed, cap, clamped, (hipStream_t)stream);
 }
 
+// ---- mesh cleaning (mesh_clean.hip): every argument is checked here, before any launch; the limits are smoothing's
+extern "C" int adamvs_clean_components(const unsigned* faces, long nf, long nv, const int* parent_in, int* parent_out, unsigned* changed,
+                                       void* stream) {
+  if (int rc = smooth_check_counts(nv, nf, "clean_components")) return rc;
+  ADAMVS_CHECK_ARG(faces && parent_in && parent_out && changed, "clean_components: null pointer");
+  ADAMVS_CHECK_ARG(parent_in != parent_out, "clean_components: the labels are double-buffered, parent_in == parent_out");
+  return launch_clean_components(faces, nf, nv, parent_in, parent_out, changed, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_clean_area(const double* area, long nf, const long long* order, const long long* seg_of, const long long* seg_start,
+                                 long ncomp, double* lead, double* first, double* out, void* stream) {
+  if (int rc = smooth_check_counts(1, nf, "clean_area")) return rc;
+  ADAMVS_CHECK_ARG(ncomp >= 1 && ncomp <= nf, "clean_area: ncomp=%ld (1 .. nf = %ld)", ncomp, nf);
+  ADAMVS_CHECK_ARG(area && order && seg_of && seg_start && lead && first && out, "clean_area: null pointer");
+  ADAMVS_CHECK_ARG(lead != first && lead != out && first != out && area != out && area != lead && area != first, "clean_area: aliased buffers");
+  return launch_clean_area(area, nf, order, seg_of, seg_start, ncomp, lead, first, out, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_clean_boundary(const long long* keys_sorted, const long long* entry, long ns, unsigned char* bnd, void* stream) {
+  if (int rc = smooth_check_counts(1, ns, "clean_boundary")) return rc;
+  ADAMVS_CHECK_ARG(keys_sorted && entry && bnd, "clean_boundary: null pointer");
+  ADAMVS_CHECK_ARG(keys_sorted != entry, "clean_boundary: keys_sorted == entry");
+  return launch_clean_boundary(keys_sorted, entry, 3 * ns, bnd, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_clean_successor(const unsigned* faces, long ns, long nv, const unsigned char* bnd, int* out_count, int* in_count,
+                                      int* out_edge, int* succ, int* lab, int* nxt, unsigned char* broken, void* stream) {
+  if (int rc = smooth_check_counts(nv, ns, "clean_successor")) return rc;
+  ADAMVS_CHECK_ARG(faces && bnd && out_count && in_count && out_edge && succ && lab && nxt && broken, "clean_successor: null pointer");
+  ADAMVS_CHECK_ARG(out_count != in_count && out_count != out_edge && in_count != out_edge && succ != lab && succ != nxt && lab != nxt &&
+                   bnd != broken, "clean_successor: aliased buffers");
+  return launch_clean_successor(faces, ns, nv, bnd, out_count, in_count, out_edge, succ, lab, nxt, broken, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_clean_double(const unsigned char* bnd, long ns, const int* lab_in, const int* nxt_in, const unsigned char* broken_in,
+                                   int* lab_out, int* nxt_out, unsigned char* broken_out, void* stream) {
+  if (int rc = smooth_check_counts(1, ns, "clean_double")) return rc;
+  ADAMVS_CHECK_ARG(bnd && lab_in && nxt_in && broken_in && lab_out && nxt_out && broken_out, "clean_double: null pointer");
+  ADAMVS_CHECK_ARG(lab_in != lab_out && nxt_in != nxt_out && broken_in != broken_out && lab_out != nxt_out && lab_out != nxt_in &&
+                   nxt_out != lab_in && bnd != broken_out, "clean_double: the round is double-buffered, an output aliases an input");
+  return launch_clean_double(bnd, 3 * ns, lab_in, nxt_in, broken_in, lab_out, nxt_out, broken_out, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_clean_validate(const unsigned char* bnd, const int* succ, const int* lab, const unsigned char* broken, long ns,
+                                     int max_hole_edges, int* count, unsigned char* bad, int* loop, unsigned char* closed, void* stream) {
+  if (int rc = smooth_check_counts(1, ns, "clean_validate")) return rc;
+  ADAMVS_CHECK_ARG(max_hole_edges >= 0 && max_hole_edges <= ADAMVS_CLEAN_MAX_HOLE_EDGES, "clean_validate: max_hole_edges=%d (0 .. %d)",
+                   max_hole_edges, ADAMVS_CLEAN_MAX_HOLE_EDGES);
+  ADAMVS_CHECK_ARG(bnd && succ && lab && broken && count && bad && loop && closed, "clean_validate: null pointer");
+  ADAMVS_CHECK_ARG(count != loop && count != succ && count != lab && loop != succ && loop != lab && bad != closed && bad != bnd &&
+                   bad != broken && closed != bnd && closed != broken, "clean_validate: aliased buffers");
+  return launch_clean_validate(bnd, succ, lab, broken, 3 * ns, max_hole_edges, count, bad, loop, closed, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_clean_accumulate(const double* p, const unsigned char* rgb, long nv, const unsigned* faces, long ns, const int* members,
+                                       long nm, const long long* start, long nl, const double* origin, double* centre,
+                                       unsigned char* colour, void* stream) {
+  if (int rc = smooth_check_counts(nv, ns, "clean_accumulate")) return rc;
+  ADAMVS_CHECK_ARG(nl >= 1 && nl <= ns, "clean_accumulate: nl=%ld (1 .. ns = %ld)", nl, ns);
+  ADAMVS_CHECK_ARG(nm >= 3 * nl && nm <= 3 * ns, "clean_accumulate: nm=%ld members (3 nl = %ld .. 3 ns = %ld)", nm, 3 * nl, 3 * ns);
+  ADAMVS_CHECK_ARG(p && rgb && faces && members && start && origin && centre && colour, "clean_accumulate: null pointer");
+  ADAMVS_CHECK_ARG(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]), "clean_accumulate: the origin is not finite");
+  ADAMVS_CHECK_ARG(p != centre && rgb != colour, "clean_accumulate: aliased buffers");
+  return launch_clean_accumulate(p, rgb, nv, faces, ns, members, start, nl, nm, origin, centre, colour, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_clean_emit(const double* xyz, const unsigned char* rgb, long nv, const int* new_index, const unsigned* faces, long ns,
+                                 const int* fill_edge, const int* loop_of, long nfill, const double* centre, const unsigned char* colour,
+                                 long nl, long nvs, double* xyz_out, unsigned char* rgb_out, unsigned* faces_out, void* stream) {
+  if (int rc = smooth_check_counts(nv, ns, "clean_emit")) return rc;
+  ADAMVS_CHECK_ARG(nvs >= 1 && nvs <= nv, "clean_emit: nvs=%ld (1 .. nv = %ld)", nvs, nv);
+  ADAMVS_CHECK_ARG(nl >= 0 && nl <= ns && nfill >= 0 && nfill <= 3 * ns && (nl == 0) == (nfill == 0) && nfill >= 3 * nl,
+                   "clean_emit: nl=%ld loops, nfill=%ld fill faces", nl, nfill);
+  ADAMVS_CHECK_ARG(nvs + nl <= SIMPLIFY_MAX && ns + nfill <= SMOOTH_MAX_FACES, "clean_emit: the output exceeds 2^31 - 1 vertices or (2^31 - 1) / 3 faces");
+  ADAMVS_CHECK_ARG(xyz && rgb && new_index && faces && xyz_out && rgb_out && faces_out, "clean_emit: null pointer");
+  ADAMVS_CHECK_ARG(nl == 0 || (fill_edge && loop_of && centre && colour), "clean_emit: null fill input");
+  ADAMVS_CHECK_ARG(xyz != xyz_out && rgb != rgb_out && faces != faces_out && centre != xyz_out && colour != rgb_out, "clean_emit: aliased buffers");
+  return launch_clean_emit(xyz, rgb, nv, new_index, faces, ns, fill_edge, loop_of, nfill, centre, colour, nl, nvs, xyz_out, rgb_out, faces_out,
+                           (hipStream_t)stream);
+}
+
 // ---- cloud distance (cloud_dist.hip): every argument is checked here, before any launch
 extern "C" int adamvs_cloud_nearest(const double* origin, double D, const long long* ukeys, const long long* tstart, int nc,
                                     const double* targets, const int* tindex, long nt, const double* queries, long nq,

@@ -207,6 +207,24 @@ int launch_smooth_centroids(const double* p, long nv, const unsigned* faces, lon
 int launch_smooth_update(const double* p0, const double* p, double* pout, long nv, const double* nrm, const double* cen, long nf,
                          const int* vface, const long long* vstart, const uint8_t* fixed, double cap, uint8_t* clamped, hipStream_t st);
 
+// mesh_clean.hip: small components dropped, small holes closed (include/adamvs_hip.h, "Mesh cleaning")
+constexpr int CLEAN_TILE = ADAMVS_CLEAN_TILE;
+constexpr int CLEAN_CHUNK = ADAMVS_CLEAN_CHUNK;
+int launch_clean_components(const unsigned* faces, long nf, long nv, const int* parent_in, int* parent_out, unsigned* changed, hipStream_t st);
+int launch_clean_area(const double* area, long nf, const long long* order, const long long* seg_of, const long long* seg_start, long ncomp,
+                      double* lead, double* first, double* out, hipStream_t st);
+int launch_clean_boundary(const long long* keys, const long long* entry, long n, uint8_t* bnd, hipStream_t st);
+int launch_clean_successor(const unsigned* faces, long ns, long nv, const uint8_t* bnd, int* out_cnt, int* in_cnt, int* out_he, int* succ,
+                           int* lab, int* nxt, uint8_t* broken, hipStream_t st);
+int launch_clean_double(const uint8_t* bnd, long n, const int* lab_in, const int* nxt_in, const uint8_t* broken_in, int* lab_out, int* nxt_out,
+                        uint8_t* broken_out, hipStream_t st);
+int launch_clean_validate(const uint8_t* bnd, const int* succ, const int* lab, const uint8_t* broken, long n, int M, int* cnt, uint8_t* bad,
+                          int* loop, uint8_t* closed, hipStream_t st);
+int launch_clean_accumulate(const double* p, const uint8_t* rgb, long nv, const unsigned* faces, long ns, const int* members,
+                            const long long* start, long nl, long nm, const double* origin, double* centre, uint8_t* colour, hipStream_t st);
+int launch_clean_emit(const double* xyz, const uint8_t* rgb, long nv, const int* new_index, const unsigned* faces, long ns, const int* fill_h,
+                      const int* loop_of, long nfill, const double* centre, const uint8_t* colour, long nl, long nvs, double* xyz_out,
+                      uint8_t* rgb_out, unsigned* faces_out, hipStream_t st);
 
 // cloud_dist.hip: bounded nearest neighbour between two clouds and the surface sampler (include/adamvs_hip.h, "Cloud distance")
 constexpr int CLOUD_TILE = ADAMVS_CLOUD_TILE;

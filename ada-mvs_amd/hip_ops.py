@@ -1044,6 +1044,157 @@ def smooth_update(p0, p, normals, cen, vface, vstart, fixed, cap, out=None, clam
     return pout, cl
 
 
+# ---- mesh cleaning (csrc/mesh_clean.hip; driven by ada_mvs_amd/clean.py) -----------------------------------------------------
+# faces int32 = uint32 [ns, 3]; half-edge arrays have 3 ns entries; labels and successors int32, flags uint8.
+def _clean_faces(faces, name="faces"):
+    faces = _dev_as(faces, name, torch.int32)
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise _lib.AdaMVSHipError("%s [ns >= 1, 3]: got %s" % (name, tuple(faces.shape)))
+    return faces
+
+
+def _clean_len(what, n, *named):
+    """Every (name, tensor, dtype) is a contiguous device tensor of n elements -> the tensors."""
+    out = []
+    for name, t, dtype in named:
+        t = _dev_as(t, name, dtype)
+        if t.numel() != n:
+            raise _lib.AdaMVSHipError("%s: %s has %d elements, not %d" % (what, name, t.numel(), n))
+        out.append(t)
+    return out
+
+
+def clean_components_round(faces, parent_in, parent_out, changed):
+    """adamvs_clean_components: one hook + compress round.  parent_in [nv] int32 -> parent_out [nv] (another buffer); changed [1]
+    int32 is set to whether a hook happened."""
+    faces = _clean_faces(faces)
+    parent_in, parent_out = _clean_len("clean_components", parent_in.numel(), ("parent_in", parent_in, torch.int32),
+                                       ("parent_out", parent_out, torch.int32))
+    changed, = _clean_len("clean_components", 1, ("changed", changed, torch.int32))
+    check(_lib.load().adamvs_clean_components(_p(faces), faces.shape[0], parent_in.numel(), _p(parent_in), _p(parent_out), _p(changed),
+                                              _stream()), "clean_components")
+    return parent_out
+
+
+def clean_area(area, order, seg_of, seg_start):
+    """adamvs_clean_area.  area [nf] float64; order [nf] int64: the faces sorted stably by label; seg_of [nf] int64: the rank of the
+    component at each sorted position; seg_start [ncomp + 1] int64 -> the components' areas [ncomp] float64."""
+    nf = area.numel()
+    area, order, seg_of = _clean_len("clean_area", nf, ("area", area, torch.float64), ("order", order, torch.int64),
+                                     ("seg_of", seg_of, torch.int64))
+    seg_start = _dev_as(seg_start, "seg_start", torch.int64)
+    ncomp = seg_start.numel() - 1
+    lead = torch.zeros((nf + _lib.CLEAN_CHUNK - 1) // _lib.CLEAN_CHUNK, device=area.device, dtype=torch.float64)
+    first = torch.zeros(max(ncomp, 1), device=area.device, dtype=torch.float64)
+    out = torch.empty(max(ncomp, 1), device=area.device, dtype=torch.float64)
+    check(_lib.load().adamvs_clean_area(_p(area), nf, _p(order), _p(seg_of), _p(seg_start), ncomp, _p(lead), _p(first), _p(out), _stream()),
+          "clean_area")
+    return out[:ncomp]
+
+
+def clean_boundary(faces):
+    """adamvs_smooth_edge_keys, a stable sort of the keys, adamvs_clean_boundary -> bnd [3 ns] uint8: the half-edges whose key occurs once."""
+    faces = _clean_faces(faces)
+    ns = faces.shape[0]
+    keys = torch.empty(3 * ns, device=faces.device, dtype=torch.int64)
+    bnd = torch.empty(3 * ns, device=faces.device, dtype=torch.uint8)
+    lib, st = _lib.load(), _stream()
+    check(lib.adamvs_smooth_edge_keys(_p(faces), ns, _p(keys), st), "smooth_edge_keys")
+    es = torch.sort(keys, stable=True)
+    ks, entry = es.values.contiguous(), es.indices.contiguous()
+    check(lib.adamvs_clean_boundary(_p(ks), _p(entry), ns, _p(bnd), st), "clean_boundary")
+    return bnd
+
+
+def clean_successor(faces, nv, bnd):
+    """adamvs_clean_successor -> dict: out_count, in_count, out_edge [nv] int32; succ, lab, nxt [3 ns] int32; broken [3 ns] uint8."""
+    faces = _clean_faces(faces)
+    ns, nv, dev = faces.shape[0], int(nv), faces.device
+    bnd, = _clean_len("clean_successor", 3 * ns, ("bnd", bnd, torch.uint8))
+    r = dict(out_count=torch.empty(nv, device=dev, dtype=torch.int32), in_count=torch.empty(nv, device=dev, dtype=torch.int32),
+             out_edge=torch.empty(nv, device=dev, dtype=torch.int32), succ=torch.empty(3 * ns, device=dev, dtype=torch.int32),
+             lab=torch.empty(3 * ns, device=dev, dtype=torch.int32), nxt=torch.empty(3 * ns, device=dev, dtype=torch.int32),
+             broken=torch.empty(3 * ns, device=dev, dtype=torch.uint8))
+    check(_lib.load().adamvs_clean_successor(_p(faces), ns, nv, _p(bnd), _p(r["out_count"]), _p(r["in_count"]), _p(r["out_edge"]), _p(r["succ"]),
+                                             _p(r["lab"]), _p(r["nxt"]), _p(r["broken"]), _stream()), "clean_successor")
+    return r
+
+
+def clean_double(bnd, state_in, state_out):
+    """adamvs_clean_double: one doubling round.  state_* = (lab int32, nxt int32, broken uint8), each [3 ns]; both states were
+    initialised from clean_successor's output.  -> state_out."""
+    n = bnd.numel()
+    if n % 3 or n < 3:
+        raise _lib.AdaMVSHipError("clean_double: %d half-edges is no multiple of 3" % n)
+    bnd, = _clean_len("clean_double", n, ("bnd", bnd, torch.uint8))
+    names = (("lab", torch.int32), ("nxt", torch.int32), ("broken", torch.uint8))
+    a = _clean_len("clean_double", n, *[(k + "_in", t, d) for (k, d), t in zip(names, state_in)])
+    b = _clean_len("clean_double", n, *[(k + "_out", t, d) for (k, d), t in zip(names, state_out)])
+    check(_lib.load().adamvs_clean_double(_p(bnd), n // 3, _p(a[0]), _p(a[1]), _p(a[2]), _p(b[0]), _p(b[1]), _p(b[2]), _stream()), "clean_double")
+    return tuple(b)
+
+
+def clean_validate(bnd, succ, lab, broken, max_hole_edges):
+    """adamvs_clean_validate -> (count [3 ns] int32: the size of each label group at its label, bad [3 ns] uint8, loop [3 ns] int32:
+    the label of each half-edge's loop or -1, closed [3 ns] uint8)."""
+    n = bnd.numel()
+    if n % 3 or n < 3:
+        raise _lib.AdaMVSHipError("clean_validate: %d half-edges is no multiple of 3" % n)
+    bnd, succ, lab, broken = _clean_len("clean_validate", n, ("bnd", bnd, torch.uint8), ("succ", succ, torch.int32), ("lab", lab, torch.int32),
+                                        ("broken", broken, torch.uint8))
+    dev = bnd.device
+    count, bad = torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.uint8)
+    loop, closed = torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev, dtype=torch.uint8)
+    check(_lib.load().adamvs_clean_validate(_p(bnd), _p(succ), _p(lab), _p(broken), n // 3, int(max_hole_edges), _p(count), _p(bad), _p(loop),
+                                            _p(closed), _stream()), "clean_validate")
+    return count, bad, loop, closed
+
+
+def clean_accumulate(p, rgb, faces, members, start, origin):
+    """adamvs_clean_accumulate.  p [nv, 3] float64 (relative to origin), rgb [nv, 3] uint8, members [nm] int32 (the closed half-edges
+    by loop, ascending within a loop), start [nl + 1] int64 -> (centre [nl, 3] float64 world, colour [nl, 3] uint8)."""
+    p, faces = _smooth_mesh(p, _clean_faces(faces))
+    rgb = _dev_as(rgb, "rgb", torch.uint8)
+    members, start = _dev_as(members, "members", torch.int32), _dev_as(start, "start", torch.int64)
+    if tuple(rgb.shape) != tuple(p.shape) or start.numel() < 2:
+        raise _lib.AdaMVSHipError("clean_accumulate: p %s, rgb %s, start %d" % (tuple(p.shape), tuple(rgb.shape), start.numel()))
+    nl = start.numel() - 1
+    keep, o, _ = _lattice(origin, 1.0)
+    centre = torch.empty(nl, 3, device=p.device, dtype=torch.float64)
+    colour = torch.empty(nl, 3, device=p.device, dtype=torch.uint8)
+    check(_lib.load().adamvs_clean_accumulate(_p(p), _p(rgb), p.shape[0], _p(faces), faces.shape[0], _p(members), members.numel(), _p(start), nl,
+                                              o, _p(centre), _p(colour), _stream()), "clean_accumulate")
+    return centre, colour
+
+
+def clean_emit(xyz, rgb, new_index, nvs, faces, fill_edge=None, loop_of=None, centre=None, colour=None):
+    """adamvs_clean_emit.  xyz [nv, 3] float64, rgb [nv, 3] uint8, new_index [nv] int32 (-1: unused; nvs used), faces [ns, 3] and,
+    where loops are closed, fill_edge, loop_of [nfill] int32, centre [nl, 3] float64, colour [nl, 3] uint8
+    -> (xyz [nvs + nl, 3], rgb [nvs + nl, 3], faces [ns + nfill, 3] int32)."""
+    xyz, faces = _smooth_mesh(xyz, _clean_faces(faces))
+    rgb = _dev_as(rgb, "rgb", torch.uint8)
+    nv, ns, dev = xyz.shape[0], faces.shape[0], xyz.device
+    new_index, = _clean_len("clean_emit", nv, ("new_index", new_index, torch.int32))
+    if tuple(rgb.shape) != tuple(xyz.shape):
+        raise _lib.AdaMVSHipError("clean_emit: xyz %s, rgb %s" % (tuple(xyz.shape), tuple(rgb.shape)))
+    nfill = 0 if fill_edge is None else fill_edge.numel()
+    nl = 0 if centre is None else centre.shape[0]
+    null = ctypes.c_void_p(0)
+    fe = lo = ce = co = null
+    if nfill or nl:
+        fill_edge, loop_of = _clean_len("clean_emit", nfill, ("fill_edge", fill_edge, torch.int32), ("loop_of", loop_of, torch.int32))
+        centre, = _clean_len("clean_emit", 3 * nl, ("centre", centre, torch.float64))
+        colour, = _clean_len("clean_emit", 3 * nl, ("colour", colour, torch.uint8))
+        fe, lo, ce, co = _p(fill_edge), _p(loop_of), _p(centre), _p(colour)
+    nvs = int(nvs)
+    xyz_out = torch.empty(max(nvs, 0) + nl, 3, device=dev, dtype=torch.float64)
+    rgb_out = torch.empty(max(nvs, 0) + nl, 3, device=dev, dtype=torch.uint8)
+    faces_out = torch.empty(ns + nfill, 3, device=dev, dtype=torch.int32)
+    check(_lib.load().adamvs_clean_emit(_p(xyz), _p(rgb), nv, _p(new_index), _p(faces), ns, fe, lo, nfill, ce, co, nl, nvs, _p(xyz_out),
+                                        _p(rgb_out), _p(faces_out), _stream()), "clean_emit")
+    return xyz_out, rgb_out, faces_out
+
+
 # ---- image orthophoto (csrc/ortho.hip; driven view by view by ada_mvs_amd/ortho.py) ------------------------------------------
 # The depth buffer is int32 holding uint32 float bits; acc is float32 [N, 4]; view and nvis int32; nvis_out int16 (uint16).
 def ortho_grid(x0, y_top, gsd, W, H, K):

@@ -12,7 +12,7 @@ integrates the depth maps (`<vid>/<name>_fused.pfm`, or `_init.pfm` with --depth
 (include/adamvs_hip.h "TSDF mesh" states every operation).  The mesh is streamed to a binary little-endian PLY (vertices
 double x y z, uchar red green blue as fuse_whu.py writes them; faces list uchar uint vertex_indices): vertices are written in
 place, faces spooled to a temporary file next to the output and appended at the end, and both counts are patched in.
-`<out>.json` records the volume, the counts and the timings.
+`<out>.json` records the volume, the counts and the timings.  clean_whu.py (ada_mvs_amd/clean.py) is the step after this one.
 
 Seam vertices between bricks are written by each brick that uses them, at bit-identical coordinates; --weld merges them by
 exact position on the GPU (it holds the whole mesh on the device).  Precision: camera-frame arithmetic is fp32 relative to the

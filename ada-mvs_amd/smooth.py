@@ -4,7 +4,8 @@
                          [--sigma_r 0.35] [--normal_iters 10] [--vertex_iters 10] [--max_move M | --max_move_voxels 1]
                          [--no_fix_boundary] [--origin X Y Z] [--out <mesh minus .ply>_smoothed.ply]
 
-The step after mesh_whu.py and before simplify_whu.py.  The zero level set of a TSDF built from predicted depth carries the
+The step after mesh_whu.py and before simplify_whu.py (clean_whu.py, ada_mvs_amd/clean.py, goes in front of it: it drops
+floaters and closes the pinholes whose rims this step would pin).  The zero level set of a TSDF built from predicted depth carries the
 voxel lattice's staircase and the depth noise the truncation band did not average out.  Here every face normal becomes the
 weighted mean of the normals of the faces around it, weighted by area, by the distance between the centroids (sigma_s) and by
 the difference between the normals (sigma_r): across a crease the last weight vanishes, so flat ground and roofs flatten and

@@ -850,6 +850,100 @@ int adamvs_smooth_update(const double* p0, const double* p, double* pout, long n
                          const int* vface, const long long* vstart, const unsigned char* fixed, double cap, unsigned char* clamped,
                          void* stream);
 
+/* ---- Mesh cleaning (after mesh_whu.py, before smooth_whu.py): small components dropped, small holes closed --------------------
+ * ada-mvs_amd/clean.py drives it; clean_whu.py is the CLI.  The zero level set of a TSDF built from predicted depth carries
+ * FLOATERS (small blobs where a few consistent but wrong depths were fused) and PINHOLES (small loops of open edges where a
+ * few voxels missed the weight threshold).  This step removes the first and closes the second; it moves no vertex.
+ *
+ * Inputs: vertices xyz [nv][3] fp64 world, rgb [nv][3] uint8, faces [nf][3] uint32, the origin O (fp64: the volume origin of
+ * <mesh>.json, else the per-axis vertex minimum), min_faces >= 0, an optional min_area > 0 (square metres) and
+ * max_hole_edges M in 0 .. ADAMVS_CLEAN_MAX_HOLE_EDGES.  fp64 without contraction; the divisions and sqrt round correctly.
+ *
+ * 1. Weld by exact position (mesh.py weld), always; positions p = xyz - O.  A vertex that is not finite is an error.
+ * 2. Degenerate faces (two equal corner indices after the weld) are dropped; the rest keep their order.  nf counts the rest.
+ * 3. Components.  Two faces are connected when they share a welded vertex; the LABEL of a component is the smallest welded
+ *    vertex index in it.  Rounds over a label per vertex, parent[v] = v at first.  One round: with the previous round's labels
+ *    r = parent[corner] of a face and m the smallest of the three, every r != m is hooked, parent'[r] = min(parent'[r], m)
+ *    (parent' starts as a copy of parent; r is a root, and an integer minimum does not depend on the order, so a round's
+ *    result is a function of its input); then every vertex is given the root of its tree (parent'[v] followed until it stops
+ *    changing).  The rounds end with the first that hooks nothing; the labels are then the unique fixed point.  A face's
+ *    label is that of its corner 0.  Per component: its face count and its AREA.  A face's area is A = |u x w| / 2 of
+ *    _smooth_faces (on p).  With the faces sorted STABLY by label (so ascending face number within a component) and that
+ *    sorted sequence cut into chunks of ADAMVS_CLEAN_CHUNK consecutive positions, a component's PIECES are its runs inside the
+ *    chunks it meets; a piece is summed from zero in ascending position, and the area of the component is its first piece plus
+ *    the others, added one by one in ascending position.  (A component of fewer faces than one chunk that lies inside one
+ *    chunk is therefore the plain sum in ascending face number.)  A component is KEPT iff faces >= min_faces and, where
+ *    min_area is given, area >= min_area.
+ * 4. The faces of kept components are the SURVIVING faces, s = 0 .. ns - 1 in input order.  Half-edge h = 3 s + k runs from
+ *    corner k (its TAIL) to corner (k + 1) % 3 (its HEAD) of surviving face s.
+ * 5. Boundary.  h is a BOUNDARY half-edge iff its key min << 32 | max occurs exactly once among the 3 ns keys (three or more
+ *    times: not boundary).  A vertex is SIMPLE iff exactly one boundary half-edge leaves it and exactly one enters it.
+ *    succ(h), for a boundary half-edge whose head is simple, is the boundary half-edge leaving head(h); else it is undefined.
+ * 6. Loops.  A LOOP is a cycle of succ all of whose vertices are simple; its label is its smallest h, its length L its number
+ *    of half-edges.  A loop is CLOSED iff 3 <= L <= M.  A chain that meets a vertex that is not simple (two holes pinched at a
+ *    vertex, a hole next to an edge of three faces) belongs to no loop and stays open.  Computed by pointer doubling,
+ *    double-buffered, from lab = h, nxt = succ(h) (or h itself where undefined), broken = (succ undefined):
+ *      lab'[h] = min(lab[h], lab[nxt[h]]),  broken'[h] = broken[h] | broken[nxt[h]],  nxt'[h] = nxt[nxt[h]].
+ *    After R rounds lab[h] is the minimum over the 2^R half-edges from h on.  With fewer rounds than the longest cycle needs
+ *    the labels on it are window minima, and a group of equal labels can be short by accident; so whatever R, a label group
+ *    is a loop only if none of its members is broken and EVERY member satisfies lab[h] == lab[succ(h)] with the original
+ *    succ: the group is then closed under an injective map, so it is a union of cycles, and as each of them contains the
+ *    group's label it is one cycle.  clean.py runs R = ceil(log2(boundary half-edges)) + 1 rounds, which labels every cycle
+ *    whole, so that the loops longer than M can be counted.
+ * 7. Fill, for every closed loop in ascending label: one new vertex at O + s / L, s the sum of p[tail(h)] over the loop's
+ *    half-edges in ascending h from zero (each axis on its own); its colour per channel floor(c / L + 0.5), c the integer sum
+ *    of the tails' channel; and for every half-edge a -> b of the loop one new face (b, a, centre), so that the shared edge
+ *    runs the other way in the new face and the orientation of the mesh carries over.
+ * 8. Output.  Vertices: the welded vertices that a surviving face uses, in welded order, with the bits of their input position
+ *    and their colour, then the fill vertices by loop label.  Faces: the surviving faces in input order, then the fill faces
+ *    in ascending h.  Where fill vertices were added clean.py welds this output once more, which only moves them to their
+ *    places in the lexicographic order (and merges one that lands exactly on an existing vertex into it, keeping that vertex's
+ *    colour): the weld of the next step then changes nothing, and cleaning a cleaned mesh returns it bit for bit.
+ *
+ * Calls, in stream order; the sorts, scans and compactions between them are the caller's.  The only atomics are integer
+ * atomicMin and atomicAdd on values that do not depend on the order; there is no floating-point atomic, so the output is
+ * bit-identical from run to run.  Workgroups cover ADAMVS_CLEAN_TILE consecutive elements, one lane each.
+ *   _clean_components  one round of step 3: parent_in [nv] int32 -> parent_out [nv] (distinct), changed [1] = whether a hook
+ *                      happened.  Before the first round parent_in[v] = v;
+ *   _clean_area        area [nf] fp64; order [nf] int64: the faces sorted stably by label; seg_of [nf] int64: the rank of the
+ *                      component at each sorted position; seg_start [ncomp + 1] int64; lead [ceil(nf / CHUNK)] and
+ *                      first [ncomp] fp64 scratch -> out [ncomp] fp64;
+ *   _clean_boundary    keys_sorted, entry [3 ns] int64 (entry: the half-edge of each sorted key) -> bnd [3 ns] uint8, all written;
+ *   _clean_successor   -> out_count, in_count [nv] int32, out_edge [nv] int32 (the smallest boundary half-edge leaving the
+ *                      vertex, 2^31 - 1 if none), succ [3 ns] int32 (-1: undefined or off the boundary), and the initial lab,
+ *                      nxt [3 ns] int32 and broken [3 ns] uint8 of step 6 (off the boundary: lab = nxt = h, broken = 1);
+ *   _clean_double      one round of step 6.  Entries off the boundary are skipped: the caller initialises BOTH buffers of
+ *                      lab, nxt and broken with _clean_successor's output;
+ *   _clean_validate    count [3 ns] int32 (the size of each label group, at its label), bad [3 ns] uint8 -> loop [3 ns] int32
+ *                      (the label of h's loop, -1 where h is in none), closed [3 ns] uint8;
+ *   _clean_accumulate  members [nm] int32: the closed half-edges sorted stably by loop label (ascending h within a loop),
+ *                      start [nl + 1] int64, origin: 3 fp64 on the HOST -> centre [nl][3] fp64 (world), colour [nl][3] uint8;
+ *   _clean_emit        new_index [nv] int32 (-1: unused), fill_edge [nfill] int32 (the closed half-edges ascending),
+ *                      loop_of [nfill] int32 (the rank of each one's loop) -> xyz_out, rgb_out [nvs + nl][3], faces_out
+ *                      [ns + nfill][3] uint32.
+ * Argument errors (<0, before any launch): a null pointer, nv < 1 or > 2^31 - 1, ns (nf) < 1 or > (2^31 - 1) / 3, ncomp, nl, nm,
+ * nfill or nvs out of range, M outside 0 .. ADAMVS_CLEAN_MAX_HOLE_EDGES, an origin that is not finite, aliased buffers. */
+#define ADAMVS_CLEAN_TILE 256
+#define ADAMVS_CLEAN_CHUNK 1024
+#define ADAMVS_CLEAN_MAX_HOLE_EDGES 4096
+#define ADAMVS_CLEAN_MAX_ROUNDS 64
+
+int adamvs_clean_components(const unsigned* faces, long nf, long nv, const int* parent_in, int* parent_out, unsigned* changed, void* stream);
+int adamvs_clean_area(const double* area, long nf, const long long* order, const long long* seg_of, const long long* seg_start, long ncomp,
+                      double* lead, double* first, double* out, void* stream);
+int adamvs_clean_boundary(const long long* keys_sorted, const long long* entry, long ns, unsigned char* bnd, void* stream);
+int adamvs_clean_successor(const unsigned* faces, long ns, long nv, const unsigned char* bnd, int* out_count, int* in_count, int* out_edge,
+                           int* succ, int* lab, int* nxt, unsigned char* broken, void* stream);
+int adamvs_clean_double(const unsigned char* bnd, long ns, const int* lab_in, const int* nxt_in, const unsigned char* broken_in, int* lab_out,
+                        int* nxt_out, unsigned char* broken_out, void* stream);
+int adamvs_clean_validate(const unsigned char* bnd, const int* succ, const int* lab, const unsigned char* broken, long ns, int max_hole_edges,
+                          int* count, unsigned char* bad, int* loop, unsigned char* closed, void* stream);
+int adamvs_clean_accumulate(const double* p, const unsigned char* rgb, long nv, const unsigned* faces, long ns, const int* members, long nm,
+                            const long long* start, long nl, const double* origin, double* centre, unsigned char* colour, void* stream);
+int adamvs_clean_emit(const double* xyz, const unsigned char* rgb, long nv, const int* new_index, const unsigned* faces, long ns,
+                      const int* fill_edge, const int* loop_of, long nfill, const double* centre, const unsigned char* colour, long nl, long nvs,
+                      double* xyz_out, unsigned char* rgb_out, unsigned* faces_out, void* stream);
+
 /* ---- Cloud distance (scoring a cloud or a mesh against a truth): bounded nearest neighbour and a surface sampler ---------------
  * ada-mvs_amd/accuracy.py drives it; accuracy_whu.py is the CLI.  Accuracy is the distance from every point of a reconstruction
  * to its nearest point of the truth, completeness the same the other way round (the DTU and Tanks-and-Temples measures); both
