@@ -238,6 +238,15 @@ SIGNATURES = {
                                         c_st]),
     "adamvs_cloud_sample_emit": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_long, c_st]),
+    "adamvs_knn_search": (c_i, [ctypes.POINTER(ctypes.c_double), ctypes.c_double, c_i, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p,
+                                ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
+                                ctypes.c_longlong, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_knn_search_host": (c_i, [ctypes.POINTER(ctypes.c_double), ctypes.c_double, c_i, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "adamvs_knn_normals": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_long, ctypes.c_void_p,
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_knn_normals_host": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_long, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "adamvs_ortho_surface": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.c_void_p, c_st]),
     "adamvs_ortho_zbuf": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.POINTER(OrthoView), ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_void_p, ctypes.c_long, c_st]),
@@ -300,6 +309,9 @@ CLEAN_MAX_HOLE_EDGES = 4096      # ADAMVS_CLEAN_MAX_HOLE_EDGES
 CLEAN_MAX_ROUNDS = 64            # ADAMVS_CLEAN_MAX_ROUNDS: cap on the rounds of the component labels
 CLOUD_TILE = 256                 # ADAMVS_CLOUD_TILE: queries per work item and candidates per tile of the cloud distance
 CLOUD_MAX_SUBDIV = 1024          # ADAMVS_CLOUD_MAX_SUBDIV: largest n of a face of the surface sampler
+KNN_MAX_K = 32                   # ADAMVS_KNN_MAX_K: largest k of the cloud neighbourhoods
+KNN_RANK_EPS = 1e-12             # ADAMVS_KNN_RANK_EPS: a neighbourhood with lambda1 <= eps lambda2 is collinear
+KNN_VALID, KNN_TOO_FEW, KNN_COLLINEAR = 0, 1, 2    # ADAMVS_KNN_VALID / _TOO_FEW / _COLLINEAR: the flag of a normal
 ORTHO_BEST, ORTHO_FEATHER = 0, 1 # ADAMVS_ORTHO_BEST / ADAMVS_ORTHO_FEATHER
 ORTHO_MAX_CELLS = 1 << 28        # ADAMVS_ORTHO_MAX_CELLS
 ORTHO_MAX_UPSAMPLE = 8           # ADAMVS_ORTHO_MAX_UPSAMPLE

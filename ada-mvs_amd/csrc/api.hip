@@ -836,6 +836,57 @@ extern "C" int adamvs_cloud_sample_emit(const double* xyz, long nv, const unsign
   return launch_cloud_sample_emit(xyz, nv, faces, nf, subdiv, offsets, points, capacity, (hipStream_t)stream);
 }
 
+// ---- cloud neighbourhoods (cloud_knn.hip): every argument is checked here, before any launch
+static int knn_check_k(int k, const char* what) {
+  ADAMVS_CHECK_ARG(k >= 1 && k <= ADAMVS_KNN_MAX_K, "%s: k=%d (1 .. %d)", what, k, ADAMVS_KNN_MAX_K);
+  return 0;
+}
+
+extern "C" int adamvs_knn_search(const double* origin, double R, int k, const long long* ukeys, const long long* tstart, int nc,
+                                 const double* sorted, const int* pindex, long n, const long long* item_key, const long long* item_first,
+                                 const int* item_count, long ni, long long row_base, long rows, float* d2, int* index, int* count,
+                                 unsigned long long* pairs, void* stream) {
+  if (int rc = simplify_check_lattice(origin, R, "knn_search")) return rc;
+  if (int rc = knn_check_k(k, "knn_search")) return rc;
+  if (int rc = simplify_check_count(n, "n", "knn_search")) return rc;
+  if (int rc = simplify_check_count(ni, "ni", "knn_search")) return rc;
+  if (int rc = simplify_check_count(rows, "rows", "knn_search")) return rc;
+  ADAMVS_CHECK_ARG(nc >= 1 && nc <= n, "knn_search: nc=%d (1 .. n = %ld)", nc, n);
+  ADAMVS_CHECK_ARG(ni <= n && rows <= n && row_base >= 0 && row_base <= n - rows, "knn_search: ni=%ld, rows=%ld from row_base=%lld (within n = %ld)",
+                   ni, rows, row_base, n);
+  ADAMVS_CHECK_ARG(ukeys && tstart && sorted && pindex && item_key && item_first && item_count && d2 && index && count && pairs,
+                   "knn_search: null pointer");
+  return launch_knn_search(origin, R, k, ukeys, tstart, nc, sorted, pindex, n, item_key, item_first, item_count, ni, row_base, rows, d2, index,
+                           count, pairs, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_knn_search_host(const double* origin, double R, int k, const double* points, long n, float* d2, int* index, int* count,
+                                      unsigned long long* pairs) {
+  if (int rc = simplify_check_lattice(origin, R, "knn_search_host")) return rc;
+  if (int rc = knn_check_k(k, "knn_search_host")) return rc;
+  if (int rc = simplify_check_count(n, "n", "knn_search_host")) return rc;
+  ADAMVS_CHECK_ARG(points && d2 && index && count, "knn_search_host: null pointer");
+  return knn_search_host(origin, R, k, points, n, d2, index, count, pairs);
+}
+
+extern "C" int adamvs_knn_normals(const double* points, long n, const int* index, const int* count, int k, long rows, const int* row_point,
+                                  double* normal, float* curvature, unsigned char* flag, void* stream) {
+  if (int rc = knn_check_k(k, "knn_normals")) return rc;
+  if (int rc = simplify_check_count(n, "n", "knn_normals")) return rc;
+  if (int rc = simplify_check_count(rows, "rows", "knn_normals")) return rc;
+  ADAMVS_CHECK_ARG(points && index && count && normal && curvature && flag, "knn_normals: null pointer");
+  return launch_knn_normals(points, n, index, count, k, rows, row_point, normal, curvature, flag, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_knn_normals_host(const double* points, long n, const int* index, const int* count, int k, long rows, const int* row_point,
+                                       double* normal, float* curvature, unsigned char* flag) {
+  if (int rc = knn_check_k(k, "knn_normals_host")) return rc;
+  if (int rc = simplify_check_count(n, "n", "knn_normals_host")) return rc;
+  if (int rc = simplify_check_count(rows, "rows", "knn_normals_host")) return rc;
+  ADAMVS_CHECK_ARG(points && index && count && normal && curvature && flag, "knn_normals_host: null pointer");
+  return knn_normals_host(points, n, index, count, k, rows, row_point, normal, curvature, flag);
+}
+
 // ---- image orthophoto (ortho.hip): every argument is checked here, before any launch
 static int ortho_check_grid(const adamvs_ortho_grid* g, const char* what) {
   ADAMVS_CHECK_ARG(g, "%s: null grid", what);

@@ -238,6 +238,18 @@ int launch_cloud_sample_count(const double* xyz, long nv, const unsigned* faces,
 int launch_cloud_sample_emit(const double* xyz, long nv, const unsigned* faces, long nf, const int* subdiv, const long long* offsets,
                              double* points, long capacity, hipStream_t st);
 
+// cloud_knn.hip: the k nearest neighbours of every point of a cloud and a normal from them (include/adamvs_hip.h, "Cloud neighbourhoods")
+constexpr int KNN_MAX_K = ADAMVS_KNN_MAX_K;
+int launch_knn_search(const double* origin, double R, int k, const long long* ukeys, const long long* tstart, int nc, const double* sorted,
+                      const int* pindex, long n, const long long* item_key, const long long* item_first, const int* item_count, long ni,
+                      long long row_base, long rows, float* d2, int* index, int* count, unsigned long long* pairs, hipStream_t st);
+int knn_search_host(const double* origin, double R, int k, const double* points, long n, float* d2, int* index, int* count,
+                    unsigned long long* pairs);
+int launch_knn_normals(const double* points, long n, const int* index, const int* count, int k, long rows, const int* row_point,
+                       double* normal, float* curvature, uint8_t* flag, hipStream_t st);
+int knn_normals_host(const double* points, long n, const int* index, const int* count, int k, long rows, const int* row_point, double* normal,
+                     float* curvature, unsigned char* flag);
+
 // ortho.hip: image orthophoto over a DSM, z-buffered per view (include/adamvs_hip.h, "Image orthophoto")
 constexpr int ORTHO_TILE = ADAMVS_ORTHO_TILE;
 constexpr int ORTHO_SMALL_PX = ADAMVS_ORTHO_SMALL_PX;

@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "jacobi.h"
 #include "kernels.h"
 
 // The header states every position as separate roundings: no fused multiply-add anywhere in this file.
@@ -29,7 +30,6 @@ namespace adamvs {
 
 static_assert(SIMPLIFY_TILE == 256, "the ballot / LDS layout below assumes four waves of 64");
 constexpr int KEY_BITS = ADAMVS_SIMPLIFY_KEY_BITS;
-constexpr int JACOBI_SWEEPS = 8;        // a 3x3 is diagonal to fp64 after 5; fixed, so that the loop unrolls fully
 
 struct Lattice {
   double o[3], c;
@@ -141,27 +141,6 @@ __global__ __launch_bounds__(256) void k_simplify_accumulate(const Lattice L, co
 #pragma unroll
     for (int k = 0; k < 3; ++k) member[3 * (size_t)j + k] = s[k], colour[3 * (size_t)j + k] = c[k];
   }
-}
-
-// One Jacobi rotation of the symmetric 3x3 in the plane (p, q), r the third index; columns p and q of V follow.
-__host__ __device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q,
-                                                       double& v1p, double& v1q, double& v2p, double& v2q) {
-  double t = 0.0;
-  if (apq != 0.0) {
-    const double theta = (aqq - app) / (2.0 * apq);
-    t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));        // theta^2 = inf gives t = 0: the rotation is below fp64
-    if (theta < 0.0) t = -t;
-  }
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  app = app - t * apq;
-  aqq = aqq + t * apq;
-  apq = 0.0;
-  const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-  arp = rp, arq = rq;
-  const double a0 = c * v0p - s * v0q, b0 = s * v0p + c * v0q;
-  const double a1 = c * v1p - s * v1q, b1 = s * v1p + c * v1q;
-  const double a2 = c * v2p - s * v2q, b2 = s * v2p + c * v2q;
-  v0p = a0, v0q = b0, v1p = a1, v1q = b1, v2p = a2, v2q = b2;
 }
 
 // Step 4 of the header for one cell: q = {A00 A01 A02 A11 A12 A22, b, sum d^2}, m the members' mean; -> p (relative to the

@@ -960,6 +960,92 @@ def cloud_sample_emit(xyz, faces, subdiv, offsets, total):
     return points[:int(total)]
 
 
+# ---- cloud neighbourhoods (csrc/cloud_knn.hip; driven by ada_mvs_amd/cloud_filter.py) ------------------------------------------
+# keys int64, point numbers int32, d2 float32, index and count int32, pair counts int64 = uint64, normals float64, flags uint8.
+def _knn_k(k):
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= _lib.KNN_MAX_K:
+        raise _lib.AdaMVSHipError("k=%r: an integer 1 .. %d" % (k, _lib.KNN_MAX_K))
+    return k
+
+
+def knn_search(origin, R, k, ukeys, tstart, points_sorted, pindex, item_key, item_first, item_count, row_base, rows):
+    """adamvs_knn_search on the work items given (a contiguous range of them).  ukeys [nc] / tstart [nc + 1] int64, points_sorted
+    [n, 3] float64 with pindex [n] int32 (their numbers in the caller's order), the items (item_key, item_first int64, item_count
+    int32) covering the sorted positions row_base .. row_base + rows -> (d2 [rows, k] float32, +inf padded; index [rows, k] int32,
+    -1 padded; count [rows] int32; pairs [ni] int64), rows in sorted order."""
+    k = _knn_k(k)
+    ukeys, tstart = _dev_as(ukeys, "ukeys", torch.int64), _dev_as(tstart, "tstart", torch.int64)
+    points_sorted, pindex = _dev_as(points_sorted, "points_sorted", torch.float64), _dev_as(pindex, "pindex", torch.int32)
+    item_key, item_first = _dev_as(item_key, "item_key", torch.int64), _dev_as(item_first, "item_first", torch.int64)
+    item_count = _dev_as(item_count, "item_count", torch.int32)
+    nc, n, ni, dev = ukeys.numel(), points_sorted.shape[0], item_key.numel(), points_sorted.device
+    row_base, rows = int(row_base), int(rows)
+    if (points_sorted.dim() != 2 or points_sorted.shape[1] != 3 or tstart.numel() != nc + 1 or pindex.numel() != n or item_first.numel() != ni
+            or item_count.numel() != ni or not (0 <= row_base and 1 <= rows and row_base + rows <= n)):
+        raise _lib.AdaMVSHipError("knn_search: nc %d, n %d, ni %d, rows %d from %d against points %s, tstart %d, pindex %d, item_first %d, "
+                                  "item_count %d" % (nc, n, ni, rows, row_base, tuple(points_sorted.shape), tstart.numel(), pindex.numel(),
+                                                     item_first.numel(), item_count.numel()))
+    keep, o, r = _lattice(origin, R)
+    d2 = torch.full((rows, k), float("inf"), device=dev, dtype=torch.float32)
+    index = torch.full((rows, k), -1, device=dev, dtype=torch.int32)
+    count = torch.zeros(rows, device=dev, dtype=torch.int32)
+    pairs = torch.zeros(ni, device=dev, dtype=torch.int64)
+    check(_lib.load().adamvs_knn_search(o, r, k, _p(ukeys), _p(tstart), nc, _p(points_sorted), _p(pindex), n, _p(item_key), _p(item_first),
+                                        _p(item_count), ni, row_base, rows, _p(d2), _p(index), _p(count), _p(pairs), _stream()),
+          "knn_search")
+    return d2, index, count, pairs
+
+
+def knn_search_host(points, R, k, origin):
+    """adamvs_knn_search_host on a numpy cloud [n, 3] -> (d2 [n, k] float32, index [n, k] int32, count [n] int32, pairs)."""
+    k = _knn_k(k)
+    pts = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    keep, o, r = _lattice(origin, R)
+    n = len(pts)
+    d2, index, count = np.zeros((n, k), np.float32), np.zeros((n, k), np.int32), np.zeros(n, np.int32)
+    pairs = ctypes.c_ulonglong(0)
+    check(_lib.load().adamvs_knn_search_host(o, r, k, pts.ctypes.data, n, d2.ctypes.data, index.ctypes.data, count.ctypes.data,
+                                             ctypes.addressof(pairs)), "knn_search_host")
+    return d2, index, count, int(pairs.value)
+
+
+def knn_normals(points, index, count, row_point=None):
+    """adamvs_knn_normals.  points [n, 3] float64, index [rows, k] int32, count [rows] int32 of knn_search, row_point [rows] int32 (the
+    number of each row's point; None: row r is point r) -> (normal [rows, 3] float64, curvature [rows] float32, flag [rows] uint8)."""
+    points, index, count = _dev_as(points, "points", torch.float64), _dev_as(index, "index", torch.int32), _dev_as(count, "count", torch.int32)
+    if points.dim() != 2 or points.shape[1] != 3 or index.dim() != 2 or count.numel() != index.shape[0]:
+        raise _lib.AdaMVSHipError("knn_normals: points %s, index %s, count %d" % (tuple(points.shape), tuple(index.shape), count.numel()))
+    rows, k = int(index.shape[0]), _knn_k(int(index.shape[1]))
+    if row_point is not None:
+        row_point = _dev_as(row_point, "row_point", torch.int32)
+        if row_point.numel() != rows:
+            raise _lib.AdaMVSHipError("knn_normals: row_point %d against rows %d" % (row_point.numel(), rows))
+    normal = torch.empty(rows, 3, device=points.device, dtype=torch.float64)
+    curvature = torch.empty(rows, device=points.device, dtype=torch.float32)
+    flag = torch.empty(rows, device=points.device, dtype=torch.uint8)
+    check(_lib.load().adamvs_knn_normals(_p(points), points.shape[0], _p(index), _p(count), k, rows, _p(row_point) if row_point is not None else None,
+                                         _p(normal), _p(curvature), _p(flag), _stream()), "knn_normals")
+    return normal, curvature, flag
+
+
+def knn_normals_host(points, index, count, row_point=None):
+    """adamvs_knn_normals_host on numpy arrays -> (normal [rows, 3] float64, curvature [rows] float32, flag [rows] uint8)."""
+    pts = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    index = np.ascontiguousarray(np.asarray(index, np.int32))
+    count = np.ascontiguousarray(np.asarray(count, np.int32).reshape(-1))
+    if index.ndim != 2 or len(count) != len(index):
+        raise _lib.AdaMVSHipError("knn_normals_host: index %s, count %d" % (index.shape, len(count)))
+    rows, k = len(index), _knn_k(int(index.shape[1]))
+    rp = None if row_point is None else np.ascontiguousarray(np.asarray(row_point, np.int32).reshape(-1))
+    if rp is not None and len(rp) != rows:
+        raise _lib.AdaMVSHipError("knn_normals_host: row_point %d against rows %d" % (len(rp), rows))
+    normal, curvature, flag = np.zeros((rows, 3), np.float64), np.zeros(rows, np.float32), np.zeros(rows, np.uint8)
+    check(_lib.load().adamvs_knn_normals_host(pts.ctypes.data, len(pts), index.ctypes.data, count.ctypes.data, k, rows,
+                                              rp.ctypes.data if rp is not None else None, normal.ctypes.data, curvature.ctypes.data,
+                                              flag.ctypes.data), "knn_normals_host")
+    return normal, curvature, flag
+
+
 # ---- mesh smoothing (csrc/mesh_smooth.hip; driven by ada_mvs_amd/smooth.py) ---------------------------------------------------
 # positions are relative to the origin (p = xyz - O); faces int32 = uint32; flags uint8.
 def _smooth_mesh(p, faces):

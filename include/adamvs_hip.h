@@ -1027,6 +1027,89 @@ int adamvs_cloud_sample_count(const double* xyz, long nv, const unsigned* faces,
 int adamvs_cloud_sample_emit(const double* xyz, long nv, const unsigned* faces, long nf, const int* subdiv, const long long* offsets,
                              double* points, long capacity, void* stream);
 
+/* ---- Cloud neighbourhoods (filtering the fused cloud): the k nearest neighbours of every point, and a normal from them --------
+ * ada-mvs_amd/cloud_filter.py drives it; filter_whu.py is the CLI (after fuse_whu.py, before everything that reads the cloud).
+ * Nothing else judges a fused point against the fused points around it: the statistical and the radius outlier rules and the
+ * normals all rest on one search: for every point the k nearest OTHER points within the radius R.
+ *
+ * Inputs: the cloud P [n][3], fp64 world; R > 0 in metres; 1 <= k <= ADAMVS_KNN_MAX_K = 32; the lattice origin O (fp64).
+ *
+ * Steps 1 to 3 are those of "Cloud distance" with D = R, the cloud being both the targets and the queries: the lattice of cell
+ * side c = R (keys by _simplify_keys; a point that is not finite or outside the lattice is an error of the driver), the
+ * candidates of a point from the 27 cells around its own, and d2 in fp32 relative to the centre C of the QUERY's cell
+ * (qf = fp32(q - C), pf = fp32(p - C), e = qf - pf, d2 = (e.x e.x + e.y e.y) + e.z e.z, every operation rounded).  d2 of the pair
+ * (i, j) is taken about the centre of i's cell and d2 of (j, i) about the centre of j's: the two may differ in the last bits.
+ * 4. Choice.  A candidate j of the point i is a NEIGHBOUR iff j != i (another NUMBER: an exact duplicate of p_i at another
+ *    number is a neighbour at d2 = 0) and d2 <= fp32(R R) (the product in fp64, rounded once: the keep rule of "Cloud
+ *    distance").  Of its neighbours the point keeps the k that are least in the lexicographic order (d2, number in the caller's
+ *    order): among equal d2 the lower number comes first, and of two equidistant candidates for the last place the lower number
+ *    stays.  Output per point:  d2 [k] fp32 ascending in that order, padded with +inf;  index [k] int32, padded with -1;
+ *    count int32 = min(k, neighbours).  The result is a function of the cloud as a set.
+ *
+ * Bound.  The arithmetic is that of "Cloud distance", so with d = sqrt(d2):  | d - d_fp64 | <= 1e-6 c  for every kept neighbour.
+ * A candidate within 1e-6 c of R may be counted or not, and two candidates within 2e-6 c of each other may swap places (or, at
+ * the last place, one may stand for the other); nothing else may differ from an fp64 search.
+ *
+ * Calls, in stream order.  The caller sorts the keys STABLY (-> sorted [n][3] fp64, the points gathered, and pindex [n] int32,
+ * their numbers in the caller's order), takes the distinct keys ascending (ukeys [nc] int64) with the start of each cell's run
+ * (tstart [nc + 1] int64, tstart[nc] = n) and cuts every run into WORK ITEMS of at most ADAMVS_CLOUD_TILE points (item_key,
+ * item_first [ni] int64: the cell and the position in the sorted order; item_count [ni] int32), exactly as for _cloud_nearest.
+ *   _knn_search        one workgroup per work item; any contiguous range of the work items may be given to one call (the driver
+ *                      runs a large cloud in such chunks, so that the [n][k] arrays never exist whole).  The point at sorted
+ *                      position s is written at ROW s - row_base of d2 [rows][k], index [rows][k], count [rows]; rows outside
+ *                      [0, rows) are not written, and rows no work item covers are left as they were.  Nine lanes find the nine
+ *                      rows of cells and the candidates pass through an LDS tile as in _cloud_nearest; with P the smallest power
+ *                      of two >= the queries of the pass the lanes form S slices, lane l serving query l mod P on candidates
+ *                      slice, slice + S, ..  Every (query, candidate) pair is evaluated once.  Each lane keeps a list of at most
+ *                      k entries in LDS columns (slot-major, so the lanes of a wave use different banks) and the list's worst
+ *                      (d2, number) in registers: an entry is appended while the list has room, later it replaces the worst,
+ *                      which one scan of the k slots finds again; once the list is full a candidate costs one compare unless it
+ *                      enters.  The S lists of a query meet in a tree under the same order (the lower half takes the upper
+ *                      half's entries), so the split does not show; the final list leaves through ranks: every entry is
+ *                      written at the position given by the number of entries before it.  One kernel per class of k:
+ *                      k <= 8 and k <= 16 with 256 lanes, k <= 32 with 128 lanes (32 KiB of lists each at most; an item
+ *                      of more than 128 queries then walks its candidates twice, for different queries).  pairs [ni] uint64:
+ *                      candidates of the item times its queries.  No atomics, no waits between workgroups: bit-identical
+ *                      from run to run, independent of the chunking, equivariant under any permutation of P;
+ *   _knn_search_host   steps 1 to 4 on the HOST for small n (host pointers; the same inline functions for the rows, the pair
+ *                      and the order; the keys are recomputed here); rows are the points in the caller's order; pairs: one
+ *                      uint64 or null.
+ *
+ * Normals.  For the point p with the neighbours x_0 .. x_(m-1), m = count, in the order of its list; fp64, every operation
+ * rounded, no contraction.  The members are the differences d_j = x_j - p and the point itself as d_m = 0:  M = m + 1,
+ *      mean = (sum of d_j, j ascending) / M;     e_j = d_j - mean  (e_m = 0 - mean);
+ *      C_ab = (sum over j = 0 .. m of e_j.a e_j.b, j ascending) / M,   the six entries of the symmetric 3x3.
+ * Cyclic Jacobi on C from V = I, 8 sweeps of the rotations (0,1), (0,2), (1,2): the rotation of "Mesh simplification".  Of
+ * the diagonal, lambda0 is the least entry (the lowest position among equals), lambda2 the largest (the highest position among
+ * equals), lambda1 the third.  The point is VALID iff m >= 3 and lambda1 > ADAMVS_KNN_RANK_EPS lambda2, rank_eps = 1e-12: points
+ * on a line leave lambda1 at rounding level, some 1e-32 lambda2, and any real spread across the line is far above 1e-12.
+ *      normal = v / sqrt((v.x v.x + v.y v.y) + v.z v.z),  v the column of V of lambda0;  flipped if the first non-zero of
+ *      (n.z, n.y, n.x) is negative (UPWARD; the fused cloud does not record its views, so nothing orients towards a camera);
+ *      curvature = fp32(l / ((l + lambda1) + lambda2)),  l = max(lambda0, 0):  the surface variation of Pauly et al. (PCL's).
+ * A point that is not valid has normal (0, 0, 0), curvature 0 and flag ADAMVS_KNN_TOO_FEW = 1 (m < 3) or ADAMVS_KNN_COLLINEAR =
+ * 2; a valid one has flag ADAMVS_KNN_VALID = 0.
+ *   _knn_normals       one lane per row.  points [n][3] fp64 in the caller's order; index [rows][k], count [rows] of _knn_search;
+ *                      row_point [rows] int32: the number of each row's point (null: row r is point r).  normal [rows][3]
+ *                      fp64, curvature [rows] fp32, flag [rows] uint8.  A neighbour number outside [0, n) is skipped;
+ *   _knn_normals_host  the same on the HOST through the same inline function.
+ * Argument errors (<0, before any launch): a null pointer (row_point and the host's pairs may be null), k outside 1 .. 32, R not
+ * finite or <= 0, O not finite, a count < 1 or > 2^31 - 1, nc > n, a row range outside the cloud. */
+#define ADAMVS_KNN_MAX_K 32
+#define ADAMVS_KNN_RANK_EPS 1e-12
+#define ADAMVS_KNN_VALID 0
+#define ADAMVS_KNN_TOO_FEW 1
+#define ADAMVS_KNN_COLLINEAR 2
+
+int adamvs_knn_search(const double* origin, double R, int k, const long long* ukeys, const long long* tstart, int nc, const double* sorted,
+                      const int* pindex, long n, const long long* item_key, const long long* item_first, const int* item_count, long ni,
+                      long long row_base, long rows, float* d2, int* index, int* count, unsigned long long* pairs, void* stream);
+int adamvs_knn_search_host(const double* origin, double R, int k, const double* points, long n, float* d2, int* index, int* count,
+                           unsigned long long* pairs);
+int adamvs_knn_normals(const double* points, long n, const int* index, const int* count, int k, long rows, const int* row_point,
+                       double* normal, float* curvature, unsigned char* flag, void* stream);
+int adamvs_knn_normals_host(const double* points, long n, const int* index, const int* count, int k, long rows, const int* row_point,
+                            double* normal, float* curvature, unsigned char* flag);
+
 /* ---- Image orthophoto (after dsm_whu.py): the source images mosaicked over a DSM into a true orthophoto -------------------
  * ada-mvs_amd/ortho.py drives it; ortho_whu.py is the CLI.  World axes: x east, y north, z up; rows run south.
  *
