@@ -24,15 +24,13 @@ and texture_whu.py's default occlusion tolerance keep working on the cleaned mes
 counts and the timings.
 """
 import argparse
-import json
 import math
-import os
 import sys
-import time
 
 import numpy as np
 
-from .simplify import CARRIED, MAX_COUNT, mesh_path_of  # noqa: F401  (the same carried keys and path rule)
+from . import mesh_stage
+from .mesh_stage import CARRIED, MAX_COUNT, mesh_path_of  # noqa: F401  (shared with simplify.py and smooth.py)
 
 DEFAULT_MIN_FACES = 100                       # a convention, not a measurement
 DEFAULT_MAX_HOLE_EDGES = 32                   # likewise
@@ -48,53 +46,30 @@ COUNTS = ("vertices_in", "faces_in", "faces_degenerate", "components", "componen
 def check_options(min_faces=DEFAULT_MIN_FACES, min_area=None, max_hole_edges=DEFAULT_MAX_HOLE_EDGES):
     if isinstance(min_faces, bool) or not isinstance(min_faces, (int, np.integer)) or not 0 <= int(min_faces) <= MAX_COUNT:
         raise ValueError("min_faces=%r must be an integer in 0 .. 2^31 - 1" % (min_faces,))
-    if min_area is not None and (isinstance(min_area, bool) or not isinstance(min_area, (int, float)) or not math.isfinite(float(min_area))
-                                 or float(min_area) <= 0):
-        raise ValueError("min_area=%r must be finite and > 0" % (min_area,))
+    if min_area is not None:
+        mesh_stage.positive("min_area", min_area)
     if isinstance(max_hole_edges, bool) or not isinstance(max_hole_edges, (int, np.integer)) or not 0 <= int(max_hole_edges) <= MAX_HOLE_EDGES:
         raise ValueError("max_hole_edges=%r must be an integer in 0 .. %d" % (max_hole_edges, MAX_HOLE_EDGES))
 
 
 def default_out(mesh_path):
-    return (mesh_path[:-4] if mesh_path.lower().endswith(".ply") else mesh_path) + "_cleaned.ply"
+    return mesh_stage.default_out(mesh_path, "_cleaned")
 
 
 def resolve_min_area(min_area, min_area_voxels, meta):
     """--min_area A (square metres), or --min_area_voxels K times the squared voxel of <mesh>.json, or neither: no area threshold."""
-    if min_area is not None and min_area_voxels is not None:
-        raise ValueError("give --min_area or --min_area_voxels, not both")
-    if min_area is not None:
-        check_options(min_area=min_area)
-        return float(min_area)
-    if min_area_voxels is None:
-        return None
-    k = min_area_voxels
-    if isinstance(k, bool) or not isinstance(k, (int, float)) or not math.isfinite(float(k)) or float(k) <= 0:
-        raise ValueError("min_area_voxels=%r must be finite and > 0" % (k,))
-    if meta is None or "voxel" not in meta:
-        raise ValueError("<mesh>.json with the voxel size is absent: give --min_area")
-    return float(k) * float(meta["voxel"]) * float(meta["voxel"])
+    return mesh_stage.resolve_metres("min_area", min_area, min_area_voxels, None, meta, power=2)
 
 
 def summary(meta, info, options, origin, source, out, seconds, device_seconds, stage_seconds=None):
     """The dict written to <out>.json: the carried keys of <mesh>.json first, unchanged."""
-    res = {k: meta[k] for k in CARRIED if meta is not None and k in meta}
-    res.update(options)
-    res.update(clean_origin=[float(v) for v in origin], source=source, ply=out)
-    res.update(info)
-    res.update(seconds=float(seconds), device_seconds=float(device_seconds), stage_seconds=dict(stage_seconds or {}))
-    return res
+    return mesh_stage.summary(meta, dict(options, clean_origin=[float(v) for v in origin], source=source, ply=out), info,
+                              seconds=float(seconds), device_seconds=float(device_seconds), stage_seconds=dict(stage_seconds or {}))
 
 
 def doubling_rounds(n):
     """Rounds after which a label is the minimum over at least 2 n half-edges: every cycle among n half-edges is labelled whole."""
     return 0 if n < 1 else int(math.ceil(math.log2(n))) + 1 if n > 1 else 1
-
-
-def _empty(dev):
-    import torch
-    return (torch.empty(0, 3, device=dev, dtype=torch.float64), torch.empty(0, 3, device=dev, dtype=torch.uint8),
-            torch.empty(0, 3, device=dev, dtype=torch.int32))
 
 
 def _weld_output(xyz, rgb, faces):
@@ -115,45 +90,24 @@ def clean(xyz, rgb, faces, min_faces=DEFAULT_MIN_FACES, min_area=None, max_hole_
     `face_labels`, `kept` [faces after the degenerate ones left], `surviving` [ns, 3], `boundary`, `successor`, `loop`, `closed`
     [3 ns]; timing: a list that receives (name, start event, end event) of the stages."""
     import torch
-    from . import _lib, hip_ops, mesh
+    from . import _lib, hip_ops
     check_options(min_faces, min_area, max_hole_edges)
-    for name, t in (("xyz", xyz), ("rgb", rgb), ("faces", faces)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.AdaMVSHipError("%s must be a GPU tensor: mesh cleaning has no CPU fallback" % name)
-    if xyz.dtype != torch.float64 or rgb.dtype != torch.uint8 or faces.dtype not in (torch.int32, torch.int64):
-        raise _lib.AdaMVSHipError("xyz float64, rgb uint8, faces int32 / int64: got %s, %s, %s" % (xyz.dtype, rgb.dtype, faces.dtype))
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or tuple(rgb.shape) != tuple(xyz.shape) or faces.dim() != 2 or faces.shape[1] != 3:
-        raise _lib.AdaMVSHipError("xyz [nv, 3], rgb [nv, 3], faces [nf, 3]: got %s, %s, %s" % (tuple(xyz.shape), tuple(rgb.shape), tuple(faces.shape)))
+    clock = mesh_stage.StageClock(timing)
+    stage = clock.stage
+    welded = mesh_stage.enter("mesh cleaning", xyz, rgb, faces, MAX_FACES, clock)
     dev = xyz.device
     min_faces, M = int(min_faces), int(max_hole_edges)
-    marks = []
-
-    def stage(name):
-        if timing is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            marks.append((name, e))
 
     def done(out):
-        stage("end")
-        if timing is not None:
-            timing.extend((a[0], a[1], b[1]) for a, b in zip(marks[:-1], marks[1:]))
+        clock.end()
         info.update(vertices=int(out[0].shape[0]), faces=int(out[2].shape[0]))
         return out + (info,)
 
     info = dict.fromkeys(COUNTS, 0)
     info.update(area_removed=0.0, faces_in=int(faces.shape[0]))
-    if xyz.shape[0] == 0:
-        if faces.shape[0]:
-            raise _lib.AdaMVSHipError("%d faces without vertices" % faces.shape[0])
-        return done(_empty(dev))
-    if faces.shape[0] > MAX_FACES or xyz.shape[0] > MAX_COUNT:
-        raise _lib.AdaMVSHipError("more than 2^31 - 1 vertices or (2^31 - 1) / 3 faces")
-    f64 = faces.to(torch.int64) & 0xFFFFFFFF
-    if faces.shape[0] and int(f64.max()) >= xyz.shape[0]:
-        raise _lib.AdaMVSHipError("a face refers to vertex %d of %d" % (int(f64.max()), xyz.shape[0]))
-    stage("weld")
-    xyz, f64, rgb = mesh.weld(xyz.contiguous(), f64, rgb.contiguous())
+    if welded is None:
+        return done(mesh_stage.empty_mesh(dev))
+    xyz, f64, rgb = welded
     nv = int(xyz.shape[0])
     info["vertices_in"] = nv
     o = np.asarray(origin, np.float64).reshape(3) if origin is not None else xyz.min(0).values.cpu().numpy()
@@ -166,7 +120,7 @@ def clean(xyz, rgb, faces, min_faces=DEFAULT_MIN_FACES, min_area=None, max_hole_
     if detail is not None:
         detail.update(xyz=xyz, rgb=rgb, faces=f64.to(torch.int32), degenerate=degenerate, origin=o)
     if nf == 0:
-        return done(_empty(dev))
+        return done(mesh_stage.empty_mesh(dev))
     faces32 = f64.to(torch.int32).contiguous()
     p0 = (xyz - torch.from_numpy(o).to(dev)).contiguous()
     stage("faces")
@@ -205,7 +159,7 @@ def clean(xyz, rgb, faces, min_faces=DEFAULT_MIN_FACES, min_area=None, max_hole_
     if detail is not None:
         detail.update(labels=parent, face_labels=face_label, kept=kept, component_area=comp_area, component_faces=count, surviving=sf)
     if ns == 0:
-        return done(_empty(dev))
+        return done(mesh_stage.empty_mesh(dev))
     # steps 5 and 6
     stage("boundary")
     bnd = hip_ops.clean_boundary(sf)
@@ -256,47 +210,16 @@ def clean(xyz, rgb, faces, min_faces=DEFAULT_MIN_FACES, min_area=None, max_hole_
 def from_file(mesh_path, out=None, min_faces=DEFAULT_MIN_FACES, min_area=None, min_area_voxels=None, max_hole_edges=DEFAULT_MAX_HOLE_EDGES,
               origin=None, device=None, log=print):
     """Clean the mesh PLY mesh_whu.py wrote -> the summary dict also written to <out>.json."""
-    import torch
-    from . import mesh
-    t_start = time.time()
-    meta = None
-    if os.path.exists(mesh_path + ".json"):
-        with open(mesh_path + ".json") as f:
-            meta = json.load(f)
-    area = resolve_min_area(min_area, min_area_voxels, meta)
-    check_options(min_faces, area, max_hole_edges)
-    if not torch.cuda.is_available():
-        raise RuntimeError("clean: needs an MI355X (there is no CPU fallback for the cleaning kernels)")
+    def resolve(meta):
+        area = resolve_min_area(min_area, min_area_voxels, meta)
+        check_options(min_faces, area, max_hole_edges)
+        return dict(min_faces=int(min_faces), min_area=area, max_hole_edges=int(max_hole_edges))
+
+    def run(opt, xyz, rgb, f, o, timing):
+        return clean(xyz, rgb, f, min_faces, opt["min_area"], max_hole_edges, o, timing=timing)
+
     out = out or default_out(mesh_path)
-    device = torch.device(device if device is not None else "cuda")
-    verts, faces = mesh.read_mesh_ply(mesh_path)
-    xyz_h = np.stack([verts["x"], verts["y"], verts["z"]], 1).astype(np.float64)
-    rgb_h = np.stack([verts["red"], verts["green"], verts["blue"]], 1)
-    if origin is not None:
-        o = np.asarray(origin, np.float64).reshape(3)
-    elif meta is not None and "origin" in meta:
-        o = np.asarray(meta["origin"], np.float64).reshape(3)
-    else:
-        o = xyz_h.min(0) if len(xyz_h) else np.zeros(3)
-    xyz = torch.from_numpy(np.ascontiguousarray(xyz_h)).to(device)
-    rgb = torch.from_numpy(np.ascontiguousarray(rgb_h)).to(device)
-    f = torch.from_numpy(faces.astype(np.int64)).to(device)
-    timing = []
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    cx, cc, cf, info = clean(xyz, rgb, f, min_faces, area, max_hole_edges, o, timing=timing)
-    e1.record()
-    torch.cuda.synchronize(device)
-    if os.path.dirname(out):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-    with mesh.MeshPlyWriter(out) as w:
-        w.write(cx.cpu().numpy(), cc.cpu().numpy(), cf.cpu().numpy().view(np.uint32))
-    options = dict(min_faces=int(min_faces), min_area=area, max_hole_edges=int(max_hole_edges))
-    res = summary(meta, info, options, o, mesh_path, out, time.time() - t_start, e0.elapsed_time(e1) / 1e3,
-                  {name: a.elapsed_time(b) / 1e3 for name, a, b in timing})
-    with open(out + ".json", "w") as fj:
-        json.dump(res, fj, indent=1)
-        fj.write("\n")
+    res, info, _ = mesh_stage.run_file("clean", "cleaning", mesh_path, out, origin, device, resolve, mesh_stage.volume_origin, run, summary)
     log("clean: %d vertices, %d faces in; %d of %d components kept (%d faces removed), %d of %d loops closed (%d too long, %d edges left "
         "open) -> %d vertices, %d faces into %s, device %.3f s, total_time = %.3f s"
         % (info["vertices_in"], info["faces_in"], info["components_kept"], info["components"], info["faces_removed"], info["loops_closed"],

@@ -672,7 +672,7 @@ extern "C" int adamvs_smooth_faces(const double* p, long nv, const unsigned* fac
 extern "C" int adamvs_smooth_edge_keys(const unsigned* faces, long nf, long long* keys, void* stream) {
   if (int rc = smooth_check_counts(1, nf, "smooth_edge_keys")) return rc;
   ADAMVS_CHECK_ARG(faces && keys, "smooth_edge_keys: null pointer");
-  return launch_smooth_edge_keys(faces, nf, keys, (hipStream_t)stream);
+  return launch_mesh_edge_keys(faces, nf, keys, "smooth_edge_keys", (hipStream_t)stream);
 }
 
 extern "C" int adamvs_smooth_boundary(const long long* keys, long n, long nv, unsigned char* fixed, void* stream) {
@@ -992,7 +992,7 @@ extern "C" int adamvs_texture_score(const adamvs_ortho_view* view, int view_inde
 extern "C" int adamvs_texture_edge_keys(const unsigned* faces, long nf, long long* keys, void* stream) {
   if (int rc = texture_check_mesh(1, nf, "texture_edge_keys")) return rc;
   ADAMVS_CHECK_ARG(faces && keys, "texture_edge_keys: null pointer");
-  return launch_tex_edge_keys(faces, nf, keys, (hipStream_t)stream);
+  return launch_mesh_edge_keys(faces, nf, keys, "texture_edge_keys", (hipStream_t)stream);
 }
 
 extern "C" int adamvs_texture_components(const long long* keys_sorted, const long long* entry, long nf, const int* label, int* parent,

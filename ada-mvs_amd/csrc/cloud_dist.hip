@@ -20,6 +20,7 @@
 #include <numeric>
 #include <vector>
 
+#include "block_prims.h"
 #include "cloud_lattice.h"
 #include "common.h"
 #include "kernels.h"
@@ -182,7 +183,6 @@ __global__ __launch_bounds__(256) void k_cloud_sample_emit(const double* __restr
 }
 
 // ---- launches -------------------------------------------------------------------------------------------------------------------
-static unsigned cloud_tiles(long n) { return (unsigned)((n + CLOUD_TILE - 1) / CLOUD_TILE); }
 
 int launch_cloud_nearest(const double* origin, double D, const long long* ukeys, const long long* tstart, int nc, const double* targets,
                          const int* tindex, long nt, const double* queries, long nq, const long long* qorder, long nqs,
@@ -195,14 +195,14 @@ int launch_cloud_nearest(const double* origin, double D, const long long* ukeys,
 }
 
 int launch_cloud_sample_count(const double* xyz, long nv, const unsigned* faces, long nf, double spacing, int* subdiv, hipStream_t st) {
-  hipLaunchKernelGGL(k_cloud_sample_count, dim3(cloud_tiles(nf)), dim3(CLOUD_TILE), 0, st, xyz, nv, faces, nf, spacing, subdiv);
+  hipLaunchKernelGGL(k_cloud_sample_count, dim3(tiles256(nf)), dim3(CLOUD_TILE), 0, st, xyz, nv, faces, nf, spacing, subdiv);
   ADAMVS_CHECK_LAUNCH("cloud_sample_count");
   return 0;
 }
 
 int launch_cloud_sample_emit(const double* xyz, long nv, const unsigned* faces, long nf, const int* subdiv, const long long* offsets,
                              double* points, long capacity, hipStream_t st) {
-  hipLaunchKernelGGL(k_cloud_sample_emit, dim3(cloud_tiles(nf * 64)), dim3(CLOUD_TILE), 0, st, xyz, nv, faces, nf, subdiv, offsets, points,
+  hipLaunchKernelGGL(k_cloud_sample_emit, dim3(tiles256(nf * 64)), dim3(CLOUD_TILE), 0, st, xyz, nv, faces, nf, subdiv, offsets, points,
                      capacity);
   ADAMVS_CHECK_LAUNCH("cloud_sample_emit");
   return 0;

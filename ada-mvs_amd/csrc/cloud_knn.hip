@@ -23,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "block_prims.h"
 #include "cloud_lattice.h"
 #include "common.h"
 #include "jacobi.h"
@@ -303,7 +304,7 @@ int launch_knn_search(const double* origin, double R, int k, const long long* uk
 
 int launch_knn_normals(const double* points, long n, const int* index, const int* count, int k, long rows, const int* row_point,
                        double* normal, float* curvature, uint8_t* flag, hipStream_t st) {
-  hipLaunchKernelGGL(k_knn_normals, dim3((unsigned)((rows + CLOUD_TILE - 1) / CLOUD_TILE)), dim3(CLOUD_TILE), 0, st, points, n, index, count, k,
+  hipLaunchKernelGGL(k_knn_normals, dim3(tiles256(rows)), dim3(CLOUD_TILE), 0, st, points, n, index, count, k,
                      rows, row_point, normal, curvature, flag);
   ADAMVS_CHECK_LAUNCH("knn_normals");
   return 0;

@@ -10,12 +10,11 @@
 // Workgroups cover FUSION_TILE consecutive pixels of the row-major image, so block order is pixel order and the point
 // buffer comes out in row-major order.  No atomics and no inter-workgroup waits: the launches are the synchronisation,
 // and the output is bit-identical from run to run.
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace adamvs {
-
-static_assert(FUSION_TILE == 256, "the ballot / LDS layout below assumes four waves of 64");
 
 // Per-source constants, fp32, formed by the host in fp64 (ada-mvs_amd/fusion.py::relative_transforms):
 //   fwd  = {A row-major (9), b (3)}: source pixel (homogeneous) = d * A [x y 1]^T + b, A = K_s R_sr K_r^-1, b = K_s t_sr
@@ -36,7 +35,6 @@ __global__ __launch_bounds__(256) void k_geo_consistency(const float* __restrict
                                                          int W, const FusionArgs a, float prob_threshold, float pix_threshold2,
                                                          float rel_depth_threshold, int min_consistent, uint8_t* __restrict__ count,
                                                          float* __restrict__ fused, unsigned* __restrict__ block_kept) {
-  __shared__ unsigned wave_kept[4];
   const long npix = (long)H * W;
   const long p = (long)blockIdx.x * FUSION_TILE + threadIdx.x;
   const bool inside = p < npix;
@@ -78,10 +76,9 @@ __global__ __launch_bounds__(256) void k_geo_consistency(const float* __restrict
     count[p] = (uint8_t)n;
     fused[p] = kept ? sum / (float)(1 + n) : 0.f;
   }
-  const unsigned long long bal = __ballot(kept);
-  if ((threadIdx.x & 63) == 0) wave_kept[threadIdx.x >> 6] = (unsigned)__popcll(bal);
-  __syncthreads();
-  if (threadIdx.x == 0) block_kept[blockIdx.x] = wave_kept[0] + wave_kept[1] + wave_kept[2] + wave_kept[3];
+  unsigned total;
+  block_rank(kept, &total);
+  if (threadIdx.x == 0) block_kept[blockIdx.x] = total;
 }
 
 // offsets[i] = sum of counts[0 .. i), offsets[nb] = total.  One workgroup of 1024 lanes, each a contiguous run of counts.
@@ -116,19 +113,13 @@ struct EmitCamera {
 __global__ __launch_bounds__(256) void k_fusion_emit(const float* __restrict__ fused, const uint8_t* __restrict__ rgba, int H, int W,
                                                      const EmitCamera cam, const unsigned* __restrict__ offsets,
                                                      double* __restrict__ xyz, uint8_t* __restrict__ rgb, long capacity) {
-  __shared__ unsigned wave_base[4];
   const long npix = (long)H * W;
   const long p = (long)blockIdx.x * FUSION_TILE + threadIdx.x;
   const bool inside = p < npix;
   const float d = inside ? fused[p] : 0.f;
   const bool kept = d > 0.f;
-  const unsigned long long bal = __ballot(kept);
-  const unsigned lane_rank = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-  if ((threadIdx.x & 63) == 0) wave_base[threadIdx.x >> 6] = (unsigned)__popcll(bal);
-  __syncthreads();
-  const int wv = threadIdx.x >> 6;
-  unsigned rank = lane_rank;
-  for (int i = 0; i < wv; ++i) rank += wave_base[i];
+  unsigned total;
+  const unsigned rank = block_rank(kept, &total);
   if (!kept) return;
   const long q = (long)offsets[blockIdx.x] + rank;
   if (q >= capacity) return;                           // cannot happen with capacity >= H W; keeps every store in bounds
@@ -146,7 +137,7 @@ __global__ __launch_bounds__(256) void k_fusion_emit(const float* __restrict__ f
   rgb[3 * q + 2] = px[2];
 }
 
-static unsigned fusion_blocks(int H, int W) { return (unsigned)(((long)H * W + FUSION_TILE - 1) / FUSION_TILE); }
+static unsigned fusion_blocks(int H, int W) { return tiles256((long)H * W); }
 
 int launch_geo_consistency(const float* ref_depth, const float* ref_conf, int H, int W, const adamvs_fusion_source* srcs, int N,
                            float prob_threshold, float pix_threshold, float rel_depth_threshold, int min_consistent, uint8_t* count,

@@ -199,7 +199,8 @@ int launch_simplify_emit(const double* pos, const uint8_t* col, const uint8_t* u
 // mesh_smooth.hip: bilateral normal filtering of the mesh (include/adamvs_hip.h, "Mesh smoothing")
 constexpr int SMOOTH_TILE = ADAMVS_SMOOTH_TILE;
 int launch_smooth_faces(const double* p, long nv, const unsigned* faces, long nf, double* rec, hipStream_t st);
-int launch_smooth_edge_keys(const unsigned* faces, long nf, long long* keys, hipStream_t st);
+// the 3 nf edge keys of a mesh, for smoothing, cleaning and texturing alike; `what` names the entry point in a launch error
+int launch_mesh_edge_keys(const unsigned* faces, long nf, long long* keys, const char* what, hipStream_t st);
 int launch_smooth_boundary(const long long* keys, long n, long nv, uint8_t* fixed, hipStream_t st);
 int launch_smooth_filter(const double* rec, const double* nin, double* nout, const unsigned* faces, long nf, long nv, const int* vface,
                          const long long* vstart, double sigma_s, double sigma_r, hipStream_t st);
@@ -270,7 +271,6 @@ int launch_tex_zbuf(int W, int H, const float* uvz, long nv, const unsigned* fac
                     unsigned* big_list, hipStream_t st);
 int launch_tex_score(int W, int H, int view, const float* uvz, long nv, const unsigned* faces, long nf, const unsigned* zbuf, float border,
                      float tol, float* best, int* label, int* nvis, float* uv, hipStream_t st);
-int launch_tex_edge_keys(const unsigned* faces, long nf, long long* keys, hipStream_t st);
 int launch_tex_components_round(const long long* keys, const long long* entry, long n, const int* label, int* parent, long nf,
                                 unsigned* changed, hipStream_t st);
 int launch_tex_rank(const int* label, const int* parent, long nf, unsigned* block_roots, unsigned* block_untex, unsigned* root_off,

@@ -11,6 +11,7 @@
 //
 // Workgroups cover MESH_TILE consecutive entries of the row-major sample / cube order, so block order is output order.  No
 // atomics and no inter-workgroup waits: the launches are the synchronisation, and the output is bit-identical from run to run.
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -18,8 +19,6 @@
 #pragma clang fp contract(off)
 
 namespace adamvs {
-
-static_assert(MESH_TILE == 256, "the scan / LDS layout below assumes four waves of 64");
 
 // ---- the Kuhn split, generated from the rule of the header --------------------------------------------------------------
 // Tet t is the axis permutation PERM[t] = (a, b, c); vertices v0 = 000, v1 = e_a, v2 = e_a + e_b, v3 = 111, as corner bits
@@ -139,23 +138,6 @@ struct MeshArgs {
 };
 
 __device__ __forceinline__ bool positive_finite_(float v) { return v > 0.f && v <= 3.402823466e38f; }
-
-// exclusive scan of v over the workgroup (256 lanes); *total = the sum.  Every lane must call it.
-__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* total) {
-  __shared__ unsigned wave_sum[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  unsigned inc = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned t = __shfl_up(inc, off, 64);
-    if (lane >= off) inc += t;
-  }
-  if (lane == 63) wave_sum[wv] = inc;
-  __syncthreads();
-  unsigned base = 0;
-  for (int i = 0; i < wv; ++i) base += wave_sum[i];
-  *total = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
-  return base + inc - v;
-}
 
 __global__ __launch_bounds__(256) void k_tsdf_integrate(const MeshArgs a, const adamvs_mesh_view* __restrict__ views, int nviews,
                                                         const int* __restrict__ list, int nlist, float* __restrict__ tsdf,
@@ -349,7 +331,7 @@ static MeshArgs mesh_args(const adamvs_mesh_brick& b) {
   return a;
 }
 
-static unsigned sample_blocks(int B) { return (unsigned)(((long)(B + 1) * (B + 1) * (B + 1) + MESH_TILE - 1) / MESH_TILE); }
+static unsigned sample_blocks(int B) { return tiles256((long)(B + 1) * (B + 1) * (B + 1)); }
 static unsigned cube_blocks(int B) { return (unsigned)((long)B * B * B / MESH_TILE); }
 
 int launch_tsdf_integrate(const adamvs_mesh_brick& b, const adamvs_mesh_view* views, int nviews, const int* list, int nlist, float* tsdf,

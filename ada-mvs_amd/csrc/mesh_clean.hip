@@ -5,7 +5,7 @@
 //
 //   k_clean_hook / k_clean_compress   one round of the vertex labels: every face hooks the larger roots of its corners to the
 //                                     smallest (read from the previous round's snapshot, integer atomicMin into the new one),
-//                                     then every vertex walks to its root
+//                                     then every vertex walks to its root (block_prims.h compress_to_root)
 //   k_clean_area_chunks / _segments   the area of every component: one lane per chunk of 1024 sorted faces, then one per component
 //   k_clean_boundary                  one lane per sorted edge key: whether its half-edge is the only one with that key
 //   k_clean_vinit / _count / _succ    per vertex the boundary half-edges leaving and entering it, and every half-edge's successor
@@ -18,14 +18,13 @@
 // floating-point sum runs in an order fixed by the sorted input, so the output is bit-identical from run to run.
 #include <math.h>
 
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
 
 #pragma clang fp contract(off)
 
 namespace adamvs {
-
-static_assert(CLEAN_TILE == 256, "the launches below assume workgroups of 256 lanes");
 
 // ---- components -------------------------------------------------------------------------------------------------------------
 // pin is the snapshot the round starts from (every pin[v] is a root: pin[pin[v]] == pin[v]); pout starts as its copy
@@ -45,15 +44,9 @@ __global__ __launch_bounds__(256) void k_clean_hook(const unsigned* __restrict__
   if (any) changed[0] = 1u;
 }
 
-// parent[x] <= x everywhere and other lanes only lower their own entries to ancestors: the walk ends at the root
 __global__ __launch_bounds__(256) void k_clean_compress(int* parent, long nv) {
   const long v = (long)blockIdx.x * CLEAN_TILE + threadIdx.x;
-  if (v >= nv) return;
-  const int p0 = parent[v];
-  if (p0 < 0 || (long)p0 > v) return;
-  int p = p0;
-  for (int q = parent[p]; q >= 0 && q < p; q = parent[p]) p = q;       // strictly downwards: it ends whatever the caller passed
-  if (p != p0) parent[v] = p;
+  if (v < nv) compress_to_root(parent, v);
 }
 
 // ---- component areas ----------------------------------------------------------------------------------------------------------
@@ -106,8 +99,8 @@ __global__ __launch_bounds__(256) void k_clean_boundary(const long long* __restr
                                                         uint8_t* __restrict__ bnd) {
   const long i = (long)blockIdx.x * CLEAN_TILE + threadIdx.x;
   if (i >= n) return;
-  const long long key = keys[i], h = entry[i];
-  const bool once = !((i > 0 && keys[i - 1] == key) || (i + 1 < n && keys[i + 1] == key));
+  const long long h = entry[i];
+  const bool once = key_occurs_once(keys, i, n);
   if (h >= 0 && h < n) bnd[h] = (uint8_t)once;
 }
 
@@ -115,13 +108,6 @@ __global__ __launch_bounds__(256) void k_clean_vinit(int* __restrict__ out_cnt, 
   const long v = (long)blockIdx.x * CLEAN_TILE + threadIdx.x;
   if (v >= nv) return;
   out_cnt[v] = 0, in_cnt[v] = 0, out_he[v] = 0x7FFFFFFF;
-}
-
-__device__ __forceinline__ void half_edge(const unsigned* __restrict__ faces, long h, unsigned& tail, unsigned& head) {
-  const long s = h / 3;
-  const int k = (int)(h - 3 * s);
-  tail = faces[3 * s + k];
-  head = faces[3 * s + (k == 2 ? 0 : k + 1)];
 }
 
 __global__ __launch_bounds__(256) void k_clean_count(const unsigned* __restrict__ faces, long n, long nv, const uint8_t* __restrict__ bnd,
@@ -273,8 +259,6 @@ __global__ __launch_bounds__(256) void k_clean_emit_fans(const unsigned* __restr
 }
 
 // ---- launches -----------------------------------------------------------------------------------------------------------
-static unsigned clean_tiles(long n) { return (unsigned)((n + CLEAN_TILE - 1) / CLEAN_TILE); }
-
 #define CLEAN_ASYNC(call, what) \
   do { hipError_t e_ = (call); \
        if (e_ != hipSuccess) return set_error((int)e_, "%s: %s", what, hipGetErrorString(e_)); } while (0)
@@ -283,9 +267,9 @@ int launch_clean_components(const unsigned* faces, long nf, long nv, const int* 
                             hipStream_t st) {
   CLEAN_ASYNC(hipMemsetAsync(changed, 0, sizeof(unsigned), st), "clean_components: hipMemsetAsync");
   CLEAN_ASYNC(hipMemcpyAsync(parent_out, parent_in, sizeof(int) * (size_t)nv, hipMemcpyDeviceToDevice, st), "clean_components: hipMemcpyAsync");
-  hipLaunchKernelGGL(k_clean_hook, dim3(clean_tiles(nf)), dim3(CLEAN_TILE), 0, st, faces, nf, nv, parent_in, parent_out, changed);
+  hipLaunchKernelGGL(k_clean_hook, dim3(tiles256(nf)), dim3(CLEAN_TILE), 0, st, faces, nf, nv, parent_in, parent_out, changed);
   ADAMVS_CHECK_LAUNCH("clean_hook");
-  hipLaunchKernelGGL(k_clean_compress, dim3(clean_tiles(nv)), dim3(CLEAN_TILE), 0, st, parent_out, nv);
+  hipLaunchKernelGGL(k_clean_compress, dim3(tiles256(nv)), dim3(CLEAN_TILE), 0, st, parent_out, nv);
   ADAMVS_CHECK_LAUNCH("clean_compress");
   return 0;
 }
@@ -293,15 +277,15 @@ int launch_clean_components(const unsigned* faces, long nf, long nv, const int* 
 int launch_clean_area(const double* area, long nf, const long long* order, const long long* seg_of, const long long* seg_start, long ncomp,
                       double* lead, double* first, double* out, hipStream_t st) {
   const long chunks = (nf + CLEAN_CHUNK - 1) / CLEAN_CHUNK;
-  hipLaunchKernelGGL(k_clean_area_chunks, dim3(clean_tiles(chunks)), dim3(CLEAN_TILE), 0, st, area, nf, order, seg_of, ncomp, lead, first);
+  hipLaunchKernelGGL(k_clean_area_chunks, dim3(tiles256(chunks)), dim3(CLEAN_TILE), 0, st, area, nf, order, seg_of, ncomp, lead, first);
   ADAMVS_CHECK_LAUNCH("clean_area_chunks");
-  hipLaunchKernelGGL(k_clean_area_segments, dim3(clean_tiles(ncomp)), dim3(CLEAN_TILE), 0, st, seg_start, ncomp, nf, lead, first, out);
+  hipLaunchKernelGGL(k_clean_area_segments, dim3(tiles256(ncomp)), dim3(CLEAN_TILE), 0, st, seg_start, ncomp, nf, lead, first, out);
   ADAMVS_CHECK_LAUNCH("clean_area_segments");
   return 0;
 }
 
 int launch_clean_boundary(const long long* keys, const long long* entry, long n, uint8_t* bnd, hipStream_t st) {
-  hipLaunchKernelGGL(k_clean_boundary, dim3(clean_tiles(n)), dim3(CLEAN_TILE), 0, st, keys, entry, n, bnd);
+  hipLaunchKernelGGL(k_clean_boundary, dim3(tiles256(n)), dim3(CLEAN_TILE), 0, st, keys, entry, n, bnd);
   ADAMVS_CHECK_LAUNCH("clean_boundary");
   return 0;
 }
@@ -309,11 +293,11 @@ int launch_clean_boundary(const long long* keys, const long long* entry, long n,
 int launch_clean_successor(const unsigned* faces, long ns, long nv, const uint8_t* bnd, int* out_cnt, int* in_cnt, int* out_he, int* succ,
                            int* lab, int* nxt, uint8_t* broken, hipStream_t st) {
   const long n = 3 * ns;
-  hipLaunchKernelGGL(k_clean_vinit, dim3(clean_tiles(nv)), dim3(CLEAN_TILE), 0, st, out_cnt, in_cnt, out_he, nv);
+  hipLaunchKernelGGL(k_clean_vinit, dim3(tiles256(nv)), dim3(CLEAN_TILE), 0, st, out_cnt, in_cnt, out_he, nv);
   ADAMVS_CHECK_LAUNCH("clean_vinit");
-  hipLaunchKernelGGL(k_clean_count, dim3(clean_tiles(n)), dim3(CLEAN_TILE), 0, st, faces, n, nv, bnd, out_cnt, in_cnt, out_he);
+  hipLaunchKernelGGL(k_clean_count, dim3(tiles256(n)), dim3(CLEAN_TILE), 0, st, faces, n, nv, bnd, out_cnt, in_cnt, out_he);
   ADAMVS_CHECK_LAUNCH("clean_count");
-  hipLaunchKernelGGL(k_clean_succ, dim3(clean_tiles(n)), dim3(CLEAN_TILE), 0, st, faces, n, nv, bnd, out_cnt, in_cnt, out_he, succ, lab, nxt,
+  hipLaunchKernelGGL(k_clean_succ, dim3(tiles256(n)), dim3(CLEAN_TILE), 0, st, faces, n, nv, bnd, out_cnt, in_cnt, out_he, succ, lab, nxt,
                      broken);
   ADAMVS_CHECK_LAUNCH("clean_succ");
   return 0;
@@ -321,7 +305,7 @@ int launch_clean_successor(const unsigned* faces, long ns, long nv, const uint8_
 
 int launch_clean_double(const uint8_t* bnd, long n, const int* lab_in, const int* nxt_in, const uint8_t* broken_in, int* lab_out, int* nxt_out,
                         uint8_t* broken_out, hipStream_t st) {
-  hipLaunchKernelGGL(k_clean_double, dim3(clean_tiles(n)), dim3(CLEAN_TILE), 0, st, bnd, n, lab_in, nxt_in, broken_in, lab_out, nxt_out,
+  hipLaunchKernelGGL(k_clean_double, dim3(tiles256(n)), dim3(CLEAN_TILE), 0, st, bnd, n, lab_in, nxt_in, broken_in, lab_out, nxt_out,
                      broken_out);
   ADAMVS_CHECK_LAUNCH("clean_double");
   return 0;
@@ -331,16 +315,16 @@ int launch_clean_validate(const uint8_t* bnd, const int* succ, const int* lab, c
                           int* loop, uint8_t* closed, hipStream_t st) {
   CLEAN_ASYNC(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)n, st), "clean_validate: hipMemsetAsync");
   CLEAN_ASYNC(hipMemsetAsync(bad, 0, (size_t)n, st), "clean_validate: hipMemsetAsync");
-  hipLaunchKernelGGL(k_clean_mark, dim3(clean_tiles(n)), dim3(CLEAN_TILE), 0, st, bnd, succ, lab, broken, n, cnt, bad);
+  hipLaunchKernelGGL(k_clean_mark, dim3(tiles256(n)), dim3(CLEAN_TILE), 0, st, bnd, succ, lab, broken, n, cnt, bad);
   ADAMVS_CHECK_LAUNCH("clean_mark");
-  hipLaunchKernelGGL(k_clean_decide, dim3(clean_tiles(n)), dim3(CLEAN_TILE), 0, st, bnd, lab, n, M, cnt, bad, loop, closed);
+  hipLaunchKernelGGL(k_clean_decide, dim3(tiles256(n)), dim3(CLEAN_TILE), 0, st, bnd, lab, n, M, cnt, bad, loop, closed);
   ADAMVS_CHECK_LAUNCH("clean_decide");
   return 0;
 }
 
 int launch_clean_accumulate(const double* p, const uint8_t* rgb, long nv, const unsigned* faces, long ns, const int* members,
                             const long long* start, long nl, long nm, const double* origin, double* centre, uint8_t* colour, hipStream_t st) {
-  hipLaunchKernelGGL(k_clean_accumulate, dim3(clean_tiles(nl)), dim3(CLEAN_TILE), 0, st, p, rgb, nv, faces, 3 * ns, members, start, nl, nm,
+  hipLaunchKernelGGL(k_clean_accumulate, dim3(tiles256(nl)), dim3(CLEAN_TILE), 0, st, p, rgb, nv, faces, 3 * ns, members, start, nl, nm,
                      origin[0], origin[1], origin[2], centre, colour);
   ADAMVS_CHECK_LAUNCH("clean_accumulate");
   return 0;
@@ -349,16 +333,16 @@ int launch_clean_accumulate(const double* p, const uint8_t* rgb, long nv, const 
 int launch_clean_emit(const double* xyz, const uint8_t* rgb, long nv, const int* new_index, const unsigned* faces, long ns, const int* fill_h,
                       const int* loop_of, long nfill, const double* centre, const uint8_t* colour, long nl, long nvs, double* xyz_out,
                       uint8_t* rgb_out, unsigned* faces_out, hipStream_t st) {
-  hipLaunchKernelGGL(k_clean_emit_vertices, dim3(clean_tiles(nv)), dim3(CLEAN_TILE), 0, st, xyz, rgb, nv, new_index, nvs, xyz_out, rgb_out);
+  hipLaunchKernelGGL(k_clean_emit_vertices, dim3(tiles256(nv)), dim3(CLEAN_TILE), 0, st, xyz, rgb, nv, new_index, nvs, xyz_out, rgb_out);
   ADAMVS_CHECK_LAUNCH("clean_emit_vertices");
-  hipLaunchKernelGGL(k_clean_emit_faces, dim3(clean_tiles(3 * ns)), dim3(CLEAN_TILE), 0, st, faces, ns, nv, new_index, faces_out);
+  hipLaunchKernelGGL(k_clean_emit_faces, dim3(tiles256(3 * ns)), dim3(CLEAN_TILE), 0, st, faces, ns, nv, new_index, faces_out);
   ADAMVS_CHECK_LAUNCH("clean_emit_faces");
   if (nl > 0) {
-    hipLaunchKernelGGL(k_clean_emit_centres, dim3(clean_tiles(nl)), dim3(CLEAN_TILE), 0, st, centre, colour, nl, nvs, xyz_out, rgb_out);
+    hipLaunchKernelGGL(k_clean_emit_centres, dim3(tiles256(nl)), dim3(CLEAN_TILE), 0, st, centre, colour, nl, nvs, xyz_out, rgb_out);
     ADAMVS_CHECK_LAUNCH("clean_emit_centres");
   }
   if (nfill > 0) {
-    hipLaunchKernelGGL(k_clean_emit_fans, dim3(clean_tiles(nfill)), dim3(CLEAN_TILE), 0, st, faces, ns, nv, new_index, fill_h, loop_of, nfill,
+    hipLaunchKernelGGL(k_clean_emit_fans, dim3(tiles256(nfill)), dim3(CLEAN_TILE), 0, st, faces, ns, nv, new_index, fill_h, loop_of, nfill,
                        nl, nvs, faces_out);
     ADAMVS_CHECK_LAUNCH("clean_emit_fans");
   }

@@ -7,18 +7,20 @@
 //   k_simplify_corners     one lane per face: the cells of its corners, its (cell, face) entries, its survive bit
 //   k_simplify_accumulate  one wave per cell: the quadric over its run of faces and the member sums over its run of vertices;
 //                          lane l takes entries l, l + 64, .. in order, the 64 partials meet in a fixed butterfly
+//                          (block_prims.h wave_sum)
 //   k_simplify_solve       one lane per cell: cyclic Jacobi on the 3x3 (registers only), rank rule, pseudo-inverse step,
 //                          in-cell test, colour
 //   k_simplify_triples     one lane per surviving face: its three cells in ascending order (the caller sorts by them)
 //   k_simplify_first       one lane per entry of that sorted order: the first face of each set of three cells is kept
 //   k_simplify_mark        one lane per face: a kept face flags its three cells as used (plain stores of 1)
 //   k_simplify_count       flags per workgroup (k_fusion_scan turns the counts into offsets)
-//   k_simplify_emit_*      used cells and kept faces at  block offset + rank in the block  (ballot + mbcnt)
+//   k_simplify_emit_*      used cells and kept faces at  block offset + rank in the block  (block_prims.h block_rank)
 //
 // No atomics and no inter-workgroup waits: the order of every sum is a function of the sorted input only, the launches are
 // the synchronisation, and the output is bit-identical from run to run.
 #include <math.h>
 
+#include "block_prims.h"
 #include "common.h"
 #include "jacobi.h"
 #include "kernels.h"
@@ -28,7 +30,6 @@
 
 namespace adamvs {
 
-static_assert(SIMPLIFY_TILE == 256, "the ballot / LDS layout below assumes four waves of 64");
 constexpr int KEY_BITS = ADAMVS_SIMPLIFY_KEY_BITS;
 
 struct Lattice {
@@ -72,15 +73,6 @@ __global__ __launch_bounds__(256) void k_simplify_corners(const unsigned* __rest
   entry_cell[3 * f + 1] = c1 == c0 ? nc : c1;
   entry_cell[3 * f + 2] = (c2 == c0 || c2 == c1) ? nc : c2;
   survive[f] = (uint8_t)(ok && c0 != c1 && c1 != c2 && c0 != c2);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int off = 32; off >= 1; off >>= 1) v += (unsigned long long)__shfl_xor((long long)v, off, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(256) void k_simplify_accumulate(const Lattice L, const long long* __restrict__ keys, int nc,
@@ -247,20 +239,6 @@ __global__ __launch_bounds__(256) void k_simplify_mark(const int* __restrict__ f
   }
 }
 
-// rank of a flagged lane among the flagged lanes of its workgroup (every lane must call it); *total = their number
-__device__ __forceinline__ unsigned block_rank(bool flag, unsigned* total) {
-  __shared__ unsigned wave_n[4];
-  const unsigned long long bal = __ballot(flag);
-  const unsigned lane_rank = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-  if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = (unsigned)__popcll(bal);
-  __syncthreads();
-  const int wv = threadIdx.x >> 6;
-  unsigned rank = lane_rank;
-  for (int i = 0; i < wv; ++i) rank += wave_n[i];
-  *total = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
-  return rank;
-}
-
 __global__ __launch_bounds__(256) void k_simplify_count(const uint8_t* __restrict__ flags, long n, unsigned* __restrict__ block_count) {
   const long i = (long)blockIdx.x * SIMPLIFY_TILE + threadIdx.x;
   unsigned total;
@@ -306,17 +284,15 @@ static Lattice lattice(const double* origin, double cell) {
   return L;
 }
 
-static unsigned tiles(long n) { return (unsigned)((n + SIMPLIFY_TILE - 1) / SIMPLIFY_TILE); }
-
 int launch_simplify_keys(const double* origin, double cell, const double* xyz, long nv, long long* keys, uint8_t* bad, hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_keys, dim3(tiles(nv)), dim3(SIMPLIFY_TILE), 0, st, lattice(origin, cell), xyz, nv, keys, bad);
+  hipLaunchKernelGGL(k_simplify_keys, dim3(tiles256(nv)), dim3(SIMPLIFY_TILE), 0, st, lattice(origin, cell), xyz, nv, keys, bad);
   ADAMVS_CHECK_LAUNCH("simplify_keys");
   return 0;
 }
 
 int launch_simplify_corners(const unsigned* faces, long nf, const int* vcell, long nv, int nc, int* fcell, int* entry_cell, uint8_t* survive,
                             hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_corners, dim3(tiles(nf)), dim3(SIMPLIFY_TILE), 0, st, faces, nf, vcell, nv, nc, fcell, entry_cell, survive);
+  hipLaunchKernelGGL(k_simplify_corners, dim3(tiles256(nf)), dim3(SIMPLIFY_TILE), 0, st, faces, nf, vcell, nv, nc, fcell, entry_cell, survive);
   ADAMVS_CHECK_LAUNCH("simplify_corners");
   return 0;
 }
@@ -325,7 +301,7 @@ int launch_simplify_accumulate(const double* origin, double cell, const long lon
                                long nv, const unsigned* faces, long nf, const long long* entry, const long long* fstart,
                                const long long* vorder, const long long* vstart, double* quadric, double* member,
                                unsigned long long* colour, hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_accumulate, dim3(tiles((long)nc * 64)), dim3(SIMPLIFY_TILE), 0, st, lattice(origin, cell), keys, nc, xyz, rgb,
+  hipLaunchKernelGGL(k_simplify_accumulate, dim3(tiles256((long)nc * 64)), dim3(SIMPLIFY_TILE), 0, st, lattice(origin, cell), keys, nc, xyz, rgb,
                      nv, faces, nf, entry, fstart, vorder, vstart, quadric, member, colour);
   ADAMVS_CHECK_LAUNCH("simplify_accumulate");
   return 0;
@@ -334,32 +310,32 @@ int launch_simplify_accumulate(const double* origin, double cell, const long lon
 int launch_simplify_solve(const double* origin, double cell, double rank_eps, const long long* keys, int nc, const double* quadric,
                           const double* member, const unsigned long long* colour, const long long* vstart, double* pos, uint8_t* col,
                           uint8_t* rank, uint8_t* fallback, double* error, hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_solve, dim3(tiles(nc)), dim3(SIMPLIFY_TILE), 0, st, lattice(origin, cell), rank_eps, keys, nc, quadric,
+  hipLaunchKernelGGL(k_simplify_solve, dim3(tiles256(nc)), dim3(SIMPLIFY_TILE), 0, st, lattice(origin, cell), rank_eps, keys, nc, quadric,
                      member, colour, vstart, pos, col, rank, fallback, error);
   ADAMVS_CHECK_LAUNCH("simplify_solve");
   return 0;
 }
 
 int launch_simplify_triples(const int* fcell, long nf, const long long* surv, long ns, int* tri, hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_triples, dim3(tiles(ns)), dim3(SIMPLIFY_TILE), 0, st, fcell, nf, surv, ns, tri);
+  hipLaunchKernelGGL(k_simplify_triples, dim3(tiles256(ns)), dim3(SIMPLIFY_TILE), 0, st, fcell, nf, surv, ns, tri);
   ADAMVS_CHECK_LAUNCH("simplify_triples");
   return 0;
 }
 
 int launch_simplify_first(const int* tri, const long long* surv, const long long* order, long ns, long nf, uint8_t* keep, hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_first, dim3(tiles(ns)), dim3(SIMPLIFY_TILE), 0, st, tri, surv, order, ns, nf, keep);
+  hipLaunchKernelGGL(k_simplify_first, dim3(tiles256(ns)), dim3(SIMPLIFY_TILE), 0, st, tri, surv, order, ns, nf, keep);
   ADAMVS_CHECK_LAUNCH("simplify_first");
   return 0;
 }
 
 int launch_simplify_mark(const int* fcell, const uint8_t* keep, long nf, int nc, uint8_t* used, hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_mark, dim3(tiles(nf)), dim3(SIMPLIFY_TILE), 0, st, fcell, keep, nf, nc, used);
+  hipLaunchKernelGGL(k_simplify_mark, dim3(tiles256(nf)), dim3(SIMPLIFY_TILE), 0, st, fcell, keep, nf, nc, used);
   ADAMVS_CHECK_LAUNCH("simplify_mark");
   return 0;
 }
 
 int launch_simplify_count(const uint8_t* flags, long n, unsigned* block_count, hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_count, dim3(tiles(n)), dim3(SIMPLIFY_TILE), 0, st, flags, n, block_count);
+  hipLaunchKernelGGL(k_simplify_count, dim3(tiles256(n)), dim3(SIMPLIFY_TILE), 0, st, flags, n, block_count);
   ADAMVS_CHECK_LAUNCH("simplify_count");
   return 0;
 }
@@ -367,10 +343,10 @@ int launch_simplify_count(const uint8_t* flags, long n, unsigned* block_count, h
 int launch_simplify_emit(const double* pos, const uint8_t* col, const uint8_t* used, int nc, const unsigned* cell_offsets, const int* fcell,
                          const uint8_t* keep, long nf, const unsigned* face_offsets, double* xyz, uint8_t* rgb, unsigned* new_index,
                          long vert_capacity, unsigned* faces, long face_capacity, hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_emit_vertices, dim3(tiles(nc)), dim3(SIMPLIFY_TILE), 0, st, pos, col, used, nc, cell_offsets, xyz, rgb,
+  hipLaunchKernelGGL(k_simplify_emit_vertices, dim3(tiles256(nc)), dim3(SIMPLIFY_TILE), 0, st, pos, col, used, nc, cell_offsets, xyz, rgb,
                      new_index, vert_capacity);
   ADAMVS_CHECK_LAUNCH("simplify_emit_vertices");
-  hipLaunchKernelGGL(k_simplify_emit_faces, dim3(tiles(nf)), dim3(SIMPLIFY_TILE), 0, st, fcell, keep, nf, nc, new_index, face_offsets, faces,
+  hipLaunchKernelGGL(k_simplify_emit_faces, dim3(tiles256(nf)), dim3(SIMPLIFY_TILE), 0, st, fcell, keep, nf, nc, new_index, face_offsets, faces,
                      face_capacity);
   ADAMVS_CHECK_LAUNCH("simplify_emit_faces");
   return 0;

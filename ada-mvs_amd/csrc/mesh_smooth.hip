@@ -4,7 +4,8 @@
 // is here, one lane per element:
 //
 //   k_smooth_faces      one lane per face: the 64-byte record  centroid, area | normal, 0  of step 1
-//   k_smooth_edge_keys  one lane per face: the three keys  min << 32 | max  of its corner pairs (the caller sorts them)
+//   k_mesh_edge_keys    one lane per edge: the key  min << 32 | max  of its corner pair (the caller sorts them); the one edge-key
+//                       kernel of the library, behind adamvs_smooth_edge_keys and adamvs_texture_edge_keys
 //   k_smooth_boundary   one lane per sorted key: a run of length one stores 1 at both ends of the edge (plain stores)
 //   k_smooth_filter     one lane per face: the bilateral sum over N(f), gathered through the vertex -> face runs in the header's
 //                       order; whether a face already appeared at an earlier corner is decided by comparing its three vertex
@@ -16,6 +17,7 @@
 // sorted input, the launches are the synchronisation, and the output is bit-identical from run to run.
 #include <math.h>
 
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -23,8 +25,6 @@
 #pragma clang fp contract(off)
 
 namespace adamvs {
-
-static_assert(SMOOTH_TILE == 256, "the launches below assume workgroups of 256 lanes");
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -52,23 +52,20 @@ __global__ __launch_bounds__(256) void k_smooth_faces(const double* __restrict__
   rec[2 * f + 1] = hi;
 }
 
-__global__ __launch_bounds__(256) void k_smooth_edge_keys(const unsigned* __restrict__ faces, long nf, long long* __restrict__ keys) {
-  const long f = (long)blockIdx.x * SMOOTH_TILE + threadIdx.x;
-  if (f >= nf) return;
-  const unsigned v[3] = {faces[3 * f], faces[3 * f + 1], faces[3 * f + 2]};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const unsigned a = v[k], b = v[(k + 1) % 3];
-    const unsigned lo = a < b ? a : b, hi = a < b ? b : a;
-    keys[3 * f + k] = (long long)(((unsigned long long)lo << 32) | hi);
-  }
+// one lane per edge, so consecutive lanes store consecutive keys; mesh cleaning and texturing take their keys from here too
+__global__ __launch_bounds__(256) void k_mesh_edge_keys(const unsigned* __restrict__ faces, long n, long long* __restrict__ keys) {
+  const long e = (long)blockIdx.x * SMOOTH_TILE + threadIdx.x;
+  if (e >= n) return;
+  unsigned a, b;
+  half_edge(faces, e, a, b);
+  keys[e] = edge_key(a, b);
 }
 
 __global__ __launch_bounds__(256) void k_smooth_boundary(const long long* __restrict__ keys, long n, long nv, uint8_t* __restrict__ fixed) {
   const long i = (long)blockIdx.x * SMOOTH_TILE + threadIdx.x;
   if (i >= n) return;
+  if (!key_occurs_once(keys, i, n)) return;
   const long long key = keys[i];
-  if ((i > 0 && keys[i - 1] == key) || (i + 1 < n && keys[i + 1] == key)) return;
   const long lo = (long)((unsigned long long)key >> 32), hi = (long)((unsigned long long)key & 0xFFFFFFFFull);
   if (lo < nv) fixed[lo] = 1;
   if (hi < nv) fixed[hi] = 1;
@@ -183,22 +180,21 @@ __global__ __launch_bounds__(256) void k_smooth_update(const double* __restrict_
 }
 
 // ---- launches -----------------------------------------------------------------------------------------------------------
-static unsigned smooth_tiles(long n) { return (unsigned)((n + SMOOTH_TILE - 1) / SMOOTH_TILE); }
-
 int launch_smooth_faces(const double* p, long nv, const unsigned* faces, long nf, double* rec, hipStream_t st) {
-  hipLaunchKernelGGL(k_smooth_faces, dim3(smooth_tiles(nf)), dim3(SMOOTH_TILE), 0, st, p, nv, faces, nf, (double4_t*)rec);
+  hipLaunchKernelGGL(k_smooth_faces, dim3(tiles256(nf)), dim3(SMOOTH_TILE), 0, st, p, nv, faces, nf, (double4_t*)rec);
   ADAMVS_CHECK_LAUNCH("smooth_faces");
   return 0;
 }
 
-int launch_smooth_edge_keys(const unsigned* faces, long nf, long long* keys, hipStream_t st) {
-  hipLaunchKernelGGL(k_smooth_edge_keys, dim3(smooth_tiles(nf)), dim3(SMOOTH_TILE), 0, st, faces, nf, keys);
-  ADAMVS_CHECK_LAUNCH("smooth_edge_keys");
+int launch_mesh_edge_keys(const unsigned* faces, long nf, long long* keys, const char* what, hipStream_t st) {
+  if (nf == 0) return 0;
+  hipLaunchKernelGGL(k_mesh_edge_keys, dim3(tiles256(3 * nf)), dim3(SMOOTH_TILE), 0, st, faces, 3 * nf, keys);
+  ADAMVS_CHECK_LAUNCH(what);
   return 0;
 }
 
 int launch_smooth_boundary(const long long* keys, long n, long nv, uint8_t* fixed, hipStream_t st) {
-  hipLaunchKernelGGL(k_smooth_boundary, dim3(smooth_tiles(n)), dim3(SMOOTH_TILE), 0, st, keys, n, nv, fixed);
+  hipLaunchKernelGGL(k_smooth_boundary, dim3(tiles256(n)), dim3(SMOOTH_TILE), 0, st, keys, n, nv, fixed);
   ADAMVS_CHECK_LAUNCH("smooth_boundary");
   return 0;
 }
@@ -206,21 +202,21 @@ int launch_smooth_boundary(const long long* keys, long n, long nv, uint8_t* fixe
 int launch_smooth_filter(const double* rec, const double* nin, double* nout, const unsigned* faces, long nf, long nv, const int* vface,
                          const long long* vstart, double sigma_s, double sigma_r, hipStream_t st) {
   const double ds = 2.0 * sigma_s * sigma_s, dr = 2.0 * sigma_r * sigma_r;
-  hipLaunchKernelGGL(k_smooth_filter, dim3(smooth_tiles(nf)), dim3(SMOOTH_TILE), 0, st, (const double4_t*)rec, nin, nout, faces, nf, nv, vface,
+  hipLaunchKernelGGL(k_smooth_filter, dim3(tiles256(nf)), dim3(SMOOTH_TILE), 0, st, (const double4_t*)rec, nin, nout, faces, nf, nv, vface,
                      vstart, ds, dr);
   ADAMVS_CHECK_LAUNCH("smooth_filter");
   return 0;
 }
 
 int launch_smooth_centroids(const double* p, long nv, const unsigned* faces, long nf, double* cen, hipStream_t st) {
-  hipLaunchKernelGGL(k_smooth_centroids, dim3(smooth_tiles(nf)), dim3(SMOOTH_TILE), 0, st, p, nv, faces, nf, cen);
+  hipLaunchKernelGGL(k_smooth_centroids, dim3(tiles256(nf)), dim3(SMOOTH_TILE), 0, st, p, nv, faces, nf, cen);
   ADAMVS_CHECK_LAUNCH("smooth_centroids");
   return 0;
 }
 
 int launch_smooth_update(const double* p0, const double* p, double* pout, long nv, const double* nrm, const double* cen, long nf,
                          const int* vface, const long long* vstart, const uint8_t* fixed, double cap, uint8_t* clamped, hipStream_t st) {
-  hipLaunchKernelGGL(k_smooth_update, dim3(smooth_tiles(nv)), dim3(SMOOTH_TILE), 0, st, p0, p, pout, nv, nrm, cen, nf, vface, vstart, fixed, cap,
+  hipLaunchKernelGGL(k_smooth_update, dim3(tiles256(nv)), dim3(SMOOTH_TILE), 0, st, p0, p, pout, nv, nrm, cen, nf, vface, vstart, fixed, cap,
                      clamped);
   ADAMVS_CHECK_LAUNCH("smooth_update");
   return 0;

@@ -10,9 +10,9 @@
 //
 // then once:
 //
-//   k_tex_edge_keys     3 F keys min(a, b) << 32 | max(a, b) (the host sorts them by key, then label, then entry)
+//   (k_mesh_edge_keys of mesh_smooth.hip: 3 F keys min(a, b) << 32 | max(a, b); the host sorts them by key, then label, then entry)
 //   k_tex_hook          one lane per sorted entry: two neighbours with the same key and label hook their roots
-//   k_tex_compress      one lane per face: pointer jumping to the root (each lane writes its own entry only)
+//   k_tex_compress      one lane per face: the walk to the root (block_prims.h compress_to_root; each lane writes its own entry only)
 //   k_tex_count         per workgroup: chart roots and untextured faces
 //   k_tex_rank          chart id of every root and palette index of every untextured face (ballot / mbcnt + a scan)
 //   k_tex_boxes         one lane per textured face: its chart id and the chart's integer pixel box (atomic min / max)
@@ -23,6 +23,7 @@
 // large-face list counter (decides only which wave writes which min) and the hook's min on a parent (the result of a round
 // may depend on the order, the fixed point does not: every chart's root is its smallest face).  Everything else is owned by
 // one lane, so the outputs are bit-identical from run to run.
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
 #include "persistent.h"
@@ -33,10 +34,6 @@
 #pragma clang fp contract(off)
 
 namespace adamvs {
-
-static_assert(TEX_TILE == 256, "kernels below assume workgroups of four waves");
-
-static unsigned tex_blocks(long n) { return (unsigned)((n + TEX_TILE - 1) / TEX_TILE); }
 
 // ---- labelling ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_tex_project(const ViewCam c, const double* __restrict__ xyz, long nv, f32x4* __restrict__ uvz) {
@@ -141,16 +138,6 @@ __global__ __launch_bounds__(256) void k_tex_score(int W, int H, int view, const
 }
 
 // ---- charts ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_tex_edge_keys(const unsigned* __restrict__ faces, long nf, long long* __restrict__ keys) {
-  const long e = (long)blockIdx.x * TEX_TILE + threadIdx.x;
-  if (e >= 3 * nf) return;
-  const long f = e / 3;
-  const int k = (int)(e - 3 * f);
-  const unsigned a = faces[3 * f + k], b = faces[3 * f + (k == 2 ? 0 : k + 1)];
-  const unsigned lo = a < b ? a : b, hi = a < b ? b : a;
-  keys[e] = (long long)(((unsigned long long)lo << 32) | hi);
-}
-
 __global__ __launch_bounds__(256) void k_tex_hook(const long long* __restrict__ keys, const long long* __restrict__ entry, long n,
                                                   const int* __restrict__ label, int* parent, unsigned* __restrict__ changed) {
   const long i = (long)blockIdx.x * TEX_TILE + threadIdx.x;
@@ -164,14 +151,9 @@ __global__ __launch_bounds__(256) void k_tex_hook(const long long* __restrict__ 
   changed[0] = 1u;
 }
 
-// parent[x] <= x everywhere and other lanes only lower their own entries to ancestors: the walk ends at the root
 __global__ __launch_bounds__(256) void k_tex_compress(int* parent, long nf) {
   const long f = (long)blockIdx.x * TEX_TILE + threadIdx.x;
-  if (f >= nf) return;
-  const int p0 = parent[f];
-  int p = p0;
-  for (int q = parent[p]; q != p; q = parent[p]) p = q;
-  if (p != p0) parent[f] = p;
+  if (f < nf) compress_to_root(parent, f);
 }
 
 __global__ __launch_bounds__(256) void k_tex_count(const int* __restrict__ label, const int* __restrict__ parent, long nf,
@@ -190,10 +172,6 @@ __global__ __launch_bounds__(256) void k_tex_count(const int* __restrict__ label
     block_roots[blockIdx.x] = wr[0] + wr[1] + wr[2] + wr[3];
     block_untex[blockIdx.x] = wu[0] + wu[1] + wu[2] + wu[3];
   }
-}
-
-__device__ __forceinline__ unsigned lane_rank(unsigned long long bal) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
 }
 
 __global__ __launch_bounds__(256) void k_tex_rank(const int* __restrict__ label, const int* __restrict__ parent, long nf,
@@ -222,14 +200,6 @@ __global__ __launch_bounds__(256) void k_tex_rank(const int* __restrict__ label,
 
 // Neighbouring faces mostly share a chart, and a large chart's four box words would serialise every lane's atomics: the lanes
 // of a wave that share the chart of the first remaining lane reduce their extremes first and one of them issues the atomics.
-__device__ __forceinline__ int wave_min(int x) {
-  for (int m = 32; m >= 1; m >>= 1) {
-    const int y = __shfl_xor(x, m);
-    x = y < x ? y : x;
-  }
-  return x;
-}
-
 __global__ __launch_bounds__(256) void k_tex_boxes(const int* __restrict__ label, const int* __restrict__ parent,
                                                    const int* __restrict__ root_chart, const float* __restrict__ uv, long nf,
                                                    int* __restrict__ chart, int* __restrict__ box) {
@@ -327,7 +297,7 @@ __global__ __launch_bounds__(256) void k_tex_coords(const int* __restrict__ labe
 // ---- launchers ------------------------------------------------------------------------------------------------------
 int launch_tex_project(const adamvs_ortho_view& v, const double* xyz, long nv, float* uvz, hipStream_t st) {
   if (nv == 0) return 0;
-  hipLaunchKernelGGL(k_tex_project, dim3(tex_blocks(nv)), dim3(TEX_TILE), 0, st, view_cam(v), xyz, nv, (f32x4*)uvz);
+  hipLaunchKernelGGL(k_tex_project, dim3(tiles256(nv)), dim3(TEX_TILE), 0, st, view_cam(v), xyz, nv, (f32x4*)uvz);
   ADAMVS_CHECK_LAUNCH("texture_project");
   return 0;
 }
@@ -335,12 +305,12 @@ int launch_tex_project(const adamvs_ortho_view& v, const double* xyz, long nv, f
 int launch_tex_zbuf(int W, int H, const float* uvz, long nv, const unsigned* faces, long nf, unsigned* zbuf, unsigned* big_count,
                     unsigned* big_list, hipStream_t st) {
   const long npx = (long)W * H;
-  hipLaunchKernelGGL(k_tex_zbuf_clear, dim3(tex_blocks(npx)), dim3(TEX_TILE), 0, st, zbuf, npx);
+  hipLaunchKernelGGL(k_tex_zbuf_clear, dim3(tiles256(npx)), dim3(TEX_TILE), 0, st, zbuf, npx);
   ADAMVS_CHECK_LAUNCH("texture_zbuf_clear");
   if (nf == 0) return 0;
   hipError_t e = hipMemsetAsync(big_count, 0, sizeof(unsigned), st);
   if (e != hipSuccess) return set_error((int)e, "texture_zbuf: hipMemsetAsync: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(k_tex_zbuf_small, dim3(tex_blocks(nf)), dim3(TEX_TILE), 0, st, W, H, (const f32x4*)uvz, nv, faces, nf, zbuf, big_count,
+  hipLaunchKernelGGL(k_tex_zbuf_small, dim3(tiles256(nf)), dim3(TEX_TILE), 0, st, W, H, (const f32x4*)uvz, nv, faces, nf, zbuf, big_count,
                      big_list);
   ADAMVS_CHECK_LAUNCH("texture_zbuf_small");
   // the list length is known on the device only: a resident grid strides over it, one wave per face
@@ -351,16 +321,9 @@ int launch_tex_zbuf(int W, int H, const float* uvz, long nv, const unsigned* fac
 int launch_tex_score(int W, int H, int view, const float* uvz, long nv, const unsigned* faces, long nf, const unsigned* zbuf, float border,
                      float tol, float* best, int* label, int* nvis, float* uv, hipStream_t st) {
   if (nf == 0) return 0;
-  hipLaunchKernelGGL(k_tex_score, dim3(tex_blocks(nf)), dim3(TEX_TILE), 0, st, W, H, view, (const f32x4*)uvz, nv, faces, nf, zbuf, border, tol,
+  hipLaunchKernelGGL(k_tex_score, dim3(tiles256(nf)), dim3(TEX_TILE), 0, st, W, H, view, (const f32x4*)uvz, nv, faces, nf, zbuf, border, tol,
                      best, label, nvis, uv);
   ADAMVS_CHECK_LAUNCH("texture_score");
-  return 0;
-}
-
-int launch_tex_edge_keys(const unsigned* faces, long nf, long long* keys, hipStream_t st) {
-  if (nf == 0) return 0;
-  hipLaunchKernelGGL(k_tex_edge_keys, dim3(tex_blocks(3 * nf)), dim3(TEX_TILE), 0, st, faces, nf, keys);
-  ADAMVS_CHECK_LAUNCH("texture_edge_keys");
   return 0;
 }
 
@@ -369,11 +332,11 @@ int launch_tex_components_round(const long long* keys, const long long* entry, l
   hipError_t e = hipMemsetAsync(changed, 0, sizeof(unsigned), st);
   if (e != hipSuccess) return set_error((int)e, "texture_components: hipMemsetAsync: %s", hipGetErrorString(e));
   if (n > 1) {
-    hipLaunchKernelGGL(k_tex_hook, dim3(tex_blocks(n - 1)), dim3(TEX_TILE), 0, st, keys, entry, n, label, parent, changed);
+    hipLaunchKernelGGL(k_tex_hook, dim3(tiles256(n - 1)), dim3(TEX_TILE), 0, st, keys, entry, n, label, parent, changed);
     ADAMVS_CHECK_LAUNCH("texture_hook");
   }
   if (nf > 0) {
-    hipLaunchKernelGGL(k_tex_compress, dim3(tex_blocks(nf)), dim3(TEX_TILE), 0, st, parent, nf);
+    hipLaunchKernelGGL(k_tex_compress, dim3(tiles256(nf)), dim3(TEX_TILE), 0, st, parent, nf);
     ADAMVS_CHECK_LAUNCH("texture_compress");
   }
   return 0;
@@ -382,7 +345,7 @@ int launch_tex_components_round(const long long* keys, const long long* entry, l
 int launch_tex_rank(const int* label, const int* parent, long nf, unsigned* block_roots, unsigned* block_untex, unsigned* root_off,
                     unsigned* untex_off, int* root_chart, int* pal, hipStream_t st) {
   if (nf == 0) return 0;
-  const int nb = (int)tex_blocks(nf);
+  const int nb = (int)tiles256(nf);
   hipLaunchKernelGGL(k_tex_count, dim3(nb), dim3(TEX_TILE), 0, st, label, parent, nf, block_roots, block_untex);
   ADAMVS_CHECK_LAUNCH("texture_count");
   if (int rc = launch_fusion_scan(block_roots, root_off, nb, st)) return rc;
@@ -396,7 +359,7 @@ int launch_tex_rank(const int* label, const int* parent, long nf, unsigned* bloc
 int launch_tex_boxes(const int* label, const int* parent, const int* root_chart, const float* uv, long nf, int* chart, int* box,
                      hipStream_t st) {
   if (nf == 0) return 0;
-  hipLaunchKernelGGL(k_tex_boxes, dim3(tex_blocks(nf)), dim3(TEX_TILE), 0, st, label, parent, root_chart, uv, nf, chart, box);
+  hipLaunchKernelGGL(k_tex_boxes, dim3(tiles256(nf)), dim3(TEX_TILE), 0, st, label, parent, root_chart, uv, nf, chart, box);
   ADAMVS_CHECK_LAUNCH("texture_boxes");
   return 0;
 }
@@ -404,7 +367,7 @@ int launch_tex_boxes(const int* label, const int* parent, const int* root_chart,
 int launch_tex_fill(const adamvs_ortho_view& v, const int* items, const long long* prefix, int n, long texels, int P, long pages,
                     unsigned char* atlas, hipStream_t st) {
   if (n == 0 || texels == 0) return 0;
-  hipLaunchKernelGGL(k_tex_fill, dim3(tex_blocks(texels)), dim3(TEX_TILE), 0, st, (const unsigned*)v.rgba, v.W, v.H, items, prefix, n, P,
+  hipLaunchKernelGGL(k_tex_fill, dim3(tiles256(texels)), dim3(TEX_TILE), 0, st, (const unsigned*)v.rgba, v.W, v.H, items, prefix, n, P,
                      pages, (unsigned*)atlas);
   ADAMVS_CHECK_LAUNCH("texture_fill");
   return 0;
@@ -414,7 +377,7 @@ int launch_tex_coords(const int* label, const int* chart, const int* pal, const 
                       int pal_oy, int pal_page, int P, long pages, const unsigned* faces, long nv, const unsigned char* vrgb,
                       unsigned char* atlas, float* tc, int* texnum, hipStream_t st) {
   if (nf == 0) return 0;
-  hipLaunchKernelGGL(k_tex_coords, dim3(tex_blocks(nf)), dim3(TEX_TILE), 0, st, label, chart, pal, uv, nf, charts, pal_ox, pal_oy, pal_page,
+  hipLaunchKernelGGL(k_tex_coords, dim3(tiles256(nf)), dim3(TEX_TILE), 0, st, label, chart, pal, uv, nf, charts, pal_ox, pal_oy, pal_page,
                      P, pages, faces, nv, vrgb, (unsigned*)atlas, tc, texnum);
   ADAMVS_CHECK_LAUNCH("texture_coords");
   return 0;

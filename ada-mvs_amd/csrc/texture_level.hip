@@ -21,6 +21,7 @@
 // a fixed order.  The scalars and the stop flag stay on the device (state[]): once the flag is set every later launch
 // returns without writing, so g and the iteration count are those of the stopping iteration.  The only atomics are the
 // owner's integer min (order-independent) and the large-face list counter.
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
 #include "persistent.h"
@@ -32,15 +33,13 @@
 
 namespace adamvs {
 
-static unsigned lvl_blocks(long n) { return (unsigned)((n + TEX_TILE - 1) / TEX_TILE); }
-
 constexpr int LVL_BATCH = 8;                  // CSR entries of a row in flight at once in the SpMV
 constexpr unsigned LVL_DATA = 0x80000000u, LVL_SEAM = 0x40000000u, LVL_INDEX = 0x3FFFFFFFu;
 // state[]: r.r, b.b, alpha, beta per channel, the stop flag, the iteration count, tol^2
 constexpr int ST_RR = 0, ST_BB = 3, ST_ALPHA = 6, ST_BETA = 9, ST_DONE = 12, ST_ITERS = 13, ST_TOL2 = 14;
 
 static int lvl_grid(long n) {
-  const long b = (n + TEX_TILE - 1) / TEX_TILE;
+  const long b = tiles256(n);
   return (int)(b < 1 ? 1 : (b < TEX_LEVEL_BLOCKS ? b : TEX_LEVEL_BLOCKS));
 }
 
@@ -425,14 +424,14 @@ __global__ __launch_bounds__(256) void k_lvl_apply(const float* __restrict__ uv,
 int launch_lvl_observe(const long long* view_tab, int nviews, const int* rowptr, const unsigned* col, long nnz, const int* node_view,
                        const float* pos, long n, float* f, hipStream_t st) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(k_lvl_observe, dim3(lvl_blocks(n)), dim3(TEX_TILE), 0, st, view_tab, nviews, rowptr, col, nnz, node_view, pos, n, f);
+  hipLaunchKernelGGL(k_lvl_observe, dim3(tiles256(n)), dim3(TEX_TILE), 0, st, view_tab, nviews, rowptr, col, nnz, node_view, pos, n, f);
   ADAMVS_CHECK_LAUNCH("texture_level_observe");
   return 0;
 }
 
 int launch_lvl_rhs(const int* rowptr, const unsigned* col, long nnz, const float* f, long n, double* b, hipStream_t st) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(k_lvl_rhs, dim3(lvl_blocks(n)), dim3(TEX_TILE), 0, st, rowptr, col, nnz, f, n, b);
+  hipLaunchKernelGGL(k_lvl_rhs, dim3(tiles256(n)), dim3(TEX_TILE), 0, st, rowptr, col, nnz, f, n, b);
   ADAMVS_CHECK_LAUNCH("texture_level_rhs");
   return 0;
 }
@@ -471,12 +470,12 @@ int launch_lvl_cg(const int* rowptr, const unsigned* col, long nnz, long n, doub
 int launch_lvl_owner(const float* uv, const int* chart, long nf, const int* charts, const long long* prefix, int nc, long texels,
                      int* owner, unsigned* big_count, unsigned* big_list, hipStream_t st) {
   if (texels == 0) return 0;
-  hipLaunchKernelGGL(k_lvl_owner_clear, dim3(lvl_blocks(texels)), dim3(TEX_TILE), 0, st, owner, texels);
+  hipLaunchKernelGGL(k_lvl_owner_clear, dim3(tiles256(texels)), dim3(TEX_TILE), 0, st, owner, texels);
   ADAMVS_CHECK_LAUNCH("texture_level_owner_clear");
   if (nf == 0 || nc == 0) return 0;
   hipError_t e = hipMemsetAsync(big_count, 0, sizeof(unsigned), st);
   if (e != hipSuccess) return set_error((int)e, "texture_level_owner: hipMemsetAsync: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(k_lvl_owner_small, dim3(lvl_blocks(nf)), dim3(TEX_TILE), 0, st, uv, chart, nf, charts, prefix, nc, texels, owner,
+  hipLaunchKernelGGL(k_lvl_owner_small, dim3(tiles256(nf)), dim3(TEX_TILE), 0, st, uv, chart, nf, charts, prefix, nc, texels, owner,
                      big_count, big_list);
   ADAMVS_CHECK_LAUNCH("texture_level_owner_small");
   return launch_resident<k_lvl_owner_large>((nf + 3) / 4, 0, st, "texture_level_owner_large", uv, chart, nf, charts, prefix, nc, texels,
@@ -485,7 +484,7 @@ int launch_lvl_owner(const float* uv, const int* chart, long nf, const int* char
 
 int launch_lvl_dilate(const int* charts, const long long* prefix, int nc, long texels, const int* in, int* out, hipStream_t st) {
   if (texels == 0 || nc == 0) return 0;
-  hipLaunchKernelGGL(k_lvl_dilate, dim3(lvl_blocks(texels)), dim3(TEX_TILE), 0, st, charts, prefix, nc, in, out);
+  hipLaunchKernelGGL(k_lvl_dilate, dim3(tiles256(texels)), dim3(TEX_TILE), 0, st, charts, prefix, nc, in, out);
   ADAMVS_CHECK_LAUNCH("texture_level_dilate");
   return 0;
 }
@@ -494,7 +493,7 @@ int launch_lvl_apply(const float* uv, const int* corner_node, long nf, const dou
                      const long long* prefix, int nc, long texels, const int* owner, int P, long pages, unsigned char* atlas,
                      hipStream_t st) {
   if (texels == 0 || nc == 0 || nf == 0) return 0;
-  hipLaunchKernelGGL(k_lvl_apply, dim3(lvl_blocks(texels)), dim3(TEX_TILE), 0, st, uv, corner_node, nf, g, n, charts, prefix, nc, owner, P,
+  hipLaunchKernelGGL(k_lvl_apply, dim3(tiles256(texels)), dim3(TEX_TILE), 0, st, uv, corner_node, nf, g, n, charts, prefix, nc, owner, P,
                      pages, (unsigned*)atlas);
   ADAMVS_CHECK_LAUNCH("texture_level_apply");
   return 0;

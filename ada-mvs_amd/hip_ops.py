@@ -1071,16 +1071,20 @@ def smooth_faces(p, faces):
     return rec
 
 
+def _edge_keys(what, faces):
+    """adamvs_<what> (smooth_edge_keys or texture_edge_keys: one kernel behind both) -> keys int64 [3 nf], entry 3 f + k: edge k of
+    face f as min << 32 | max."""
+    keys = torch.empty(3 * faces.shape[0], device=faces.device, dtype=torch.int64)
+    check(getattr(_lib.load(), "adamvs_" + what)(_p(faces), faces.shape[0], _p(keys), _stream()), what)
+    return keys
+
+
 def smooth_boundary(faces, nv):
     """adamvs_smooth_edge_keys, a sort of the keys, adamvs_smooth_boundary -> fixed [nv] uint8: the ends of every edge that occurs once."""
     faces = _dev_as(faces, "faces", torch.int32)
-    nf = faces.shape[0]
-    keys = torch.empty(3 * nf, device=faces.device, dtype=torch.int64)
     fixed = torch.zeros(int(nv), device=faces.device, dtype=torch.uint8)
-    lib, st = _lib.load(), _stream()
-    check(lib.adamvs_smooth_edge_keys(_p(faces), nf, _p(keys), st), "smooth_edge_keys")
-    keys = torch.sort(keys, stable=True).values
-    check(lib.adamvs_smooth_boundary(_p(keys), 3 * nf, int(nv), _p(fixed), st), "smooth_boundary")
+    keys = torch.sort(_edge_keys("smooth_edge_keys", faces), stable=True).values
+    check(_lib.load().adamvs_smooth_boundary(_p(keys), keys.numel(), int(nv), _p(fixed), _stream()), "smooth_boundary")
     return fixed
 
 
@@ -1182,13 +1186,10 @@ def clean_boundary(faces):
     """adamvs_smooth_edge_keys, a stable sort of the keys, adamvs_clean_boundary -> bnd [3 ns] uint8: the half-edges whose key occurs once."""
     faces = _clean_faces(faces)
     ns = faces.shape[0]
-    keys = torch.empty(3 * ns, device=faces.device, dtype=torch.int64)
     bnd = torch.empty(3 * ns, device=faces.device, dtype=torch.uint8)
-    lib, st = _lib.load(), _stream()
-    check(lib.adamvs_smooth_edge_keys(_p(faces), ns, _p(keys), st), "smooth_edge_keys")
-    es = torch.sort(keys, stable=True)
+    es = torch.sort(_edge_keys("smooth_edge_keys", faces), stable=True)
     ks, entry = es.values.contiguous(), es.indices.contiguous()
-    check(lib.adamvs_clean_boundary(_p(ks), _p(entry), ns, _p(bnd), st), "clean_boundary")
+    check(_lib.load().adamvs_clean_boundary(_p(ks), _p(entry), ns, _p(bnd), _stream()), "clean_boundary")
     return bnd
 
 
@@ -1400,10 +1401,7 @@ def texture_score(view, view_index, uvz, faces, zbuf, border, tol, best, label, 
 
 def texture_edge_keys(faces):
     """adamvs_texture_edge_keys -> keys int64 [3 nf] (entry 3 f + k: edge k of face f as min << 32 | max)."""
-    faces = _dev_as(faces, "faces", torch.int32)
-    keys = torch.empty(3 * faces.shape[0], device=faces.device, dtype=torch.int64)
-    check(_lib.load().adamvs_texture_edge_keys(_p(faces), faces.shape[0], _p(keys), _stream()), "texture_edge_keys")
-    return keys
+    return _edge_keys("texture_edge_keys", _dev_as(faces, "faces", torch.int32))
 
 
 def texture_components_round(keys_sorted, entry, label, parent, changed):

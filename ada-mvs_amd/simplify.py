@@ -21,17 +21,15 @@ origin is (the volume origin of `<mesh>.json`, else the per-axis vertex minimum)
 height sits exactly on a cell boundary and splits into two sheets of cells.
 """
 import argparse
-import json
 import math
-import os
 import sys
-import time
 
 import numpy as np
 
-CARRIED = ("voxel", "mu", "origin", "views")      # of <mesh>.json, unchanged into <out>.json
+from . import mesh_stage
+from .mesh_stage import CARRIED, MAX_COUNT, mesh_path_of  # noqa: F401  (shared with smooth.py and clean.py)
+
 DEFAULT_CELL_VOXELS = 4.0
-MAX_COUNT = (1 << 31) - 1
 
 
 def check_options(cell, rank_eps=1e-3):
@@ -42,7 +40,7 @@ def check_options(cell, rank_eps=1e-3):
 
 
 def default_out(mesh_path):
-    return (mesh_path[:-4] if mesh_path.lower().endswith(".ply") else mesh_path) + "_simplified.ply"
+    return mesh_stage.default_out(mesh_path, "_simplified")
 
 
 def default_lattice_origin(cell, meta_origin, vertex_min):
@@ -56,34 +54,24 @@ def default_lattice_origin(cell, meta_origin, vertex_min):
     return o
 
 
+def _check_size(name, v):
+    """cell as check_options has it; cell_voxels is whatever float() takes."""
+    if name == "cell":
+        check_options(v)
+    elif not (math.isfinite(float(v)) and float(v) > 0):
+        raise ValueError("%s=%r must be finite and > 0" % (name, v))
+
+
 def resolve_cell(cell, cell_voxels, meta):
     """--cell M, or --cell_voxels K (default 4) times the voxel of <mesh>.json."""
-    if cell is not None and cell_voxels is not None:
-        raise ValueError("give --cell or --cell_voxels, not both")
-    if cell is not None:
-        check_options(cell)
-        return float(cell)
-    k = DEFAULT_CELL_VOXELS if cell_voxels is None else float(cell_voxels)
-    if not (math.isfinite(k) and k > 0):
-        raise ValueError("cell_voxels=%r must be finite and > 0" % (cell_voxels,))
-    if meta is None or "voxel" not in meta:
-        raise ValueError("<mesh>.json with the voxel size is absent: give --cell")
-    return k * float(meta["voxel"])
+    return mesh_stage.resolve_metres("cell", cell, cell_voxels, DEFAULT_CELL_VOXELS, meta, check=_check_size)
 
 
 def summary(meta, info, cell, lattice_origin, source, out, seconds, device_seconds):
     """The dict written to <out>.json: the carried keys of <mesh>.json first, unchanged."""
-    res = {k: meta[k] for k in CARRIED if meta is not None and k in meta}
-    res.update(cell=float(cell), lattice_origin=[float(v) for v in lattice_origin], source=source, ply=out)
-    res.update(info)
-    res.update(vertices=int(info["cells_used"]), faces=int(info["faces_out"]), seconds=float(seconds), device_seconds=float(device_seconds))
-    return res
-
-
-def _empty(device):
-    import torch
-    return (torch.empty(0, 3, device=device, dtype=torch.float64), torch.empty(0, 3, device=device, dtype=torch.uint8),
-            torch.empty(0, 3, device=device, dtype=torch.int32))
+    return mesh_stage.summary(meta, dict(cell=float(cell), lattice_origin=[float(v) for v in lattice_origin], source=source, ply=out), info,
+                              vertices=int(info["cells_used"]), faces=int(info["faces_out"]), seconds=float(seconds),
+                              device_seconds=float(device_seconds))
 
 
 def simplify(xyz, rgb, faces, cell, origin=None, rank_eps=1e-3, detail=None, timing=None):
@@ -93,37 +81,17 @@ def simplify(xyz, rgb, faces, cell, origin=None, rank_eps=1e-3, detail=None, tim
     minimum - cell / 3).  detail: a dict that receives the intermediates (device tensors); timing: a list that receives
     (name, start event, end event) of the stages."""
     import torch
-    from . import _lib, hip_ops, mesh
+    from . import _lib, hip_ops
     check_options(cell, rank_eps)
-    for name, t in (("xyz", xyz), ("rgb", rgb), ("faces", faces)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.AdaMVSHipError("%s must be a GPU tensor: mesh simplification has no CPU fallback" % name)
-    if xyz.dtype != torch.float64 or rgb.dtype != torch.uint8 or faces.dtype not in (torch.int32, torch.int64):
-        raise _lib.AdaMVSHipError("xyz float64, rgb uint8, faces int32 / int64: got %s, %s, %s" % (xyz.dtype, rgb.dtype, faces.dtype))
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or tuple(rgb.shape) != tuple(xyz.shape) or faces.dim() != 2 or faces.shape[1] != 3:
-        raise _lib.AdaMVSHipError("xyz [nv, 3], rgb [nv, 3], faces [nf, 3]: got %s, %s, %s" % (tuple(xyz.shape), tuple(rgb.shape), tuple(faces.shape)))
+    clock = mesh_stage.StageClock(timing)
+    stage = clock.stage
+    welded = mesh_stage.enter("mesh simplification", xyz, rgb, faces, MAX_COUNT, clock)
     dev, c = xyz.device, float(cell)
-    marks = []
-
-    def stage(name):
-        if timing is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            marks.append((name, e))
-
     info = dict(cells=0, cells_used=0, vertices_in=int(xyz.shape[0]), faces_in=int(faces.shape[0]), faces_collapsed=int(faces.shape[0]),
                 faces_duplicate=0, faces_out=0, rank_hist=[0, 0, 0, 0], fallbacks=0)
-    if xyz.shape[0] == 0:
-        if faces.shape[0]:
-            raise _lib.AdaMVSHipError("%d faces without vertices" % faces.shape[0])
-        return _empty(dev) + (info,)
-    if faces.shape[0] > MAX_COUNT or xyz.shape[0] > MAX_COUNT:
-        raise _lib.AdaMVSHipError("more than 2^31 - 1 vertices or faces")
-    f64 = faces.to(torch.int64) & 0xFFFFFFFF
-    if faces.shape[0] and int(f64.max()) >= xyz.shape[0]:
-        raise _lib.AdaMVSHipError("a face refers to vertex %d of %d" % (int(f64.max()), xyz.shape[0]))
-    stage("weld")
-    xyz, f64, rgb = mesh.weld(xyz.contiguous(), f64, rgb.contiguous())
+    if welded is None:
+        return mesh_stage.empty_mesh(dev) + (info,)
+    xyz, f64, rgb = welded
     nv, nf = int(xyz.shape[0]), int(f64.shape[0])
     info["vertices_in"] = nv
     o = np.asarray(origin, np.float64).reshape(3) if origin is not None else default_lattice_origin(c, None, xyz.min(0).values.cpu().numpy())
@@ -143,7 +111,7 @@ def simplify(xyz, rgb, faces, cell, origin=None, rank_eps=1e-3, detail=None, tim
     bounds = torch.arange(nc + 1, device=dev, dtype=torch.int32)
     vstart = torch.searchsorted(vcell[vorder].contiguous(), bounds).to(torch.int64)
     if nf == 0:
-        return _empty(dev) + (info,)
+        return mesh_stage.empty_mesh(dev) + (info,)
     faces32 = f64.to(torch.int32).contiguous()
     # the canonical face list of step 2: corners ascending by (welded) vertex number, faces ascending by those triples
     stage("sort_canonical")
@@ -175,9 +143,7 @@ def simplify(xyz, rgb, faces, cell, origin=None, rank_eps=1e-3, detail=None, tim
         keep = torch.zeros(nf, device=dev, dtype=torch.uint8)
     stage("emit")
     out_xyz, out_rgb, out_faces, used = hip_ops.simplify_emit(pos, col, fcell, keep)
-    stage("end")
-    if timing is not None:
-        timing.extend((a[0], a[1], b[1]) for a, b in zip(marks[:-1], marks[1:]))
+    clock.end()
     nk = int(out_faces.shape[0])
     info.update(cells_used=int(out_xyz.shape[0]), faces_collapsed=nf - ns, faces_duplicate=ns - nk, faces_out=nk,
                 rank_hist=[int(v) for v in torch.bincount(rank.to(torch.int64), minlength=4).cpu().tolist()[:4]],
@@ -190,44 +156,20 @@ def simplify(xyz, rgb, faces, cell, origin=None, rank_eps=1e-3, detail=None, tim
 
 def from_file(mesh_path, out=None, cell=None, cell_voxels=None, origin=None, rank_eps=1e-3, device=None, log=print):
     """Simplify the mesh PLY mesh_whu.py wrote -> the summary dict also written to <out>.json."""
-    import torch
-    from . import mesh
-    t_start = time.time()
-    meta = None
-    if os.path.exists(mesh_path + ".json"):
-        with open(mesh_path + ".json") as f:
-            meta = json.load(f)
-    c = resolve_cell(cell, cell_voxels, meta)
-    check_options(c, rank_eps)
-    if not torch.cuda.is_available():
-        raise RuntimeError("simplify: needs an MI355X (there is no CPU fallback for the simplification kernels)")
+    def resolve(meta):
+        c = resolve_cell(cell, cell_voxels, meta)
+        check_options(c, rank_eps)
+        return c
+
+    def lattice_origin(c, meta, xyz_h):
+        if len(xyz_h):
+            return default_lattice_origin(c, meta.get("origin") if meta else None, xyz_h.min(0))
+        return default_lattice_origin(c, meta.get("origin") if meta else np.zeros(3), None)
+
     out = out or default_out(mesh_path)
-    device = torch.device(device if device is not None else "cuda")
-    verts, faces = mesh.read_mesh_ply(mesh_path)
-    xyz_h = np.stack([verts["x"], verts["y"], verts["z"]], 1).astype(np.float64)
-    rgb_h = np.stack([verts["red"], verts["green"], verts["blue"]], 1)
-    if origin is not None:
-        o = np.asarray(origin, np.float64).reshape(3)
-    elif len(xyz_h):
-        o = default_lattice_origin(c, meta.get("origin") if meta else None, xyz_h.min(0))
-    else:
-        o = default_lattice_origin(c, meta.get("origin") if meta else np.zeros(3), None)
-    xyz = torch.from_numpy(np.ascontiguousarray(xyz_h)).to(device)
-    rgb = torch.from_numpy(np.ascontiguousarray(rgb_h)).to(device)
-    f = torch.from_numpy(faces.astype(np.int64)).to(device)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    sx, sc, sf, info = simplify(xyz, rgb, f, c, o, rank_eps)
-    e1.record()
-    torch.cuda.synchronize(device)
-    if os.path.dirname(out):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-    with mesh.MeshPlyWriter(out) as w:
-        w.write(sx.cpu().numpy(), sc.cpu().numpy(), sf.cpu().numpy().view(np.uint32))
-    res = summary(meta, info, c, o, mesh_path, out, time.time() - t_start, e0.elapsed_time(e1) / 1e3)
-    with open(out + ".json", "w") as fj:
-        json.dump(res, fj, indent=1)
-        fj.write("\n")
+    res, info, c = mesh_stage.run_file("simplify", "simplification", mesh_path, out, origin, device, resolve, lattice_origin,
+                                       lambda c, xyz, rgb, f, o, timing: simplify(xyz, rgb, f, c, o, rank_eps),
+                                       lambda meta, info, c, o, src, out, s, ds, stages: summary(meta, info, c, o, src, out, s, ds))
     log("simplify: %d -> %d vertices, %d -> %d faces (%d collapsed, %d duplicate) over %d cells of %g m (%d fallbacks) into %s, "
         "device %.3f s, total_time = %.3f s" % (info["vertices_in"], res["vertices"], info["faces_in"], res["faces"], info["faces_collapsed"],
                                                 info["faces_duplicate"], info["cells"], c, info["fallbacks"], out, res["device_seconds"],
@@ -247,14 +189,6 @@ def build_parser():
     ap.add_argument("--rank_eps", type=float, default=1e-3, help="an eigenvalue of a cell's quadric counts iff it exceeds this share of the largest")
     ap.add_argument("--out", default=None, help="PLY to write (default <mesh minus .ply>_simplified.ply); the summary goes to <out>.json")
     return ap
-
-
-def mesh_path_of(args):
-    if args.mesh:
-        return args.mesh
-    if not args.output_folder:
-        raise ValueError("give --mesh or --output_folder")
-    return os.path.join(args.output_folder, "mesh.ply")
 
 
 def main(argv=None):

@@ -20,15 +20,12 @@ texture_whu.py's default occlusion tolerance keep working on the smoothed mesh) 
 the largest and the RMS move and the timings.
 """
 import argparse
-import json
-import math
-import os
 import sys
-import time
 
 import numpy as np
 
-from .simplify import CARRIED, MAX_COUNT, mesh_path_of  # noqa: F401  (the same carried keys and path rule)
+from . import mesh_stage
+from .mesh_stage import CARRIED, MAX_COUNT, mesh_path_of, positive as _positive  # noqa: F401  (shared with simplify.py and clean.py)
 
 DEFAULT_SIGMA_S_VOXELS = 1.0
 DEFAULT_SIGMA_R = 0.35
@@ -36,11 +33,6 @@ DEFAULT_ITERS = 10
 DEFAULT_MAX_MOVE_VOXELS = 1.0
 MAX_ITERS = 1000
 MAX_FACES = MAX_COUNT // 3                    # the 3 nf (vertex, face) entries are counted in 31 bits
-
-
-def _positive(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)) or float(v) <= 0:
-        raise ValueError("%s=%r must be finite and > 0" % (name, v))
 
 
 def _iters(name, v):
@@ -57,40 +49,23 @@ def check_options(sigma_s, sigma_r=DEFAULT_SIGMA_R, normal_iters=DEFAULT_ITERS, 
 
 
 def default_out(mesh_path):
-    return (mesh_path[:-4] if mesh_path.lower().endswith(".ply") else mesh_path) + "_smoothed.ply"
-
-
-def _resolve(name, metres, voxels, default_voxels, meta):
-    if metres is not None and voxels is not None:
-        raise ValueError("give --%s or --%s_voxels, not both" % (name, name))
-    if metres is not None:
-        _positive(name, metres)
-        return float(metres)
-    k = default_voxels if voxels is None else voxels
-    _positive(name + "_voxels", k)
-    if meta is None or "voxel" not in meta:
-        raise ValueError("<mesh>.json with the voxel size is absent: give --%s" % name)
-    return float(k) * float(meta["voxel"])
+    return mesh_stage.default_out(mesh_path, "_smoothed")
 
 
 def resolve_sigma_s(sigma_s, sigma_s_voxels, meta):
     """--sigma_s M, or --sigma_s_voxels K (default 1) times the voxel of <mesh>.json."""
-    return _resolve("sigma_s", sigma_s, sigma_s_voxels, DEFAULT_SIGMA_S_VOXELS, meta)
+    return mesh_stage.resolve_metres("sigma_s", sigma_s, sigma_s_voxels, DEFAULT_SIGMA_S_VOXELS, meta)
 
 
 def resolve_max_move(max_move, max_move_voxels, meta):
     """--max_move M, or --max_move_voxels K (default 1) times the voxel of <mesh>.json."""
-    return _resolve("max_move", max_move, max_move_voxels, DEFAULT_MAX_MOVE_VOXELS, meta)
+    return mesh_stage.resolve_metres("max_move", max_move, max_move_voxels, DEFAULT_MAX_MOVE_VOXELS, meta)
 
 
 def summary(meta, info, options, origin, source, out, seconds, device_seconds, stage_seconds=None):
     """The dict written to <out>.json: the carried keys of <mesh>.json first, unchanged."""
-    res = {k: meta[k] for k in CARRIED if meta is not None and k in meta}
-    res.update(options)
-    res.update(smooth_origin=[float(v) for v in origin], source=source, ply=out)
-    res.update(info)
-    res.update(seconds=float(seconds), device_seconds=float(device_seconds), stage_seconds=dict(stage_seconds or {}))
-    return res
+    return mesh_stage.summary(meta, dict(options, smooth_origin=[float(v) for v in origin], source=source, ply=out), info,
+                              seconds=float(seconds), device_seconds=float(device_seconds), stage_seconds=dict(stage_seconds or {}))
 
 
 def smooth(xyz, rgb, faces, sigma_s, sigma_r=DEFAULT_SIGMA_R, normal_iters=DEFAULT_ITERS, vertex_iters=DEFAULT_ITERS, max_move=None,
@@ -101,40 +76,19 @@ def smooth(xyz, rgb, faces, sigma_s, sigma_r=DEFAULT_SIGMA_R, normal_iters=DEFAU
     origin: O (default: the per-axis vertex minimum).  detail: a dict that receives the intermediates (device tensors);
     timing: a list that receives (name, start event, end event) of the stages."""
     import torch
-    from . import _lib, hip_ops, mesh
+    from . import _lib, hip_ops
     if max_move is None:
         raise ValueError("max_move (metres) is required")
     check_options(sigma_s, sigma_r, normal_iters, vertex_iters, max_move)
-    for name, t in (("xyz", xyz), ("rgb", rgb), ("faces", faces)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.AdaMVSHipError("%s must be a GPU tensor: mesh smoothing has no CPU fallback" % name)
-    if xyz.dtype != torch.float64 or rgb.dtype != torch.uint8 or faces.dtype not in (torch.int32, torch.int64):
-        raise _lib.AdaMVSHipError("xyz float64, rgb uint8, faces int32 / int64: got %s, %s, %s" % (xyz.dtype, rgb.dtype, faces.dtype))
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or tuple(rgb.shape) != tuple(xyz.shape) or faces.dim() != 2 or faces.shape[1] != 3:
-        raise _lib.AdaMVSHipError("xyz [nv, 3], rgb [nv, 3], faces [nf, 3]: got %s, %s, %s" % (tuple(xyz.shape), tuple(rgb.shape), tuple(faces.shape)))
+    clock = mesh_stage.StageClock(timing)
+    stage = clock.stage
+    welded = mesh_stage.enter("mesh smoothing", xyz, rgb, faces, MAX_FACES, clock)
     dev = xyz.device
     normal_iters, vertex_iters = int(normal_iters), int(vertex_iters)
-    marks = []
-
-    def stage(name):
-        if timing is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            marks.append((name, e))
-
     info = dict(vertices=int(xyz.shape[0]), faces=int(faces.shape[0]), fixed=0, degenerate_faces=0, clamped=0, largest_move=0.0, rms_move=0.0)
-    if xyz.shape[0] == 0:
-        if faces.shape[0]:
-            raise _lib.AdaMVSHipError("%d faces without vertices" % faces.shape[0])
-        return (torch.empty(0, 3, device=dev, dtype=torch.float64), torch.empty(0, 3, device=dev, dtype=torch.uint8),
-                torch.empty(0, 3, device=dev, dtype=torch.int32), info)
-    if faces.shape[0] > MAX_FACES or xyz.shape[0] > MAX_COUNT:
-        raise _lib.AdaMVSHipError("more than 2^31 - 1 vertices or (2^31 - 1) / 3 faces")
-    f64 = faces.to(torch.int64) & 0xFFFFFFFF
-    if faces.shape[0] and int(f64.max()) >= xyz.shape[0]:
-        raise _lib.AdaMVSHipError("a face refers to vertex %d of %d" % (int(f64.max()), xyz.shape[0]))
-    stage("weld")
-    xyz, f64, rgb = mesh.weld(xyz.contiguous(), f64, rgb.contiguous())
+    if welded is None:
+        return mesh_stage.empty_mesh(dev) + (info,)
+    xyz, f64, rgb = welded
     nv, nf = int(xyz.shape[0]), int(f64.shape[0])
     info["vertices"] = nv
     o = np.asarray(origin, np.float64).reshape(3) if origin is not None else xyz.min(0).values.cpu().numpy()
@@ -183,9 +137,7 @@ def smooth(xyz, rgb, faces, sigma_s, sigma_r=DEFAULT_SIGMA_R, normal_iters=DEFAU
     move2 = ((p - p0) ** 2).sum(1)
     stats = torch.stack([move2.max().sqrt(), move2.mean().sqrt(), fixed.sum().to(torch.float64), clamped.sum().to(torch.float64),
                          (rec[:, 3] == 0).sum().to(torch.float64)]).cpu().tolist()
-    stage("end")
-    if timing is not None:
-        timing.extend((a[0], a[1], b[1]) for a, b in zip(marks[:-1], marks[1:]))
+    clock.end()
     info.update(largest_move=float(stats[0]), rms_move=float(stats[1]), fixed=int(stats[2]), clamped=int(stats[3]), degenerate_faces=int(stats[4]))
     if detail is not None:
         detail.update(xyz=xyz, rgb=rgb, faces=faces32, origin=o, p0=p0, p=p, rec=rec, normals=normals, vface=vface, vstart=vstart, fixed=fixed,
@@ -196,49 +148,18 @@ def smooth(xyz, rgb, faces, sigma_s, sigma_r=DEFAULT_SIGMA_R, normal_iters=DEFAU
 def from_file(mesh_path, out=None, sigma_s=None, sigma_s_voxels=None, sigma_r=DEFAULT_SIGMA_R, normal_iters=DEFAULT_ITERS,
               vertex_iters=DEFAULT_ITERS, max_move=None, max_move_voxels=None, fix_boundary=True, origin=None, device=None, log=print):
     """Smooth the mesh PLY mesh_whu.py wrote -> the summary dict also written to <out>.json."""
-    import torch
-    from . import mesh
-    t_start = time.time()
-    meta = None
-    if os.path.exists(mesh_path + ".json"):
-        with open(mesh_path + ".json") as f:
-            meta = json.load(f)
-    ss = resolve_sigma_s(sigma_s, sigma_s_voxels, meta)
-    cap = resolve_max_move(max_move, max_move_voxels, meta)
-    check_options(ss, sigma_r, normal_iters, vertex_iters, cap)
-    if not torch.cuda.is_available():
-        raise RuntimeError("smooth: needs an MI355X (there is no CPU fallback for the smoothing kernels)")
+    def resolve(meta):
+        ss = resolve_sigma_s(sigma_s, sigma_s_voxels, meta)
+        cap = resolve_max_move(max_move, max_move_voxels, meta)
+        check_options(ss, sigma_r, normal_iters, vertex_iters, cap)
+        return dict(sigma_s=ss, sigma_r=float(sigma_r), normal_iters=int(normal_iters), vertex_iters=int(vertex_iters), max_move=cap,
+                    fix_boundary=bool(fix_boundary))
+
+    def run(opt, xyz, rgb, f, o, timing):
+        return smooth(xyz, rgb, f, opt["sigma_s"], sigma_r, normal_iters, vertex_iters, opt["max_move"], fix_boundary, o, timing=timing)
+
     out = out or default_out(mesh_path)
-    device = torch.device(device if device is not None else "cuda")
-    verts, faces = mesh.read_mesh_ply(mesh_path)
-    xyz_h = np.stack([verts["x"], verts["y"], verts["z"]], 1).astype(np.float64)
-    rgb_h = np.stack([verts["red"], verts["green"], verts["blue"]], 1)
-    if origin is not None:
-        o = np.asarray(origin, np.float64).reshape(3)
-    elif meta is not None and "origin" in meta:
-        o = np.asarray(meta["origin"], np.float64).reshape(3)
-    else:
-        o = xyz_h.min(0) if len(xyz_h) else np.zeros(3)
-    xyz = torch.from_numpy(np.ascontiguousarray(xyz_h)).to(device)
-    rgb = torch.from_numpy(np.ascontiguousarray(rgb_h)).to(device)
-    f = torch.from_numpy(faces.astype(np.int64)).to(device)
-    timing = []
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    sx, sc, sf, info = smooth(xyz, rgb, f, ss, sigma_r, normal_iters, vertex_iters, cap, fix_boundary, o, timing=timing)
-    e1.record()
-    torch.cuda.synchronize(device)
-    if os.path.dirname(out):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-    with mesh.MeshPlyWriter(out) as w:
-        w.write(sx.cpu().numpy(), sc.cpu().numpy(), sf.cpu().numpy().view(np.uint32))
-    options = dict(sigma_s=ss, sigma_r=float(sigma_r), normal_iters=int(normal_iters), vertex_iters=int(vertex_iters), max_move=cap,
-                   fix_boundary=bool(fix_boundary))
-    res = summary(meta, info, options, o, mesh_path, out, time.time() - t_start, e0.elapsed_time(e1) / 1e3,
-                  {name: a.elapsed_time(b) / 1e3 for name, a, b in timing})
-    with open(out + ".json", "w") as fj:
-        json.dump(res, fj, indent=1)
-        fj.write("\n")
+    res, info, _ = mesh_stage.run_file("smooth", "smoothing", mesh_path, out, origin, device, resolve, mesh_stage.volume_origin, run, summary)
     log("smooth: %d vertices, %d faces (%d fixed, %d degenerate faces, %d clamped), largest move %.4g m, rms %.4g m into %s, "
         "device %.3f s, total_time = %.3f s" % (info["vertices"], info["faces"], info["fixed"], info["degenerate_faces"], info["clamped"],
                                                 info["largest_move"], info["rms_move"], out, res["device_seconds"], res["seconds"]))

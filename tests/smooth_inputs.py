@@ -119,6 +119,17 @@ def strip(nf):
     return xyz, colours(len(xyz)), faces
 
 
+EDGE_TILE_FACES = (85, 86, 171)               # 255, 258 and 513 edges: a partial tile of 256 lanes, a second tile, a third
+
+
+def renamed_strip_faces(nf):
+    """strip(nf)'s faces with its last two vertices, nf and nf + 1, renamed to numbers with bit 31 set -> (faces int64 [nf, 3], the
+    same as the int32 bits a kernel reads).  The edge between the two has bit 31 in both halves of its key."""
+    faces = strip(nf)[2]
+    big = np.where(faces == nf, 0x80000005, np.where(faces == nf + 1, 0xFFFFFFF9, faces)).astype(np.int64)
+    return big, big.astype(np.uint32).view(np.int32)
+
+
 def fan(nf):
     """nf faces around one apex (vertex 0), closed, on a wavy rim: every face neighbours every other through the apex."""
     t = 2 * np.pi * np.arange(nf) / nf

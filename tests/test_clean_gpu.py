@@ -80,8 +80,19 @@ def test_hand_made_mesh_every_intermediate(min_faces, M):
 
 
 # ---- components -----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nf", [255, 256, 257])
+@pytest.mark.parametrize("nf", list(SI.EDGE_TILE_FACES) + [255, 256, 257])
 def test_strips_across_a_workgroup_boundary(nf):
+    import torch
+    # the open edges alone, with vertex numbers that have bit 31 set: the restatement on the strip before the renaming (the same
+    # half-edges), and smoothing's marks are the ends of cleaning's open half-edges
+    big, bits = SI.renamed_strip_faces(nf)
+    f32 = torch.from_numpy(bits).cuda()
+    bnd = hip_ops.clean_boundary(f32).cpu().numpy().astype(bool)
+    assert np.array_equal(bnd, R.boundary(SI.strip(nf)[2], nf + 2)[0]) and bnd.sum() == nf + 2
+    ends = np.concatenate([a[bnd] for a in R.half_edges(big)])
+    marks = np.zeros(nf, bool)
+    marks[ends[ends < nf]] = True
+    assert np.array_equal(hip_ops.smooth_boundary(f32, nf).cpu().numpy().astype(bool), marks)
     g, _ = both(*SI.strip(nf), "strip %d:" % nf, min_faces=nf, max_hole_edges=0)
     assert g["info"]["components"] == g["info"]["components_kept"] == 1 and len(g["out_faces"]) == nf
     g, _ = both(*SI.strip(nf), "strip %d, dropped:" % nf, min_faces=nf + 1, max_hole_edges=0)

@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 import ada_mvs_amd  # noqa: F401
-from ada_mvs_amd import _lib, mesh, simplify, smooth
+from ada_mvs_amd import _lib, hip_ops, mesh, simplify, smooth
+import clean_ref as CR
 import simplify_inputs as I
 import smooth_inputs as SI
 import smooth_ref as R
@@ -91,9 +92,21 @@ def test_hand_made_mesh_normals(iters):
 
 
 # ---- kernel edges ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("nf", [255, 256, 257])
+@pytest.mark.parametrize("nf", list(SI.EDGE_TILE_FACES) + [255, 256, 257])
 def test_strips_across_a_workgroup_boundary(nf):
+    import torch
     xyz, rgb, faces = SI.strip(nf)
+    # the edge keys alone (one lane per edge), with vertex numbers that have bit 31 set: both entry points against the half-edges of
+    # the cleaning restatement; then the marks of the vertices below nf against the restatement on the strip before the renaming
+    big, bits = SI.renamed_strip_faces(nf)
+    f32 = torch.from_numpy(bits).cuda()
+    tail, head = CR.half_edges(big)
+    want = (np.minimum(tail, head) << 32) | np.maximum(tail, head)
+    keys = hip_ops._edge_keys("smooth_edge_keys", f32).cpu().numpy()
+    assert keys.tobytes() == want.tobytes() and (want < 0).sum() == 1 and (want & 0x80000000 != 0).sum() >= 3
+    assert hip_ops.texture_edge_keys(f32).cpu().numpy().tobytes() == keys.tobytes()
+    fixed = hip_ops.smooth_boundary(f32, nf).cpu().numpy()
+    assert np.array_equal(fixed.astype(bool), R.boundary_vertices(faces, nf + 2)[:nf]) and fixed.all()
     for fix in (True, False):
         kw = dict(sigma_s=1.0, sigma_r=0.5, normal_iters=3, vertex_iters=3, max_move=0.125, fix_boundary=fix)
         r = R.smooth(xyz, rgb, faces, **kw)

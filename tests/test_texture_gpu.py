@@ -286,6 +286,26 @@ def test_non_manifold_edge_connects_equal_labels():
                 break
         np.testing.assert_array_equal(parent.cpu().numpy(), R.components(np.array(lab), faces.cpu().numpy()))
         assert list(parent.cpu().numpy()) == want[lab]
+    # strips whose 3 nf edges end inside the first tile of 256 lanes, in the second and in the third, two vertex numbers with bit 31
+    # set: one chart, charts of seven faces with untextured faces between them, and the roots after the guarded walk
+    import smooth_inputs as SI
+    for nf in SI.EDGE_TILE_FACES:
+        big, bits = SI.renamed_strip_faces(nf)
+        faces = torch.from_numpy(bits).cuda()
+        keys = hip_ops.texture_edge_keys(faces)
+        for lab in (np.zeros(nf, np.int64), np.where(np.arange(nf) % 8 == 7, -1, (np.arange(nf) // 8) % 2)):
+            label = torch.from_numpy(lab.astype(np.int32)).cuda()
+            p1 = torch.sort(label.repeat_interleave(3), stable=True).indices
+            ks, p2 = torch.sort(keys[p1], stable=True)
+            parent = torch.arange(nf, dtype=torch.int32, device="cuda")
+            changed = torch.ones(1, dtype=torch.int32, device="cuda")
+            for _ in range(64):
+                if int(changed.item()) == 0:
+                    break
+                hip_ops.texture_components_round(ks, p1[p2].contiguous(), label, parent, changed)
+            assert int(changed.item()) == 0
+            np.testing.assert_array_equal(parent.cpu().numpy(), R.components(lab, big))
+            assert len(np.unique(parent.cpu().numpy())) == (1 if lab.max() == 0 else len(np.unique(np.arange(nf) // 8)) + (lab < 0).sum())
 
 
 def test_odd_image_sizes():
