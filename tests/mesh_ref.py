@@ -73,6 +73,18 @@ def pixel_margin(H, W, floor=1e-4):
     return max(floor, 8.0 * float(np.spacing(np.float32(max(H, W)))))
 
 
+def project(voxel, B, b, V):
+    """-> (z, u, v) fp64 [(B+1)^3] of brick b's samples in view record V: x = g sf - c, p = R_cw x, z = p.z, (u, v) = (K p).xy / z
+    (inf or NaN where z = 0)."""
+    K, R, c = V["K"].astype(np.float64), V["R"].astype(np.float64), V["c"].astype(np.float64)
+    p = (sample_grid(B, b).astype(np.float64) * float(np.float32(voxel)) - c) @ R.T
+    z = p[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = (K[0, 0] * p[:, 0] + K[0, 1] * p[:, 1] + K[0, 2] * z) / z
+        v = (K[1, 0] * p[:, 0] + K[1, 1] * p[:, 1] + K[1, 2] * z) / z
+    return z, u, v
+
+
 def integrate(voxel, mu, B, b, views, view_list):
     """-> dict(tsdf fp32, weight uint16, rgba uint32, tie bool): the samples of brick b, views[i] for i in view_list, in order.
     tie: some view's decision lies within the header's error bound of a threshold (the fp32 kernel may decide it either way)."""
@@ -89,21 +101,17 @@ def integrate(voxel, mu, B, b, views, view_list):
         V = views[vi]
         K, R, c = V["K"].astype(np.float64), V["R"].astype(np.float64), V["c"].astype(np.float64)
         H, W = V["depth"].shape
-        x = gs - c
-        p = x @ R.T
-        z = p[:, 2]
+        z, u, v = project(voxel, B, b, V)
         L = np.linalg.norm(gs, axis=1) + np.linalg.norm(c)
         dz = 16 * EPS32 * L
-        with np.errstate(divide="ignore", invalid="ignore"):
-            u = (K[0, 0] * p[:, 0] + K[0, 1] * p[:, 1] + K[0, 2] * z) / z
-            v = (K[1, 0] * p[:, 0] + K[1, 1] * p[:, 1] + K[1, 2] * z) / z
         front = z > 0
         tie |= np.abs(z) <= dz
         zz = np.where(front, z, 1.0)
         mpx = pixel_margin(H, W) + 4.0 * (abs(K[0, 0]) + abs(K[1, 1]) + abs(K[0, 1])) * dz / zz + 8 * EPS32 * (np.abs(u) + np.abs(v) + 1)
         fu, fv = np.floor(u + 0.5), np.floor(v + 0.5)
         for q, fq in ((u, fu), (v, fv)):
-            frac = (q + 0.5) - fq
+            with np.errstate(invalid="ignore"):                            # z = 0: inf - inf, behind `front`
+                frac = (q + 0.5) - fq
             tie |= front & ((frac < mpx) | (1.0 - frac < mpx))
         ok = front & (fu >= 0) & (fu < W) & (fv >= 0) & (fv < H)
         iu, iv = np.where(ok, fu, 0).astype(np.int64), np.where(ok, fv, 0).astype(np.int64)
@@ -156,6 +164,7 @@ def extract(origin, voxel, B, b, tsdf, weight, rgba, min_weight=1, vertex_base=0
         for start, e in tet_edges(t).values():
             users[e].add(tuple(start))
     mask = np.zeros((B1, B1, B1), np.uint8)
+    cmask = np.zeros((B1, B1, B1), np.uint8)                             # sign changes alone, used or not
     pp = np.zeros((B + 2, B + 2, B + 2), bool)                           # processed, padded by one on both sides
     pp[1:B + 1, 1:B + 1, 1:B + 1] = processed
     for e in range(7):
@@ -170,6 +179,7 @@ def extract(origin, voxel, B, b, tsdf, weight, rgba, min_weight=1, vertex_base=0
             # cube of sample l is l - s: padded index l - s + 1
             used |= pp[1 - sz:1 - sz + B1, 1 - sy:1 - sy + B1, 1 - sx:1 - sx + B1]
         mask |= ((change & used).astype(np.uint8) << e)
+        cmask |= (change.astype(np.uint8) << e)
     flat_mask = mask.ravel()
     bits = (flat_mask[:, None] >> np.arange(7)) & 1
     counts = bits.sum(1)
@@ -196,13 +206,10 @@ def extract(origin, voxel, B, b, tsdf, weight, rgba, min_weight=1, vertex_base=0
     # triangles: cube row-major, then tet, then table order
     cubes = np.nonzero(processed.ravel())[0]
     cz, cy, cx = cubes // (B * B), (cubes // B) % B, cubes % B
-    ins = inside.reshape(B1, B1, B1)
+    cases = cube_cases(B, tsdf)[cubes]
     per_tet = []
     for t in range(6):
-        v = tet_vertices(t)
-        case = np.zeros(len(cubes), np.int64)
-        for k in range(4):
-            case |= ins[cz + v[k, 2], cy + v[k, 1], cx + v[k, 0]].astype(np.int64) << k
+        case = cases[:, t]
         edges = tet_edges(t)
         idx = {}
         for (i, j), (s, e) in edges.items():
@@ -217,7 +224,25 @@ def extract(origin, voxel, B, b, tsdf, weight, rgba, min_weight=1, vertex_base=0
         per_tet.append(tris)
     allt = np.stack(per_tet, 1).reshape(-1, 3)                          # [cube][tet][r]
     faces = (allt[allt[:, 0] >= 0] + vertex_base).astype(np.uint32)
-    return dict(xyz=xyz, rgb=rgb, faces=faces, edge_mask=flat_mask, processed=processed.ravel())
+    return dict(xyz=xyz, rgb=rgb, faces=faces, edge_mask=flat_mask, processed=processed.ravel(), sign_change=cmask.ravel())
+
+
+def cube_cases(B, tsdf):
+    """-> [B^3, 6] int64: the sign case of tet t of every cube, cube row-major (sum over k of inside(v_k) << k, inside iff tsdf < 0)."""
+    B1 = B + 1
+    ins = (np.asarray(tsdf, np.float32) < 0).reshape(B1, B1, B1)
+    out = np.zeros((B, B, B, 6), np.int64)
+    for t in range(6):
+        v = tet_vertices(t)
+        for k in range(4):
+            out[..., t] |= ins[v[k, 2]:v[k, 2] + B, v[k, 1]:v[k, 1] + B, v[k, 0]:v[k, 0] + B].astype(np.int64) << k
+    return out.reshape(-1, 6)
+
+
+def case_triangle_count(case):
+    """Triangles of a sign case (the same for every tet), elementwise."""
+    nin = _popcount(case)
+    return np.where((nin == 0) | (nin == 4), 0, np.where(nin == 2, 2, 1))
 
 
 def _popcount(x):

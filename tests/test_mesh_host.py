@@ -1,13 +1,16 @@
 """TSDF mesh, host side (no GPU): the restatement (tests/mesh_ref.py) on cases known in closed form, conservative view culling,
-the mesh PLY writer, argument errors of the C ABI and the wrapper's refusal of host tensors."""
+the mesh PLY writer, argument errors of the C ABI, the wrapper's refusal of host tensors, and the crafted inputs of
+tests/mesh_inputs.py against the restatement: every precondition that tests/test_mesh_edges_gpu.py relies on."""
 import ctypes
 import itertools
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
 import ada_mvs_amd  # noqa: F401
 from ada_mvs_amd import _lib, fusion_synth, mesh
+import mesh_inputs as I
 import mesh_ref as M
 
 SPHERE_CENTRE = (32.37, 31.81, 32.23)
@@ -239,3 +242,109 @@ def test_wrapper_refuses_host_tensors():
         hip_ops.tsdf_integrate(b, torch.zeros(112, dtype=torch.uint8), 1, torch.zeros(1, dtype=torch.int32))
     with pytest.raises(_lib.AdaMVSHipError, match="GPU tensor"):
         hip_ops.mesh_views([(np.eye(3), np.eye(3), np.zeros(3), torch.zeros(4, 5), torch.zeros(4, 5, 4, dtype=torch.uint8))], "cpu")
+
+
+# ---- the crafted inputs of tests/mesh_inputs.py: every precondition of the GPU tests, from the restatement alone -------------
+@pytest.mark.parametrize("B,voxel,mu,b,min_weights", I.SCENE_CASES)
+def test_scene_bricks_at_64_and_128_have_views_surface_and_few_ties(B, voxel, mu, b, min_weights):
+    case = I.scene_reference(B, voxel, mu, b)
+    ref = case["ref"]
+    assert len(case["vl"]) >= 3
+    assert (~ref["tie"]).mean() > 0.8, ref["tie"].mean()
+    assert (B + 1) ** 3 > 1 << 16 and I.SCENE_ORIGIN[0] + b[0] * B * voxel != 0
+    # a cube processed at the largest min_weight is processed at every smaller one, and a cube's triangles depend on signs alone:
+    # the face count at the largest min_weight bounds the others from below
+    faces = M.extract(I.SCENE_ORIGIN, voxel, B, b, ref["tsdf"], ref["weight"], ref["rgba"], max(min_weights))["faces"]
+    assert len(faces) > 100
+
+
+def test_threshold_scene_is_exact_and_meets_every_threshold():
+    recs = I.threshold_records()
+    for vl in ([0, 1], [0, 1, 2]):
+        exact = I.exact_samples(recs, vl)
+        ref = I.threshold_reference(vl)
+        assert exact.sum() >= 3000
+        assert (exact & (ref["weight"] >= 1)).sum() > 250 and (exact & (ref["rgba"] != 0)).sum() > 100
+        assert ref["tie"][exact].mean() > 0.2                  # samples the tie mask would have left out
+        for name, hit in I.threshold_events(recs, vl).items():
+            assert (hit & exact).sum() > 0, (vl, name)
+    # with the wide nadir view most EXACT samples carry weight
+    assert (ref["weight"][exact] >= 1).mean() > 0.5
+    # the planted and the bad pixels do what they were placed for (sample (x, y, z) -> entry (z 33 + y) 33 + x)
+    at = lambda x, y, z: (z * 33 + y) * 33 + x  # noqa: E731
+    one = I.threshold_reference([1])
+    assert exact[at(14, 16, 17)] and one["weight"][at(14, 16, 17)] == 1 and one["tsdf"][at(14, 16, 17)] == -1.0     # depth 1e-45 at z = 4
+    assert one["rgba"][at(14, 16, 17)] != 0
+    assert one["weight"][at(26, 8, 17)] == 1 and one["tsdf"][at(26, 8, 17)] == -1.0 and one["rgba"][at(26, 8, 17)] != 0   # sdf = -mu
+    assert one["weight"][at(26, 10, 17)] == 0                                                                          # sdf = -mu - 1/4
+    assert one["weight"][at(18, 12, 17)] == 1 and one["tsdf"][at(18, 12, 17)] == 1.0 and one["rgba"][at(18, 12, 17)] != 0  # sdf = +mu
+    assert one["weight"][at(18, 13, 17)] == 1 and one["rgba"][at(18, 13, 17)] == 0                                     # sdf = +mu + 1/4
+    assert one["weight"][at(18, 20, 17)] == 1 and one["tsdf"][at(18, 20, 17)] == 1.0 and one["rgba"][at(18, 20, 17)] == 0   # FLT_MAX
+    assert (one["weight"][[at(18, y, 17) for y in range(15, 20)]] == 0).all()                     # NaN, +inf, -inf, 0, -3 are unknown
+    assert (one["weight"][M.sample_grid(32, (0, 0, 0))[:, 0] <= 10] == 0).all()                   # at or behind the side camera
+
+
+def test_threshold_scene_view_lists():
+    recs = I.threshold_records()
+    exact = I.exact_samples(recs, [0, 1])
+    a, b = I.threshold_reference([0, 1]), I.threshold_reference([1, 0])
+    assert np.array_equal(a["weight"], b["weight"]) and np.array_equal(a["rgba"], b["rgba"])
+    assert np.array_equal(a["tsdf"][exact], b["tsdf"][exact])                                      # exact sums do not feel the order
+    many = I.records(I.many_views(), I.TH["origin"])
+    ref = M.integrate(I.TH["voxel"], I.TH["mu"], I.TH["B"], I.TH["b"], many, list(range(len(many))))
+    assert len(many) == 300 and (ref["weight"][exact] == 300).sum() > 0 and ref["weight"].max() == 300
+    both = ref["weight"] == 300
+    assert np.array_equal(ref["rgba"][both], a["rgba"][both])                                     # 150 times the same two pixels
+
+
+@pytest.mark.parametrize("B,tiny", [(32, False), (32, True), (64, False), (128, False)])
+def test_crafted_volume_holds_every_case_and_scattered_unprocessed_cubes(B, tiny):
+    vol = I.crafted_volume(B, tiny=tiny)
+    ref = I.extraction_reference(I.FAR_ORIGIN, 0.1, B, (0, 0, 0), vol, key=(B, tiny, "far"))
+    assert 0.15 < ref["processed"].mean() < 0.3
+    cases = M.cube_cases(B, vol[0])[ref["processed"]]
+    assert all(set(np.unique(cases[:, t])) == set(range(16)) for t in range(6))                   # all 96 (tet, case) pairs
+    unused = I.used_by_none(B, ref)
+    for e in range(7):
+        assert ((ref["edge_mask"] >> e) & 1).sum() > 0 and ((unused >> e) & 1).sum() > 0, e
+    assert np.isfinite(ref["xyz"]).all() and len(ref["faces"]) > 1000 and len(ref["xyz"]) > 1000
+    t = vol[0]
+    assert (np.signbit(t) & (t == 0)).any() and ((t == 0) & ~np.signbit(t)).any()                 # -0 and +0
+    if B == 32 and not tiny:
+        # voxel 0.1 shows a contracted multiply-add along z, where the origin is small: O + g s rounded once (exact rationals)
+        # differs from the two roundings
+        bits = (ref["edge_mask"][:, None] >> np.arange(7)) & 1
+        n_idx, e_idx = (a[::20] for a in np.nonzero(bits))
+        lam = (t[n_idx] / (t[n_idx] - t[n_idx + M.DIRS[e_idx] @ [1, B + 1, (B + 1) ** 2]])).astype(np.float32)
+        g = M.sample_grid(B, (0, 0, 0))[n_idx, 2] + np.where(M.DIRS[e_idx, 2] == 1, lam.astype(np.float64), 0.0)
+        once = np.array([float(Fraction(I.FAR_ORIGIN[2]) + Fraction(float(x)) * Fraction(0.1)) for x in g])
+        assert 50 < (once != ref["xyz"][::20, 2]).sum() < len(once) // 2
+    tiny_values = (t != 0) & (np.abs(t) < 2.0 ** -126)
+    assert tiny_values.any() == tiny
+    if tiny:
+        # a subnormal value decides a sign: its edge to a zero or a positive neighbour carries a vertex
+        B1 = B + 1
+        n = np.nonzero(tiny_values & (t < 0))[0]
+        n = n[(n % B1 < B)]
+        assert ((t[n + 1] >= 0) & ((ref["edge_mask"][n] & 1) == 1)).sum() > 0
+
+
+def test_crafted_special_volumes():
+    B = 32
+    t, w, c = I.crafted_volume(B)
+    assert len(I.extraction_reference(I.FAR_ORIGIN, 0.1, B, (0, 0, 0), (t, w, c), 2)["faces"]) > 0
+    for vol in ((np.abs(t) + np.float32(0.0), w, c), (t, np.zeros_like(w), c)):
+        ref = M.extract(I.FAR_ORIGIN, 0.1, B, (0, 0, 0), *vol)
+        assert len(ref["xyz"]) == 0 and len(ref["faces"]) == 0
+    assert not np.signbit(np.abs(t) + np.float32(0.0)).any()
+    for cube in ((0, 0, 0), (B - 1, B - 1, B - 1)):
+        ref = M.extract(I.FAR_ORIGIN, 0.1, B, (0, 0, 0), *I.single_cube_volume(B, cube))
+        assert ref["processed"].sum() == 1 and len(ref["faces"]) >= 6 and len(ref["xyz"]) >= 7
+    last = I.single_cube_volume(B, (B - 1, B - 1, B - 1))
+    assert np.nonzero(last[1])[0].min() // 256 >= 131 and np.nonzero(last[1])[0].max() == 33 ** 3 - 1 == 140 * 256 + 96
+    # the last brick inside the extent, and a vertex_base at the top of uint32
+    ref = I.extraction_reference(I.FAR_ORIGIN, 1.0, B, (511, 0, 3), (t, w, c), key=(B, "extent"))
+    assert (511 + 1) * B * 1.0 == mesh.MAX_EXTENT and ref["xyz"][:, 0].max() > I.FAR_ORIGIN[0] + 16383
+    nv = len(ref["xyz"])
+    top = M.extract(I.FAR_ORIGIN, 1.0, B, (511, 0, 3), t, w, c, 1, 0xFFFFFFFF - nv)["faces"]
+    assert top.dtype == np.uint32 and top.max() == 0xFFFFFFFE and np.array_equal(top - np.uint32(0xFFFFFFFF - nv), ref["faces"])
