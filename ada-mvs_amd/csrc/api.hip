@@ -287,7 +287,10 @@ static int stage_forward(const adamvs_stage_desc* desc, const float* feat, const
   const size_t c1_stride = (size_t)s.B * hw * 8;
   GruStateRing rb{{ws + c.h1[0], ws + c.h1[1], ws + c.h1[2], ws + c.h1[3]}, ws + c.rh1, ws + c.u1, {ws + c.c2[0], ws + c.c2[1]},
                   {ws + c.h2[0], ws + c.h2[1]}, ws + c.rh2, ws + c.u2};
-  const int mode = recurrence_mode(s.precision_fuse, (long)s.B * s.h * s.w);
+  // schedule 0 with conv2 in the level-1 gate launch runs on the pipelined driver below as schedule 6 (lags {1, 1}, one role per
+  // launch: launch_lagged_step); adamvs_recurrence_schedule keeps reporting 0 for it
+  int mode = recurrence_mode(s.precision_fuse, (long)s.B * s.h * s.w);
+  if (mode == 0 && conv2_in_gates1_applies(fw, s.h, s.w, s.precision_fuse)) mode = 6;
   const bool pipelined = mode != 0;
   const int lag = recurrence_lags(mode, s.precision_fuse).dec;       // the decoder runs `lag` hypotheses behind level 1
   if (do_rec) {      // zero initial states (adamvs.py:448-449): h1[-1] = ring slot 3, h2[-1] = ring slot 1 (slot 0 when sequential)

@@ -28,6 +28,13 @@ struct FuseWeights {          // mirrors adamvs_fuse_weights in include/adamvs_h
   const float* gates1_w; const float* gates2_w; const float* cand2_w; const float* cand1_w;
 };
 int gru_wino_mask();          // which GRU convolutions run in the F(2x2, 3x3) form in one-role launches (slice_red.hip)
+// two more bits of option gru_wino, both SET = the launches of before: conv2 in a launch of its own although the F(2x2, 3x3) gate
+// tiles of level 1 hold its window (clear: Gates1Conv2WinoRole); cand1 with a launch of its own on 8 x 16 tiles (clear: 8 x 32)
+// and one that is CLEAR by default: slot A of the pipelined schedule 1 as Gates1Conv2WinoRole alone instead of gates1 | conv2 (not
+// measured at the sizes that take schedule 1: it stays an opt-in until it is)
+enum { GRU_WINO_CONV2_APART = 16, GRU_WINO_CAND1_TILE16 = 32, GRU_WINO_SLOT_A_FUSED = 64 };
+inline bool conv2_in_gates1_enabled() { return !(gru_wino_mask() & GRU_WINO_CONV2_APART); }
+inline bool cand1_tile32_enabled() { return !(gru_wino_mask() & GRU_WINO_CAND1_TILE16); }
 
 struct StepBuffers {          // all channel-last
   float* h1; float* rh1; float* u1;              // [B][hw][8]
@@ -45,6 +52,11 @@ int recurrence_mode(int precision, long pixels);
 RecurLags recurrence_lags(int schedule, int precision);
 int launch_recur_pipeline_step(const GruStateRing& rb, const FuseWeights& fw, int B, int h, int w, int D, int t, const float* c1_t,
                                float* vol_dec, int D_vol, int d_dec, int in_up, int precision, int schedule, hipStream_t st);
+// schedule 0 with conv2(t-1) inside the launch of gates1(t) (slice_red.hip): whether it applies, and its step t = 0 .. D
+bool conv2_in_gates1_applies(const FuseWeights& fw, int h, int w, int precision);
+int launch_lagged_step(const FuseWeights& fw, int B, int h, int w, int D, int t, const float* c1_t, const float* h1_prev, float* h1_new,
+                       float* rh1, float* u1, float* c2, const float* h2_prev, float* h2_new, float* rh2, float* u2, float* vol_dec, int D_vol,
+                       int d_dec, int in_up, hipStream_t st);
 int launch_soft_argmin_chunk(const float* vol, int vol_D, PlaneSrc planes, int D, int d0, int nd, float* acc, int first, int last,
                              float* depth, float* conf, int B, int h, int w, int in_up, hipStream_t st);
 int sweep_chunk_planes(int D);

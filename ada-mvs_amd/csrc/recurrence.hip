@@ -60,6 +60,7 @@ template <> struct min_blocks<Gru2FusedBx3Role> { static constexpr int value = 2
 // stage 1 of cfg4's share 4.8 -> 6.4 ms, before this bound)
 template <> struct min_blocks<Gru2FusedRole<4>> { static constexpr int value = 2; };
 template <> struct min_blocks<ConvWinoRole<16, 16, 2, EPI_GATES>> { static constexpr int value = 2; };
+template <> struct min_blocks<Gates1Conv2WinoRole> { static constexpr int value = 4; };      // the four of the gates alone
 // (Gru1FusedRole<8, 2> held to three workgroups per CU -- 168 registers, 18 of its 194 spilled -- is slower than at two:
 //  stage 2 of cfg3 at 32 tiles 28.3 against 27.8 ms, the separate kernels 26.5)
 constexpr int imax3(int a, int b, int c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
@@ -216,6 +217,7 @@ typedef ConvSmallRole<8, 0, 1, 2, EPI_RELU> Conv2;
 typedef ConvSmallRole<16, 16, 2, 1, EPI_GATES> Gates2;
 typedef ConvSmallRole<16, 16, 1, 1, EPI_CAND> Cand2;
 typedef ConvWinoRole<8, 8, 1, EPI_GATES> Gates1W;      // the same convolutions in the F(2x2, 3x3) form (slice_roles_wino.h), 8 x 32 tiles
+typedef Gates1Conv2WinoRole Gates1Conv2W;              // ... with conv2 of the state it reads
 typedef ConvWinoRole<16, 16, 2, EPI_GATES> Gates2W;
 typedef ConvWinoRole<16, 16, 1, EPI_CAND> Cand2W;
 typedef Gru1FusedRole<4, 2> Gru1S;      // fp32, both levels fused: 4 x 30 / 4 x 14 tiles for stages with few tiles per CU
@@ -302,8 +304,11 @@ template <class R> static RoleUse<R> none() { return RoleUse<R>{nullptr, 0.f, 0.
 // (Schedule 2 of round 2 -- gates2, the one role that needs 234 registers, in a launch of its own -- was never chosen by size and
 // was removed in round 6.)
 //   schedule 5 (both levels one kernel each)   gru1(t) | conv2(t-1) | gru2(t-2) | decoder(t-3): ONE launch per hypothesis
+//   schedule 6 (internal: what recurrence_mode 0 becomes unless option gru_wino has bit 16; fp32, F(2x2, 3x3) gates1, even maps)
+//                                    five launches, one role each: gates1(t) + conv2(t-1), gates2(t-1), cand2(t-1), decoder(t-1), cand1(t)
 RecurLags recurrence_lags(int schedule, int precision) {
   if (schedule == 5) return RecurLags{2, 3};       // one launch: gru2 two, the decoder three behind
+  if (schedule == 6) return RecurLags{1, 1};       // one role per launch, conv2(t-1) inside gates1(t): level 2 and the decoder one behind
   return RecurLags{1, 2};
 }
 
@@ -323,6 +328,9 @@ int launch_recur_pipeline_step(const GruStateRing& rb, const FuseWeights& fw, in
   auto C2 = [&](int s) { return rb.c2[((s % 2) + 2) % 2]; };
   const RoleCosts& k = role_costs();
   int rc;
+  if (schedule == 6)
+    return launch_lagged_step(fw, B, h, w, D, t, c1_t, H1(t - 1), H1(t), rb.rh1, rb.u1, C2(t - 1), H2(t - 2), H2(t - 1), rb.rh2, rb.u2, vol_dec,
+                              D_vol, d_dec, in_up, st);
   DecoderArgs da{H2(sd), H1(sd), fw.upconv1, fw.upconv1_b, fw.final_w, vol_dec, h, w, D_vol, d_dec};
 
   if (precision == PRECISION_BF16X3) {
@@ -405,7 +413,13 @@ int launch_recur_pipeline_step(const GruStateRing& rb, const FuseWeights& fw, in
     SmallConvArgs g1w = g1, g2w = g2, c2w = c2;
     g1w.wpk = fw.gates1_w; g2w.wpk = fw.gates2_w; c2w.wpk = fw.cand2_w;
     const float kg1 = 4.f * 0.76f * k.g1, kg2 = 4.f * 0.69f * k.g2, kc2 = 4.f * 0.89f * k.c2;
-    if (l1 || l2)
+    if (l1 && (gru_wino_mask() & GRU_WINO_SLOT_A_FUSED) && !(h & 1) && !(w & 1)) {
+      // slot A is one role: the gate tile's window holds conv2's inputs (Gates1Conv2WinoRole)
+      Gates1Conv2Args gv{g1w, l2 ? C2(s2) : nullptr, fw.conv2};
+      if ((rc = launch_slot<Gates1Conv2W, NopRole, NopRole>(use<Gates1Conv2W>(&gv, kg1), none<NopRole>(), none<NopRole>(), B, st,
+                                                            "recurrence slot A (F(2x2,3x3), conv2 inside)")))
+        return rc;
+    } else if (l1 || l2)
       if ((rc = launch_slot<Gates1W, Conv2, NopRole>(l1 ? use<Gates1W>(&g1w, kg1) : none<Gates1W>(), l2 ? use<Conv2>(&v2, k.v2) : none<Conv2>(),
                                                      none<NopRole>(), B, st, "recurrence slot A (F(2x2,3x3))")))
         return rc;

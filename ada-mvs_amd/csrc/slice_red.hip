@@ -23,6 +23,13 @@ __global__ __launch_bounds__(256, 2) void k_conv_small_wino(SmallConvArgs a, Til
   ConvWinoRole<CA, CB, NT, EPI>::run(a, tg, TileRange{0, tg.ntiles}, blockIdx.x, gridDim.x, lds);
 }
 
+// The level-1 gates with conv2 of the previous hypothesis's state in the same tile loop (Gates1Conv2WinoRole), held to the four
+// workgroups per CU of k_conv_small_wino<8, 8, 1, EPI_GATES>
+__global__ __launch_bounds__(256, 4) void k_gates1_conv2_wino(Gates1Conv2Args a, TileGrid tg) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  Gates1Conv2WinoRole::run(a, tg, TileRange{0, tg.ntiles}, blockIdx.x, gridDim.x, lds);
+}
+
 // One role per launch (the one-step op adamvs_slice_reg_step, conv3x3_pair of MS-REDNet); the software-pipelined
 // recurrence of a whole stage runs the same roles several per launch (recurrence.hip).
 template <int CA, int CB, int NT, int STRIDE, int EPI, int TR, int RW>
@@ -50,6 +57,11 @@ __global__ __launch_bounds__(256, DEC_WAVES) void k_decoder(DecoderArgs a, TileG
 __global__ __launch_bounds__(256) void k_cand1_two_row(SmallConvArgs a, TileGrid tg) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   Cand1TwoRowRole::run(a, tg, TileRange{0, tg.ntiles}, blockIdx.x, gridDim.x, lds);
+}
+// the same on 8 x 32 tiles, two runs per wave (option gru_wino without bit 32), held to the four workgroups per CU of the 8 x 16 form
+__global__ __launch_bounds__(256, 4) void k_cand1_two_row32(SmallConvArgs a, TileGrid tg) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  Cand1TwoRowRole32::run(a, tg, TileRange{0, tg.ntiles}, blockIdx.x, gridDim.x, lds);
 }
 
 
@@ -122,7 +134,7 @@ static int launch_small_wino(const SmallConvArgs& a, int B, hipStream_t st, cons
 }
 
 // option gru_wino: bit mask of the GRU convolutions that run in the F(2x2, 3x3) form when a role has a launch of its own
-// (1 gates1, 2 gates2, 4 cand2, 8 cand1; default 7; 0 = the direct kernels, which the pipelined schedules use: their maps
+// (1 gates1, 2 gates2, 4 cand2, 8 cand1; 16 / 32: kernels.h; default 7; 0 = the direct kernels, which the pipelined schedules use: their maps
 // equal the direct kernels' bit for bit, the F(2x2, 3x3) ones to ~1e-7).
 // Measured at cfg2, 128 tiles (recurrence per step, ms): none 79.8; gates1 74.9; gates2 74.2; cand2 78.6; all three 68.3.
 int gru_wino_mask() { return opt(OPT_GRU_WINO); }
@@ -243,6 +255,11 @@ __global__ __launch_bounds__(256) void k_conv1_two_row(const float* __restrict__
 
 
 static int launch_cand1_two_row(const SmallConvArgs& a, int B, hipStream_t st) {
+  if (cand1_tile32_enabled()) {
+    TileGrid tg;
+    if (int rc = make_tile_grid(tg, Cand1TwoRowRole32::tiles_x(a), Cand1TwoRowRole32::tiles_y(a), B)) return rc;
+    return launch_resident<k_cand1_two_row32>(tg.ntiles, Cand1TwoRowRole32::LDS_BYTES, st, "cand1 (two-row, 8 x 32)", a, tg);
+  }
   constexpr int G = 4;
   constexpr size_t lds = (size_t)G * group_pitch(plane_pitch16(10 * 18), G) * sizeof(float);
   TileGrid tg;
@@ -766,6 +783,78 @@ int launch_conv1(const float* cost, const float* w, float* c1, int N, int C, int
   return set_error(-1, "conv1: C=%d unsupported (8, 16 or 32)", C);
 }
 
+// ---- schedule 0 with conv2 inside the level-1 gate launch (option gru_wino without bit 16): five launches per step t = 0 .. D,
+//   gates1(t) + conv2(t-1) | gates2(t-1) | cand2(t-1) | decoder(t-1) | cand1(t)
+// level 2 and the decoder one hypothesis behind level 1.  The kernels of level 2, the decoder and the candidate are those of
+// launch_slice_step; step t = D (nothing left for level 1) runs the stand-alone conv2.
+bool conv2_in_gates1_applies(const FuseWeights& fw, int h, int w, int precision) {
+  return precision == PRECISION_FP32 && conv2_in_gates1_enabled() && (gru_wino_mask() & 1) && fw.gates1_w && !(h & 1) && !(w & 1);
+}
+
+// The launches both drivers of one-role-per-launch steps share (launch_slice_step, launch_lagged_step): which form a role takes is
+// decided here and nowhere else.
+// cand1: h1_new = blend(u1, h1_prev, tanh(conv(cat(c1, r * h1)))); h1_prev == h1_new: updated in place
+static int launch_cand1(const FuseWeights& fw, const float* c1, float* rh1, float* u1, float* h1_new, const float* h1_prev, int B, int h, int w,
+                        hipStream_t st) {
+  SmallConvArgs c{c1, rh1, fw.cand1, fw.cand1_b, h1_new, u1, h, w, h, w, 8, h1_prev == h1_new ? nullptr : h1_prev};     // two-row fragments
+  if ((gru_wino_mask() & 8) && fw.cand1_w) {
+    c.wpk = fw.cand1_w;
+    return launch_small_wino<8, 8, 1, EPI_CAND>(c, B, st, "cand1 (F(2x2,3x3))");
+  }
+  return launch_cand1_two_row(c, B, st);
+}
+
+static int launch_decoder(const FuseWeights& fw, const float* h2s, const float* h1, float* vol, int B, int h, int w, int D, int d, int in_up,
+                          hipStream_t st) {
+  DecoderArgs da{h2s, h1, fw.upconv1, fw.upconv1_b, fw.final_w, vol, h, w, D, d};
+  TileGrid tg;
+  if (int rc = make_tile_grid(tg, cdiv(w, DecoderRole<true>::TCI), cdiv(h, DecoderRole<true>::TRI), B)) return rc;
+  constexpr size_t dlds = DecoderRole<true>::LDS_BYTES;
+  if (in_up) return launch_resident<k_decoder<true>>(tg.ntiles, dlds, st, "decoder", da, tg);
+  return launch_resident<k_decoder<false>>(tg.ntiles, dlds, st, "decoder", da, tg);
+}
+
+// GRU level 2 on c2: gates, candidate; h2_prev == h2_new: updated in place
+static int launch_level2(const FuseWeights& fw, float* c2, const float* h2_prev, float* h2_new, float* rh2, float* u2, int B, int h, int w,
+                         hipStream_t st) {
+  const int h2 = h / 2, w2 = w / 2;
+  int rc;
+  SmallConvArgs g{c2, h2_prev, fw.gates2, fw.gates2_b, rh2, u2, h2, w2, h2, w2, 32};
+  if ((gru_wino_mask() & 2) && fw.gates2_w) {
+    g.wpk = fw.gates2_w;
+    if ((rc = launch_small_wino<16, 16, 2, EPI_GATES>(g, B, st, "gates2 (F(2x2,3x3))"))) return rc;
+  } else if ((rc = launch_small<16, 16, 2, 1, EPI_GATES>(g, B, st, "gates2"))) return rc;
+  SmallConvArgs c{c2, rh2, fw.cand2, fw.cand2_b, h2_new, u2, h2, w2, h2, w2, 16, h2_prev == h2_new ? nullptr : h2_prev};
+  if ((gru_wino_mask() & 4) && fw.cand2_w) {
+    c.wpk = fw.cand2_w;
+    return launch_small_wino<16, 16, 1, EPI_CAND>(c, B, st, "cand2 (F(2x2,3x3))");
+  }
+  return launch_small<16, 16, 1, 1, EPI_CAND>(c, B, st, "cand2");
+}
+
+// c1_t: conv1 of hypothesis t (t < D); h1_prev / h1_new: h1(t-1) / h1(t); c2: conv2(h1(t-1)); h2_prev / h2_new: h2(t-2) / h2(t-1);
+// vol_dec, d_dec: where the decoded hypothesis t-1 goes
+int launch_lagged_step(const FuseWeights& fw, int B, int h, int w, int D, int t, const float* c1_t, const float* h1_prev, float* h1_new,
+                       float* rh1, float* u1, float* c2, const float* h2_prev, float* h2_new, float* rh2, float* u2, float* vol_dec, int D_vol,
+                       int d_dec, int in_up, hipStream_t st) {
+  const int h2 = h / 2, w2 = w / 2;
+  const bool l1 = t < D, l2 = t >= 1 && t <= D;
+  int rc;
+  if (l1) {
+    Gates1Conv2Args a{SmallConvArgs{c1_t, h1_prev, fw.gates1_w, fw.gates1_b, rh1, u1, h, w, h, w, 16}, l2 ? c2 : nullptr, fw.conv2};
+    TileGrid tg;
+    if ((rc = make_tile_grid(tg, Gates1Conv2WinoRole::tiles_x(a), Gates1Conv2WinoRole::tiles_y(a), B))) return rc;
+    if ((rc = launch_resident<k_gates1_conv2_wino>(tg.ntiles, Gates1Conv2WinoRole::LDS_BYTES, st, "gates1 + conv2 (F(2x2,3x3))", a, tg))) return rc;
+  } else if (l2) {
+    SmallConvArgs a{h1_prev, nullptr, fw.conv2, nullptr, c2, nullptr, h, w, h2, w2, 16};
+    if ((rc = launch_small<8, 0, 1, 2, EPI_RELU>(a, B, st, "conv2"))) return rc;
+  }
+  if (l2 && (rc = launch_level2(fw, c2, h2_prev, h2_new, rh2, u2, B, h, w, st))) return rc;
+  if (l2 && (rc = launch_decoder(fw, h2_new, h1_prev, vol_dec, B, h, w, D_vol, d_dec, in_up, st))) return rc;
+  if (l1 && (rc = launch_cand1(fw, c1_t, rh1, u1, h1_new, h1_prev, B, h, w, st))) return rc;
+  return 0;
+}
+
 // One recurrent step after conv1: c1 -> GRU1 -> conv2 -> GRU2 -> decoder -> vol[:, d].
 int launch_slice_step(const float* c1, const FuseWeights& fw, const StepBuffers& sb, float* vol, int B, int h, int w, int D,
                       int d, int in_up, int precision, hipStream_t st, float** h1_now, float** h2_now) {
@@ -781,37 +870,17 @@ int launch_slice_step(const float* c1, const FuseWeights& fw, const StepBuffers&
       g.wpk = fw.gates1_w;
       if ((rc = launch_small_wino<8, 8, 1, EPI_GATES>(g, B, st, "gates1 (F(2x2,3x3))"))) return rc;
     } else if ((rc = launch_small<8, 8, 1, 1, EPI_GATES>(g, B, st, "gates1"))) return rc;
-    SmallConvArgs c{c1, sb.rh1, fw.cand1, fw.cand1_b, sb.h1, sb.u1, h, w, h, w, 8};     // cand1: two-row fragments
-    if ((gru_wino_mask() & 8) && fw.cand1_w) {
-      c.wpk = fw.cand1_w;
-      if ((rc = launch_small_wino<8, 8, 1, EPI_CAND>(c, B, st, "cand1 (F(2x2,3x3))"))) return rc;
-    } else if ((rc = launch_cand1_two_row(c, B, st))) return rc;
+    if ((rc = launch_cand1(fw, c1, sb.rh1, sb.u1, sb.h1, sb.h1, B, h, w, st))) return rc;
   }
   {  // conv2: 8 -> 16, stride 2, ReLU
     SmallConvArgs a{h1, nullptr, fw.conv2, nullptr, sb.c2, nullptr, h, w, h2, w2, 16};
     if ((rc = launch_small<8, 0, 1, 2, EPI_RELU>(a, B, st, "conv2"))) return rc;
   }
-  {  // GRU level 2
-    SmallConvArgs g{sb.c2, sb.h2, fw.gates2, fw.gates2_b, sb.rh2, sb.u2, h2, w2, h2, w2, 32};
-    if ((gru_wino_mask() & 2) && fw.gates2_w) {
-      g.wpk = fw.gates2_w;
-      if ((rc = launch_small_wino<16, 16, 2, EPI_GATES>(g, B, st, "gates2 (F(2x2,3x3))"))) return rc;
-    } else if ((rc = launch_small<16, 16, 2, 1, EPI_GATES>(g, B, st, "gates2"))) return rc;
-    SmallConvArgs c{sb.c2, sb.rh2, fw.cand2, fw.cand2_b, sb.h2, sb.u2, h2, w2, h2, w2, 16};
-    if ((gru_wino_mask() & 4) && fw.cand2_w) {
-      c.wpk = fw.cand2_w;
-      if ((rc = launch_small_wino<16, 16, 1, EPI_CAND>(c, B, st, "cand2 (F(2x2,3x3))"))) return rc;
-    } else if ((rc = launch_small<16, 16, 1, 1, EPI_CAND>(c, B, st, "cand2"))) return rc;
-  }
+  if ((rc = launch_level2(fw, sb.c2, sb.h2, sb.h2, sb.rh2, sb.u2, B, h, w, st))) return rc;      // GRU level 2
   }
   if (h1_now) *h1_now = h1;
   if (h2_now) *h2_now = h2s;
-  DecoderArgs da{h2s, h1, fw.upconv1, fw.upconv1_b, fw.final_w, vol, h, w, D, d};
-  TileGrid tg;
-  if ((rc = make_tile_grid(tg, cdiv(w, DecoderRole<true>::TCI), cdiv(h, DecoderRole<true>::TRI), B))) return rc;
-  constexpr size_t dlds = DecoderRole<true>::LDS_BYTES;
-  if (in_up) return launch_resident<k_decoder<true>>(tg.ntiles, dlds, st, "decoder", da, tg);
-  return launch_resident<k_decoder<false>>(tg.ntiles, dlds, st, "decoder", da, tg);
+  return launch_decoder(fw, h2s, h1, vol, B, h, w, D, d, in_up, st);
 }
 
 int launch_soft_argmin(const float* vol, const float* planes, float* depth, float* conf, int B, int D, int h, int w,

@@ -909,14 +909,17 @@ struct DecoderRole {
 // lane's own pixel requested before the chain; h updated in place), the tile and pipeline of k_conv1_two_row.
 // EPI2 = TR_CAND: that epilogue.  EPI2 = TR_BIAS_RELU: out = ReLU(conv + bias) -- the same two-source, two-row convolution as a
 // plain layer (FeatureNet0's deconv2.conv: 3x3 on cat(deconv output, skip), 16 -> 8 channels + folded BatchNorm + ReLU).
+// RW: 16-column runs per wave.  At RW = 2 (8 x 32 tiles, 10 x 34 window) a wave feeds its two-row A fragments to two runs of its
+// row pair, each with its own accumulator: the same sum per pixel, and the window's halo along x is 34 / 32 of the tile instead of
+// 18 / 16 -- in 128-byte lines of the channel-last sources 1.25 instead of 1.5 (the level-1 candidate at 256 tiles is HBM-bound).
 enum { TR_CAND = 0, TR_BIAS_RELU = 1 };
-template <int EPI2>
+template <int EPI2, int RW = 1>
 struct TwoRowPairRole {
   typedef SmallConvArgs Args;
-  static constexpr int CA = 8, CB = 8, C = 16, KC = C / 4, G = C / 4, GA = CA / 4, TR = 8, TC = 16, LR = TR + 2, LC = TC + 2;
+  static constexpr int CA = 8, CB = 8, C = 16, KC = C / 4, G = C / 4, GA = CA / 4, TR = 8, TC = 16 * RW, LR = TR + 2, LC = TC + 2;
   static constexpr int NPIX = LR * LC, PLANE = plane_pitch16(NPIX), GP = group_pitch(PLANE, G);
   static constexpr int NA = (NPIX * GA + 255) / 256, NL = 2 * NA;     // loads per source: a load's base must be uniform
-  static constexpr size_t LDS_BYTES = (size_t)G * GP * sizeof(float);         // tile [G][GP]
+  static constexpr size_t LDS_BYTES = (size_t)(G * GP + (RW > 1 ? 8 : 0)) * sizeof(float);         // tile [G][GP] (RW > 1: + the bias)
   static constexpr int TILE_W = TC, TILE_H = TR;
   static int tiles_x(const Args& a) { return cdiv(a.wo, TC); }
   static int tiles_y(const Args& a) { return cdiv(a.ho, TR); }
@@ -925,28 +928,40 @@ struct TwoRowPairRole {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int p = lane & 15, q = lane >> 4;
   const int h = a.hi, w = a.wi;
+  // RW > 1: window rows 0 and 3 of a row pair feed one output row each -- MFMA rows 8-15 of the fragments of row 0 and rows 0-7
+  // of those of row 3 are zeros -- so the two share their registers (slots 0-2: lanes of rows 0-7 hold row 0's, the others row
+  // 3's) and the zero halves are selected per MFMA: 12 registers for 24 selects per 96 MFMAs, the same operands bit for bit.
+  const bool lower = p < 8;
   float wf[12][KC];
 #pragma unroll
-  for (int t = 0; t < 12; ++t)
+  for (int t = 0; t < (RW > 1 ? 9 : 12); ++t)
 #pragma unroll
-    for (int kc = 0; kc < KC; ++kc) wf[t][kc] = a.wpk[(t * KC + kc) * 64 + lane];
-  const f32x4 bias = *(const f32x4*)(a.bias + 4 * (q & 1));
+    for (int kc = 0; kc < KC; ++kc) wf[t][kc] = a.wpk[(((RW > 1 && t < 3 && !lower) ? t + 9 : t) * KC + kc) * 64 + lane];
+  f32x4 bias = {0.f, 0.f, 0.f, 0.f};
+  if (RW == 1) bias = *(const f32x4*)(a.bias + 4 * (q & 1));
+  else if (tid < 8) lds[G * GP + tid] = a.bias[tid];          // read back in the epilogue (visible after the first barrier)
 
+  // (RW > 1: the two sources have the same shape, so item k of the second has the offsets of item k - NA of the first, its LDS
+  //  address GA groups further on, and the k-chunks of a B fragment are immediates from the first: the registers that the second
+  //  run's accumulator and epilogue operands take, at the same four workgroups per CU)
+  constexpr bool SHARE = RW > 1;
+  constexpr int NI = SHARE ? NA : NL, NX = SHARE ? 1 : KC;
   unsigned goff[NL], lbyte[NL];
   int rc[NL];
 #pragma unroll
-  for (int k = 0; k < NL; ++k) {
+  for (int k = 0; k < NI; ++k) {
     const bool isA = k < NA;
     const int j = min(tid + (isA ? k : k - NA) * 256, NPIX * GA - 1);          // surplus lanes repeat the last item
     const int g = j % GA, pp = j / GA, r = pp / LC, c = pp % LC;
     goff[k] = (unsigned)(((r * w + c) * CA + 4 * g) * 4);
     lbyte[k] = (unsigned)((((isA ? 0 : GA) + g) * GP + r * LC + c) * 4);
     rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]); pin(rc[k]);
+    pin(goff[k]); pin(lbyte[k]);
+    if (!SHARE) pin(rc[k]);                                                    // (SHARE: formed again on edge tiles)
   }
   unsigned xbyte[KC];
 #pragma unroll
-  for (int kc = 0; kc < KC; ++kc) {
+  for (int kc = 0; kc < NX; ++kc) {
     xbyte[kc] = (unsigned)((kc * GP + q * PLANE + (2 * wave) * LC + p) * 4);
     pin(xbyte[kc]);
   }
@@ -961,19 +976,20 @@ struct TwoRowPairRole {
     const buf_rsrc rb = make_rsrc((const char*)a.srcB + pix0 * (CB * 4));
     if (iy0 >= 0 && ix0 >= 0 && iy0 + LR <= h && ix0 + LC <= w) {
 #pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(k < NA ? ra : rb, goff[k]);
+      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(k < NA ? ra : rb, goff[k % NI]);
     } else {
 #pragma unroll
       for (int k = 0; k < NL; ++k) {
-        const int iy = iy0 + (rc[k] & 0xffff), ix = ix0 + (rc[k] >> 16);
-        stage[k] = buf_load4(k < NA ? ra : rb, ((unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w) ? goff[k] : BUF_OOB);
+        const int pp = min(tid + (k % NA) * 256, NPIX * GA - 1) / GA;
+        const int iy = iy0 + (SHARE ? pp / LC : rc[k] & 0xffff), ix = ix0 + (SHARE ? pp % LC : rc[k] >> 16);
+        stage[k] = buf_load4(k < NA ? ra : rb, ((unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w) ? goff[k % NI] : BUF_OOB);
       }
     }
   };
   auto store_tile = [&](const f32x4 (&stage)[NL]) {
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
-      float* dl = (float*)((char*)lds + lbyte[k]);
+      float* dl = (float*)((char*)lds + lbyte[k % NI] + (SHARE && k >= NA ? GA * GP * 4 : 0));
       f32x4 v = stage[k];
       dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
     }
@@ -994,10 +1010,15 @@ struct TwoRowPairRole {
     const buf_rsrc rh = make_rsrc((char*)a.dst0 + opix0 * 32);          // new h (the same buffer as the old one when hin is null)
     const buf_rsrc rin = make_rsrc((const char*)(a.hin ? a.hin : a.dst0) + opix0 * 32);     // h of the previous step
     const buf_rsrc ru = make_rsrc((const char*)a.dst1 + opix0 * 32);    // u
-    unsigned oo = ooff;
-    if (!(y0 + TR <= h && x0 + TC <= w)) oo = (y0 + orow < h && x0 + p < w) ? ooff : BUF_OOB;
-    f32x4 pre_u = {0.f, 0.f, 0.f, 0.f}, pre_h = pre_u;
-    if (EPI2 == TR_CAND) { pre_u = buf_load4(ru, oo); pre_h = buf_load4(rin, oo); }      // epilogue operands first, then the next tile
+    unsigned oo[RW];
+    f32x4 pre_u[RW], pre_h[RW];
+#pragma unroll
+    for (int j = 0; j < RW; ++j) {
+      oo[j] = ooff + (unsigned)(j * 16 * 32);
+      if (!(y0 + TR <= h && x0 + TC <= w)) oo[j] = (y0 + orow < h && x0 + 16 * j + p < w) ? oo[j] : BUF_OOB;
+      pre_u[j] = pre_h[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (EPI2 == TR_CAND) { pre_u[j] = buf_load4(ru, oo[j]); pre_h[j] = buf_load4(rin, oo[j]); }      // epilogue operands first, then the next tile
+    }
     const int tn = t + nwg;
     const bool more = tn < tr.end;
     int nn = 0, txn = 0, tyn = 0;
@@ -1005,26 +1026,37 @@ struct TwoRowPairRole {
       tile_coords(tg, tn, nn, txn, tyn);
       load_tile(stage, nn, txn, tyn);
     }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[RW];
+#pragma unroll
+    for (int j = 0; j < RW; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float zero = 0.f;
+    if (RW > 1) pin(zero);                          // (a per-tile value: the selects below are not hoisted out of the tile loop)
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr)
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc)
-          acc = mfma16(wf[rr * 3 + kx][kc], *(const float*)((const char*)lds + xbyte[kc] + (rr * LC + kx) * 4), acc);
-    drain(acc);
+#pragma unroll
+          for (int j = 0; j < RW; ++j)
+            acc[j] = mfma16(RW == 1 ? wf[rr * 3 + kx][kc] : (rr == 0 ? (lower ? wf[kx][kc] : zero) : (rr == 3 ? (lower ? zero : wf[kx][kc]) : wf[rr * 3 + kx][kc])),
+                            *(const float*)((const char*)lds + xbyte[kc % NX] + ((SHARE ? kc * GP : 0) + rr * LC + kx + 16 * j) * 4), acc[j]);
+#pragma unroll
+    for (int j = 0; j < RW; ++j) drain(acc[j]);
 
     wait_vmem_all();
     __syncthreads();                                // every wave is done reading the tile
     if (more) store_tile(stage);
 
-    const f32x4 v = acc + bias;
-    if (EPI2 == TR_CAND) {
-      const f32x4 cnd = {tanh_fast(v.x), tanh_fast(v.y), tanh_fast(v.z), tanh_fast(v.w)};
-      buf_store4(rh, oo, pre_u * pre_h + (1.0f - pre_u) * cnd);
-    } else {
-      buf_store4(rh, oo, f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)});
+#pragma unroll
+    for (int j = 0; j < RW; ++j) {
+      const f32x4 v = acc[j] + (RW == 1 ? bias : *(const f32x4*)(lds + G * GP + 4 * (q & 1)));
+      if (EPI2 == TR_CAND) {
+        const f32x4 cnd = {tanh_fast(v.x), tanh_fast(v.y), tanh_fast(v.z), tanh_fast(v.w)};
+        buf_store4(rh, oo[j], pre_u[j] * pre_h[j] + (1.0f - pre_u[j]) * cnd);
+      } else {
+        buf_store4(rh, oo[j], f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)});
+      }
     }
     if (!more) break;
     __syncthreads();                                // next tile visible
@@ -1033,5 +1065,6 @@ struct TwoRowPairRole {
   }
 };
 typedef TwoRowPairRole<TR_CAND> Cand1TwoRowRole;
+typedef TwoRowPairRole<TR_CAND, 2> Cand1TwoRowRole32;      // a launch of its own (option gru_wino without bit 32)
 
 }  // namespace adamvs

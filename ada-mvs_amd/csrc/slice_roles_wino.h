@@ -1,9 +1,11 @@
 // The 3x3 convolutions of the ConvGRU cells (reference models/module.py:24-52) in the minimal-filtering form F(2x2, 3x3),
 // fp32 throughout: 16 products per 2x2 outputs and channel pair instead of 36.
 //
-// Why here: the recurrence is matrix-bound on the fp32 pipe at 60-70 % utilisation (lesson 7) and every
-// other way round that bound has been built and measured (fused levels, shared launches, deeper prefetch: none moves it).
-// What is left is the number of multiplications.  CostRegNet2D's stride-1 layers already run this way (costreg2d_wino.hip);
+// Why here: at 128 tiles per step, with the direct kernels, the recurrence was matrix-bound on the fp32 pipe at 60-70 % utilisation
+// (lesson 7) and every other way round that bound had been built and measured (fused levels, shared launches,
+// deeper prefetch: none moved it); what was left was the number of multiplications.  (With these kernels, at 256 tiles, the
+// recurrence is HBM-bound launch by launch -- lesson 7's table -- and what is left is bytes: Gates1Conv2WinoRole below.)
+// CostRegNet2D's stride-1 layers already run this way (costreg2d_wino.hip);
 // for the 16- and 32-channel convolutions of the GRU cells the same algebra needs a different mapping, because K is short
 // and the weights of a whole layer fit the register file:
 //   * workgroup = 4 waves = the 4 ROWS i of the transformed 4x4 patch (as in k_conv_wino): wave i reads two raw patch rows
@@ -58,11 +60,23 @@ struct ConvWinoRole {
   // level-2 gates (NT = 2: 47 + 32 KB) would lose a workgroup per CU to it and keep 1.
   static constexpr int RPR = (WINO_GRU_RPR2 && EPI == EPI_CAND && NT == 1 && KC == 8) ? 2 : 1;
   static constexpr size_t LDS_BYTES = (size_t)(Z0 + 2 * RPR * ZBUF) * sizeof(float);
+  static constexpr int BL0 = Z0 + 2 * RPR * ZBUF;                      // CONV2: the scaled bias [4 q][4], then four zeros (80 bytes)
   static constexpr int TILE_W = TC, TILE_H = TR;
   static int tiles_x(const Args& a) { return cdiv(a.wo, TC); }
   static int tiles_y(const Args& a) { return cdiv(a.ho, TR); }
 
   static __device__ __forceinline__ void run(const Args& a, const TileGrid& tg, TileRange tr, int wg, int nwg, float* lds) {
+    run_impl<false>(a, tg, tr, wg, nwg, lds, nullptr, nullptr);
+  }
+
+  // CONV2 (Gates1Conv2WinoRole below, level-1 gates only): the state half of the window is h1 of the previous hypothesis, and
+  // the 8 x 32 pixels + ring of a tile are exactly the window of the 4 x 16 half-resolution outputs of conv2 (8 -> 16, stride 2,
+  // pad 1, ReLU) under it: wave r forms output row r from the h1 planes before the exchange rounds begin and stores it to `c2`
+  // (null, uniform: no conv2 in this launch).  `c2w`: conv2's A fragments [9][2][64].
+  template <bool CONV2>
+  static __device__ __forceinline__ void run_impl(const Args& a, const TileGrid& tg, TileRange tr, int wg, int nwg, float* lds, float* c2,
+                                                  const float* c2w) {
+  static_assert(!CONV2 || (EPI == EPI_GATES && CA == 8 && CB == 8 && NT == 1), "conv2 reads the level-1 state window");
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave = patch row i
   const int p = lane & 15, q = lane >> 4;
 
@@ -85,18 +99,31 @@ struct ConvWinoRole {
   // accumulator position (1, 1) (round 5): At E A is all ones for the unit element E11, so the sum that wave 1 starts from the bias
   // carries it into all four outputs of a tile (costreg2d_wino.hip does the same) and the epilogue adds nothing.
   constexpr float PRE = EPI == EPI_GATES ? -1.4426950408889634f : 2.8853900817779268f;
+  // (CONV2: the bias of accumulator position (1, 1) waits in LDS, four registers the conv2 fragments need; wave 1 reads its
+  //  q's four values, the other waves the zeros behind them)
+  constexpr bool BL = CONV2 && WINO_GRU_IL && IL;
+  unsigned bb = 0u;
+  if (BL) {
+    if (tid < 20) lds[BL0 + tid] = tid < 16 ? a.bias[((tid & 2) ? 8 : 0) + 2 * (tid >> 2) + (tid & 1)] * PRE : 0.f;      // visible after the first barrier
+    bb = (unsigned)((BL0 + (wave == 1 ? 4 * q : 16)) * 4);
+    pin(bb);
+  }
   f32x4 bias[NT];
 #pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
+  for (int nt = 0; nt < NT && !BL; ++nt) {
     const f32x4 b = IL ? f32x4{a.bias[2 * q], a.bias[2 * q + 1], a.bias[8 + 2 * q], a.bias[8 + 2 * q + 1]} : *(const f32x4*)(a.bias + nt * 16 + 4 * q);
     bias[nt] = WINO_GRU_IL ? (wave == 1 ? b * PRE : f32x4{0.f, 0.f, 0.f, 0.f}) : b * PRE;
     if (WINO_GRU_IL) drain(bias[nt]);             // (kept in registers: the select is made once)
   }
 
   // ---- window fill: as ConvSmallRole (two sources, planar groups)
+  // (CONV2: the two sources have the same shape, so item k of the state half has the offsets of item k - NA of the input half, its
+  //  LDS address GA groups further on: six registers the conv2 fragments need, or the kernel loses a workgroup per CU)
+  constexpr bool SHARE = CONV2 && CA == CB;
+  constexpr int LSH = SHARE ? GA * GP * 4 : 0;
   unsigned goff[NL], lbyte[NL];
 #pragma unroll
-  for (int k = 0; k < NL; ++k) {
+  for (int k = 0; k < (SHARE ? NA : NL); ++k) {
     const bool isA = k < NA;
     const int gs = isA ? GA : GB, cs = isA ? CA : CB;
     int j = tid + (isA ? k : k - NA) * 256;
@@ -112,19 +139,36 @@ struct ConvWinoRole {
   const float sgn = wave == 1 ? 1.0f : -1.0f;
   const f32x2w sgn2 = {sgn, sgn};
   unsigned pa = (unsigned)((q * PLANE + rowA * LC + 2 * p) * 4), pb = (unsigned)((q * PLANE + rowB * LC + 2 * p) * 4);
-  pin(pa); pin(pb);
+  pin(pa);
+  if (!CONV2) pin(pb);                                                 // (CONV2: pa + a wave-uniform distance, formed per use)
   // epilogue: wave (oa, ob) owns output pixel (2 t + oa, 2 p + ob) of every 2x2 tile of tile row t
   const int oa = wave >> 1, ob = wave & 1;
   const float os = oa ? -1.0f : 1.0f;
   const int CO = HC;                                                   // channels per pixel of both destinations
   unsigned ooff = (unsigned)(((oa * a.wo + 2 * p + ob) * CO + 4 * q) * 4);      // + 2 t rows; GATES: r*h and u share it (co4 or co4 - HC)
-  pin(ooff);
+  if (!(CONV2 && IL)) pin(ooff);                                       // (IL stores through ooff2)
   // GATES: the state channels 4 q .. of the wave's pixel, in the window (pixel (2 t + oa + 1, 2 p + ob + 1)); IL: channels 2 q, 2 q + 1
   const unsigned hbyte = IL ? (unsigned)(((GA + (q >> 1)) * GP + 2 * (q & 1) * PLANE + (oa + 1) * LC + 2 * p + ob + 1) * 4)
                             : (unsigned)(((GA + min(q, GB - 1)) * GP + (oa + 1) * LC + 2 * p + ob + 1) * 4);
   unsigned ooff2 = (unsigned)(((oa * a.wo + 2 * p + ob) * CO + 2 * q) * 4);     // IL: the lane's channel pair of both destinations
   if (IL) pin(ooff2);
   float* zl = lds + Z0;
+  // CONV2: fragments in conv2's own order (tap, k-chunk); the lane's B-fragment origin = plane q of state group kc, window pixel
+  // (2 wave, 2 p) (output (r, p) reads window rows 2 r .. 2 r + 2, columns 2 p .. 2 p + 2: window row 0 is y0 - 1); its output
+  // pixel (wave, p), channels 4 q .. of 16
+  float cw[CONV2 ? 9 : 1][2];
+  unsigned cx = 0u, coff = 0u;
+  const int h2 = a.ho >> 1, w2 = a.wo >> 1;
+  if (CONV2) {
+#pragma unroll
+    for (int t9 = 0; t9 < 9; ++t9)
+#pragma unroll
+      for (int kc = 0; kc < 2; ++kc) cw[CONV2 ? t9 : 0][kc] = c2w[(t9 * 2 + kc) * 64 + lane];
+    cx = (unsigned)((GA * GP + q * PLANE + (2 * wave) * LC + 2 * p) * 4);
+    pin(cx);
+    coff = (unsigned)(((wave * w2 + p) * 16 + 4 * q) * 4);
+    pin(coff);
+  }
 
   auto load_tile = [&](f32x4 (&stage)[NL], int b, int tx, int ty) {
     const int ix0 = tx * TC - 1, iy0 = ty * TR - 1;
@@ -133,7 +177,7 @@ struct ConvWinoRole {
     const buf_rsrc rb = make_rsrc((const char*)a.srcB + pix0 * (CB * 4));
     if (iy0 >= 0 && ix0 >= 0 && iy0 + LR <= a.hi && ix0 + LC <= a.wi) {
 #pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(k < NA ? ra : rb, goff[k]);
+      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(k < NA ? ra : rb, goff[SHARE && k >= NA ? k - NA : k]);
     } else {
 #pragma unroll
       for (int k = 0; k < NL; ++k) {
@@ -141,14 +185,14 @@ struct ConvWinoRole {
         const int gs = isA ? GA : GB;
         const int pp = min(tid + (isA ? k : k - NA) * 256, NPIX * gs - 1) / gs;
         const int iy = iy0 + pp / LC, ix = ix0 + pp % LC;
-        stage[k] = buf_load4(isA ? ra : rb, ((unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi) ? goff[k] : BUF_OOB);
+        stage[k] = buf_load4(isA ? ra : rb, ((unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi) ? goff[SHARE && k >= NA ? k - NA : k] : BUF_OOB);
       }
     }
   };
   auto store_tile = [&](const f32x4 (&stage)[NL]) {
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
-      float* dl = (float*)((char*)lds + lbyte[k]);
+      float* dl = (float*)((char*)lds + lbyte[SHARE && k >= NA ? k - NA : k] + (k >= NA ? LSH : 0));
       const f32x4 v = stage[k];
       dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
     }
@@ -193,6 +237,22 @@ struct ConvWinoRole {
       tile_coords(tg, tn, bn, txn, tyn);
       load_tile(stage, bn, txn, tyn);                                  // in flight during the four tile rows
     }
+    if (CONV2 && c2) {                                                 // uniform.  The sum of ConvSmallRole<8, 0, 1, 2, EPI_RELU>: taps in
+      f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};                               // row order, k-chunks inside, one accumulator chain
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+          for (int kc = 0; kc < 2; ++kc)
+            acc2 = mfma16(cw[CONV2 ? ky * 3 + kx : 0][kc], *(const float*)((const char*)lds + cx + (kc * GP + ky * LC + kx) * 4), acc2);
+      drain(acc2);
+      const buf_rsrc rc2 = make_rsrc((char*)c2 + (((long)b * h2 + ty * (TR / 2)) * w2 + tx * (TC / 2)) * 64);
+      const bool in2 = ty * (TR / 2) + wave < h2 && tx * (TC / 2) + p < w2;
+      f32x4 v2 = acc2 + f32x4{0.f, 0.f, 0.f, 0.f};                     // (that role's zero bias)
+      v2.x = fmaxf(v2.x, 0.f); v2.y = fmaxf(v2.y, 0.f); v2.z = fmaxf(v2.z, 0.f); v2.w = fmaxf(v2.w, 0.f);
+      buf_store4(rc2, in2 ? coff : BUF_OOB, v2);
+    }
 
 #pragma unroll
     for (int rd = 0; rd < 4 / RPR; ++rd) {                             // exchange round: tile rows rd * RPR .. (output rows 2 tr4, 2 tr4 + 1 each)
@@ -202,7 +262,8 @@ struct ConvWinoRole {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) m[rr][nt][j] = (WINO_GRU_IL && j == 1) ? bias[nt] : f32x4{0.f, 0.f, 0.f, 0.f};
+          for (int j = 0; j < 4; ++j)
+            m[rr][nt][j] = (WINO_GRU_IL && j == 1) ? (BL ? *(const f32x4*)((const char*)lds + bb) : bias[nt]) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int kc = 0; kc < KC; ++kc)
 #pragma unroll
@@ -245,7 +306,7 @@ struct ConvWinoRole {
 #pragma unroll
       for (int rr = 0; rr < RPR; ++rr) {
       const int tr4 = rd * RPR + rr;
-      unsigned oo = ooff + (unsigned)(2 * tr4 * a.wo * CO * 4);
+      unsigned oo = (CONV2 && IL) ? 0u : ooff + (unsigned)(2 * tr4 * a.wo * CO * 4);
       if (!full && !(oy0 + 2 * tr4 + oa < a.ho && ox0 + 2 * p + ob < a.wo)) oo = BUF_OOB;
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
@@ -288,6 +349,26 @@ struct ConvWinoRole {
     __syncthreads();                   // next tile visible
     t = tn; b = bn; tx = txn; ty = tyn;
   }
+  }
+};
+
+// The level-1 gates plus conv2 of the state they read (h1 of the previous hypothesis): conv2's own read of h1 and its launch are
+// gone, its outputs bit for bit those of ConvSmallRole<8, 0, 1, 2, EPI_RELU>.  The maps are even in h and w (the driver checks), so
+// the 8 x 32 gate tiles and conv2's 4 x 16 tiles are the same grid.
+struct Gates1Conv2Args {
+  SmallConvArgs g;        // the gate convolution: srcA = c1(t), srcB = h1(t - 1), ...
+  float* c2;              // [B][(h/2)*(w/2)][16] = ReLU(conv2(h1(t - 1))); null: no conv2 in this launch (t = 0)
+  const float* conv2_w;   // A fragments [1][9][2][64]
+};
+struct Gates1Conv2WinoRole {
+  typedef Gates1Conv2Args Args;
+  typedef ConvWinoRole<8, 8, 1, EPI_GATES> Base;
+  static constexpr size_t LDS_BYTES = Base::LDS_BYTES + 80;               // + the bias the gates start their sums from
+  static constexpr int TILE_W = Base::TILE_W, TILE_H = Base::TILE_H;
+  static int tiles_x(const Args& a) { return Base::tiles_x(a.g); }
+  static int tiles_y(const Args& a) { return Base::tiles_y(a.g); }
+  static __device__ __forceinline__ void run(const Args& a, const TileGrid& tg, TileRange tr, int wg, int nwg, float* lds) {
+    Base::run_impl<true>(a.g, tg, tr, wg, nwg, lds, a.c2, a.conv2_w);
   }
 };
 

@@ -64,6 +64,9 @@ def pack_conv1_two_row(w):
     w = w.detach().to(torch.float32).cpu()
     cout, cin = w.shape[0], w.shape[1]
     assert cout == 8 and cin % 4 == 0
+    # MFMA rows 8-15 of window row rr = 0 and rows 0-7 of rr = 3 stay EXACT zeros: the 8 x 32 form of cand1 (csrc/slice_roles.h,
+    # TwoRowPairRole<., 2>) never loads those halves -- it keeps rows 0-7 of rr = 0 and rows 8-15 of rr = 3 in one register set and
+    # selects a zero for the other half -- so anything else written there would be dropped by that kernel and used by the 8 x 16 one
     wp = torch.zeros(4, 3, 16, cin)                       # [rr][kx][row16][cin]
     for rr in range(4):
         if rr <= 2:
@@ -71,6 +74,7 @@ def pack_conv1_two_row(w):
         if rr >= 1:
             wp[rr, :, 8:] = w[:, :, rr - 1, :].permute(2, 0, 1)
     # (rr, kx, row16, kc, k4) -> (rr, kx, kc, k4, row16): lane = k4*16 + row16
+    assert not wp[0, :, 8:].any() and not wp[3, :, :8].any()
     return wp.reshape(4, 3, 16, cin // 4, 4).permute(0, 1, 3, 4, 2).contiguous().reshape(-1)
 
 

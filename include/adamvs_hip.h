@@ -59,9 +59,17 @@ const char* adamvs_last_error_string(void);
  *   fconv_f23                1     FeatureNet0's stride-1 3x3 layers in the F(2, 3)-along-x form; 0: k_fconv
  *   gru_wino                 7     fp32 ConvGRU convolutions (module.py:24-52) in the F(2x2, 3x3) form where a role has a launch of
  *                                  its own and in the three-launch schedule: 1 gates1, 2 gates2, 4 cand2, 8 cand1; 0: direct kernels
- *                                  (the software-pipelined schedules 3 and 5 always use the direct / fused roles)
- *   recur_mode              -1     launches per hypothesis of the recurrence: 0 one role per launch (six; bf16x3: four), 1 three,
- *                                  3 two, 5 one (both levels one kernel each); -1: by stage size (adamvs_recurrence_schedule)
+ *                                  (the software-pipelined schedules 3 and 5 always use the direct / fused roles).
+ *                                  Two more bits, both CLEAR by default, give back the launches of before: + 16 conv2 (adamvs.py:418)
+ *                                  in a launch of its own (clear: with bit 1, on even maps, conv2 of hypothesis t - 1 runs inside the
+ *                                  gate launch of level 1 of hypothesis t, whose tile window holds its inputs; level 2 and the
+ *                                  decoder then run one hypothesis behind level 1 and schedule 0 has five launches per hypothesis);
+ *                                  + 32 cand1 with a launch of its own on 8 x 16 tiles (clear: 8 x 32).  And one that is clear by
+ *                                  default and switches a form ON: + 64 slot A of the three-launch schedule (recur_mode 1) is the
+ *                                  level-1 gate role with conv2 inside instead of gates1 | conv2.  Same maps bit for bit.
+ *   recur_mode              -1     launches per hypothesis of the recurrence: 0 one role per launch (six, or five: gru_wino; bf16x3:
+ *                                  four), 1 three, 3 two, 5 one (both levels one kernel each); -1: by stage size
+ *                                  (adamvs_recurrence_schedule)
  */
 int adamvs_option_count(void);
 const char* adamvs_option_name(int index);                   /* 0 <= index < adamvs_option_count(); NULL outside */
