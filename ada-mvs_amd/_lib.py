@@ -247,6 +247,16 @@ SIGNATURES = {
                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
     "adamvs_knn_normals_host": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_long, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "adamvs_rigid_apply": (c_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                 ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_rigid_apply_host": (c_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                      ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]),
+    "adamvs_icp_accumulate": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                    ctypes.c_long, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.c_void_p, c_st]),
+    "adamvs_icp_accumulate_host": (c_i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_long, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    "adamvs_icp_reduce": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_icp_reduce_host": (c_i, [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p]),
     "adamvs_ortho_surface": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.c_void_p, c_st]),
     "adamvs_ortho_zbuf": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.POINTER(OrthoView), ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_void_p, ctypes.c_long, c_st]),
@@ -312,6 +322,7 @@ CLOUD_MAX_SUBDIV = 1024          # ADAMVS_CLOUD_MAX_SUBDIV: largest n of a face 
 KNN_MAX_K = 32                   # ADAMVS_KNN_MAX_K: largest k of the cloud neighbourhoods
 KNN_RANK_EPS = 1e-12             # ADAMVS_KNN_RANK_EPS: a neighbourhood with lambda1 <= eps lambda2 is collinear
 KNN_VALID, KNN_TOO_FEW, KNN_COLLINEAR = 0, 1, 2    # ADAMVS_KNN_VALID / _TOO_FEW / _COLLINEAR: the flag of a normal
+ICP_TERMS = 32                   # ADAMVS_ICP_TERMS: sums of one accumulation of the cloud registration
 ORTHO_BEST, ORTHO_FEATHER = 0, 1 # ADAMVS_ORTHO_BEST / ADAMVS_ORTHO_FEATHER
 ORTHO_MAX_CELLS = 1 << 28        # ADAMVS_ORTHO_MAX_CELLS
 ORTHO_MAX_UPSAMPLE = 8           # ADAMVS_ORTHO_MAX_UPSAMPLE

@@ -8,7 +8,8 @@ every point of the truth to the nearest point of the reconstruction; precision a
 those distances <= tau, and F = 2 P R / (P + R).  Both directions are one bounded nearest-neighbour search (include/adamvs_hip.h
 "Cloud distance" states every operation, csrc/cloud_dist.hip holds the kernels): distances beyond --max_dist D are not looked
 for.  The mean and the RMSE count them as D (the DTU convention); the other figures are over the points within D.  Both inputs
-are taken to share a frame, as every product of this pipeline does: nothing is registered.
+are taken to share a frame, as every product of this pipeline does: nothing is registered here.  A truth georeferenced on its
+own is aligned first by register_whu.py (ada_mvs_amd/register.py: point-to-plane ICP), whose `<out>.ply` is scored here.
 
 Each input is a point PLY (fuse_whu.py's layout) or a mesh PLY (mesh_whu.py's); a mesh is scored through points sampled on its
 faces at --spacing (default D / 4; or --spacing_voxels times the voxel of `<mesh>.json`): every point of the surface lies within
@@ -101,6 +102,40 @@ def _cloud(t, name):
     return t.contiguous()
 
 
+def sort_targets(targets, tkeys):
+    """The targets under their keys, sorted stably -> (ukeys [nc] int64: the occupied cells ascending; tstart [nc + 1] int64: the start
+    of each cell's run; the sorted targets [nt, 3]; tindex [nt] int32: their numbers in the caller's order)."""
+    import torch
+    ts = torch.sort(tkeys, stable=True)
+    ukeys, tcount = torch.unique_consecutive(ts.values, return_counts=True)
+    tstart = torch.zeros(int(ukeys.numel()) + 1, device=tkeys.device, dtype=torch.int64)
+    tstart[1:] = torch.cumsum(tcount, 0)
+    return ukeys, tstart, targets[ts.indices].contiguous(), ts.indices.to(torch.int32)
+
+
+def work_items(qs):
+    """qs: the stable sort of the query keys -> (outside: the queries with a key of -1; qorder [nqs] int64: the others in sorted
+    order; (item_key, item_first, item_count): every run of equal keys cut into work items of at most CLOUD_TILE queries, or None
+    where no query lies in the lattice)."""
+    import torch
+    from . import _lib
+    dev = qs.values.device
+    outside = int(torch.searchsorted(qs.values, torch.zeros(1, device=dev, dtype=torch.int64)))     # keys of -1 sort first
+    qorder = qs.indices[outside:].contiguous()
+    if qorder.numel() == 0:
+        return outside, qorder, None
+    cell_key, cell_count = torch.unique_consecutive(qs.values[outside:], return_counts=True)
+    cell_first = torch.cumsum(cell_count, 0) - cell_count
+    T = _lib.CLOUD_TILE
+    pieces = (cell_count + (T - 1)) // T
+    owner = torch.repeat_interleave(torch.arange(cell_key.numel(), device=dev), pieces)
+    rank = torch.arange(owner.numel(), device=dev) - (torch.cumsum(pieces, 0) - pieces)[owner]
+    item_key = cell_key[owner].contiguous()
+    item_first = (cell_first[owner] + rank * T).contiguous()
+    item_count = torch.clamp(cell_count[owner] - rank * T, max=T).to(torch.int32)
+    return outside, qorder, (item_key, item_first, item_count)
+
+
 def nearest(targets, queries, D, detail=None, timing=None, origin=None):
     """targets [nt, 3], queries [nq, 3] float64 device tensors -> (dist [nq] float32: the distance to the nearest target, +inf where
     none lies within D; index [nq] int32: that target's number, or -1; info: targets, queries, cells, items, within, pairs).
@@ -135,29 +170,15 @@ def nearest(targets, queries, D, detail=None, timing=None, origin=None):
                                   "origin %s)" % (int((bad == 1).sum()), int((bad == 2).sum()), c, o.tolist()))
     qkeys, _ = hip_ops.simplify_keys(queries, c, o)
     stage("sorts")
-    ts = torch.sort(tkeys, stable=True)
-    ukeys, tcount = torch.unique_consecutive(ts.values, return_counts=True)
+    ukeys, tstart, targets_sorted, tindex = sort_targets(targets, tkeys)
     nc = int(ukeys.numel())
-    tstart = torch.zeros(nc + 1, device=dev, dtype=torch.int64)
-    tstart[1:] = torch.cumsum(tcount, 0)
-    targets_sorted = targets[ts.indices].contiguous()
-    tindex = ts.indices.to(torch.int32)
     qs = torch.sort(qkeys, stable=True)
     stage("items")
-    outside = int(torch.searchsorted(qs.values, torch.zeros(1, device=dev, dtype=torch.int64)))     # keys of -1 sort first
-    qorder = qs.indices[outside:].contiguous()
+    outside, qorder, items = work_items(qs)
     info.update(cells=nc, outside=outside)
-    if qorder.numel() == 0:
+    if items is None:
         return dist, index, info
-    cell_key, cell_count = torch.unique_consecutive(qs.values[outside:], return_counts=True)
-    cell_first = torch.cumsum(cell_count, 0) - cell_count
-    T = _lib.CLOUD_TILE
-    pieces = (cell_count + (T - 1)) // T
-    owner = torch.repeat_interleave(torch.arange(cell_key.numel(), device=dev), pieces)
-    rank = torch.arange(owner.numel(), device=dev) - (torch.cumsum(pieces, 0) - pieces)[owner]
-    item_key = cell_key[owner].contiguous()
-    item_first = (cell_first[owner] + rank * T).contiguous()
-    item_count = torch.clamp(cell_count[owner] - rank * T, max=T).to(torch.int32)
+    item_key, item_first, item_count = items
     stage("nearest")
     d2, index, pairs = hip_ops.cloud_nearest(o, c, ukeys, tstart, targets_sorted, tindex, queries, qorder, item_key, item_first, item_count)
     dist = torch.sqrt(d2)

@@ -890,6 +890,73 @@ extern "C" int adamvs_knn_normals_host(const double* points, long n, const int* 
   return knn_normals_host(points, n, index, count, k, rows, row_point, normal, curvature, flag);
 }
 
+// ---- cloud registration (cloud_register.hip): every argument is checked here, before any launch
+static int register_check_count(long n, const char* name, const char* what) {
+  ADAMVS_CHECK_ARG(n >= 0 && n <= SIMPLIFY_MAX, "%s: %s=%ld (0 .. 2^31 - 1)", what, name, n);
+  return 0;
+}
+
+static int register_check_motion(const double* R, const double* c, const double* u, const char* what) {
+  ADAMVS_CHECK_ARG(R && c && u, "%s: null R, c or u", what);
+  for (int k = 0; k < 9; ++k) ADAMVS_CHECK_ARG(std::isfinite(R[k]), "%s: R is not finite", what);
+  for (int k = 0; k < 3; ++k) ADAMVS_CHECK_ARG(std::isfinite(c[k]) && std::isfinite(u[k]), "%s: c or u is not finite", what);
+  return 0;
+}
+
+static int register_check_frame(const double* c, double L, double delta, const char* what) {
+  ADAMVS_CHECK_ARG(c && std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]), "%s: the pivot c is null or not finite", what);
+  ADAMVS_CHECK_ARG(std::isfinite(L) && L > 0, "%s: L=%g must be finite and > 0", what, L);
+  ADAMVS_CHECK_ARG(!std::isnan(delta), "%s: delta is NaN (<= 0: Huber off)", what);
+  return 0;
+}
+
+extern "C" int adamvs_rigid_apply(const double* R, const double* c, const double* u, const double* x, long n, double* y, void* stream) {
+  if (int rc = register_check_motion(R, c, u, "rigid_apply")) return rc;
+  if (int rc = register_check_count(n, "n", "rigid_apply")) return rc;
+  ADAMVS_CHECK_ARG((x && y) || n == 0, "rigid_apply: null pointer");
+  return launch_rigid_apply(R, c, u, x, n, y, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_rigid_apply_host(const double* R, const double* c, const double* u, const double* x, long n, double* y) {
+  if (int rc = register_check_motion(R, c, u, "rigid_apply_host")) return rc;
+  if (int rc = register_check_count(n, "n", "rigid_apply_host")) return rc;
+  ADAMVS_CHECK_ARG((x && y) || n == 0, "rigid_apply_host: null pointer");
+  return rigid_apply_host(R, c, u, x, n, y);
+}
+
+extern "C" int adamvs_icp_accumulate(const double* y, const int* index, long nq, const double* targets, const double* normals,
+                                     const unsigned char* flag, long nt, const double* c, double L, double delta, double* partial,
+                                     void* stream) {
+  if (int rc = register_check_frame(c, L, delta, "icp_accumulate")) return rc;
+  if (int rc = register_check_count(nq, "nq", "icp_accumulate")) return rc;
+  if (int rc = register_check_count(nt, "nt", "icp_accumulate")) return rc;
+  ADAMVS_CHECK_ARG((y && index && partial) || nq == 0, "icp_accumulate: null pointer");
+  ADAMVS_CHECK_ARG((targets && normals && flag) || nt == 0, "icp_accumulate: null pointer");
+  return launch_icp_accumulate(y, index, nq, targets, normals, flag, nt, c, L, delta, partial, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_icp_accumulate_host(const double* y, const int* index, long nq, const double* targets, const double* normals,
+                                          const unsigned char* flag, long nt, const double* c, double L, double delta, double* partial) {
+  if (int rc = register_check_frame(c, L, delta, "icp_accumulate_host")) return rc;
+  if (int rc = register_check_count(nq, "nq", "icp_accumulate_host")) return rc;
+  if (int rc = register_check_count(nt, "nt", "icp_accumulate_host")) return rc;
+  ADAMVS_CHECK_ARG((y && index && partial) || nq == 0, "icp_accumulate_host: null pointer");
+  ADAMVS_CHECK_ARG((targets && normals && flag) || nt == 0, "icp_accumulate_host: null pointer");
+  return icp_accumulate_host(y, index, nq, targets, normals, flag, nt, c, L, delta, partial);
+}
+
+extern "C" int adamvs_icp_reduce(const double* partial, long nb, double* sums, void* stream) {
+  if (int rc = register_check_count(nb, "nb", "icp_reduce")) return rc;
+  ADAMVS_CHECK_ARG((partial || nb == 0) && sums, "icp_reduce: null pointer");
+  return launch_icp_reduce(partial, nb, sums, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_icp_reduce_host(const double* partial, long nb, double* sums) {
+  if (int rc = register_check_count(nb, "nb", "icp_reduce_host")) return rc;
+  ADAMVS_CHECK_ARG((partial || nb == 0) && sums, "icp_reduce_host: null pointer");
+  return icp_reduce_host(partial, nb, sums);
+}
+
 // ---- image orthophoto (ortho.hip): every argument is checked here, before any launch
 static int ortho_check_grid(const adamvs_ortho_grid* g, const char* what) {
   ADAMVS_CHECK_ARG(g, "%s: null grid", what);

@@ -1,9 +1,9 @@
 // The workgroup and mesh-topology primitives that fusion.hip, mesh.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_clean.hip,
-// cloud_dist.hip, cloud_knn.hip, texture.hip and texture_level.hip share: the 256-lane tile count, ranks and scans over a
-// workgroup of four waves, wave reductions in a fixed butterfly order, undirected edge keys, half-edges, the run-of-one test on
-// sorted keys and the walk to the root of a label forest.  Integer work and plain additions only: several includers switch fp
-// contraction off after their includes, and a helper that multiplies and then adds floats would round differently from one
-// includer to the next.
+// cloud_dist.hip, cloud_knn.hip, cloud_register.hip, texture.hip and texture_level.hip share: the 256-lane tile count, ranks and
+// scans over a workgroup of four waves, wave reductions in a fixed butterfly order, undirected edge keys, half-edges, the
+// run-of-one test on sorted keys and the walk to the root of a label forest.  Integer work and plain additions only: several
+// includers switch fp contraction off after their includes, and a helper that multiplies and then adds floats would round
+// differently from one includer to the next.
 #pragma once
 #include "common.h"
 #include "kernels.h"

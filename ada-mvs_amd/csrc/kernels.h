@@ -263,6 +263,17 @@ int launch_knn_normals(const double* points, long n, const int* index, const int
 int knn_normals_host(const double* points, long n, const int* index, const int* count, int k, long rows, const int* row_point, double* normal,
                      float* curvature, unsigned char* flag);
 
+// cloud_register.hip: the rigid motion of a cloud and the sums of point-to-plane ICP (include/adamvs_hip.h, "Cloud registration")
+constexpr int ICP_TERMS = ADAMVS_ICP_TERMS;
+int launch_rigid_apply(const double* R, const double* c, const double* u, const double* x, long n, double* y, hipStream_t st);
+int rigid_apply_host(const double* R, const double* c, const double* u, const double* x, long n, double* y);
+int launch_icp_accumulate(const double* y, const int* index, long nq, const double* targets, const double* normals, const unsigned char* flag,
+                          long nt, const double* c, double L, double delta, double* partial, hipStream_t st);
+int icp_accumulate_host(const double* y, const int* index, long nq, const double* targets, const double* normals, const unsigned char* flag,
+                        long nt, const double* c, double L, double delta, double* partial);
+int launch_icp_reduce(const double* partial, long nb, double* sums, hipStream_t st);
+int icp_reduce_host(const double* partial, long nb, double* sums);
+
 // ortho.hip: image orthophoto over a DSM, z-buffered per view (include/adamvs_hip.h, "Image orthophoto")
 constexpr int ORTHO_TILE = ADAMVS_ORTHO_TILE;
 constexpr int ORTHO_SMALL_PX = ADAMVS_ORTHO_SMALL_PX;

@@ -1046,6 +1046,109 @@ def knn_normals_host(points, index, count, row_point=None):
     return normal, curvature, flag
 
 
+# ---- cloud registration (csrc/cloud_register.hip; driven by ada_mvs_amd/register.py) --------------------------------------------
+# points, normals, partial sums float64, index int32, flags uint8; R [3, 3], the pivot c and u = c + t are host doubles.
+def _vec(v, size, name):
+    a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+    if a.size != size:
+        raise _lib.AdaMVSHipError("%s: %d doubles, got %d" % (name, size, a.size))
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def _motion(R, c, t):
+    """-> the arrays (kept alive by the caller) and the pointers of R, c and u = c + t."""
+    c0 = np.asarray(c, np.float64).reshape(-1)
+    t0 = np.asarray(t, np.float64).reshape(-1)
+    if c0.size != 3 or t0.size != 3:
+        raise _lib.AdaMVSHipError("pivot and t: 3 doubles each, got %d and %d" % (c0.size, t0.size))
+    (Ra, Rp), (ca, cp), (ua, up) = _vec(R, 9, "R"), _vec(c0, 3, "pivot"), _vec(c0 + t0, 3, "u")
+    return (Ra, ca, ua), Rp, cp, up
+
+
+def _xyz64(t, name):
+    t = _dev_as(t, name, torch.float64)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise _lib.AdaMVSHipError("%s: [n, 3] float64, got %s" % (name, tuple(t.shape)))
+    return t
+
+
+def rigid_apply(x, R, c, t):
+    """adamvs_rigid_apply.  x [n, 3] float64 -> y [n, 3] float64 = R (x - c) + (c + t)."""
+    x = _xyz64(x, "x")
+    keep, Rp, cp, up = _motion(R, c, t)
+    y = torch.empty_like(x)
+    check(_lib.load().adamvs_rigid_apply(Rp, cp, up, _p(x), x.shape[0], _p(y), _stream()), "rigid_apply")
+    return y
+
+
+def rigid_apply_host(x, R, c, t):
+    """adamvs_rigid_apply_host on a numpy cloud [n, 3] -> y [n, 3] float64."""
+    x = np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1, 3))
+    keep, Rp, cp, up = _motion(R, c, t)
+    y = np.zeros_like(x)
+    check(_lib.load().adamvs_rigid_apply_host(Rp, cp, up, x.ctypes.data, len(x), y.ctypes.data), "rigid_apply_host")
+    return y
+
+
+def icp_blocks(nq):
+    """Workgroups (and rows of the partial sums) of adamvs_icp_accumulate for nq queries."""
+    return (int(nq) + _lib.CLOUD_TILE - 1) // _lib.CLOUD_TILE
+
+
+def icp_accumulate(y, index, targets, normals, flag, c, L, delta):
+    """adamvs_icp_accumulate.  y [nq, 3] float64 (the moved queries), index [nq] int32 of cloud_nearest, targets / normals [nt, 3]
+    float64 and flag [nt] uint8 in the caller's order, the pivot c, the length scale L, the Huber width delta (<= 0: off)
+    -> partial [ceil(nq / 256), 32] float64."""
+    y, index = _xyz64(y, "y"), _dev_as(index, "index", torch.int32)
+    targets, normals, flag = _xyz64(targets, "targets"), _xyz64(normals, "normals"), _dev_as(flag, "flag", torch.uint8)
+    nq, nt = y.shape[0], targets.shape[0]
+    if index.numel() != nq or normals.shape[0] != nt or flag.numel() != nt:
+        raise _lib.AdaMVSHipError("icp_accumulate: nq %d, nt %d against index %d, normals %d, flag %d"
+                                  % (nq, nt, index.numel(), normals.shape[0], flag.numel()))
+    ca, cp = _vec(c, 3, "pivot")
+    partial = torch.empty(icp_blocks(nq), _lib.ICP_TERMS, device=y.device, dtype=torch.float64)
+    check(_lib.load().adamvs_icp_accumulate(_p(y), _p(index), nq, _p(targets), _p(normals), _p(flag), nt, cp, float(L), float(delta),
+                                            _p(partial), _stream()), "icp_accumulate")
+    return partial
+
+
+def icp_accumulate_host(y, index, targets, normals, flag, c, L, delta):
+    """adamvs_icp_accumulate_host on numpy arrays -> partial [ceil(nq / 256), 32] float64."""
+    y = np.ascontiguousarray(np.asarray(y, np.float64).reshape(-1, 3))
+    index = np.ascontiguousarray(np.asarray(index, np.int32).reshape(-1))
+    targets = np.ascontiguousarray(np.asarray(targets, np.float64).reshape(-1, 3))
+    normals = np.ascontiguousarray(np.asarray(normals, np.float64).reshape(-1, 3))
+    flag = np.ascontiguousarray(np.asarray(flag, np.uint8).reshape(-1))
+    nq, nt = len(y), len(targets)
+    if len(index) != nq or len(normals) != nt or len(flag) != nt:
+        raise _lib.AdaMVSHipError("icp_accumulate_host: nq %d, nt %d against index %d, normals %d, flag %d"
+                                  % (nq, nt, len(index), len(normals), len(flag)))
+    ca, cp = _vec(c, 3, "pivot")
+    partial = np.zeros((icp_blocks(nq), _lib.ICP_TERMS), np.float64)
+    check(_lib.load().adamvs_icp_accumulate_host(y.ctypes.data, index.ctypes.data, nq, targets.ctypes.data, normals.ctypes.data,
+                                                 flag.ctypes.data, nt, cp, float(L), float(delta), partial.ctypes.data),
+          "icp_accumulate_host")
+    return partial
+
+
+def icp_reduce(partial):
+    """adamvs_icp_reduce.  partial [nb, 32] float64 -> sums [32] float64."""
+    partial = _dev_as(partial, "partial", torch.float64)
+    if partial.dim() != 2 or partial.shape[1] != _lib.ICP_TERMS:
+        raise _lib.AdaMVSHipError("partial: [nb, %d] float64, got %s" % (_lib.ICP_TERMS, tuple(partial.shape)))
+    sums = torch.empty(_lib.ICP_TERMS, device=partial.device, dtype=torch.float64)
+    check(_lib.load().adamvs_icp_reduce(_p(partial), partial.shape[0], _p(sums), _stream()), "icp_reduce")
+    return sums
+
+
+def icp_reduce_host(partial):
+    """adamvs_icp_reduce_host on a numpy array [nb, 32] -> sums [32] float64."""
+    partial = np.ascontiguousarray(np.asarray(partial, np.float64).reshape(-1, _lib.ICP_TERMS))
+    sums = np.zeros(_lib.ICP_TERMS, np.float64)
+    check(_lib.load().adamvs_icp_reduce_host(partial.ctypes.data, len(partial), sums.ctypes.data), "icp_reduce_host")
+    return sums
+
+
 # ---- mesh smoothing (csrc/mesh_smooth.hip; driven by ada_mvs_amd/smooth.py) ---------------------------------------------------
 # positions are relative to the origin (p = xyz - O); faces int32 = uint32; flags uint8.
 def _smooth_mesh(p, faces):

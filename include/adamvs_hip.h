@@ -1118,6 +1118,67 @@ int adamvs_knn_normals(const double* points, long n, const int* index, const int
 int adamvs_knn_normals_host(const double* points, long n, const int* index, const int* count, int k, long rows, const int* row_point,
                             double* normal, float* curvature, unsigned char* flag);
 
+/* ---- Cloud registration (before accuracy_whu.py): a reconstruction aligned to the truth by point-to-plane ICP ----------------
+ * ada-mvs_amd/register.py drives it; register_whu.py is the CLI.  A reconstruction and an independently georeferenced truth
+ * never share a frame exactly, and a residual shift or tilt lands in every figure of "Cloud distance"; DTU and Tanks and
+ * Temples register by ICP before they score.  The SOURCE (the reconstruction) is moved onto the TARGET (the truth).
+ *
+ * All arithmetic below is fp64 without contraction: every operation written is one rounding.
+ *
+ * Transform.  (R [3][3] row-major, t [3]) about a pivot c [3]:  y = R (x - c) + c + t.  The driver takes c as the centre of the
+ * targets' bounding box, (min + max) / 2 per axis (exact, and independent of the targets' order), so that the products R d
+ * are formed on numbers of the size of the scene, not of its georeferenced offset.
+ *   _rigid_apply        one lane per point.  d = x - c;  y_k = ((R_k0 d_0 + R_k1 d_1) + R_k2 d_2) + u_k,  with u = c + t formed by
+ *                       the caller in fp64.  A point that is not finite stays not finite (every component of y).  With R = I and
+ *                       t = 0 a point whose components lie within [c_k / 2, 2 c_k] (a georeferenced scene about its own centre)
+ *                       comes back with its own bits: the difference is then exact;
+ *   _rigid_apply_host   the same on the HOST through the same inline function.
+ *
+ * Correspondences.  The moved source Y [nq][3] is searched against the targets by _cloud_nearest with D = the truncation
+ * distance: index [nq] int32, the nearest target's number in the caller's order or -1.  The targets P [nt][3] carry normals
+ * N [nt][3] fp64 and flags [nt] uint8 of "Cloud neighbourhoods" (ADAMVS_KNN_VALID = 0), all in the caller's order.  The sign
+ * of a normal does not matter below.
+ *
+ * Sums.  With the pivot c, a length scale L > 0 (the driver's: max(half the diagonal of the targets' box, D)) and a Huber
+ * width delta (delta <= 0: off), query i is a PAIR iff 0 <= j = index[i] < nt, flag[j] == 0 and y = Y_i is finite.  For a pair,
+ * with p = P_j and n = N_j:
+ *      e = y - p;    r = (e_0 n_0 + e_1 n_1) + e_2 n_2;    q = (y - c) / L  (three divisions);
+ *      a = (q x n, n), six numbers:  a_0 = q_1 n_2 - q_2 n_1,  a_1 = q_2 n_0 - q_0 n_2,  a_2 = q_0 n_1 - q_1 n_0  (each the
+ *      difference of two products),  a_3 .. a_5 = n;
+ *      w = 1 if delta <= 0 or |r| <= delta, else delta / |r|.
+ * To first order a rotation by the vector omega about c and a shift dt change r by a . x with x = (L omega, dt): L makes the six
+ * unknowns of one size.  The ADAMVS_ICP_TERMS = 32 TERMS of a pair, in this order:
+ *      0 .. 20   (w a_u) a_v for u <= v, row-major: (0,0) (0,1) .. (0,5) (1,1) .. (5,5);
+ *      21 .. 26  (w a_u) r;
+ *      27 .. 31  (w r) r,   r r,   (e_0 e_0 + e_1 e_1) + e_2 e_2,   1.0,   w.
+ * A query that is no pair contributes 32 zeros.  The sums of 0 .. 20 are the upper triangle of A = sum w a a^T, those of
+ * 21 .. 26 are g = sum w a r; the driver solves A x = -g on the host through the eigenpairs of A, keeping those with
+ * lambda_i > min_eig_ratio lambda_max (a flat scene constrains three of the six freedoms; the others stay where they were).
+ * Sum 30 is the number of pairs, 28 and 29 over it the mean squares of the point-to-plane and point-to-point residuals.
+ *   _icp_accumulate     workgroup b (256 lanes) owns queries 256 b .. 256 b + 255 (lanes past nq hold zeros).  Each term is summed
+ *                       within each wave by the fixed butterfly over lane distances 32, 16, .. 1 (s_l <- s_l + s_(l xor m),
+ *                       every lane ends with the same bits), then the four wave sums as (W0 + W1) + (W2 + W3).
+ *                       partial [nb][32] fp64, nb = ceil(nq / 256);
+ *   _icp_reduce         one workgroup of 256.  Lane l adds partial[b] for b = l, l + 256, .. ascending, starting from 0.0; then
+ *                       the same wave and (W0 + W1) + (W2 + W3) order.  sums [32] fp64.  nb = 0 gives zeros;
+ *   _icp_accumulate_host, _icp_reduce_host   the same on the HOST (host pointers) through the same inline functions and the same
+ *                       order of additions, so that the whole loop can be checked on a machine without a device.
+ * No atomics and no inter-workgroup waits.  The sums depend on the queries' order and on nothing else: not on the launch
+ * shape, and (the index naming a target by its number in the caller's order) not on how the search ordered the targets; they
+ * are bit-identical from run to run.
+ * Argument errors (<0, before any launch): a null pointer, a count < 0 or > 2^31 - 1, R, c or u not finite, L not finite or
+ * <= 0, delta NaN. */
+#define ADAMVS_ICP_TERMS 32
+
+int adamvs_rigid_apply(const double* R, const double* c, const double* u, const double* x, long n, double* y, void* stream);
+int adamvs_rigid_apply_host(const double* R, const double* c, const double* u, const double* x, long n, double* y);
+int adamvs_icp_accumulate(const double* y, const int* index, long nq, const double* targets, const double* normals,
+                          const unsigned char* flag, long nt, const double* c, double L, double delta, double* partial, void* stream);
+int adamvs_icp_accumulate_host(const double* y, const int* index, long nq, const double* targets, const double* normals,
+                               const unsigned char* flag, long nt, const double* c, double L, double delta, double* partial);
+int adamvs_icp_reduce(const double* partial, long nb, double* sums, void* stream);
+int adamvs_icp_reduce_host(const double* partial, long nb, double* sums);
+
 /* ---- Image orthophoto (after dsm_whu.py): the source images mosaicked over a DSM into a true orthophoto -------------------
  * ada-mvs_amd/ortho.py drives it; ortho_whu.py is the CLI.  World axes: x east, y north, z up; rows run south.
  *
