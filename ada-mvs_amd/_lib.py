@@ -76,6 +76,12 @@ class DsmFillStats(ctypes.Structure):
                 ("cells_empty", ctypes.c_long)]
 
 
+class DtmStats(ctypes.Structure):
+    """adamvs_dtm_stats"""
+    _fields_ = [("levels", ctypes.c_int), ("cells_valid", ctypes.c_long), ("cells_ground", ctypes.c_long),
+                ("cells_object", ctypes.c_long), ("cells_empty", ctypes.c_long), ("cells_level", ctypes.c_long * 17)]
+
+
 class MeshView(ctypes.Structure):
     """adamvs_mesh_view"""
     _fields_ = [("K", ctypes.c_float * 9), ("R", ctypes.c_float * 9), ("c", ctypes.c_float * 3), ("H", ctypes.c_int), ("W", ctypes.c_int),
@@ -176,6 +182,10 @@ SIGNATURES = {
     "adamvs_dsm_fill": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i,
                               ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                               ctypes.POINTER(DsmFillStats), c_st]),
+    "adamvs_dtm_workspace_bytes": (ctypes.c_long, [c_i, c_i]),
+    "adamvs_dsm_open": (c_i, [c_i, c_i, ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_dtm_classify": (c_i, [c_i, c_i, ctypes.c_void_p, c_i, ctypes.POINTER(c_i), ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
+                                  ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(DtmStats), c_st]),
     "adamvs_mesh_check_views": (c_i, [ctypes.POINTER(MeshView), c_i]),
     "adamvs_tsdf_integrate": (c_i, [ctypes.POINTER(MeshBrick), ctypes.c_void_p, c_i, ctypes.c_void_p, c_i, c_f, ctypes.c_void_p,
                                     ctypes.c_void_p, c_st]),
@@ -306,6 +316,9 @@ FUSION_TILE = 256                # ADAMVS_FUSION_TILE: pixels per workgroup of t
 DSM_MAX, DSM_MEAN = 0, 1         # ADAMVS_DSM_MAX / ADAMVS_DSM_MEAN
 DSM_MAX_CELLS = 1 << 28          # ADAMVS_DSM_MAX_CELLS
 DSM_FILL_MAX_RADIUS = 1024       # ADAMVS_DSM_FILL_MAX_RADIUS
+DTM_MAX_RADIUS = 1024            # ADAMVS_DTM_MAX_RADIUS: largest radius of an opening, cells
+DTM_MAX_LEVELS = 16              # ADAMVS_DTM_MAX_LEVELS: most levels of the ground filter
+DTM_TILE = 1024                  # ADAMVS_DTM_TILE: cells of a row per workgroup of the running min / max
 MESH_TILE = 256                  # ADAMVS_MESH_TILE: samples / cubes per workgroup of the mesh kernels
 MESH_BRICKS = (32, 64, 128)      # the brick sizes B
 MESH_MAX_VIEWS = 65535           # ADAMVS_MESH_MAX_VIEWS

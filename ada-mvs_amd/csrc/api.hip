@@ -474,6 +474,50 @@ extern "C" int adamvs_dsm_fill(int W, int H, const float* dsm, const unsigned ch
                          stats, (hipStream_t)stream);
 }
 
+// ---- DSM ground filter (dsm_dtm.hip)
+// true iff the byte ranges [a, a + na) and [b, b + nb) share a byte
+static bool dtm_overlap(const void* a, long na, const void* b, long nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+}
+
+extern "C" long adamvs_dtm_workspace_bytes(int W, int H) {
+  if (int rc = dsm_fill_check_size(W, H, "dtm_workspace_bytes")) return rc;
+  return dtm_workspace_bytes(W, H);
+}
+
+extern "C" int adamvs_dsm_open(int W, int H, const float* src, int r, void* workspace, long workspace_bytes, float* dst, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "dsm_open")) return rc;
+  ADAMVS_CHECK_ARG(src && workspace && dst, "dsm_open: null pointer");
+  ADAMVS_CHECK_ARG(r >= 1 && r <= ADAMVS_DTM_MAX_RADIUS, "dsm_open: r=%d (1 .. %d)", r, ADAMVS_DTM_MAX_RADIUS);
+  const long need = dtm_workspace_bytes(W, H), n4 = 4L * W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "dsm_open: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  ADAMVS_CHECK_ARG(!dtm_overlap(src, n4, dst, n4) && !dtm_overlap(src, n4, workspace, need) && !dtm_overlap(dst, n4, workspace, need),
+                   "dsm_open: src, dst and the workspace must not overlap");
+  return launch_dsm_open(W, H, src, r, workspace, dst, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_dtm_classify(int W, int H, const float* dsm, int levels, const int* radius, const double* dh, void* workspace,
+                                   long workspace_bytes, unsigned char* level, float* opened, adamvs_dtm_stats* stats, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "dtm_classify")) return rc;
+  ADAMVS_CHECK_ARG(dsm && radius && dh && workspace && level && opened && stats, "dtm_classify: null pointer");
+  ADAMVS_CHECK_ARG(levels >= 1 && levels <= ADAMVS_DTM_MAX_LEVELS, "dtm_classify: levels=%d (1 .. %d)", levels, ADAMVS_DTM_MAX_LEVELS);
+  for (int k = 0; k < levels; ++k) {
+    ADAMVS_CHECK_ARG(radius[k] >= 1 && radius[k] <= ADAMVS_DTM_MAX_RADIUS, "dtm_classify: radius[%d]=%d (1 .. %d)", k, radius[k],
+                     ADAMVS_DTM_MAX_RADIUS);
+    ADAMVS_CHECK_ARG(k == 0 || radius[k] > radius[k - 1], "dtm_classify: radius[%d]=%d does not exceed radius[%d]=%d", k, radius[k], k - 1,
+                     radius[k - 1]);
+    ADAMVS_CHECK_ARG(std::isfinite(dh[k]) && dh[k] > 0.0, "dtm_classify: dh[%d]=%g must be finite and > 0", k, dh[k]);
+  }
+  const long need = dtm_workspace_bytes(W, H), n = (long)W * H, n4 = 4 * n;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "dtm_classify: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  ADAMVS_CHECK_ARG(!dtm_overlap(dsm, n4, opened, n4) && !dtm_overlap(dsm, n4, level, n) && !dtm_overlap(opened, n4, level, n) &&
+                       !dtm_overlap(dsm, n4, workspace, need) && !dtm_overlap(opened, n4, workspace, need) &&
+                       !dtm_overlap(level, n, workspace, need),
+                   "dtm_classify: dsm, level, opened and the workspace must not overlap");
+  return launch_dtm_classify(W, H, dsm, levels, radius, dh, workspace, level, opened, stats, (hipStream_t)stream);
+}
+
 // ---- TSDF mesh (mesh.hip): every argument is checked here, before any launch
 static int mesh_check_brick(const adamvs_mesh_brick* b, const char* what) {
   ADAMVS_CHECK_ARG(b, "%s: null brick", what);

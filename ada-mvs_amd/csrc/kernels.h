@@ -174,6 +174,13 @@ int launch_dsm_fill(int W, int H, const float* dsm, const uint8_t* rgba, double 
                     int max_cycles, void* workspace, float* dsm_out, uint8_t* rgba_out, int* dist2, uint8_t* filled,
                     adamvs_dsm_fill_stats* stats, hipStream_t st);
 
+// dsm_dtm.hip: grey-scale opening and the progressive morphological ground filter (include/adamvs_hip.h, "DSM ground filter")
+constexpr int DTM_TILE = ADAMVS_DTM_TILE;
+long dtm_workspace_bytes(int W, int H);
+int launch_dsm_open(int W, int H, const float* src, int r, void* workspace, float* dst, hipStream_t st);
+int launch_dtm_classify(int W, int H, const float* dsm, int levels, const int* radius, const double* dh, void* workspace,
+                        uint8_t* level, float* opened, adamvs_dtm_stats* stats, hipStream_t st);
+
 // mesh.hip: TSDF integration and marching-tetrahedra extraction per brick (include/adamvs_hip.h, "TSDF mesh")
 constexpr int MESH_TILE = ADAMVS_MESH_TILE;
 int launch_tsdf_integrate(const adamvs_mesh_brick& b, const adamvs_mesh_view* views, int nviews, const int* list, int nlist, float* tsdf,

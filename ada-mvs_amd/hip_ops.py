@@ -668,6 +668,48 @@ def dsm_fill(dsm, rgba, r_cells, tol_height=1e-6, tol_colour=1e-3, max_cycles=20
     return dsm_out, rgba_out, dist2, filled, stats
 
 
+def _dtm_raster(dsm):
+    dsm = _dev_as(dsm, "dsm", torch.float32)
+    if dsm.dim() != 2:
+        raise _lib.AdaMVSHipError("dsm must be [H, W], got %s" % (tuple(dsm.shape),))
+    H, W = dsm.shape
+    need = _lib.load().adamvs_dtm_workspace_bytes(W, H)
+    check(0 if need >= 0 else int(need), "dtm_workspace_bytes")
+    return dsm, H, W, need
+
+
+def dsm_open(dsm, r, workspace=None):
+    """adamvs_dsm_open: one grey-scale opening with the square window of radius r cells (dsm [H, W] float32, device; empty
+    cells NaN) -> opened [H, W] float32.  Enqueued on the current stream."""
+    dsm, H, W, need = _dtm_raster(dsm)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=dsm.device, dtype=torch.uint8)
+    out = torch.empty_like(dsm)
+    check(_lib.load().adamvs_dsm_open(W, H, _p(dsm), int(r), _p(workspace), workspace.numel(), _p(out), _stream()), "dsm_open")
+    return out
+
+
+def dtm_classify(dsm, radius, dh, workspace=None):
+    """adamvs_dtm_classify: the progressive morphological ground filter (dsm [H, W] float32, device; radius: ascending integer
+    radii in cells, dh: one height threshold per radius, host sequences) -> (level [H, W] uint8 (0 ground, k flagged at level
+    k, 255 empty), opened [H, W] float32, _lib.DtmStats).  Blocks until done."""
+    dsm, H, W, need = _dtm_raster(dsm)
+    radius = [int(v) for v in radius]
+    dh = [float(v) for v in dh]
+    if len(radius) != len(dh):
+        raise _lib.AdaMVSHipError("%d radii, %d thresholds" % (len(radius), len(dh)))
+    K = len(radius)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=dsm.device, dtype=torch.uint8)
+    level = torch.empty(H, W, device=dsm.device, dtype=torch.uint8)
+    opened = torch.empty_like(dsm)
+    stats = _lib.DtmStats()
+    check(_lib.load().adamvs_dtm_classify(W, H, _p(dsm), K, (ctypes.c_int * max(K, 1))(*radius), (ctypes.c_double * max(K, 1))(*dh),
+                                          _p(workspace), workspace.numel(), _p(level), _p(opened), ctypes.byref(stats), _stream()),
+          "dtm_classify")
+    return level, opened, stats
+
+
 # ---- TSDF mesh (csrc/mesh.hip; driven brick by brick by ada_mvs_amd/mesh.py) ------------------------------------------------
 # Per-sample state as torch tensors of the signed type of each C type's width: weight int16 = uint16, rgba int32 = uint32
 # (little-endian r g b a), cube_code int32 = uint32, faces int32 = uint32.

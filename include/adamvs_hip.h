@@ -610,6 +610,68 @@ int adamvs_dsm_fill(int W, int H, const float* dsm, const unsigned char* rgba, d
                     int max_cycles, void* workspace, long workspace_bytes, float* dsm_out, unsigned char* rgba_out, int* dist2,
                     unsigned char* filled, adamvs_dsm_fill_stats* stats, void* stream);
 
+/* ---- DSM ground filter (after _dsm_finalize or _dsm_fill): which cells of the DSM are bare earth -----------------------------
+ * ada-mvs_amd/dtm.py ground_filter(); dtm_whu.py is the CLI.  A progressive morphological filter (Zhang et al. 2003, the
+ * raster method behind PCL's and PDAL's `pmf`) with square windows.
+ * Input: dsm [H][W] fp32 as _dsm_finalize / _dsm_fill write it.  A cell is VALID iff its value is finite; NaN and +-inf are
+ * empty.  W H <= ADAMVS_DSM_MAX_CELLS.
+ *
+ * Opening open(Z, r), integer radius 1 <= r <= ADAMVS_DTM_MAX_RADIUS.  The window of cell c = (i, j) is the square
+ * |i' - i| <= r, |j' - j| <= r; cells outside the grid and empty cells are ignored.
+ *   E(c) = min of Z over the valid cells of the window of c (none if it holds no valid cell);
+ *   O(c) = max of E over the cells of the window of c that have an E;
+ *   output = O(c) on valid c, NaN (0x7fc00000) on empty c.
+ * On a valid c, O is finite and O(c) <= Z(c): every window that holds c has E <= Z(c), and c's own window has an E.  Square
+ * windows are separable (the row pass followed by the column pass is the 2-D result), and min / max select input values, so
+ * the result is exact: equal to a restatement value for value (-0 and +0 compare equal; which of the two is selected is not
+ * specified).
+ *
+ * Schedule (computed by the caller, ada-mvs_amd/dtm.py schedule(), and passed in as HOST arrays, so the kernel and a reference
+ * use the same doubles): R = floor(max_radius / gsd), 1 <= R <= ADAMVS_DTM_MAX_RADIUS; radii r_k = 1, 2, 4, ... while below R,
+ * then R: K <= ADAMVS_DTM_MAX_LEVELS levels; w_k = 2 r_k + 1, w_0 = 1;
+ *   dh_k = min(dh_max, dh0 + slope * gsd * (w_k - w_{k-1}))   in fp64.
+ * The entry point takes any strictly ascending radii and any finite dh > 0.
+ *
+ * Filter.  Z_0 = dsm.  For k = 1 .. K:  O_k = open(Z_{k-1}, r_k); a valid cell that is not yet flagged gets level = k iff
+ *   (double)Z_{k-1}(c) - (double)O_k(c) > dh_k    (strictly);
+ * Z_k = O_k.  Empty cells stay NaN at every level.
+ *   level   uint8 [H][W]: 0 ground, k the level at which the cell was flagged as object, 255 empty.
+ *   opened  fp32 [H][W]: Z_K.
+ *   stats   (a HOST pointer) integer counts: cells valid, ground, object, empty, and cells_level[k] flagged at level k
+ *           (cells_level[0] = ground; entries above `levels` are 0).
+ * The products built on it (ada-mvs_amd/dtm.py): ground = dsm where level == 0, else NaN; dtm = the gap fill of ground
+ * (_dsm_fill, unchanged: ground cells bit for bit, object and empty cells within the fill radius of ground by harmonic
+ * interpolation, NaN farther away); ndsm = (float)((double)dsm - (double)dtm) where both are finite, NaN elsewhere.
+ * Limits: an object wider than 2 R + 1 cells in both axes survives every opening and is kept as ground; an object lower than
+ * dh_k is not flagged; a plane with gradients (gx, gy) per metre is left alone only while |gx| + |gy| < slope (the L1 norm:
+ * the window is a square); at the high edge of a slope the dh_max cap can flag ground.
+ *
+ * Kernels (csrc/dsm_dtm.hip): a running min / max along rows (the segment and r halo cells in LDS, windows formed by doubling:
+ * log2 r steps per cell, one form for every r) and a tiled transpose; the column passes are row passes on the transposed
+ * raster.  _dtm_classify enqueues all K levels on `stream` with no host round trip between them, the flag and count step
+ * folded into the last pass of each level, then reads the counts back once: it blocks.  _dsm_open does not block.
+ * Every count is an integer sum: level, opened and the counts are bit-identical from run to run.
+ * src / dsm, dst / opened: device [H][W] fp32; level: device [H][W] uint8; radius, dh: HOST arrays of `levels` entries.
+ * workspace: device memory of at least _dtm_workspace_bytes(W, H) bytes (about 8 bytes per cell), 256-byte aligned.
+ * Argument errors (<0, before any launch): a null pointer, W or H <= 0 or W H > ADAMVS_DSM_MAX_CELLS, r or a radius outside
+ * 1 .. ADAMVS_DTM_MAX_RADIUS, levels outside 1 .. ADAMVS_DTM_MAX_LEVELS, radii not strictly ascending, a dh not finite or
+ * not > 0, any two of the buffers (workspace included) overlapping, workspace_bytes below the query.
+ * _dtm_workspace_bytes returns < 0 for W or H <= 0 or W H > ADAMVS_DSM_MAX_CELLS. */
+#define ADAMVS_DTM_MAX_RADIUS 1024
+#define ADAMVS_DTM_MAX_LEVELS 16
+#define ADAMVS_DTM_TILE 1024 /* cells of a row per workgroup of the running min / max */
+
+typedef struct {
+  int levels;
+  long cells_valid, cells_ground, cells_object, cells_empty;
+  long cells_level[ADAMVS_DTM_MAX_LEVELS + 1];
+} adamvs_dtm_stats;
+
+long adamvs_dtm_workspace_bytes(int W, int H);
+int adamvs_dsm_open(int W, int H, const float* src, int r, void* workspace, long workspace_bytes, float* dst, void* stream);
+int adamvs_dtm_classify(int W, int H, const float* dsm, int levels, const int* radius, const double* dh, void* workspace,
+                        long workspace_bytes, unsigned char* level, float* opened, adamvs_dtm_stats* stats, void* stream);
+
 /* ---- TSDF mesh (after fuse_whu.py): the depth maps of all views integrated into a truncated signed-distance field on a voxel
  * grid, brick by brick, and its zero level set extracted as a coloured triangle mesh ---------------------------------------
  * ada-mvs_amd/mesh.py drives it per brick; mesh_whu.py is the CLI.  World axes: x east, y north, z up.
