@@ -82,6 +82,12 @@ class DtmStats(ctypes.Structure):
                 ("cells_object", ctypes.c_long), ("cells_empty", ctypes.c_long), ("cells_level", ctypes.c_long * 17)]
 
 
+class BldStats(ctypes.Structure):
+    """adamvs_bld_stats"""
+    _fields_ = [("rounds", ctypes.c_int), ("converged", ctypes.c_int), ("tiles", ctypes.c_long), ("pairs", ctypes.c_long),
+                ("ms_tile", ctypes.c_float), ("ms_rounds", ctypes.c_float), ("ms_compress", ctypes.c_float)]
+
+
 class MeshView(ctypes.Structure):
     """adamvs_mesh_view"""
     _fields_ = [("K", ctypes.c_float * 9), ("R", ctypes.c_float * 9), ("c", ctypes.c_float * 3), ("H", ctypes.c_int), ("W", ctypes.c_int),
@@ -186,6 +192,11 @@ SIGNATURES = {
     "adamvs_dsm_open": (c_i, [c_i, c_i, ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
     "adamvs_dtm_classify": (c_i, [c_i, c_i, ctypes.c_void_p, c_i, ctypes.POINTER(c_i), ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
                                   ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(DtmStats), c_st]),
+    "adamvs_bld_workspace_bytes": (ctypes.c_long, [c_i, c_i]),
+    "adamvs_bld_flags": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, c_i, c_i, ctypes.c_double, ctypes.c_void_p,
+                               ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_bld_label": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.POINTER(BldStats), c_st]),
+    "adamvs_bld_table": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
     "adamvs_mesh_check_views": (c_i, [ctypes.POINTER(MeshView), c_i]),
     "adamvs_tsdf_integrate": (c_i, [ctypes.POINTER(MeshBrick), ctypes.c_void_p, c_i, ctypes.c_void_p, c_i, c_f, ctypes.c_void_p,
                                     ctypes.c_void_p, c_st]),
@@ -319,6 +330,12 @@ DSM_FILL_MAX_RADIUS = 1024       # ADAMVS_DSM_FILL_MAX_RADIUS
 DTM_MAX_RADIUS = 1024            # ADAMVS_DTM_MAX_RADIUS: largest radius of an opening, cells
 DTM_MAX_LEVELS = 16              # ADAMVS_DTM_MAX_LEVELS: most levels of the ground filter
 DTM_TILE = 1024                  # ADAMVS_DTM_TILE: cells of a row per workgroup of the running min / max
+BLD_TILE_W, BLD_TILE_H = 64, 64  # ADAMVS_BLD_TILE_W / _H: cells of a tile of the component labelling
+BLD_MAX_STRIDE = 64              # ADAMVS_BLD_MAX_STRIDE: largest stride of the flatness flag, cells
+BLD_MAX_ROUNDS = 64              # ADAMVS_BLD_MAX_ROUNDS: cap on the border rounds of the component labelling
+BLD_NOT_CONVERGED = -2           # ADAMVS_BLD_NOT_CONVERGED
+BLD_COLUMNS = ("cells", "smooth", "rough", "undetermined", "row_min", "row_max", "col_min", "col_max", "height_sum",
+               "height_max_bits")  # ADAMVS_BLD_CELLS .. ADAMVS_BLD_HEIGHT_MAX_BITS: the rows of the component table
 MESH_TILE = 256                  # ADAMVS_MESH_TILE: samples / cubes per workgroup of the mesh kernels
 MESH_BRICKS = (32, 64, 128)      # the brick sizes B
 MESH_MAX_VIEWS = 65535           # ADAMVS_MESH_MAX_VIEWS

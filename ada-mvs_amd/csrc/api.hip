@@ -518,6 +518,61 @@ extern "C" int adamvs_dtm_classify(int W, int H, const float* dsm, int levels, c
   return launch_dtm_classify(W, H, dsm, levels, radius, dh, workspace, level, opened, stats, (hipStream_t)stream);
 }
 
+// ---- Building extraction (dsm_buildings.hip)
+struct BldBuffer {
+  const void* p;
+  long bytes;
+};
+
+static bool bld_any_overlap(const BldBuffer* b, int count) {
+  for (int i = 0; i < count; ++i)
+    for (int j = i + 1; j < count; ++j)
+      if (dtm_overlap(b[i].p, b[i].bytes, b[j].p, b[j].bytes)) return true;
+  return false;
+}
+
+extern "C" long adamvs_bld_workspace_bytes(int W, int H) {
+  if (int rc = dsm_fill_check_size(W, H, "bld_workspace_bytes")) return rc;
+  return bld_workspace_bytes(W, H);
+}
+
+extern "C" int adamvs_bld_flags(int W, int H, const float* dsm, const float* ndsm, double min_height, int r_open, int s, double smooth_tol,
+                                void* workspace, long workspace_bytes, unsigned char* flags, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "bld_flags")) return rc;
+  ADAMVS_CHECK_ARG(dsm && ndsm && workspace && flags, "bld_flags: null pointer");
+  ADAMVS_CHECK_ARG(std::isfinite(min_height) && min_height > 0.0, "bld_flags: min_height=%g must be finite and > 0", min_height);
+  ADAMVS_CHECK_ARG(r_open >= 0 && r_open <= ADAMVS_DTM_MAX_RADIUS, "bld_flags: r_open=%d (0 .. %d)", r_open, ADAMVS_DTM_MAX_RADIUS);
+  ADAMVS_CHECK_ARG(s >= 1 && s <= ADAMVS_BLD_MAX_STRIDE, "bld_flags: s=%d (1 .. %d)", s, ADAMVS_BLD_MAX_STRIDE);
+  ADAMVS_CHECK_ARG(std::isfinite(smooth_tol) && smooth_tol >= 0.0, "bld_flags: smooth_tol=%g must be finite and >= 0", smooth_tol);
+  const long need = bld_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "bld_flags: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{dsm, 4 * n}, {ndsm, 4 * n}, {flags, n}, {workspace, need}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 4), "bld_flags: dsm, ndsm, flags and the workspace must not overlap");
+  return launch_bld_flags(W, H, dsm, ndsm, min_height, r_open, s, smooth_tol, workspace, flags, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_bld_label(int W, int H, const unsigned char* flags, void* workspace, long workspace_bytes, int* parent,
+                                adamvs_bld_stats* stats, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "bld_label")) return rc;
+  ADAMVS_CHECK_ARG(flags && workspace && parent && stats, "bld_label: null pointer");
+  const long need = bld_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "bld_label: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{flags, n}, {parent, 4 * n}, {workspace, need}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 3), "bld_label: flags, parent and the workspace must not overlap");
+  return launch_bld_label(W, H, flags, workspace, parent, stats, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_bld_table(int W, int H, const unsigned char* flags, const float* ndsm, const int* label, long N, long long* table,
+                                void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "bld_table")) return rc;
+  const long n = (long)W * H;
+  ADAMVS_CHECK_ARG(N >= 0 && N <= n, "bld_table: N=%ld (0 .. W H = %ld)", N, n);
+  ADAMVS_CHECK_ARG(flags && ndsm && label && (table || N == 0), "bld_table: null pointer");
+  const BldBuffer b[] = {{flags, n}, {ndsm, 4 * n}, {label, 4 * n}, {table, 8L * ADAMVS_BLD_COLUMNS * N}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, N ? 4 : 3), "bld_table: flags, ndsm, label and the table must not overlap");
+  return launch_bld_table(W, H, flags, ndsm, label, N, table, (hipStream_t)stream);
+}
+
 // ---- TSDF mesh (mesh.hip): every argument is checked here, before any launch
 static int mesh_check_brick(const adamvs_mesh_brick* b, const char* what) {
   ADAMVS_CHECK_ARG(b, "%s: null brick", what);

@@ -181,6 +181,15 @@ int launch_dsm_open(int W, int H, const float* src, int r, void* workspace, floa
 int launch_dtm_classify(int W, int H, const float* dsm, int levels, const int* radius, const double* dh, void* workspace,
                         uint8_t* level, float* opened, adamvs_dtm_stats* stats, hipStream_t st);
 
+// dsm_buildings.hip: candidate mask, flatness flags, component labels and the per-component table (include/adamvs_hip.h,
+// "Building extraction")
+constexpr int BLD_TILE_W = ADAMVS_BLD_TILE_W, BLD_TILE_H = ADAMVS_BLD_TILE_H;
+long bld_workspace_bytes(int W, int H);
+int launch_bld_flags(int W, int H, const float* dsm, const float* ndsm, double min_height, int r_open, int s, double smooth_tol,
+                     void* workspace, uint8_t* flags, hipStream_t st);
+int launch_bld_label(int W, int H, const uint8_t* flags, void* workspace, int* parent, adamvs_bld_stats* stats, hipStream_t st);
+int launch_bld_table(int W, int H, const uint8_t* flags, const float* ndsm, const int* label, long N, long long* table, hipStream_t st);
+
 // mesh.hip: TSDF integration and marching-tetrahedra extraction per brick (include/adamvs_hip.h, "TSDF mesh")
 constexpr int MESH_TILE = ADAMVS_MESH_TILE;
 int launch_tsdf_integrate(const adamvs_mesh_brick& b, const adamvs_mesh_view* views, int nviews, const int* list, int nlist, float* tsdf,

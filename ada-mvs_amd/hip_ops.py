@@ -710,6 +710,64 @@ def dtm_classify(dsm, radius, dh, workspace=None):
     return level, opened, stats
 
 
+def _bld_raster(t, name, dtype, shape=None):
+    t = _dev_as(t, name, dtype)
+    if t.dim() != 2 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise _lib.AdaMVSHipError("%s must be [H, W]%s, got %s" % (name, "" if shape is None else " = %s" % (tuple(shape),), tuple(t.shape)))
+    return t
+
+
+def _bld_workspace(H, W, device, workspace):
+    need = _lib.load().adamvs_bld_workspace_bytes(W, H)
+    check(0 if need >= 0 else int(need), "bld_workspace_bytes")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=device, dtype=torch.uint8)
+    return workspace
+
+
+def bld_flags(dsm, ndsm, min_height, r_open, s, smooth_tol, workspace=None):
+    """adamvs_bld_flags: dsm, ndsm [H, W] float32 (device) -> flags [H, W] uint8 (0 not a candidate, 1 removed by the opening,
+    2 undetermined, 3 smooth, 4 rough).  Enqueued on the current stream."""
+    dsm = _bld_raster(dsm, "dsm", torch.float32)
+    ndsm = _bld_raster(ndsm, "ndsm", torch.float32, dsm.shape)
+    H, W = dsm.shape
+    workspace = _bld_workspace(H, W, dsm.device, workspace)
+    flags = torch.empty(H, W, device=dsm.device, dtype=torch.uint8)
+    check(_lib.load().adamvs_bld_flags(W, H, _p(dsm), _p(ndsm), float(min_height), int(r_open), int(s), float(smooth_tol), _p(workspace),
+                                       workspace.numel(), _p(flags), _stream()), "bld_flags")
+    return flags
+
+
+def bld_label(flags, workspace=None):
+    """adamvs_bld_label and the numbering: flags [H, W] uint8 (device) -> (label [H, W] int32: 0 outside the mask flags >= 2,
+    otherwise 1 .. N in ascending order of the component's smallest cell index; N; _lib.BldStats).  Blocks until done."""
+    flags = _bld_raster(flags, "flags", torch.uint8)
+    H, W = flags.shape
+    workspace = _bld_workspace(H, W, flags.device, workspace)
+    parent = torch.empty(H, W, device=flags.device, dtype=torch.int32)
+    stats = _lib.BldStats()
+    check(_lib.load().adamvs_bld_label(W, H, _p(flags), _p(workspace), workspace.numel(), _p(parent), ctypes.byref(stats), _stream()),
+          "bld_label")
+    flat = parent.view(-1)
+    root = flat == torch.arange(H * W, device=flags.device, dtype=torch.int32)
+    number = torch.cumsum(root, 0, dtype=torch.int32)               # the scan over the roots: 1 .. N in ascending cell index
+    N = int(number[-1])
+    label = torch.where(flat >= 0, number[flat.clamp(min=0).long()], torch.zeros((), device=flags.device, dtype=torch.int32))
+    return label.view(H, W), N, stats
+
+
+def bld_table(flags, ndsm, label, N):
+    """adamvs_bld_table: -> table [len(_lib.BLD_COLUMNS), N] int64 (device), row k - 1 of each column for component k.
+    Enqueued on the current stream."""
+    flags = _bld_raster(flags, "flags", torch.uint8)
+    ndsm = _bld_raster(ndsm, "ndsm", torch.float32, flags.shape)
+    label = _bld_raster(label, "label", torch.int32, flags.shape)
+    H, W = flags.shape
+    table = torch.empty(len(_lib.BLD_COLUMNS), int(N), device=flags.device, dtype=torch.int64)
+    check(_lib.load().adamvs_bld_table(W, H, _p(flags), _p(ndsm), _p(label), int(N), _p(table), _stream()), "bld_table")
+    return table
+
+
 # ---- TSDF mesh (csrc/mesh.hip; driven brick by brick by ada_mvs_amd/mesh.py) ------------------------------------------------
 # Per-sample state as torch tensors of the signed type of each C type's width: weight int16 = uint16, rgba int32 = uint32
 # (little-endian r g b a), cube_code int32 = uint32, faces int32 = uint32.

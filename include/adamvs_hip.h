@@ -672,6 +672,78 @@ int adamvs_dsm_open(int W, int H, const float* src, int r, void* workspace, long
 int adamvs_dtm_classify(int W, int H, const float* dsm, int levels, const int* radius, const double* dh, void* workspace,
                         long workspace_bytes, unsigned char* level, float* opened, adamvs_dtm_stats* stats, void* stream);
 
+/* ---- Building extraction (after the ground filter): which cells of the nDSM belong to a building, as labelled components ----
+ * ada-mvs_amd/buildings.py extract(); buildings_whu.py is the CLI.  Inputs: dsm [H][W] fp32 (Z) and ndsm [H][W] fp32 as
+ * dtm_whu.py writes them (NaN where there is no value).  W H <= ADAMVS_DSM_MAX_CELLS.  A cell is c = (i, j), its index i W + j.
+ *
+ * 1. Candidate mask.  M0(c) iff ndsm(c) is finite and (double)ndsm(c) >= min_height.
+ * 2. Opening.  M = (open(M0 as 0.0 / 1.0, r_open) == 1.0) with _dsm_open above, unchanged: every cell of the 0 / 1 raster is
+ *    valid and the window is clipped at the grid.  r_open = 0 skips it (M = M0).  The caller computes
+ *    r_open = floor(min_width / (2 gsd)) cells; 0 <= r_open <= ADAMVS_DTM_MAX_RADIUS.  M is a subset of M0.
+ * 3. Flatness flag of every cell of M, at the stride 1 <= s <= ADAMVS_BLD_MAX_STRIDE cells (the caller computes
+ *    s = max(1, round(smooth_span / gsd))).  Directions d in {(0, 1), (1, 0), (1, 1), (1, -1)}.  A direction COUNTS iff
+ *    c - s d and c + s d are both inside the grid, both in M, and both have a finite Z.  For a counting direction
+ *      D = fabs(((double)Z(c - s d) + (double)Z(c + s d)) - 2.0 * (double)Z(c))
+ *    every operation in fp64, in this order, no contraction.  A cell with no counting direction is undetermined; otherwise
+ *    it is smooth iff D <= smooth_tol holds for every counting direction (a NaN D, from a non-finite Z(c), fails it), else
+ *    rough.  flags uint8 [H][W]: 0 not a candidate, 1 removed by the opening, 2 undetermined, 3 smooth, 4 rough.
+ *    A planar roof of any pitch has D = 0; a ridge is rough only across the ridge line; a crown is rough everywhere.
+ * 4. Components: the 4-connected components of M (cells that touch only at a corner are not joined).
+ *    _bld_label writes parent int32 [H][W]: -1 outside M, otherwise the smallest cell index of the cell's component.  The
+ *    components are numbered 1 .. N in ascending order of that index (the caller scans the cells with parent == own index);
+ *    label int32 [H][W] holds that number, 0 outside M.  The numbering follows from the mask alone.
+ * 5. Table, int64 [ADAMVS_BLD_COLUMNS][N], row k - 1 for component k: cells; smooth, rough, undetermined (counts of the flags
+ *    3, 4, 2); row_min, row_max, col_min, col_max; height_sum = the integer sum of llrint(min((double)ndsm, 65535.0) * 1024.0)
+ *    (round to nearest, ties to even); height_max_bits = the largest fp32 bit pattern of ndsm (the values are positive, so
+ *    the order of the patterns is the order of the values).  Integer sums, minima and maxima only.
+ * 6. Selection and 7. vectorising run on the host (ada-mvs_amd/buildings.py select(), polygons()).
+ *
+ * Kernels (csrc/dsm_buildings.hip).  _bld_flags: the mask, the opening's six passes, then one pass that reads up to eight
+ * neighbours of M and of Z at the stride directly (each such read is a coalesced row segment served by L2; a tile with an
+ * s-cell halo in LDS would load (1 + 2 s / T)^2 times the tile to use nine points of it).  _bld_label: one workgroup resolves a
+ * tile of ADAMVS_BLD_TILE_W x ADAMVS_BLD_TILE_H cells in LDS (row runs from wave ballots, unions by atomicMin on LDS labels
+ * until a pass changes nothing), then rounds over the pairs of adjacent cells on tile borders only: read both roots (one
+ * kernel), hook the larger root to the smaller by integer atomicMin (the next kernel, so every read saw the previous round's
+ * state), walk the border cells to their roots (a third), until a round finds no pair with two roots; at most
+ * ADAMVS_BLD_MAX_ROUNDS rounds, more is an error return (ADAMVS_BLD_NOT_CONVERGED), never a longer loop.  No workgroup waits
+ * on another; visibility between rounds comes from the kernel boundaries.  _bld_table: one pass; the lanes of a wave that
+ * follow one another in a row with the same label are summed in registers and one lane issues the atomics of the run.
+ * flags, parent, label and the table are bit-identical from run to run: no floating-point atomic, no floating-point sum.
+ * _bld_flags and _bld_table do not block; _bld_label reads one word per round back and blocks.
+ * dsm, ndsm, flags, parent, label, table, workspace: device memory; workspace of at least _bld_workspace_bytes(W, H) bytes
+ * (about 16 bytes per cell), 256-byte aligned; stats: a HOST pointer.
+ * Argument errors (<0, before any launch): a null pointer, W or H <= 0 or W H > ADAMVS_DSM_MAX_CELLS, min_height not finite or
+ * <= 0, r_open outside 0 .. ADAMVS_DTM_MAX_RADIUS, s outside 1 .. ADAMVS_BLD_MAX_STRIDE, smooth_tol not finite or < 0,
+ * N < 0 or N > W H, workspace_bytes below the query, any two of the buffers (workspace included) overlapping.
+ * _bld_workspace_bytes returns < 0 for W or H <= 0 or W H > ADAMVS_DSM_MAX_CELLS. */
+#define ADAMVS_BLD_TILE_W 64 /* cells of a row per tile of the labelling: one wave */
+#define ADAMVS_BLD_TILE_H 64
+#define ADAMVS_BLD_MAX_STRIDE 64
+#define ADAMVS_BLD_MAX_ROUNDS 64
+#define ADAMVS_BLD_NOT_CONVERGED (-2)
+#define ADAMVS_BLD_COLUMNS 10
+enum {
+  ADAMVS_BLD_CELLS = 0, ADAMVS_BLD_SMOOTH = 1, ADAMVS_BLD_ROUGH = 2, ADAMVS_BLD_UNDETERMINED = 3, ADAMVS_BLD_ROW_MIN = 4,
+  ADAMVS_BLD_ROW_MAX = 5, ADAMVS_BLD_COL_MIN = 6, ADAMVS_BLD_COL_MAX = 7, ADAMVS_BLD_HEIGHT_SUM = 8, ADAMVS_BLD_HEIGHT_MAX_BITS = 9
+};
+
+typedef struct {
+  int rounds;      /* border rounds that hooked something (<= ADAMVS_BLD_MAX_ROUNDS) */
+  int converged;   /* 1 unless the cap was hit */
+  long tiles;      /* workgroups of the tile phase */
+  long pairs;      /* pairs of adjacent cells on tile borders examined per round */
+  float ms_tile, ms_rounds, ms_compress; /* device time of the tile phase, of the border rounds (their read-backs included)
+                                            and of the final walk to the roots, in milliseconds; -1 if the events failed */
+} adamvs_bld_stats;
+
+long adamvs_bld_workspace_bytes(int W, int H);
+int adamvs_bld_flags(int W, int H, const float* dsm, const float* ndsm, double min_height, int r_open, int s, double smooth_tol,
+                     void* workspace, long workspace_bytes, unsigned char* flags, void* stream);
+int adamvs_bld_label(int W, int H, const unsigned char* flags, void* workspace, long workspace_bytes, int* parent,
+                     adamvs_bld_stats* stats, void* stream);
+int adamvs_bld_table(int W, int H, const unsigned char* flags, const float* ndsm, const int* label, long N, long long* table,
+                     void* stream);
+
 /* ---- TSDF mesh (after fuse_whu.py): the depth maps of all views integrated into a truncated signed-distance field on a voxel
  * grid, brick by brick, and its zero level set extracted as a coloured triangle mesh ---------------------------------------
  * ada-mvs_amd/mesh.py drives it per brick; mesh_whu.py is the CLI.  World axes: x east, y north, z up.
