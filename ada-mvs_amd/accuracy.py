@@ -32,7 +32,8 @@ import time
 
 import numpy as np
 
-MAX_COUNT = (1 << 31) - 1
+from .cloud_lattice import MAX_COUNT
+
 KEY_BITS = 21
 BEYOND_RGB = (255, 0, 255)
 QUANTILES = (("median_within", 0.5), ("p90_within", 0.9))
@@ -54,9 +55,9 @@ def default_thresholds(D):
 
 
 def default_lattice_origin(cell, target_min):
-    """Per axis the minimum of the targets - c / 3 - c (simplify.default_lattice_origin, lowered by one whole cell, so that the
-    lower neighbour of every target's cell lies in the lattice)."""
-    return np.asarray(target_min, np.float64).reshape(3) - float(cell) / 3.0 - float(cell)
+    """cloud_lattice.default_origin, under the name tests and tools call."""
+    from . import cloud_lattice
+    return cloud_lattice.default_origin(cell, target_min)
 
 
 def resolve_spacing(spacing, spacing_voxels, D, meta):
@@ -90,61 +91,15 @@ def ramp(dist, D):
     return rgb
 
 
-def _cloud(t, name):
-    import torch
-    from . import _lib
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.AdaMVSHipError("%s must be a GPU tensor: the cloud distance has no CPU fallback" % name)
-    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
-        raise _lib.AdaMVSHipError("%s: [n, 3] float64, got %s %s" % (name, tuple(t.shape), t.dtype))
-    if t.shape[0] > MAX_COUNT:
-        raise _lib.AdaMVSHipError("%s: more than 2^31 - 1 points" % name)
-    return t.contiguous()
-
-
-def sort_targets(targets, tkeys):
-    """The targets under their keys, sorted stably -> (ukeys [nc] int64: the occupied cells ascending; tstart [nc + 1] int64: the start
-    of each cell's run; the sorted targets [nt, 3]; tindex [nt] int32: their numbers in the caller's order)."""
-    import torch
-    ts = torch.sort(tkeys, stable=True)
-    ukeys, tcount = torch.unique_consecutive(ts.values, return_counts=True)
-    tstart = torch.zeros(int(ukeys.numel()) + 1, device=tkeys.device, dtype=torch.int64)
-    tstart[1:] = torch.cumsum(tcount, 0)
-    return ukeys, tstart, targets[ts.indices].contiguous(), ts.indices.to(torch.int32)
-
-
-def work_items(qs):
-    """qs: the stable sort of the query keys -> (outside: the queries with a key of -1; qorder [nqs] int64: the others in sorted
-    order; (item_key, item_first, item_count): every run of equal keys cut into work items of at most CLOUD_TILE queries, or None
-    where no query lies in the lattice)."""
-    import torch
-    from . import _lib
-    dev = qs.values.device
-    outside = int(torch.searchsorted(qs.values, torch.zeros(1, device=dev, dtype=torch.int64)))     # keys of -1 sort first
-    qorder = qs.indices[outside:].contiguous()
-    if qorder.numel() == 0:
-        return outside, qorder, None
-    cell_key, cell_count = torch.unique_consecutive(qs.values[outside:], return_counts=True)
-    cell_first = torch.cumsum(cell_count, 0) - cell_count
-    T = _lib.CLOUD_TILE
-    pieces = (cell_count + (T - 1)) // T
-    owner = torch.repeat_interleave(torch.arange(cell_key.numel(), device=dev), pieces)
-    rank = torch.arange(owner.numel(), device=dev) - (torch.cumsum(pieces, 0) - pieces)[owner]
-    item_key = cell_key[owner].contiguous()
-    item_first = (cell_first[owner] + rank * T).contiguous()
-    item_count = torch.clamp(cell_count[owner] - rank * T, max=T).to(torch.int32)
-    return outside, qorder, (item_key, item_first, item_count)
-
-
 def nearest(targets, queries, D, detail=None, timing=None, origin=None):
     """targets [nt, 3], queries [nq, 3] float64 device tensors -> (dist [nq] float32: the distance to the nearest target, +inf where
     none lies within D; index [nq] int32: that target's number, or -1; info: targets, queries, cells, items, within, pairs).
     origin: the lattice origin (default: default_lattice_origin).  detail: a dict that receives d2 and the intermediates (device
     tensors); timing: a list that receives (name, start event, end event) of the stages keys, sorts, items, nearest."""
     import torch
-    from . import _lib, hip_ops
+    from . import cloud_lattice, hip_ops, mesh_stage
     check_options(D)
-    targets, queries = _cloud(targets, "targets"), _cloud(queries, "queries")
+    targets, queries = cloud_lattice.cloud(targets, "targets"), cloud_lattice.cloud(queries, "queries")
     dev, c = queries.device, float(D)
     nt, nq = int(targets.shape[0]), int(queries.shape[0])
     info = dict(targets=nt, queries=nq, cells=0, items=0, within=0, pairs=0)
@@ -152,39 +107,25 @@ def nearest(targets, queries, D, detail=None, timing=None, origin=None):
     index = torch.full((nq,), -1, device=dev, dtype=torch.int32)
     if nt == 0 or nq == 0:
         return dist, index, info
-    marks = []
-
-    def stage(name):
-        if timing is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            marks.append((name, e))
-
-    stage("keys")
-    o = np.asarray(origin, np.float64).reshape(3) if origin is not None else default_lattice_origin(c, targets.min(0).values.cpu().numpy())
-    if not np.isfinite(o).all():
-        raise _lib.AdaMVSHipError("the lattice origin %r is not finite (a target is not?)" % (o,))
-    tkeys, bad = hip_ops.simplify_keys(targets, c, o)
-    if int(bad.max()):
-        raise _lib.AdaMVSHipError("nearest: %d targets are not finite, %d lie outside the lattice of 2^21 cells per axis (cell %g, lattice "
-                                  "origin %s)" % (int((bad == 1).sum()), int((bad == 2).sum()), c, o.tolist()))
+    clock = mesh_stage.StageClock(timing)
+    clock.stage("keys")
+    o = cloud_lattice.origin_of(origin, c, targets, "target")
+    tkeys = cloud_lattice.keyed(targets, c, o, "nearest", "targets")
     qkeys, _ = hip_ops.simplify_keys(queries, c, o)
-    stage("sorts")
-    ukeys, tstart, targets_sorted, tindex = sort_targets(targets, tkeys)
-    nc = int(ukeys.numel())
+    clock.stage("sorts")
+    cells = cloud_lattice.Cells(targets, tkeys)
+    ukeys, tstart, tindex = cells.ukeys, cells.tstart, cells.index
     qs = torch.sort(qkeys, stable=True)
-    stage("items")
-    outside, qorder, items = work_items(qs)
-    info.update(cells=nc, outside=outside)
+    clock.stage("items")
+    outside, qorder, items = cloud_lattice.work_items(qs.values, qs.indices)
+    info.update(cells=int(ukeys.numel()), outside=outside)
     if items is None:
         return dist, index, info
     item_key, item_first, item_count = items
-    stage("nearest")
-    d2, index, pairs = hip_ops.cloud_nearest(o, c, ukeys, tstart, targets_sorted, tindex, queries, qorder, item_key, item_first, item_count)
+    clock.stage("nearest")
+    d2, index, pairs = hip_ops.cloud_nearest(o, c, ukeys, tstart, cells.sorted, tindex, queries, qorder, item_key, item_first, item_count)
     dist = torch.sqrt(d2)
-    stage("end")
-    if timing is not None:
-        timing.extend((a[0], a[1], b[1]) for a, b in zip(marks[:-1], marks[1:]))
+    clock.end()
     info.update(items=int(item_key.numel()), within=int((index >= 0).sum()), pairs=int(pairs.sum()))
     if detail is not None:
         detail.update(d2=d2, lattice_origin=o, tkeys=tkeys, qkeys=qkeys, ukeys=ukeys, tstart=tstart, tindex=tindex, qorder=qorder,
@@ -196,9 +137,9 @@ def sample_mesh(xyz, faces, spacing):
     """xyz [nv, 3] float64, faces [nf, 3] int32 (uint32) or int64: device tensors -> points [m, 3] float64 on the faces, every point
     of the surface within spacing / sqrt(3) of one (include/adamvs_hip.h "Cloud distance", surface sampler)."""
     import torch
-    from . import _lib, hip_ops
+    from . import _lib, cloud_lattice, hip_ops
     check_options(1.0, spacing=spacing)
-    xyz = _cloud(xyz, "xyz")
+    xyz = cloud_lattice.cloud(xyz, "xyz")
     if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
         raise _lib.AdaMVSHipError("faces must be a GPU tensor: the surface sampler has no CPU fallback")
     if faces.dtype not in (torch.int32, torch.int64) or faces.dim() != 2 or faces.shape[1] != 3:
@@ -292,27 +233,19 @@ def compare(recon, truth, D, thresholds=None, detail=None, timing=None):
     """recon [n, 3], truth [m, 3] float64 device tensors -> dict: accuracy (summarise of the distances recon -> truth), completeness
     (truth -> recon), scores [{tau, precision, recall, fscore}], pairs (pair evaluations of both searches).  detail receives
     accuracy_dist and completeness_dist (device, float32)."""
-    import torch
+    from . import mesh_stage
     thresholds = default_thresholds(D) if thresholds is None else [float(t) for t in thresholds]
     check_options(D, thresholds)
-    marks = []
-
-    def stage(name):
-        if timing is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            marks.append((name, e))
-
     t_acc, t_com = [], []
     acc_d, _, acc_i = nearest(truth, recon, D, timing=t_acc if timing is not None else None)
     com_d, _, com_i = nearest(recon, truth, D, timing=t_com if timing is not None else None)
-    stage("statistics")
+    clock = mesh_stage.StageClock(timing)
+    clock.stage("statistics")
     acc, com = summarise(acc_d, D, thresholds), summarise(com_d, D, thresholds)
-    stage("end")
     if timing is not None:
         timing.extend(("accuracy_" + n, a, b) for n, a, b in t_acc)
         timing.extend(("completeness_" + n, a, b) for n, a, b in t_com)
-        timing.append((marks[0][0], marks[0][1], marks[1][1]))
+    clock.end()
     if detail is not None:
         detail.update(accuracy_dist=acc_d, completeness_dist=com_d)
     return dict(max_dist=float(D), accuracy=acc, completeness=com, scores=combine(acc, com), pairs=acc_i["pairs"] + com_i["pairs"],

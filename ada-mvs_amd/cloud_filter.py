@@ -38,7 +38,6 @@ import time
 
 import numpy as np
 
-MAX_COUNT = (1 << 31) - 1
 DEFAULT_K = 16
 DEFAULT_STD_RATIO = 2.0
 DEFAULT_CHUNK = 1 << 20
@@ -60,59 +59,24 @@ def check_options(radius, k=DEFAULT_K, std_ratio=None, min_neighbours=None, chun
         raise ValueError("chunk_queries=%r (>= 1)" % (chunk_queries,))
 
 
-def _cloud(t, name="points"):
-    import torch
-    from . import _lib
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.AdaMVSHipError("%s must be a GPU tensor: the neighbour search has no CPU fallback" % name)
-    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
-        raise _lib.AdaMVSHipError("%s: [n, 3] float64, got %s %s" % (name, tuple(t.shape), t.dtype))
-    if t.shape[0] > MAX_COUNT:
-        raise _lib.AdaMVSHipError("%s: more than 2^31 - 1 points" % name)
-    return t.contiguous()
-
-
 class Search:
     """The cloud keyed, sorted and cut into the work items of accuracy.nearest (one cell, at most 256 queries), the cloud being both
     the targets and the queries; chunks() runs _knn_search over contiguous ranges of the items."""
 
     def __init__(self, points, R, k, origin=None, chunk_queries=DEFAULT_CHUNK):
-        import torch
-        from . import _lib, accuracy, hip_ops
+        from . import cloud_lattice
         check_options(R, k, chunk_queries=chunk_queries)
-        self.points = points = _cloud(points)
+        self.points = points = cloud_lattice.cloud(points, "points", "the neighbour search")
         self.R, self.k, self.chunk_queries = float(R), k, chunk_queries
         self.n = n = int(points.shape[0])
         self.pairs, self.items, self.cells = 0, 0, 0
         if n == 0:
             return
-        dev = points.device
-        o = np.asarray(origin, np.float64).reshape(3) if origin is not None else \
-            accuracy.default_lattice_origin(self.R, points.min(0).values.cpu().numpy())
-        if not np.isfinite(o).all():
-            raise _lib.AdaMVSHipError("the lattice origin %r is not finite (a point is not?)" % (o,))
-        self.origin = o
-        keys, bad = hip_ops.simplify_keys(points, self.R, o)
-        if int(bad.max()):
-            raise _lib.AdaMVSHipError("knn: %d points are not finite, %d lie outside the lattice of 2^21 cells per axis (cell %g, lattice "
-                                      "origin %s)" % (int((bad == 1).sum()), int((bad == 2).sum()), self.R, o.tolist()))
-        ks = torch.sort(keys, stable=True)
-        self.ukeys, cell_count = torch.unique_consecutive(ks.values, return_counts=True)
-        nc = int(self.ukeys.numel())
-        self.tstart = torch.zeros(nc + 1, device=dev, dtype=torch.int64)
-        self.tstart[1:] = torch.cumsum(cell_count, 0)
-        self.order = ks.indices
-        self.sorted = points[ks.indices].contiguous()
-        self.pindex = ks.indices.to(torch.int32)
-        T = _lib.CLOUD_TILE
-        cell_first = self.tstart[:-1]
-        pieces = (cell_count + (T - 1)) // T
-        owner = torch.repeat_interleave(torch.arange(nc, device=dev), pieces)
-        rank = torch.arange(owner.numel(), device=dev) - (torch.cumsum(pieces, 0) - pieces)[owner]
-        self.item_key = self.ukeys[owner].contiguous()
-        self.item_first = (cell_first[owner] + rank * T).contiguous()
-        self.item_count = torch.clamp(cell_count[owner] - rank * T, max=T).to(torch.int32)
-        self.cells, self.items = nc, int(self.item_key.numel())
+        self.origin = cloud_lattice.origin_of(origin, self.R, points, "point")
+        cells = cloud_lattice.Cells(points, cloud_lattice.keyed(points, self.R, self.origin, "knn", "points"))
+        self.ukeys, self.tstart, self.order, self.sorted, self.pindex = cells.ukeys, cells.tstart, cells.order, cells.sorted, cells.index
+        self.item_key, self.item_first, self.item_count = cells.items()
+        self.cells, self.items = int(self.ukeys.numel()), int(self.item_key.numel())
         self.item_end = (self.item_first + self.item_count).cpu().numpy()            # ascending: the items tile the sorted order
 
     def ranges(self):
@@ -270,7 +234,7 @@ def from_file(ply, radius, k=DEFAULT_K, std_ratio=DEFAULT_STD_RATIO, min_neighbo
               chunk_queries=DEFAULT_CHUNK, device=None, log=print):
     """Filter the point PLY `ply` (fuse_whu.py's layout) -> the dict also written to <out>.json."""
     import torch
-    from . import _lib, dsm, fusion
+    from . import _lib, dsm, fusion, mesh_stage
     t_start = time.time()
     check_options(radius, k, std_ratio, min_neighbours, chunk_queries)
     if not torch.cuda.is_available():
@@ -281,14 +245,9 @@ def from_file(ply, radius, k=DEFAULT_K, std_ratio=DEFAULT_STD_RATIO, min_neighbo
     xyz = np.concatenate([p[0] for p in parts]) if parts else np.zeros((0, 3), np.float64)
     rgb = np.concatenate([p[1] for p in parts]) if parts else np.zeros((0, 3), np.uint8)
     pts = torch.from_numpy(xyz).to(device)
-    marks = []
-
-    def stage(name):
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        marks.append((name, e))
-
-    stage("filter")
+    timing = []
+    clock = mesh_stage.StageClock(timing)
+    clock.stage("filter")
     keep, res = filter_points(pts, radius, k, std_ratio, min_neighbours, chunk_queries=chunk_queries)
     kept = keep.cpu().numpy()
     json_path, kept_ply, removed_ply, normals_ply = output_paths(out)
@@ -296,12 +255,12 @@ def from_file(ply, radius, k=DEFAULT_K, std_ratio=DEFAULT_STD_RATIO, min_neighbo
         os.makedirs(os.path.dirname(out), exist_ok=True)
     nres = None
     if with_normals:
-        stage("normals")
+        clock.stage("normals")
         info = {}
         nrm, curv, flag, _ = normals(pts[keep].contiguous(), radius, k, chunk_queries=chunk_queries, info=info)
         nres = dict(valid=int((flag == _lib.KNN_VALID).sum()), too_few=int((flag == _lib.KNN_TOO_FEW).sum()),
                     collinear=int((flag == _lib.KNN_COLLINEAR).sum()), pairs=info.get("pairs", 0))
-    stage("end")
+    clock.end()
     torch.cuda.synchronize(device)
     for path, sel in ((kept_ply, kept), (removed_ply, ~kept)):
         with fusion.PlyWriter(path) as w:
@@ -311,8 +270,8 @@ def from_file(ply, radius, k=DEFAULT_K, std_ratio=DEFAULT_STD_RATIO, min_neighbo
     res.update(input=ply, options=dict(radius=float(radius), k=k, std_ratio=std_ratio, min_neighbours=min_neighbours, normals=bool(with_normals),
                                        chunk_queries=chunk_queries),
                ply=kept_ply, removed_ply=removed_ply, normals_ply=normals_ply if with_normals else None, normals=nres,
-               stage_ms={a[0]: a[1].elapsed_time(b[1]) for a, b in zip(marks[:-1], marks[1:])},
-               device_seconds=marks[0][1].elapsed_time(marks[-1][1]) / 1e3, seconds=time.time() - t_start)
+               stage_ms={name: a.elapsed_time(b) for name, a, b in timing},
+               device_seconds=timing[0][1].elapsed_time(timing[-1][2]) / 1e3, seconds=time.time() - t_start)
     with open(json_path, "w") as fj:
         json.dump(res, fj, indent=1)
         fj.write("\n")

@@ -644,33 +644,34 @@ extern "C" int adamvs_mesh_emit(const adamvs_mesh_brick* brick, const float* tsd
                           vert_capacity, faces, tri_capacity, (hipStream_t)stream);
 }
 
-// ---- mesh simplification (mesh_simplify.hip): every argument is checked here, before any launch
+// ---- the lattice and the counts of mesh simplification and the cloud stages: one check each
 static const long SIMPLIFY_MAX = (1L << 31) - 1;
 
-static int simplify_check_lattice(const double* origin, double cell, const char* what) {
+static int check_lattice(const double* origin, double cell, const char* what) {
   ADAMVS_CHECK_ARG(origin, "%s: null origin", what);
   ADAMVS_CHECK_ARG(std::isfinite(cell) && cell > 0, "%s: cell=%g must be finite and > 0", what, cell);
   ADAMVS_CHECK_ARG(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]), "%s: origin is not finite", what);
   return 0;
 }
 
-static int simplify_check_count(long n, const char* name, const char* what) {
-  ADAMVS_CHECK_ARG(n >= 1 && n <= SIMPLIFY_MAX, "%s: %s=%ld (1 .. 2^31 - 1)", what, name, n);
+static int check_count(long n, const char* name, const char* what, long least = 1) {
+  ADAMVS_CHECK_ARG(n >= least && n <= SIMPLIFY_MAX, "%s: %s=%ld (%ld .. 2^31 - 1)", what, name, n, least);
   return 0;
 }
 
+// ---- mesh simplification (mesh_simplify.hip): every argument is checked here, before any launch
 extern "C" int adamvs_simplify_keys(const double* origin, double cell, const double* xyz, long nv, long long* keys, unsigned char* bad,
                                     void* stream) {
-  if (int rc = simplify_check_lattice(origin, cell, "simplify_keys")) return rc;
-  if (int rc = simplify_check_count(nv, "nv", "simplify_keys")) return rc;
+  if (int rc = check_lattice(origin, cell, "simplify_keys")) return rc;
+  if (int rc = check_count(nv, "nv", "simplify_keys")) return rc;
   ADAMVS_CHECK_ARG(xyz && keys && bad, "simplify_keys: null pointer");
   return launch_simplify_keys(origin, cell, xyz, nv, keys, bad, (hipStream_t)stream);
 }
 
 extern "C" int adamvs_simplify_corners(const unsigned* faces, long nf, const int* vcell, long nv, int nc, int* fcell, int* entry_cell,
                                        unsigned char* survive, void* stream) {
-  if (int rc = simplify_check_count(nf, "nf", "simplify_corners")) return rc;
-  if (int rc = simplify_check_count(nv, "nv", "simplify_corners")) return rc;
+  if (int rc = check_count(nf, "nf", "simplify_corners")) return rc;
+  if (int rc = check_count(nv, "nv", "simplify_corners")) return rc;
   ADAMVS_CHECK_ARG(nc >= 1 && nc <= nv, "simplify_corners: nc=%d (1 .. nv = %ld)", nc, nv);
   ADAMVS_CHECK_ARG(faces && vcell && fcell && entry_cell && survive, "simplify_corners: null pointer");
   return launch_simplify_corners(faces, nf, vcell, nv, nc, fcell, entry_cell, survive, (hipStream_t)stream);
@@ -680,9 +681,9 @@ extern "C" int adamvs_simplify_accumulate(const double* origin, double cell, con
                                           const unsigned char* rgb, long nv, const unsigned* faces, long nf, const long long* entry,
                                           const long long* fstart, const long long* vorder, const long long* vstart, double* quadric,
                                           double* member, unsigned long long* colour, void* stream) {
-  if (int rc = simplify_check_lattice(origin, cell, "simplify_accumulate")) return rc;
-  if (int rc = simplify_check_count(nf, "nf", "simplify_accumulate")) return rc;
-  if (int rc = simplify_check_count(nv, "nv", "simplify_accumulate")) return rc;
+  if (int rc = check_lattice(origin, cell, "simplify_accumulate")) return rc;
+  if (int rc = check_count(nf, "nf", "simplify_accumulate")) return rc;
+  if (int rc = check_count(nv, "nv", "simplify_accumulate")) return rc;
   ADAMVS_CHECK_ARG(nc >= 1 && nc <= nv, "simplify_accumulate: nc=%d (1 .. nv = %ld)", nc, nv);
   ADAMVS_CHECK_ARG(keys && xyz && rgb && faces && entry && fstart && vorder && vstart && quadric && member && colour,
                    "simplify_accumulate: null pointer");
@@ -694,8 +695,8 @@ extern "C" int adamvs_simplify_solve(const double* origin, double cell, double r
                                      const double* quadric, const double* member, const unsigned long long* colour,
                                      const long long* vstart, double* pos, unsigned char* col, unsigned char* rank, unsigned char* fallback,
                                      double* error, void* stream) {
-  if (int rc = simplify_check_lattice(origin, cell, "simplify_solve")) return rc;
-  if (int rc = simplify_check_count(nc, "nc", "simplify_solve")) return rc;
+  if (int rc = check_lattice(origin, cell, "simplify_solve")) return rc;
+  if (int rc = check_count(nc, "nc", "simplify_solve")) return rc;
   ADAMVS_CHECK_ARG(rank_eps >= 0 && rank_eps < 1, "simplify_solve: rank_eps=%g (0 <= rank_eps < 1)", rank_eps);
   ADAMVS_CHECK_ARG(keys && quadric && member && colour && vstart && pos && col && rank && fallback && error, "simplify_solve: null pointer");
   return launch_simplify_solve(origin, cell, rank_eps, keys, nc, quadric, member, colour, vstart, pos, col, rank, fallback, error,
@@ -704,7 +705,7 @@ extern "C" int adamvs_simplify_solve(const double* origin, double cell, double r
 
 extern "C" int adamvs_simplify_solve_host(const double* quadric, const double* mean, long n, double cell, double rank_eps, double* p,
                                           int* rank, int* fallback, double* error) {
-  if (int rc = simplify_check_count(n, "n", "simplify_solve_host")) return rc;
+  if (int rc = check_count(n, "n", "simplify_solve_host")) return rc;
   ADAMVS_CHECK_ARG(std::isfinite(cell) && cell > 0, "simplify_solve_host: cell=%g must be finite and > 0", cell);
   ADAMVS_CHECK_ARG(rank_eps >= 0 && rank_eps < 1, "simplify_solve_host: rank_eps=%g (0 <= rank_eps < 1)", rank_eps);
   ADAMVS_CHECK_ARG(quadric && mean && p && rank && fallback && error, "simplify_solve_host: null pointer");
@@ -714,7 +715,7 @@ extern "C" int adamvs_simplify_solve_host(const double* quadric, const double* m
 }
 
 extern "C" int adamvs_simplify_triples(const int* fcell, long nf, const long long* surv, long ns, int* tri, void* stream) {
-  if (int rc = simplify_check_count(nf, "nf", "simplify_triples")) return rc;
+  if (int rc = check_count(nf, "nf", "simplify_triples")) return rc;
   ADAMVS_CHECK_ARG(ns >= 1 && ns <= nf, "simplify_triples: ns=%ld (1 .. nf = %ld)", ns, nf);
   ADAMVS_CHECK_ARG(fcell && surv && tri, "simplify_triples: null pointer");
   return launch_simplify_triples(fcell, nf, surv, ns, tri, (hipStream_t)stream);
@@ -722,21 +723,21 @@ extern "C" int adamvs_simplify_triples(const int* fcell, long nf, const long lon
 
 extern "C" int adamvs_simplify_first(const int* tri, const long long* surv, const long long* order, long ns, long nf, unsigned char* keep,
                                      void* stream) {
-  if (int rc = simplify_check_count(nf, "nf", "simplify_first")) return rc;
+  if (int rc = check_count(nf, "nf", "simplify_first")) return rc;
   ADAMVS_CHECK_ARG(ns >= 1 && ns <= nf, "simplify_first: ns=%ld (1 .. nf = %ld)", ns, nf);
   ADAMVS_CHECK_ARG(tri && surv && order && keep, "simplify_first: null pointer");
   return launch_simplify_first(tri, surv, order, ns, nf, keep, (hipStream_t)stream);
 }
 
 extern "C" int adamvs_simplify_mark(const int* fcell, const unsigned char* keep, long nf, int nc, unsigned char* used, void* stream) {
-  if (int rc = simplify_check_count(nf, "nf", "simplify_mark")) return rc;
-  if (int rc = simplify_check_count(nc, "nc", "simplify_mark")) return rc;
+  if (int rc = check_count(nf, "nf", "simplify_mark")) return rc;
+  if (int rc = check_count(nc, "nc", "simplify_mark")) return rc;
   ADAMVS_CHECK_ARG(fcell && keep && used, "simplify_mark: null pointer");
   return launch_simplify_mark(fcell, keep, nf, nc, used, (hipStream_t)stream);
 }
 
 extern "C" int adamvs_simplify_count(const unsigned char* flags, long n, unsigned* block_count, void* stream) {
-  if (int rc = simplify_check_count(n, "n", "simplify_count")) return rc;
+  if (int rc = check_count(n, "n", "simplify_count")) return rc;
   ADAMVS_CHECK_ARG(flags && block_count, "simplify_count: null pointer");
   return launch_simplify_count(flags, n, block_count, (hipStream_t)stream);
 }
@@ -745,8 +746,8 @@ extern "C" int adamvs_simplify_emit(const double* pos, const unsigned char* col,
                                     const unsigned* cell_offsets, const int* fcell, const unsigned char* keep, long nf,
                                     const unsigned* face_offsets, double* xyz, unsigned char* rgb, unsigned* new_index, long vert_capacity,
                                     unsigned* faces, long face_capacity, void* stream) {
-  if (int rc = simplify_check_count(nf, "nf", "simplify_emit")) return rc;
-  if (int rc = simplify_check_count(nc, "nc", "simplify_emit")) return rc;
+  if (int rc = check_count(nf, "nf", "simplify_emit")) return rc;
+  if (int rc = check_count(nc, "nc", "simplify_emit")) return rc;
   ADAMVS_CHECK_ARG(pos && col && used && cell_offsets && fcell && keep && face_offsets && new_index, "simplify_emit: null pointer");
   ADAMVS_CHECK_ARG(vert_capacity >= 0 && face_capacity >= 0, "simplify_emit: capacity < 0");
   ADAMVS_CHECK_ARG((xyz && rgb) || vert_capacity == 0, "simplify_emit: null vertex output");
@@ -897,11 +898,11 @@ extern "C" int adamvs_cloud_nearest(const double* origin, double D, const long l
                                     const double* targets, const int* tindex, long nt, const double* queries, long nq,
                                     const long long* qorder, long nqs, const long long* item_key, const long long* item_first,
                                     const int* item_count, long ni, float* d2, int* index, unsigned long long* pairs, void* stream) {
-  if (int rc = simplify_check_lattice(origin, D, "cloud_nearest")) return rc;
-  if (int rc = simplify_check_count(nt, "nt", "cloud_nearest")) return rc;
-  if (int rc = simplify_check_count(nq, "nq", "cloud_nearest")) return rc;
-  if (int rc = simplify_check_count(nqs, "nqs", "cloud_nearest")) return rc;
-  if (int rc = simplify_check_count(ni, "ni", "cloud_nearest")) return rc;
+  if (int rc = check_lattice(origin, D, "cloud_nearest")) return rc;
+  if (int rc = check_count(nt, "nt", "cloud_nearest")) return rc;
+  if (int rc = check_count(nq, "nq", "cloud_nearest")) return rc;
+  if (int rc = check_count(nqs, "nqs", "cloud_nearest")) return rc;
+  if (int rc = check_count(ni, "ni", "cloud_nearest")) return rc;
   ADAMVS_CHECK_ARG(nc >= 1 && nc <= nt, "cloud_nearest: nc=%d (1 .. nt = %ld)", nc, nt);
   ADAMVS_CHECK_ARG(nqs <= nq && ni <= nqs, "cloud_nearest: nqs=%ld, ni=%ld (ni <= nqs <= nq = %ld)", nqs, ni, nq);
   ADAMVS_CHECK_ARG(ukeys && tstart && targets && tindex && queries && qorder && item_key && item_first && item_count && d2 && index && pairs,
@@ -912,17 +913,17 @@ extern "C" int adamvs_cloud_nearest(const double* origin, double D, const long l
 
 extern "C" int adamvs_cloud_nearest_host(const double* origin, double D, const double* targets, long nt, const double* queries, long nq,
                                          float* d2, int* index, unsigned long long* pairs) {
-  if (int rc = simplify_check_lattice(origin, D, "cloud_nearest_host")) return rc;
-  if (int rc = simplify_check_count(nt, "nt", "cloud_nearest_host")) return rc;
-  if (int rc = simplify_check_count(nq, "nq", "cloud_nearest_host")) return rc;
+  if (int rc = check_lattice(origin, D, "cloud_nearest_host")) return rc;
+  if (int rc = check_count(nt, "nt", "cloud_nearest_host")) return rc;
+  if (int rc = check_count(nq, "nq", "cloud_nearest_host")) return rc;
   ADAMVS_CHECK_ARG(targets && queries && d2 && index, "cloud_nearest_host: null pointer");
   return cloud_nearest_host(origin, D, targets, nt, queries, nq, d2, index, pairs);
 }
 
 extern "C" int adamvs_cloud_sample_count(const double* xyz, long nv, const unsigned* faces, long nf, double spacing, int* subdiv,
                                          void* stream) {
-  if (int rc = simplify_check_count(nv, "nv", "cloud_sample_count")) return rc;
-  if (int rc = simplify_check_count(nf, "nf", "cloud_sample_count")) return rc;
+  if (int rc = check_count(nv, "nv", "cloud_sample_count")) return rc;
+  if (int rc = check_count(nf, "nf", "cloud_sample_count")) return rc;
   ADAMVS_CHECK_ARG(std::isfinite(spacing) && spacing > 0, "cloud_sample_count: spacing=%g must be finite and > 0", spacing);
   ADAMVS_CHECK_ARG(xyz && faces && subdiv, "cloud_sample_count: null pointer");
   return launch_cloud_sample_count(xyz, nv, faces, nf, spacing, subdiv, (hipStream_t)stream);
@@ -930,8 +931,8 @@ extern "C" int adamvs_cloud_sample_count(const double* xyz, long nv, const unsig
 
 extern "C" int adamvs_cloud_sample_emit(const double* xyz, long nv, const unsigned* faces, long nf, const int* subdiv,
                                         const long long* offsets, double* points, long capacity, void* stream) {
-  if (int rc = simplify_check_count(nv, "nv", "cloud_sample_emit")) return rc;
-  if (int rc = simplify_check_count(nf, "nf", "cloud_sample_emit")) return rc;
+  if (int rc = check_count(nv, "nv", "cloud_sample_emit")) return rc;
+  if (int rc = check_count(nf, "nf", "cloud_sample_emit")) return rc;
   ADAMVS_CHECK_ARG(nf <= SIMPLIFY_MAX / 64, "cloud_sample_emit: nf=%ld (one wave per face: at most (2^31 - 1) / 64)", nf);
   ADAMVS_CHECK_ARG(capacity >= 0, "cloud_sample_emit: capacity < 0");
   ADAMVS_CHECK_ARG(xyz && faces && subdiv && offsets && (points || capacity == 0), "cloud_sample_emit: null pointer");
@@ -948,11 +949,11 @@ extern "C" int adamvs_knn_search(const double* origin, double R, int k, const lo
                                  const double* sorted, const int* pindex, long n, const long long* item_key, const long long* item_first,
                                  const int* item_count, long ni, long long row_base, long rows, float* d2, int* index, int* count,
                                  unsigned long long* pairs, void* stream) {
-  if (int rc = simplify_check_lattice(origin, R, "knn_search")) return rc;
+  if (int rc = check_lattice(origin, R, "knn_search")) return rc;
   if (int rc = knn_check_k(k, "knn_search")) return rc;
-  if (int rc = simplify_check_count(n, "n", "knn_search")) return rc;
-  if (int rc = simplify_check_count(ni, "ni", "knn_search")) return rc;
-  if (int rc = simplify_check_count(rows, "rows", "knn_search")) return rc;
+  if (int rc = check_count(n, "n", "knn_search")) return rc;
+  if (int rc = check_count(ni, "ni", "knn_search")) return rc;
+  if (int rc = check_count(rows, "rows", "knn_search")) return rc;
   ADAMVS_CHECK_ARG(nc >= 1 && nc <= n, "knn_search: nc=%d (1 .. n = %ld)", nc, n);
   ADAMVS_CHECK_ARG(ni <= n && rows <= n && row_base >= 0 && row_base <= n - rows, "knn_search: ni=%ld, rows=%ld from row_base=%lld (within n = %ld)",
                    ni, rows, row_base, n);
@@ -964,9 +965,9 @@ extern "C" int adamvs_knn_search(const double* origin, double R, int k, const lo
 
 extern "C" int adamvs_knn_search_host(const double* origin, double R, int k, const double* points, long n, float* d2, int* index, int* count,
                                       unsigned long long* pairs) {
-  if (int rc = simplify_check_lattice(origin, R, "knn_search_host")) return rc;
+  if (int rc = check_lattice(origin, R, "knn_search_host")) return rc;
   if (int rc = knn_check_k(k, "knn_search_host")) return rc;
-  if (int rc = simplify_check_count(n, "n", "knn_search_host")) return rc;
+  if (int rc = check_count(n, "n", "knn_search_host")) return rc;
   ADAMVS_CHECK_ARG(points && d2 && index && count, "knn_search_host: null pointer");
   return knn_search_host(origin, R, k, points, n, d2, index, count, pairs);
 }
@@ -974,8 +975,8 @@ extern "C" int adamvs_knn_search_host(const double* origin, double R, int k, con
 extern "C" int adamvs_knn_normals(const double* points, long n, const int* index, const int* count, int k, long rows, const int* row_point,
                                   double* normal, float* curvature, unsigned char* flag, void* stream) {
   if (int rc = knn_check_k(k, "knn_normals")) return rc;
-  if (int rc = simplify_check_count(n, "n", "knn_normals")) return rc;
-  if (int rc = simplify_check_count(rows, "rows", "knn_normals")) return rc;
+  if (int rc = check_count(n, "n", "knn_normals")) return rc;
+  if (int rc = check_count(rows, "rows", "knn_normals")) return rc;
   ADAMVS_CHECK_ARG(points && index && count && normal && curvature && flag, "knn_normals: null pointer");
   return launch_knn_normals(points, n, index, count, k, rows, row_point, normal, curvature, flag, (hipStream_t)stream);
 }
@@ -983,18 +984,13 @@ extern "C" int adamvs_knn_normals(const double* points, long n, const int* index
 extern "C" int adamvs_knn_normals_host(const double* points, long n, const int* index, const int* count, int k, long rows, const int* row_point,
                                        double* normal, float* curvature, unsigned char* flag) {
   if (int rc = knn_check_k(k, "knn_normals_host")) return rc;
-  if (int rc = simplify_check_count(n, "n", "knn_normals_host")) return rc;
-  if (int rc = simplify_check_count(rows, "rows", "knn_normals_host")) return rc;
+  if (int rc = check_count(n, "n", "knn_normals_host")) return rc;
+  if (int rc = check_count(rows, "rows", "knn_normals_host")) return rc;
   ADAMVS_CHECK_ARG(points && index && count && normal && curvature && flag, "knn_normals_host: null pointer");
   return knn_normals_host(points, n, index, count, k, rows, row_point, normal, curvature, flag);
 }
 
 // ---- cloud registration (cloud_register.hip): every argument is checked here, before any launch
-static int register_check_count(long n, const char* name, const char* what) {
-  ADAMVS_CHECK_ARG(n >= 0 && n <= SIMPLIFY_MAX, "%s: %s=%ld (0 .. 2^31 - 1)", what, name, n);
-  return 0;
-}
-
 static int register_check_motion(const double* R, const double* c, const double* u, const char* what) {
   ADAMVS_CHECK_ARG(R && c && u, "%s: null R, c or u", what);
   for (int k = 0; k < 9; ++k) ADAMVS_CHECK_ARG(std::isfinite(R[k]), "%s: R is not finite", what);
@@ -1011,14 +1007,14 @@ static int register_check_frame(const double* c, double L, double delta, const c
 
 extern "C" int adamvs_rigid_apply(const double* R, const double* c, const double* u, const double* x, long n, double* y, void* stream) {
   if (int rc = register_check_motion(R, c, u, "rigid_apply")) return rc;
-  if (int rc = register_check_count(n, "n", "rigid_apply")) return rc;
+  if (int rc = check_count(n, "n", "rigid_apply", 0)) return rc;
   ADAMVS_CHECK_ARG((x && y) || n == 0, "rigid_apply: null pointer");
   return launch_rigid_apply(R, c, u, x, n, y, (hipStream_t)stream);
 }
 
 extern "C" int adamvs_rigid_apply_host(const double* R, const double* c, const double* u, const double* x, long n, double* y) {
   if (int rc = register_check_motion(R, c, u, "rigid_apply_host")) return rc;
-  if (int rc = register_check_count(n, "n", "rigid_apply_host")) return rc;
+  if (int rc = check_count(n, "n", "rigid_apply_host", 0)) return rc;
   ADAMVS_CHECK_ARG((x && y) || n == 0, "rigid_apply_host: null pointer");
   return rigid_apply_host(R, c, u, x, n, y);
 }
@@ -1027,8 +1023,8 @@ extern "C" int adamvs_icp_accumulate(const double* y, const int* index, long nq,
                                      const unsigned char* flag, long nt, const double* c, double L, double delta, double* partial,
                                      void* stream) {
   if (int rc = register_check_frame(c, L, delta, "icp_accumulate")) return rc;
-  if (int rc = register_check_count(nq, "nq", "icp_accumulate")) return rc;
-  if (int rc = register_check_count(nt, "nt", "icp_accumulate")) return rc;
+  if (int rc = check_count(nq, "nq", "icp_accumulate", 0)) return rc;
+  if (int rc = check_count(nt, "nt", "icp_accumulate", 0)) return rc;
   ADAMVS_CHECK_ARG((y && index && partial) || nq == 0, "icp_accumulate: null pointer");
   ADAMVS_CHECK_ARG((targets && normals && flag) || nt == 0, "icp_accumulate: null pointer");
   return launch_icp_accumulate(y, index, nq, targets, normals, flag, nt, c, L, delta, partial, (hipStream_t)stream);
@@ -1037,21 +1033,21 @@ extern "C" int adamvs_icp_accumulate(const double* y, const int* index, long nq,
 extern "C" int adamvs_icp_accumulate_host(const double* y, const int* index, long nq, const double* targets, const double* normals,
                                           const unsigned char* flag, long nt, const double* c, double L, double delta, double* partial) {
   if (int rc = register_check_frame(c, L, delta, "icp_accumulate_host")) return rc;
-  if (int rc = register_check_count(nq, "nq", "icp_accumulate_host")) return rc;
-  if (int rc = register_check_count(nt, "nt", "icp_accumulate_host")) return rc;
+  if (int rc = check_count(nq, "nq", "icp_accumulate_host", 0)) return rc;
+  if (int rc = check_count(nt, "nt", "icp_accumulate_host", 0)) return rc;
   ADAMVS_CHECK_ARG((y && index && partial) || nq == 0, "icp_accumulate_host: null pointer");
   ADAMVS_CHECK_ARG((targets && normals && flag) || nt == 0, "icp_accumulate_host: null pointer");
   return icp_accumulate_host(y, index, nq, targets, normals, flag, nt, c, L, delta, partial);
 }
 
 extern "C" int adamvs_icp_reduce(const double* partial, long nb, double* sums, void* stream) {
-  if (int rc = register_check_count(nb, "nb", "icp_reduce")) return rc;
+  if (int rc = check_count(nb, "nb", "icp_reduce", 0)) return rc;
   ADAMVS_CHECK_ARG((partial || nb == 0) && sums, "icp_reduce: null pointer");
   return launch_icp_reduce(partial, nb, sums, (hipStream_t)stream);
 }
 
 extern "C" int adamvs_icp_reduce_host(const double* partial, long nb, double* sums) {
-  if (int rc = register_check_count(nb, "nb", "icp_reduce_host")) return rc;
+  if (int rc = check_count(nb, "nb", "icp_reduce_host", 0)) return rc;
   ADAMVS_CHECK_ARG((partial || nb == 0) && sums, "icp_reduce_host: null pointer");
   return icp_reduce_host(partial, nb, sums);
 }

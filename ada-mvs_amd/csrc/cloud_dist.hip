@@ -1,24 +1,20 @@
 // Cloud distance: the bounded nearest neighbour of every query among the targets, and a deterministic surface sampler, so that
 // clouds and meshes can be scored against a truth (include/adamvs_hip.h "Cloud distance" states every operation).  The caller
 // (ada-mvs_amd/accuracy.py) keys both clouds on the lattice of side c = D (adamvs_simplify_keys), sorts them stably, numbers the
-// occupied target cells (unique) and cuts the sorted queries into work items of one cell and at most 256 queries; cloud_lattice.h
-// holds the row search, the pair arithmetic and the keep rule (shared with cloud_knn.hip); here:
+// occupied target cells (unique) and cuts the sorted queries into work items of one cell and at most 256 queries
+// (ada-mvs_amd/cloud_lattice.py).  cloud_lattice.h holds the walk that cloud_knn.hip shares: the nine rows of a work item, the
+// candidate tiles in the LDS, the split of the lanes into slices, the pair arithmetic and the keep rule, and on the host the keyed,
+// sorted cloud and the candidates of a query; here:
 //
-//   k_cloud_nearest       one 256-lane workgroup per work item: nine lanes find the nine (dy, dz) rows of the 27 cells (two binary
-//                         searches each: with x in the low key bits the three x-neighbours are one run of the sorted targets),
-//                         the workgroup walks the nine runs packed into tiles of 256 candidates through the LDS; the lanes
-//                         split into slices of one lane per query, each slice sweeps its share of a tile with reads of one
-//                         address per slice and keeps (d2, index) under the lexicographic rule, and the slices meet in a tree
+//   k_cloud_nearest       one 256-lane workgroup per work item walks the item's candidates (CloudWalk) in tiles of 256; each slice
+//                         sweeps its share of a tile with reads of one address per slice and keeps (d2, index) under the
+//                         lexicographic rule, the slices meet in a tree, and the truncation at D closes
 //   k_cloud_sample_count  one lane per face: n = max(1, ceil(longest edge / s))
 //   k_cloud_sample_emit   one wave per face: the (n + 1)(n + 2) / 2 barycentric lattice points, i ascending, then j
 //
 // No atomics and no inter-workgroup waits: every lane writes its own element only, and the result of a query is a function of
 // the targets as a set, so the output is bit-identical from run to run and under any permutation of either cloud.
 #include <math.h>
-
-#include <algorithm>
-#include <numeric>
-#include <vector>
 
 #include "block_prims.h"
 #include "cloud_lattice.h"
@@ -37,9 +33,7 @@ __global__ __launch_bounds__(256) void k_cloud_nearest(const CloudLattice L, flo
                                                        const long long* __restrict__ item_key, const long long* __restrict__ item_first,
                                                        const int* __restrict__ item_count, float* __restrict__ d2, int* __restrict__ index,
                                                        unsigned long long* __restrict__ pairs) {
-  __shared__ __attribute__((aligned(16))) CloudEntry tile[CLOUD_TILE];
-  __shared__ long long row_start[9];
-  __shared__ int row_off[10], row_len[9];
+  __shared__ __attribute__((aligned(16))) CloudWalk<CLOUD_TILE> w;
   const int lane = threadIdx.x;
   const long item = blockIdx.x;
   const long long key = item_key[item];
@@ -48,32 +42,9 @@ __global__ __launch_bounds__(256) void k_cloud_nearest(const CloudLattice L, flo
   count = count < 0 ? 0 : (count > CLOUD_TILE ? CLOUD_TILE : count);
   double ctr[3];
   cloud_centre(L, key < 0 ? 0 : key, ctr);
-  if (lane < 9) {
-    int a, b;
-    cloud_row_range(ukeys, nc, key, lane % 3 - 1, lane / 3 - 1, &a, &b);
-    long long s = tstart[a], e = tstart[b];
-    s = s < 0 ? 0 : (s > nt ? nt : s);
-    e = e < s ? s : (e > nt ? nt : e);
-    row_start[lane] = s;
-    row_len[lane] = (int)(e - s);
-  }
-  __syncthreads();
-  if (lane == 0) {
-    int acc = 0;
-    for (int r = 0; r < 9; ++r) {
-      row_off[r] = acc;
-      const int len = row_len[r];
-      acc = len > 0x7fffffff - acc ? 0x7fffffff : acc + len;
-    }
-    row_off[9] = acc;
-  }
-  // The item's queries take P lanes, P the smallest power of two >= count, and the workgroup splits into S = 256 / P SLICES: lane l
-  // serves query l mod P and sweeps candidates slice, slice + S, .. of every tile.  A cell of a fused cloud holds ten queries, not
-  // 256: with one lane per query the other lanes would idle through the sweep.
-  int P = 1;
-  while (P < count) P <<= 1;
-  const int S = CLOUD_TILE / P;
-  const int ql = lane & (P - 1), slice = lane / P;
+  cloud_walk_rows(w, ukeys, tstart, nc, key, nt);
+  const CloudSlices sl = cloud_slices(count, CLOUD_TILE, lane);
+  const int P = sl.P, S = sl.S, ql = sl.ql, slice = sl.slice;
   const long long slot = first + ql;
   long long qi = -1;
   if (ql < count && slot >= 0 && slot < nqs) qi = qorder[slot];
@@ -86,39 +57,24 @@ __global__ __launch_bounds__(256) void k_cloud_nearest(const CloudLattice L, flo
   }
   float best = INFINITY;
   int best_idx = 0x7fffffff;
-  __syncthreads();
-  const int total = row_off[9];
+  const int total = cloud_walk_total(w);
   for (long long base = 0; base < total; base += CLOUD_TILE) {
-    const long long g = base + lane;
-    long long src = -1;
-#pragma unroll
-    for (int r = 0; r < 9; ++r) {
-      const int lo = row_off[r], hi = row_off[r + 1];
-      if (g >= lo && g < hi) src = row_start[r] + (g - lo);
-    }
-    CloudEntry e = {0.f, 0.f, 0.f, 0x7fffffff};
-    if (src >= 0 && src < nt) {
-      e.x = (float)(targets[3 * src] - ctr[0]);
-      e.y = (float)(targets[3 * src + 1] - ctr[1]);
-      e.z = (float)(targets[3 * src + 2] - ctr[2]);
-      e.idx = tindex[src];
-    }
-    tile[lane] = e;
+    cloud_walk_fill(w, base, targets, tindex, nt, ctr);
     __syncthreads();
     const int n = total - base < CLOUD_TILE ? (int)(total - base) : CLOUD_TILE;
 #pragma unroll 8
     for (int k = slice; k < n; k += S) {
-      const CloudEntry p = tile[k];
+      const CloudEntry p = w.tile[k];
       cloud_pair_update(qx, qy, qz, p.x, p.y, p.z, p.idx, best, best_idx);
     }
     __syncthreads();
   }
   // the S partial results of a query meet in a tree through the LDS (the tile is free after the last barrier); S is uniform
   for (int h = S >> 1; h >= 1; h >>= 1) {
-    tile[lane].x = best;
-    tile[lane].idx = best_idx;
+    w.tile[lane].x = best;
+    w.tile[lane].idx = best_idx;
     __syncthreads();
-    if (slice < h) cloud_keep(tile[lane + h * P].x, tile[lane + h * P].idx, best, best_idx);
+    if (slice < h) cloud_keep(w.tile[lane + h * P].x, w.tile[lane + h * P].idx, best, best_idx);
     __syncthreads();
   }
   if (live && slice == 0) {
@@ -213,39 +169,18 @@ int cloud_nearest_host(const double* origin, double D, const double* targets, lo
                        unsigned long long* pairs) {
   const CloudLattice L = cloud_lattice(origin, D);
   const float limit = (float)(D * D);
-  std::vector<long long> tkey(nt);
-  for (long i = 0; i < nt; ++i) {
-    int err;
-    tkey[i] = cloud_key_host(L, targets + 3 * i, &err);
-    if (err) return set_error(-1, "cloud_nearest_host: target %ld is %s", i, err == 1 ? "not finite" : "outside the lattice of 2^21 cells per axis");
-  }
-  std::vector<long> order(nt);
-  std::iota(order.begin(), order.end(), 0L);
-  std::stable_sort(order.begin(), order.end(), [&](long a, long b) { return tkey[a] < tkey[b]; });
-  std::vector<long long> ukeys, tstart;
-  for (long i = 0; i < nt; ++i)
-    if (i == 0 || tkey[order[i]] != tkey[order[i - 1]]) ukeys.push_back(tkey[order[i]]), tstart.push_back(i);
-  tstart.push_back(nt);
-  const int nc = (int)ukeys.size();
+  CloudCells cells;
+  if (int rc = cloud_cells_host(L, targets, nt, "cloud_nearest_host: target", cells)) return rc;
   unsigned long long evaluated = 0;
   for (long q = 0; q < nq; ++q) {
     int err;
-    const long long key = cloud_key_host(L, queries + 3 * q, &err);
+    const long long key = cloud_key(L, queries + 3 * q, &err);
     float best = INFINITY;
     int best_idx = 0x7fffffff;
-    if (!err) {
-      double ctr[3];
-      cloud_centre(L, key, ctr);
-      const float qx = (float)(queries[3 * q] - ctr[0]), qy = (float)(queries[3 * q + 1] - ctr[1]), qz = (float)(queries[3 * q + 2] - ctr[2]);
-      for (int r = 0; r < 9; ++r) {
-        int a, b;
-        cloud_row_range(ukeys.data(), nc, key, r % 3 - 1, r / 3 - 1, &a, &b);
-        for (long long s = tstart[a]; s < tstart[b]; ++s, ++evaluated) {
-          const double* p = targets + 3 * order[s];
-          cloud_pair_update(qx, qy, qz, (float)(p[0] - ctr[0]), (float)(p[1] - ctr[1]), (float)(p[2] - ctr[2]), (int)order[s], best, best_idx);
-        }
-      }
-    }
+    if (!err)
+      evaluated += cloud_visit_host(L, cells, targets, key, queries + 3 * q, [&](float qx, float qy, float qz, float px, float py, float pz, int idx) {
+        cloud_pair_update(qx, qy, qz, px, py, pz, idx, best, best_idx);
+      });
     cloud_truncate(limit, best, best_idx);
     d2[q] = best, index[q] = best_idx;
   }

@@ -2,10 +2,11 @@
 // that a fused cloud can be filtered before anything reads it (include/adamvs_hip.h "Cloud neighbourhoods" states every
 // operation).  The caller (ada-mvs_amd/cloud_filter.py) keys the cloud on the lattice of side c = R, sorts it stably, numbers the
 // occupied cells and cuts the sorted points into the work items of "Cloud distance" (one cell, at most 256 queries); the cloud
-// is both the targets and the queries.  cloud_lattice.h holds what the search shares with cloud_dist.hip; here:
+// is both the targets and the queries (ada-mvs_amd/cloud_lattice.py).  cloud_lattice.h holds the walk that cloud_dist.hip
+// shares: rows, candidate tiles, slices, pair arithmetic, and the host's keyed cloud and candidate visitor; here:
 //
-//   k_knn_search   one workgroup per work item, the walk of k_cloud_nearest: nine lanes find the nine rows, the candidates pass
-//                  through an LDS tile, the lanes form S slices of P queries.  Each lane keeps a partial list of its k best in LDS
+//   k_knn_search   one workgroup per work item walks the item's candidates (CloudWalk, the tile as wide as the workgroup), the
+//                  lanes in S slices of P queries.  Each lane keeps a partial list of its k best in LDS
 //                  columns (slot-major: the lanes of a wave hit different banks) and the list's worst (d2, index) in registers, so
 //                  that once the list is full most candidates cost one compare.  The S lists of a query meet in a tree under the
 //                  same total order; the result leaves ranked by counting.  One instantiation per class of k: k <= 8 and k <= 16
@@ -19,7 +20,6 @@
 #include <math.h>
 
 #include <algorithm>
-#include <numeric>
 #include <utility>
 #include <vector>
 
@@ -83,12 +83,10 @@ __global__ __launch_bounds__(LANES) void k_knn_search(const CloudLattice L, floa
                                                       const long long* __restrict__ item_first, const int* __restrict__ item_count,
                                                       long long row_base, long rows, float* __restrict__ d2, int* __restrict__ index,
                                                       int* __restrict__ count, unsigned long long* __restrict__ pairs) {
-  __shared__ __attribute__((aligned(16))) CloudEntry tile[LANES];
+  __shared__ __attribute__((aligned(16))) CloudWalk<LANES> w;
   __shared__ float list_d[KC][LANES];
   __shared__ int list_i[KC][LANES];
   __shared__ int fill[LANES];
-  __shared__ long long row_start[9];
-  __shared__ int row_off[10], row_len[9];
   const int lane = threadIdx.x;
   const long item = blockIdx.x;
   const long long key = item_key[item];
@@ -98,37 +96,15 @@ __global__ __launch_bounds__(LANES) void k_knn_search(const CloudLattice L, floa
   k = k < 1 ? 1 : (k > KC ? KC : k);
   double ctr[3];
   cloud_centre(L, key < 0 ? 0 : key, ctr);
-  if (lane < 9) {
-    int a, b;
-    cloud_row_range(ukeys, nc, key, lane % 3 - 1, lane / 3 - 1, &a, &b);
-    long long s = tstart[a], e = tstart[b];
-    s = s < 0 ? 0 : (s > n ? n : s);
-    e = e < s ? s : (e > n ? n : e);
-    row_start[lane] = s;
-    row_len[lane] = (int)(e - s);
-  }
-  __syncthreads();
-  if (lane == 0) {
-    int acc = 0;
-    for (int r = 0; r < 9; ++r) {
-      row_off[r] = acc;
-      const int len = row_len[r];
-      acc = len > 0x7fffffff - acc ? 0x7fffffff : acc + len;
-    }
-    row_off[9] = acc;
-  }
-  __syncthreads();
-  const int total = row_off[9];
+  cloud_walk_rows(w, ukeys, tstart, nc, key, n);
+  const int total = cloud_walk_total(w);
   KnnList<KC, LANES> list;
   list.d = list_d, list.i = list_i, list.lane = lane, list.k = k;
   // an item of more than LANES queries takes its queries LANES at a time (uniform: every lane walks the same passes)
   for (int q0 = 0; q0 < cnt_item; q0 += LANES) {
     const int cnt = cnt_item - q0 < LANES ? cnt_item - q0 : LANES;
-    // P lanes for the pass's queries, P the smallest power of two >= cnt, and S = LANES / P slices, as k_cloud_nearest
-    int P = 1;
-    while (P < cnt) P <<= 1;
-    const int S = LANES / P;
-    const int ql = lane & (P - 1), slice = lane / P;
+    const CloudSlices sl = cloud_slices(cnt, LANES, lane);
+    const int P = sl.P, S = sl.S, ql = sl.ql, slice = sl.slice;
     const long long slot = first + q0 + ql;
     const bool live = ql < cnt && slot >= 0 && slot < n;
     float qx = 0.f, qy = 0.f, qz = 0.f;
@@ -141,21 +117,7 @@ __global__ __launch_bounds__(LANES) void k_knn_search(const CloudLattice L, floa
     }
     list.reset();
     for (long long base = 0; base < total; base += LANES) {
-      const long long g = base + lane;
-      long long src = -1;
-#pragma unroll
-      for (int r = 0; r < 9; ++r) {
-        const int lo = row_off[r], hi = row_off[r + 1];
-        if (g >= lo && g < hi) src = row_start[r] + (g - lo);
-      }
-      CloudEntry e = {0.f, 0.f, 0.f, 0x7fffffff};
-      if (src >= 0 && src < n) {
-        e.x = (float)(sorted[3 * src] - ctr[0]);
-        e.y = (float)(sorted[3 * src + 1] - ctr[1]);
-        e.z = (float)(sorted[3 * src + 2] - ctr[2]);
-        e.idx = pindex[src];
-      }
-      tile[lane] = e;
+      cloud_walk_fill(w, base, sorted, pindex, n, ctr);
       __syncthreads();
       const int nn = total - base < LANES ? (int)(total - base) : LANES;
       // four candidates at a time: their reads and distances come first, straight-line, the rare entries into the list after them,
@@ -166,7 +128,7 @@ __global__ __launch_bounds__(LANES) void k_knn_search(const CloudLattice L, floa
 #pragma unroll
         for (int u = 0; u < KNN_BATCH; ++u) {
           const int cu = c + u * S;
-          const CloudEntry p = tile[cu < nn ? cu : c];
+          const CloudEntry p = w.tile[cu < nn ? cu : c];
           dd[u] = cu < nn ? cloud_pair_d2(qx, qy, qz, p.x, p.y, p.z) : INFINITY;
           id[u] = p.idx;
         }
@@ -315,36 +277,16 @@ int knn_search_host(const double* origin, double R, int k, const double* points,
                     unsigned long long* pairs) {
   const CloudLattice L = cloud_lattice(origin, R);
   const float limit = (float)(R * R);
-  std::vector<long long> pkey(n);
-  for (long i = 0; i < n; ++i) {
-    int err;
-    pkey[i] = cloud_key_host(L, points + 3 * i, &err);
-    if (err) return set_error(-1, "knn_search_host: point %ld is %s", i, err == 1 ? "not finite" : "outside the lattice of 2^21 cells per axis");
-  }
-  std::vector<long> order(n);
-  std::iota(order.begin(), order.end(), 0L);
-  std::stable_sort(order.begin(), order.end(), [&](long a, long b) { return pkey[a] < pkey[b]; });
-  std::vector<long long> ukeys, tstart;
-  for (long i = 0; i < n; ++i)
-    if (i == 0 || pkey[order[i]] != pkey[order[i - 1]]) ukeys.push_back(pkey[order[i]]), tstart.push_back(i);
-  tstart.push_back(n);
-  const int nc = (int)ukeys.size();
+  CloudCells cells;
+  if (int rc = cloud_cells_host(L, points, n, "knn_search_host: point", cells)) return rc;
   unsigned long long evaluated = 0;
   std::vector<std::pair<float, int>> found;
   for (long q = 0; q < n; ++q) {
-    double ctr[3];
-    cloud_centre(L, pkey[q], ctr);
-    const float qx = (float)(points[3 * q] - ctr[0]), qy = (float)(points[3 * q + 1] - ctr[1]), qz = (float)(points[3 * q + 2] - ctr[2]);
     found.clear();
-    for (int r = 0; r < 9; ++r) {
-      int a, b;
-      cloud_row_range(ukeys.data(), nc, pkey[q], r % 3 - 1, r / 3 - 1, &a, &b);
-      for (long long s = tstart[a]; s < tstart[b]; ++s, ++evaluated) {
-        const double* p = points + 3 * order[s];
-        const float dd = cloud_pair_d2(qx, qy, qz, (float)(p[0] - ctr[0]), (float)(p[1] - ctr[1]), (float)(p[2] - ctr[2]));
-        if (knn_accept(dd, (int)order[s], limit, (int)q, 0, 1, INFINITY, 0x7fffffff)) found.emplace_back(dd, (int)order[s]);
-      }
-    }
+    evaluated += cloud_visit_host(L, cells, points, cells.key[q], points + 3 * q, [&](float qx, float qy, float qz, float px, float py, float pz, int idx) {
+      const float dd = cloud_pair_d2(qx, qy, qz, px, py, pz);
+      if (knn_accept(dd, idx, limit, (int)q, 0, 1, INFINITY, 0x7fffffff)) found.emplace_back(dd, idx);
+    });
     std::sort(found.begin(), found.end(), [](const std::pair<float, int>& a, const std::pair<float, int>& b) {
       return knn_before(a.first, a.second, b.first, b.second);
     });

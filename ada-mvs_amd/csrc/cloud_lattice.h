@@ -1,9 +1,16 @@
-// The lattice search that cloud_dist.hip (the nearest target of every query) and cloud_knn.hip (the k nearest neighbours of every
-// point) share: cell centres, the nine-row search in the sorted unique keys, the pair arithmetic in fp32 and the lexicographic
-// keep rule (include/adamvs_hip.h "Cloud distance", steps 1 to 4).  Inline and __host__ __device__: the kernels and their host
-// twins run the same functions.
+// The lattice of cubic cells under the 63-bit keys of adamvs_simplify_keys, and the one walk of it that every search runs:
+// the key of a point (mesh_simplify.hip's k_simplify_keys is this function per vertex), cell centres, the nine-row search in
+// the sorted unique keys, the pair arithmetic in fp32 and the lexicographic keep rule (include/adamvs_hip.h "Cloud distance",
+// steps 1 to 4).  On the device the walk is CloudWalk: the rows of a work item, the candidate tiles in the LDS and the split of
+// the lanes into slices (cloud_dist.hip sweeps the tiles for the nearest target, cloud_knn.hip for the k nearest).  On the
+// host it is CloudCells (the keyed, sorted cloud) and cloud_visit_host (the candidates of one query).  Inline and
+// __host__ __device__ wherever both sides compute: the kernels and their host twins run the same functions.
 #pragma once
 #include <math.h>
+
+#include <algorithm>
+#include <numeric>
+#include <vector>
 
 #include "common.h"
 #include "kernels.h"
@@ -21,7 +28,30 @@ struct CloudLattice {
   double o[3], c;
 };
 
-// key (>= 0) -> the centre of its cell, as mesh_simplify.hip's cell_centre
+static inline CloudLattice cloud_lattice(const double* origin, double cell) {
+  CloudLattice L;
+  for (int i = 0; i < 3; ++i) L.o[i] = origin[i];
+  L.c = cell;
+  return L;
+}
+
+// Step 1 of "Mesh simplification": the key of the point p, or -1 with *err = 1 (a coordinate is NaN or infinite) or 2 (outside
+// the lattice); the first axis at fault names the error.
+__host__ __device__ __forceinline__ long long cloud_key(const CloudLattice& L, const double* p, int* err) {
+  long long key = 0;
+  int e = 0;
+  for (int ax = 0; ax < 3; ++ax) {
+    const double x = p[ax];
+    const double t = (x - L.o[ax]) / L.c;
+    if (!(fabs(x) <= 1.7976931348623157e308)) e = e ? e : 1;
+    else if (!(t >= 0.0 && t < (double)(1 << CKEY_BITS))) e = e ? e : 2;
+    else key |= (long long)floor(t) << (ax * CKEY_BITS);
+  }
+  *err = e;
+  return e ? -1 : key;
+}
+
+// key (>= 0) -> the centre of its cell
 __host__ __device__ __forceinline__ void cloud_centre(const CloudLattice& L, long long key, double* ctr) {
   ctr[0] = L.o[0] + ((double)(key & CKEY_MASK) + 0.5) * L.c;
   ctr[1] = L.o[1] + ((double)((key >> CKEY_BITS) & CKEY_MASK) + 0.5) * L.c;
@@ -79,31 +109,134 @@ __host__ __device__ __forceinline__ void cloud_truncate(float limit, float& best
   if (!(best <= limit)) best = INFINITY, best_idx = -1;
 }
 
+// ---- the walk on the device: one workgroup of LANES lanes per work item (one cell, at most CLOUD_TILE queries) -------------------
 struct CloudEntry {      // one candidate in the LDS: 16 bytes, read as one ds_read_b128 at an address a slice's lanes share
   float x, y, z;
   int idx;
 };
 
-static inline CloudLattice cloud_lattice(const double* origin, double cell) {
-  CloudLattice L;
-  for (int i = 0; i < 3; ++i) L.o[i] = origin[i];
-  L.c = cell;
-  return L;
+template <int LANES>
+struct CloudWalk {       // a __shared__ variable of the kernel
+  __attribute__((aligned(16))) CloudEntry tile[LANES];
+  long long row_start[9];
+  int row_off[10], row_len[9];
+};
+
+// Nine lanes find the nine (dy, dz) rows of the 27 cells around `key` (two binary searches each: with x in the low key bits the
+// three x-neighbours are one run of the n sorted points), clamped to [0, n]; after a barrier lane 0 packs the runs end to end
+// (row_off, saturating).  Every lane of the workgroup calls this, then cloud_walk_total.
+template <int LANES>
+__device__ __forceinline__ void cloud_walk_rows(CloudWalk<LANES>& w, const long long* __restrict__ ukeys, const long long* __restrict__ tstart,
+                                                int nc, long long key, long n) {
+  const int lane = threadIdx.x;
+  if (lane < 9) {
+    int a, b;
+    cloud_row_range(ukeys, nc, key, lane % 3 - 1, lane / 3 - 1, &a, &b);
+    long long s = tstart[a], e = tstart[b];
+    s = s < 0 ? 0 : (s > n ? n : s);
+    e = e < s ? s : (e > n ? n : e);
+    w.row_start[lane] = s;
+    w.row_len[lane] = (int)(e - s);
+  }
+  __syncthreads();
+  if (lane == 0) {
+    int acc = 0;
+    for (int r = 0; r < 9; ++r) {
+      w.row_off[r] = acc;
+      const int len = w.row_len[r];
+      acc = len > 0x7fffffff - acc ? 0x7fffffff : acc + len;
+    }
+    w.row_off[9] = acc;
+  }
 }
 
+// The barrier that publishes cloud_walk_rows' packing -> the item's candidates.  Apart from the rows so that a kernel can set up
+// its queries while lane 0 packs.
+template <int LANES>
+__device__ __forceinline__ int cloud_walk_total(const CloudWalk<LANES>& w) {
+  __syncthreads();
+  return w.row_off[9];
+}
 
-// key of step 1 of "Mesh simplification" (k_simplify_keys' arithmetic), -1 for a point that is not finite or outside the lattice
-static inline long long cloud_key_host(const CloudLattice& L, const double* p, int* err) {
-  long long key = 0;
-  *err = 0;
-  for (int ax = 0; ax < 3; ++ax) {
-    const double x = p[ax];
-    const double t = (x - L.o[ax]) / L.c;
-    if (!(fabs(x) <= 1.7976931348623157e308)) *err = *err ? *err : 1;
-    else if (!(t >= 0.0 && t < (double)(1 << CKEY_BITS))) *err = *err ? *err : 2;
-    else key |= (long long)floor(t) << (ax * CKEY_BITS);
+// Candidate base + lane of the packed runs into the tile: centre-relative fp32 and its number in the caller's order; past the
+// last candidate a padding entry.  The caller's barrier follows.
+template <int LANES>
+__device__ __forceinline__ void cloud_walk_fill(CloudWalk<LANES>& w, long long base, const double* __restrict__ points,
+                                                const int* __restrict__ pindex, long n, const double* ctr) {
+  const int lane = threadIdx.x;
+  const long long g = base + lane;
+  long long src = -1;
+#pragma unroll
+  for (int r = 0; r < 9; ++r) {
+    const int lo = w.row_off[r], hi = w.row_off[r + 1];
+    if (g >= lo && g < hi) src = w.row_start[r] + (g - lo);
   }
-  return *err ? -1 : key;
+  CloudEntry e = {0.f, 0.f, 0.f, 0x7fffffff};
+  if (src >= 0 && src < n) {
+    e.x = (float)(points[3 * src] - ctr[0]);
+    e.y = (float)(points[3 * src + 1] - ctr[1]);
+    e.z = (float)(points[3 * src + 2] - ctr[2]);
+    e.idx = pindex[src];
+  }
+  w.tile[lane] = e;
+}
+
+// `count` queries take P lanes, P the smallest power of two >= count, and the LANES lanes split into S = LANES / P SLICES: lane l
+// serves query ql = l mod P and sweeps candidates slice, slice + S, .. of every tile.  A cell of a fused cloud holds ten queries,
+// not 256: with one lane per query the other lanes would idle through the sweep.  P and S are uniform over the workgroup.
+struct CloudSlices {
+  int P, S, ql, slice;
+};
+
+__device__ __forceinline__ CloudSlices cloud_slices(int count, int lanes, int lane) {
+  int P = 1;
+  while (P < count) P <<= 1;
+  return {P, lanes / P, lane & (P - 1), lane / P};
+}
+
+// ---- the walk on the host --------------------------------------------------------------------------------------------------------
+struct CloudCells {      // a cloud keyed and sorted stably: point order[s] is at position s, cell ukeys[j] is positions tstart[j] .. tstart[j + 1]
+  std::vector<long long> key, ukeys, tstart;
+  std::vector<long> order;
+};
+
+// Fills `cells` from points [n][3]; a point that is not finite or outside the lattice is refused as "<what> <i> is ..." (what:
+// the caller's name and noun, "cloud_nearest_host: target").
+static inline int cloud_cells_host(const CloudLattice& L, const double* points, long n, const char* what, CloudCells& cells) {
+  cells.key.resize(n);
+  for (long i = 0; i < n; ++i) {
+    int err;
+    cells.key[i] = cloud_key(L, points + 3 * i, &err);
+    if (err) return set_error(-1, "%s %ld is %s", what, i, err == 1 ? "not finite" : "outside the lattice of 2^21 cells per axis");
+  }
+  const std::vector<long long>& key = cells.key;
+  cells.order.resize(n);
+  std::iota(cells.order.begin(), cells.order.end(), 0L);
+  std::stable_sort(cells.order.begin(), cells.order.end(), [&](long a, long b) { return key[a] < key[b]; });
+  for (long i = 0; i < n; ++i)
+    if (i == 0 || key[cells.order[i]] != key[cells.order[i - 1]]) cells.ukeys.push_back(key[cells.order[i]]), cells.tstart.push_back(i);
+  cells.tstart.push_back(n);
+  return 0;
+}
+
+// The candidates of the query q (in the cell `key` >= 0) among `points`, the cloud of `cells`: the nine rows in order, every
+// candidate as visit(qx, qy, qz, px, py, pz, its number), centre-relative fp32 -> the pairs evaluated.
+template <class Visit>
+static inline unsigned long long cloud_visit_host(const CloudLattice& L, const CloudCells& cells, const double* points, long long key,
+                                                  const double* q, Visit&& visit) {
+  double ctr[3];
+  cloud_centre(L, key, ctr);
+  const float qx = (float)(q[0] - ctr[0]), qy = (float)(q[1] - ctr[1]), qz = (float)(q[2] - ctr[2]);
+  unsigned long long evaluated = 0;
+  for (int r = 0; r < 9; ++r) {
+    int a, b;
+    cloud_row_range(cells.ukeys.data(), (int)cells.ukeys.size(), key, r % 3 - 1, r / 3 - 1, &a, &b);
+    for (long long s = cells.tstart[a]; s < cells.tstart[b]; ++s, ++evaluated) {
+      const double* p = points + 3 * cells.order[s];
+      visit(qx, qy, qz, (float)(p[0] - ctr[0]), (float)(p[1] - ctr[1]), (float)(p[2] - ctr[2]), (int)cells.order[s]);
+    }
+  }
+  return evaluated;
 }
 
 }  // namespace adamvs

@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "block_prims.h"
+#include "cloud_lattice.h"
 #include "common.h"
 #include "jacobi.h"
 #include "kernels.h"
@@ -30,33 +31,12 @@
 
 namespace adamvs {
 
-constexpr int KEY_BITS = ADAMVS_SIMPLIFY_KEY_BITS;
-
-struct Lattice {
-  double o[3], c;
-};
-
-__device__ __forceinline__ void cell_centre(const Lattice& L, long long key, double* ctr) {
-  const long long mask = (1LL << KEY_BITS) - 1;
-  ctr[0] = L.o[0] + ((double)(key & mask) + 0.5) * L.c;
-  ctr[1] = L.o[1] + ((double)((key >> KEY_BITS) & mask) + 0.5) * L.c;
-  ctr[2] = L.o[2] + ((double)(key >> (2 * KEY_BITS)) + 0.5) * L.c;
-}
-
-__global__ __launch_bounds__(256) void k_simplify_keys(const Lattice L, const double* __restrict__ xyz, long nv, long long* __restrict__ keys,
+__global__ __launch_bounds__(256) void k_simplify_keys(const CloudLattice L, const double* __restrict__ xyz, long nv, long long* __restrict__ keys,
                                                        uint8_t* __restrict__ bad) {
   const long v = (long)blockIdx.x * SIMPLIFY_TILE + threadIdx.x;
   if (v >= nv) return;
-  long long key = 0;
-  int err = 0;
-  for (int ax = 0; ax < 3; ++ax) {
-    const double x = xyz[3 * v + ax];
-    const double t = (x - L.o[ax]) / L.c;
-    if (!(fabs(x) <= 1.7976931348623157e308)) err = err ? err : 1;                  // NaN or infinite
-    else if (!(t >= 0.0 && t < (double)(1 << KEY_BITS))) err = err ? err : 2;       // outside the lattice
-    else key |= (long long)floor(t) << (ax * KEY_BITS);
-  }
-  keys[v] = err ? -1 : key;
+  int err;
+  keys[v] = cloud_key(L, xyz + 3 * v, &err);
   bad[v] = (uint8_t)err;
 }
 
@@ -75,7 +55,7 @@ __global__ __launch_bounds__(256) void k_simplify_corners(const unsigned* __rest
   survive[f] = (uint8_t)(ok && c0 != c1 && c1 != c2 && c0 != c2);
 }
 
-__global__ __launch_bounds__(256) void k_simplify_accumulate(const Lattice L, const long long* __restrict__ keys, int nc,
+__global__ __launch_bounds__(256) void k_simplify_accumulate(const CloudLattice L, const long long* __restrict__ keys, int nc,
                                                              const double* __restrict__ xyz, const uint8_t* __restrict__ rgb, long nv,
                                                              const unsigned* __restrict__ faces, long nf,
                                                              const long long* __restrict__ entry, const long long* __restrict__ fstart,
@@ -86,7 +66,7 @@ __global__ __launch_bounds__(256) void k_simplify_accumulate(const Lattice L, co
   const int j = __builtin_amdgcn_readfirstlane(blockIdx.x * (SIMPLIFY_TILE / 64) + (threadIdx.x >> 6));     // the wave's cell
   if (j >= nc) return;
   double ctr[3];
-  cell_centre(L, keys[j], ctr);
+  cloud_centre(L, keys[j], ctr);
   // the quadric: faces e0 .. e1 of the sorted (cell, face) entries
   const long long e0 = fstart[j], e1 = fstart[j + 1];
   double q[10] = {0., 0., 0., 0., 0., 0., 0., 0., 0., 0.};
@@ -169,7 +149,7 @@ __host__ __device__ __forceinline__ void simplify_solve_cell(const double* q, co
   *fallback_out = fb ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void k_simplify_solve(const Lattice L, double rank_eps, const long long* __restrict__ keys, int nc,
+__global__ __launch_bounds__(256) void k_simplify_solve(const CloudLattice L, double rank_eps, const long long* __restrict__ keys, int nc,
                                                         const double* __restrict__ quadric, const double* __restrict__ member,
                                                         const unsigned long long* __restrict__ colour,
                                                         const long long* __restrict__ vstart, double* __restrict__ pos,
@@ -187,7 +167,7 @@ __global__ __launch_bounds__(256) void k_simplify_solve(const Lattice L, double 
   int rk, fb;
   double err;
   simplify_solve_cell(q, m, L.c / 2.0, rank_eps, p, &rk, &fb, &err);
-  cell_centre(L, keys[j], ctr);
+  cloud_centre(L, keys[j], ctr);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     pos[3 * (size_t)j + k] = ctr[k] + p[k];
@@ -277,15 +257,8 @@ __global__ __launch_bounds__(256) void k_simplify_emit_faces(const int* __restri
 }
 
 // ---- launches -----------------------------------------------------------------------------------------------------------
-static Lattice lattice(const double* origin, double cell) {
-  Lattice L;
-  for (int i = 0; i < 3; ++i) L.o[i] = origin[i];
-  L.c = cell;
-  return L;
-}
-
 int launch_simplify_keys(const double* origin, double cell, const double* xyz, long nv, long long* keys, uint8_t* bad, hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_keys, dim3(tiles256(nv)), dim3(SIMPLIFY_TILE), 0, st, lattice(origin, cell), xyz, nv, keys, bad);
+  hipLaunchKernelGGL(k_simplify_keys, dim3(tiles256(nv)), dim3(SIMPLIFY_TILE), 0, st, cloud_lattice(origin, cell), xyz, nv, keys, bad);
   ADAMVS_CHECK_LAUNCH("simplify_keys");
   return 0;
 }
@@ -301,7 +274,7 @@ int launch_simplify_accumulate(const double* origin, double cell, const long lon
                                long nv, const unsigned* faces, long nf, const long long* entry, const long long* fstart,
                                const long long* vorder, const long long* vstart, double* quadric, double* member,
                                unsigned long long* colour, hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_accumulate, dim3(tiles256((long)nc * 64)), dim3(SIMPLIFY_TILE), 0, st, lattice(origin, cell), keys, nc, xyz, rgb,
+  hipLaunchKernelGGL(k_simplify_accumulate, dim3(tiles256((long)nc * 64)), dim3(SIMPLIFY_TILE), 0, st, cloud_lattice(origin, cell), keys, nc, xyz, rgb,
                      nv, faces, nf, entry, fstart, vorder, vstart, quadric, member, colour);
   ADAMVS_CHECK_LAUNCH("simplify_accumulate");
   return 0;
@@ -310,7 +283,7 @@ int launch_simplify_accumulate(const double* origin, double cell, const long lon
 int launch_simplify_solve(const double* origin, double cell, double rank_eps, const long long* keys, int nc, const double* quadric,
                           const double* member, const unsigned long long* colour, const long long* vstart, double* pos, uint8_t* col,
                           uint8_t* rank, uint8_t* fallback, double* error, hipStream_t st) {
-  hipLaunchKernelGGL(k_simplify_solve, dim3(tiles256(nc)), dim3(SIMPLIFY_TILE), 0, st, lattice(origin, cell), rank_eps, keys, nc, quadric,
+  hipLaunchKernelGGL(k_simplify_solve, dim3(tiles256(nc)), dim3(SIMPLIFY_TILE), 0, st, cloud_lattice(origin, cell), rank_eps, keys, nc, quadric,
                      member, colour, vstart, pos, col, rank, fallback, error);
   ADAMVS_CHECK_LAUNCH("simplify_solve");
   return 0;

@@ -140,8 +140,8 @@ class _Device:
 
     def __init__(self, source, target, D, huber, normal_radius, k, timing):
         import torch
-        from . import _lib, accuracy, cloud_filter, hip_ops
-        self.source, self.target = accuracy._cloud(source, "source"), accuracy._cloud(target, "target")
+        from . import _lib, cloud_filter, cloud_lattice
+        self.source, self.target = cloud_lattice.cloud(source, "source"), cloud_lattice.cloud(target, "target")
         self.nq, self.nt, self.D, self.delta, self.timing = int(self.source.shape[0]), int(self.target.shape[0]), float(D), float(huber or 0.0), timing
         self.search_pairs = torch.zeros((), device=self.target.device, dtype=torch.int64)
         if self.nq == 0 or self.nt == 0:
@@ -154,11 +154,8 @@ class _Device:
         d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
         self.rho = math.sqrt(float(torch.where(torch.isfinite(d2), d2, torch.zeros_like(d2)).max()))
         self.normal, _, self.flag, _ = cloud_filter.normals(self.target, float(normal_radius or D), k)
-        self.origin = accuracy.default_lattice_origin(self.D, tmin)
-        tkeys, bad = hip_ops.simplify_keys(self.target, self.D, self.origin)
-        if int(bad.max()):
-            raise _lib.AdaMVSHipError("register: %d targets lie outside the lattice of 2^21 cells per axis (cell %g)" % (int((bad != 0).sum()), self.D))
-        self.ukeys, self.tstart, self.sorted, self.tindex = accuracy.sort_targets(self.target, tkeys)
+        self.origin = cloud_lattice.default_origin(self.D, tmin)
+        self.cells = cloud_lattice.Cells(self.target, cloud_lattice.keyed(self.target, self.D, self.origin, "register", "targets"))
 
     def move(self, x, R, t):
         from . import hip_ops
@@ -166,7 +163,7 @@ class _Device:
 
     def evaluate(self, R, t, detail):
         import torch
-        from . import accuracy, hip_ops, mesh_stage
+        from . import cloud_lattice, hip_ops, mesh_stage
         clock = mesh_stage.StageClock(self.timing)
         clock.stage("move")
         Y = self.move(self.source, R, t)
@@ -175,11 +172,12 @@ class _Device:
         clock.stage("sort")
         qs = torch.sort(qkeys, stable=True)
         clock.stage("items")
-        _, qorder, items = accuracy.work_items(qs)
+        _, qorder, items = cloud_lattice.work_items(qs.values, qs.indices)
         clock.stage("nearest")
         index = torch.full((self.nq,), -1, device=Y.device, dtype=torch.int32)
         if items is not None:
-            _, index, pairs = hip_ops.cloud_nearest(self.origin, self.D, self.ukeys, self.tstart, self.sorted, self.tindex, Y, qorder, *items)
+            t = self.cells
+            _, index, pairs = hip_ops.cloud_nearest(self.origin, self.D, t.ukeys, t.tstart, t.sorted, t.index, Y, qorder, *items)
             self.search_pairs = self.search_pairs + pairs.sum()
         clock.stage("accumulate")
         partial = hip_ops.icp_accumulate(Y, index, self.target, self.normal, self.flag, self.c, self.L, self.delta)
@@ -295,8 +293,8 @@ def icp_host(source, target, D, init=None, max_iter=DEFAULT_MAX_ITER, tol=None, 
 
 def transform(points, R, t, pivot):
     """points [n, 3] float64 device tensor -> R (points - pivot) + pivot + t (adamvs_rigid_apply)."""
-    from . import accuracy, hip_ops
-    return hip_ops.rigid_apply(accuracy._cloud(points, "points"), R, pivot, t)
+    from . import cloud_lattice, hip_ops
+    return hip_ops.rigid_apply(cloud_lattice.cloud(points, "points"), R, pivot, t)
 
 
 def output_paths(out):

@@ -8,8 +8,8 @@ import numpy as np
 import accuracy_inputs as I
 import filter_ref as F
 
-HAND_KS = (1, 8, 32)
-TIE_CENTRES = {1: (200.5, 30.5, 10.5), 8: (220.5, 30.5, 10.5), 32: (240.5, 30.5, 10.5)}
+HAND_KS = (1, 8, 9, 16, 32)      # 9 and 16 take the kernel's form for k <= 16, 9 with a list that is not full width
+TIE_CENTRES = {1: (200.5, 30.5, 10.5), 8: (220.5, 30.5, 10.5), 32: (240.5, 30.5, 10.5), 9: (260.5, 30.5, 10.5), 16: (280.5, 30.5, 10.5)}
 TIE_PAIR = ((0.75, 0.0, 0.0), (-0.75, 0.0, 0.0))            # the k-th and the (k + 1)-th candidate: both at d2 = 0.5625
 
 
