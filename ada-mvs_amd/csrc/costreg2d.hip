@@ -1497,7 +1497,8 @@ __global__ __launch_bounds__(256) void k_softmax_regress(const float* __restrict
 // ---------------------------------------------------------------------------
 // Layer plan.  Packed weights: 11 layers x (9*D*D fragment floats + D bias floats), in the order
 // conv0..conv6, conv7, conv9, conv11, prob; fp32 with D in {64, 128, 192, 256}: followed by the five stride-1 layers
-// (conv0, conv2, conv4, conv6, prob) in the F(2x2, 3x3) form, 16*D*D floats each (costreg2d_wino.hip).
+// (conv0, conv2, conv4, conv6, prob) in the F(2x2, 3x3) form, 16*D*D floats each (costreg2d_wino.hip); D >= 128: then conv0 and
+// prob in the F(2x4, 3x3) form, 24*D*D floats each (costreg2d_wino24.hip).
 // Workspace: 3 * N*h*w*D floats.
 // sm_vw != null: the `prob` layer reduces its scores over D in its epilogue (costreg_softmax.h) and writes the view
 // weights / pair depths of softmax_max_regress directly (score is not written); the caller skips launch_softmax_regress.
@@ -1509,6 +1510,16 @@ bool cost_reg_softmax_fusable(int D, int precision, const PlaneSrc& planes) {
 // option winograd = 0: the stride-1 layers on the direct kernel, as in rounds 1-2 (A/B)
 bool cost_reg_winograd(int D, int precision) {
   return opt(OPT_WINOGRAD) != 0 && precision == PRECISION_FP32 && wino_depth_supported(D);
+}
+
+// conv0 and prob -- the two stride-1 layers on the full-size map, 24 % of cfg2's step -- in the F(2x4, 3x3) form: 24 MFMAs where
+// F(2x2, 3x3) issues 32.  Not at D = 64 (the blob carries no such blocks there) and only where its 64-pixel blocks fit the width:
+// 256 maps at D = 192, 96 x 192: 10.92 against 11.73 ms; 48 x 96 (two blocks for 96 columns): 3.35 against 2.89.
+// Option winograd + 2: never (the maps of before, bit for bit).
+bool wino24_depth_supported(int D) { return wino_depth_supported(D) && D >= 128; }
+bool cost_reg_wino24(int D, int h, int w) {
+  (void)h;
+  return !(opt(OPT_WINOGRAD) & 2) && wino24_depth_supported(D) && w >= 128 && cdiv(w, 64) * 64 * 8 <= w * 9;
 }
 
 int launch_cost_reg_net_2d(const float* x, const float* wpk, float* ws, float* score, int N, int D, int h, int w,
@@ -1568,12 +1579,15 @@ int launch_cost_reg_net_2d(const float* x, const float* wpk, float* ws, float* s
       // a pixel are different workgroups there, so the softmax behind the last layer is every lane's partial + a merge kernel
       // (uniform planes: stage 1); with per-pixel planes, or ADAMVS_WINO_SOFTMAX=0, the scores go through the score volume to
       // k_softmax_regress
-      const float* ww = wpk + (size_t)11 * LW + (size_t)(i == 10 ? 4 : i / 2) * 16 * D * D;
+      const bool w24 = (i == 0 || i == 10) && cost_reg_wino24(D, h, w);
+      const float* ww = w24 ? wpk + (size_t)11 * LW + (size_t)5 * 16 * D * D + (size_t)(i == 10) * 24 * D * D
+                            : wpk + (size_t)11 * LW + (size_t)(i == 10 ? 4 : i / 2) * 16 * D * D;
       if (i == 10 && fuse_softmax && wino_softmax_fused() && sm_planes->mode == PLANES_UNIFORM && (n_planes > 0 ? n_planes : D) > 1) {
         // every lane's softmax partial instead of the scores (D bytes per pixel instead of 4 D), in the score volume's place
-        rc = launch_conv_wino_softmax(plan[i].in, ww, wl + (size_t)9 * D * D, score, *sm_planes, sm_vw, sm_pd, N, sm_B, D, n_planes, h, w, st);
+        rc = (w24 ? launch_conv_wino24_softmax : launch_conv_wino_softmax)(plan[i].in, ww, wl + (size_t)9 * D * D, score, *sm_planes, sm_vw, sm_pd, N,
+                                                                           sm_B, D, n_planes, h, w, st);
       } else {
-        rc = launch_conv_wino(plan[i].in, ww, wl + (size_t)9 * D * D, nullptr, plan[i].out, N, D, plan[i].hi, plan[i].wi, plan[i].relu, st);
+        rc = (w24 ? launch_conv_wino24 : launch_conv_wino)(plan[i].in, ww, wl + (size_t)9 * D * D, nullptr, plan[i].out, N, D, plan[i].hi, plan[i].wi, plan[i].relu, st);
         if (!rc && i == 10 && fuse_softmax) rc = launch_softmax_regress(score, *sm_planes, sm_vw, sm_pd, N / sm_B, sm_B, D, h, w, st, n_planes);
       }
     } else {
@@ -1638,7 +1652,8 @@ extern "C" int adamvs_cost_reg_width(int D, int precision) {
 
 size_t adamvs::cost_reg_weight_floats(int D, int precision) {
   if (!(precision == PRECISION_BF16X3 ? costreg_bf16x3_depth_supported(D) : costreg_depth_supported(D))) return 0;
-  return (size_t)11 * ((size_t)9 * D * D + D) + (precision == PRECISION_FP32 && wino_depth_supported(D) ? (size_t)5 * 16 * D * D : 0);
+  return (size_t)11 * ((size_t)9 * D * D + D) + (precision == PRECISION_FP32 && wino_depth_supported(D) ? (size_t)5 * 16 * D * D : 0) +
+         (precision == PRECISION_FP32 && wino24_depth_supported(D) ? (size_t)2 * 24 * D * D : 0);
 }
 extern "C" size_t adamvs_cost_reg_net_2d_weight_floats(int D, int precision) { return cost_reg_weight_floats(D, precision); }
 

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "costreg_wino.h"
 #include "kernels.h"
 #include "persistent.h"
 #include "planes.h"
@@ -38,21 +39,7 @@
 
 namespace adamvs {
 
-struct WinoArgs {
-  const float* in;     // [N][h*w][D]
-  const float* wpk;    // [D/4][4][D/16][64][4]: k-step, patch row i, channel tile, lane (A-fragment order), patch column j
-  const float* bias;   // [D]
-  const float* skip;   // [N][h*w][D] or null; added after the ReLU
-  float* out;          // [N][h*w][D]
-  int D, h, w, relu;
-  // SM kernels (the `prob` layer under adamvs_depth_stage_forward): no `out`; every lane reduces the 16 scores it holds of a
-  // pixel to (max, sum of exp, sum of exp * plane) and stores that partial, [N][h*w][D/16][4]; k_softmax_merge finishes
-  float* sm_part;
-  PlaneSrc sm_planes;
-  int sm_B, sm_D;      // image n belongs to tile n % sm_B; sm_D hypothesis planes (<= D: pad channels score -1e30)
-};
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+// WinoArgs (costreg_wino.h); wpk: [D/4][4][D/16][64][4]: k-step, patch row i, channel tile, lane (A-fragment order), patch column j
 
 template <int MT, int NT>
 struct WinoGeom {
@@ -80,6 +67,7 @@ struct WinoGeom {
 template <int MT, int NT, int WPS, bool SM>
 __global__ __launch_bounds__(256, WPS) void k_conv_wino(WinoArgs a, TileGrid tg, int groups, unsigned mgroups) {
   using G = WinoGeom<MT, NT>;
+  static_assert(!SM || MT == 4, "k_softmax_merge reads four partials per channel group of 64");
   constexpr int KC = G::KC, KS = G::KS, LC = G::LC, NPIX = G::NPIX, PLANE = G::PLANE, GP = G::GP, CHUNK = G::CHUNK;
   constexpr int NITEMS = NPIX * (KC / 4), NITA = (NITEMS + 255) / 256;
   __shared__ __attribute__((aligned(16))) float lds[G::LDS_FLOATS + 512];   // + the layer's bias vector (D <= 512)
@@ -439,6 +427,12 @@ __global__ __launch_bounds__(256) void k_softmax_merge(const f32x4* __restrict__
   }
 }
 
+int launch_softmax_merge(const float* part, float* vw, float* pd, size_t npix, int np, hipStream_t st) {
+  hipLaunchKernelGGL(k_softmax_merge, dim3((unsigned)((npix + 63) / 64)), dim3(256), 0, st, (const f32x4*)part, vw, pd, npix, np);
+  ADAMVS_CHECK_LAUNCH("softmax_merge");
+  return 0;
+}
+
 // option wino_softmax = 0: the scores of `prob` through the score volume to k_softmax_regress, as in rounds 3-4 (A/B)
 bool wino_softmax_fused() { return opt(OPT_WINO_SOFTMAX) != 0; }
 
@@ -456,11 +450,8 @@ int launch_conv_wino_softmax(const float* in, const float* wpk, const float* bia
   const int forced = opt(OPT_WINO_WPS);
   const bool two = forced ? forced == 2 : h * w >= 1024;
   if (int rc = two ? launch_wino_cfg<4, 2, 2, true>(a, N, st) : launch_wino_cfg<4, 3, 1, true>(a, N, st)) return rc;
-  const size_t npix = (size_t)N * h * w;
   // a lane's partial covers the MT = 4 channel tiles of its workgroup: 4 partials per channel group of 64 and pixel
-  hipLaunchKernelGGL(k_softmax_merge, dim3((unsigned)((npix + 63) / 64)), dim3(256), 0, st, (const f32x4*)part, vw, pd, npix, D / 16);
-  ADAMVS_CHECK_LAUNCH("softmax_merge");
-  return 0;
+  return launch_softmax_merge(part, vw, pd, (size_t)N * h * w, D / 16, st);
 }
 
 }  // namespace adamvs

@@ -14,32 +14,37 @@
 // (32 B per CU and clock).  With four rows of six positions the wave keeps 6 x MT 4 x NT 2 = 48 accumulator tiles -- the
 // 192 registers of the F(2x2, 3x3) kernel -- and the same 48 MFMAs per k-step, for 4 x 64 instead of 6 x 32 output pixels.
 // Rounding: the column transform has the factors 4, 5, 8 and 1/24: 9e-7 relative L1 against a float64 convolution at
-// D = 192 where the direct kernel has 6e-7 and F(2x2, 3x3) 4e-7 (tools/wino_bench.py, tools/experiments/wino24/wino24.py --check-gpu).
+// D = 192 where the direct kernel has 6e-7 and F(2x2, 3x3) 4e-7; per element at most 2.9e-6 of max |ref| (tests/test_costreg_wino24.py).
 //
-// OUTCOME (round 4): a third fewer MFMAs, 3.5 % less time.  512 maps of 96 x 192 pixels at D = 192: 23.3 ms against 24.1 for
-// F(2x2, 3x3) -- 57 % of the fp32 matrix rate against 73 %; slower on every smaller level of the hourglass (48x96: 7.4 against
-// 6.0 ms) and at D = 64.  Per k-step the wave issues the same 48 MFMAs (0.64 us) next to 18 packed transforms, 12 LDS reads,
-// 8 fragment loads and 9 fill instructions where F(2x2, 3x3) has 12 / 12 / 4 / 6: 0.33 us against 0.17 on top of the MFMAs,
-// and 7.4 against 3.3 us per tile for start + epilogue.  Timing builds (-DWINO24_EXP, of 5.84 ms per 128 maps): no epilogue -0.53,
-// no fragment loads -0.68, no transform -0.71, no window fill and barrier -0.97, no raw-row reads -0.57 -- every part a tenth,
-// none dominant.  adamvs_cost_reg_net_2d therefore stays on F(2x2, 3x3); this kernel is an op-level entry point with its tests.
+// OUTCOME.  Round 4 (one workgroup per CU, MT 4 x NT 2): a quarter fewer MFMAs than F(2x2, 3x3), 3.5 % less time at 96 x 192, slower on
+// every smaller level of the hourglass; the network stayed on F(2x2, 3x3).  Round 9: two workgroups per CU (WPS 2, 24 accumulator
+// tiles per wave: MT 2 x NT 2 or MT 4 x NT 1), the bias through the accumulators, the softmax partials of `prob` (SM).  256 maps of
+// 96 x 192 at D = 192: 10.92 ms (MT 2 x NT 2) / 11.01 (MT 4 x NT 1) / 11.13 (one workgroup) against 11.73 for F(2x2, 3x3); with the
+// softmax partials 10.97 (MT 4 x NT 1) / 12.11 (one workgroup) against 12.02.  48 x 96, where 64-pixel blocks cover 128 columns: 3.35
+// against 2.89.  conv0 and prob of the network take this form on maps at least 128 wide (costreg2d.hip::cost_reg_wino24): cfg2's step
+// 385.7 -> 376.9 ms.  Timing builds of round 4 (-DWINO24_EXP, of 5.84 ms per 128 maps, one workgroup per CU): no epilogue -0.53, no
+// fragment loads -0.68, no transform -0.71, no window fill and barrier -0.97, no raw-row reads -0.57 -- every part a tenth, none dominant.
 //
-// Mapping (as costreg2d_wino.hip unless said): workgroup = 4 waves = patch rows i; a tile = NT 2 tile rows x 16 tiles x
-// MT 4 channel tiles = 4 x 64 output pixels x 64 channels; LDS window 6 x 66 pixels x 16 input channels, double-buffered,
+// Mapping (as costreg2d_wino.hip unless said): workgroup = 4 waves = patch rows i; a tile = NT tile rows x 16 tiles x
+// MT channel tiles = 2 NT x 64 output pixels x 16 MT channels; LDS window (2 NT + 2) x 66 pixels x 16 input channels, double-buffered,
 // one barrier per chunk.  Per tile row and k-step a wave reads two raw rows of six (six ds_read_b64), forms
 // T = rowA + sgn rowB (three packed FMAs) and the six column values in six more:
 //     (v0, v5) = 4 (t0, t1) - 5 (t2, t3) + (t4, t5)
 //     (a, c) = t4 - (4, 1) t2,  (b, e) = t3 - (4, 1) t1,   (v1, v2) = a +- b,   (v3, v4) = c +- 2 e
 // -- every operand a register pair as it was loaded (op_sel picks the half), nine packed instructions per 24 MFMAs.
 // Weight fragments: per (k-step, row i, channel tile) a lane holds the six positions of its row, fetched as 16 + 8 bytes
-// from two arrays.  Epilogue: Z_i[b] = sum_j At4[b][j] M[i][j] (b = 0..3) in registers, through LDS (64 KB: 4 rows x 4 b x MT
-// x 1 KB), wave (a, b') forms Y[a][b] = sum_i At2[a][i] Z_i[b] for b = 2 b', 2 b' + 1, adds bias / ReLU / skip and stores.
+// from two arrays.  Epilogue: Z_i[b] = sum_j At4[b][j] M[i][j] (b = 0..3) in registers, through LDS (4 rows x 4 b x MT x 1 KB),
+// wave (a, b') forms Y[a][b] = sum_i At2[a][i] Z_i[b] for b = 2 b', 2 b' + 1, applies ReLU / skip and stores (the bias came through
+// accumulator position (1, 1)); SM: the softmax partial of the lane's 16 MT channels instead, as k_conv_wino<..., SM>.
 #include <stdlib.h>
 #include <type_traits>
 
 #include "common.h"
+#include "costreg_softmax.h"
+#include "costreg_wino.h"
 #include "kernels.h"
 #include "persistent.h"
+#include "planes.h"
 
 // Timing builds only (tools/build_variant.py <name> -DWINO24_EXP=<bits>; results are wrong): 1 no epilogue, 2 no weight loads in the loop,
 // 4 no input transform, 8 no window fill / barrier (32 no barrier only, 64 no LDS stores only, 128 no window loads only), 256 no raw-row reads.
@@ -49,16 +54,8 @@
 
 namespace adamvs {
 
-struct Wino24Args {
-  const float* in;     // [N][h*w][D]
-  const float* wpk;    // [D/4][4][D/16][64][4] (patch columns 0-3) then [D/4][4][D/16][64][2] (columns 4, 5): k-step, patch row i, channel tile, lane (A-fragment order)
-  const float* bias;   // [D]
-  const float* skip;   // [N][h*w][D] or null; added after the ReLU
-  float* out;          // [N][h*w][D]
-  int D, h, w, relu;
-};
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+// WinoArgs (costreg_wino.h); wpk: [D/4][4][D/16][64][4] (patch columns 0-3) then [D/4][4][D/16][64][2] (columns 4, 5): k-step, patch
+// row i, channel tile, lane (A-fragment order) -- 24 bytes per lane and (k-step, channel tile), fetched as 16 + 8
 
 template <int MT, int NT>
 struct Wino24Geom {
@@ -70,15 +67,17 @@ struct Wino24Geom {
   static constexpr int CHUNK = KS * GP;                      // floats per buffer
   static constexpr int ZFLOATS = 4 * 4 * MT * 64 * 4;        // epilogue exchange of one tile row
   static constexpr int LDS_FLOATS = (2 * CHUNK > ZFLOATS) ? 2 * CHUNK : ZFLOATS;
-  static_assert(PLANE >= NPIX && LDS_FLOATS * 4 <= 65536, "plane pitch / LDS");
+  static constexpr size_t LDS_BYTES = (size_t)(LDS_FLOATS + 512) * 4;   // dynamic: above 64 KB with MT = 4
+  static_assert(PLANE >= NPIX, "plane pitch");
 };
 
-template <int MT, int NT>
-__global__ __launch_bounds__(256) void k_conv_wino24(Wino24Args a, TileGrid tg, int groups, unsigned mgroups) {
+template <int MT, int NT, int WPS, bool SM>
+__global__ __launch_bounds__(256, WPS) void k_conv_wino24(WinoArgs a, TileGrid tg, int groups, unsigned mgroups) {
   using G = Wino24Geom<MT, NT>;
+  static_assert(!SM || MT == 4, "k_softmax_merge reads four partials per channel group of 64");
   constexpr int KC = G::KC, KS = G::KS, LC = G::LC, NPIX = G::NPIX, PLANE = G::PLANE, GP = G::GP, CHUNK = G::CHUNK;
   constexpr int NITEMS = NPIX * (KC / 4), NITA = (NITEMS + 255) / 256;
-  __shared__ __attribute__((aligned(16))) float lds[G::LDS_FLOATS];
+  extern __shared__ __attribute__((aligned(16))) float lds[];   // G::LDS_BYTES: the buffers / the epilogue's exchange + the layer's bias vector (D <= 512)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave = patch row i
   const int p = lane & 15, q = lane >> 4;
   const int D = a.D, NTILES = D / 16, NC = D / KC;
@@ -136,7 +135,10 @@ __global__ __launch_bounds__(256) void k_conv_wino24(Wino24Args a, TileGrid tg, 
   f32x4 xs[NITA];
   struct Frag { f32x4 lo[MT]; f32x2 hi[MT]; };               // positions 0-3 | 4, 5 of the wave's row
   Frag wf0, wf1, wf2, wf3;                                   // four named fragment sets (below)
-  f32x4 bias4[MT];
+  // The bias rides in the accumulators: At2 E A4 is all ones for E = the unit matrix element (1, 1) in this form too (column 1 of
+  // At2 and of At4 is all ones), so position (1, 1) of every tile starts from the bias (wave 1, first k-step); from LDS, as in k_conv_wino
+  f32x4 cb[MT];
+  for (int i = tid; i < D; i += 256) lds[G::LDS_FLOATS + i] = a.bias[i];
   int cg = 0;                                                // channel group of the fragments being requested
 
   auto load_w = [&](Frag& wf, int ks) {                      // ks: global k-step
@@ -153,9 +155,13 @@ __global__ __launch_bounds__(256) void k_conv_wino24(Wino24Args a, TileGrid tg, 
     for (int it = 0; it < NITA; ++it)
       xs[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xoff[it], (unsigned)ch * 4u, 0));
   };
-  auto load_bias = [&]() {
+  auto read_bias = [&]() {                                   // before the first k-step of a tile (cg = its channel group)
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) bias4[mt] = *(const f32x4*)(a.bias + (cg * MT + mt) * 16 + 4 * q);
+    for (int mt = 0; mt < MT; ++mt) {
+      const f32x4 b = *(const f32x4*)(lds + G::LDS_FLOATS + (cg * MT + mt) * 16 + 4 * q);
+      cb[mt] = wave == 1 ? b : zero;
+    }
   };
   auto store_items = [&](int buf, int i0, int i1) {          // window items [i0, i1) of the staged chunk -> buffer `buf`
 #pragma unroll
@@ -187,7 +193,7 @@ __global__ __launch_bounds__(256) void k_conv_wino24(Wino24Args a, TileGrid tg, 
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       acc[0][mt][t] = mfma16(wf.lo[mt].x, v05.x, FIRST ? zero : acc[0][mt][t]);
-      acc[1][mt][t] = mfma16(wf.lo[mt].y, v12.x, FIRST ? zero : acc[1][mt][t]);
+      acc[1][mt][t] = mfma16(wf.lo[mt].y, v12.x, FIRST ? cb[mt] : acc[1][mt][t]);
       acc[2][mt][t] = mfma16(wf.lo[mt].z, v12.y, FIRST ? zero : acc[2][mt][t]);
       acc[3][mt][t] = mfma16(wf.lo[mt].w, v34.x, FIRST ? zero : acc[3][mt][t]);
       acc[4][mt][t] = mfma16(wf.hi[mt].x, v34.y, FIRST ? zero : acc[4][mt][t]);
@@ -216,6 +222,18 @@ __global__ __launch_bounds__(256) void k_conv_wino24(Wino24Args a, TileGrid tg, 
     constexpr int CUR = decltype(curc)::value;
     Raw r;
     read_raw(r, CUR, 0, 0);
+    if constexpr (WPS == 2) {                                // two sets, one k-step ahead
+      kstep(wf0, r, CUR, 0, fill, next_ch, firstc);
+      load_w(wf0, min(c * KS + 2, last_ks));
+      kstep(wf1, r, CUR, 1, false, 0, std::false_type{});
+      load_w(wf1, min(c * KS + 3, last_ks));
+      kstep(wf0, r, CUR, 2, false, 0, std::false_type{});
+      load_w(wf0, min(c * KS + 4, last_ks));
+      kstep(wf1, r, CUR, 3, false, 0, std::false_type{});
+      load_w(wf1, min(c * KS + 5, last_ks));
+      if (!(WINO24_EXP & (8 | 32))) __syncthreads();
+      return;
+    }
     load_w(wf3, min(c * KS + 3, last_ks));
     kstep(wf0, r, CUR, 0, fill, next_ch, firstc);
     load_w(wf0, min(c * KS + 4, last_ks));
@@ -239,7 +257,7 @@ __global__ __launch_bounds__(256) void k_conv_wino24(Wino24Args a, TileGrid tg, 
   load_x(0);
   load_w(wf0, 0);
   load_w(wf1, min(1, last_ks));
-  load_w(wf2, min(2, last_ks));
+  if (WPS == 1) load_w(wf2, min(2, last_ks));
   wait_vmem_all();
   while (true) {
     const int next = tile + (int)gridDim.x;
@@ -247,6 +265,7 @@ __global__ __launch_bounds__(256) void k_conv_wino24(Wino24Args a, TileGrid tg, 
     store_items(0, 0, NITA);
     load_x(KC);
     __syncthreads();
+    read_bias();
     chunk(0, std::integral_constant<int, 0>{}, std::true_type{}, true, 2 * KC);
     chunk(1, std::integral_constant<int, 1>{}, std::false_type{}, true, 3 * KC);
     for (int c = 2; c < NC - 2; c += 2) {                    // NC is even (>= 4) for every supported D
@@ -265,13 +284,12 @@ __global__ __launch_bounds__(256) void k_conv_wino24(Wino24Args a, TileGrid tg, 
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) drain(acc[j][mt][0]);   // (tile row 0 is read first; tools/mfma_hazard_lint.py checks the rest)
 
-    cg = done.cg;
-    load_bias();                                             // before the next tile's fragment sets: vmcnt retires in order
     cg = cur.cg;
+    // the next tile's first fragment sets fly during the epilogue
     if (more) {
       load_w(wf0, 0);
       load_w(wf1, min(1, last_ks));
-      load_w(wf2, min(2, last_ks));
+      if (WPS == 1) load_w(wf2, min(2, last_ks));
     }
     // ---- epilogue of `done`: the four rows meet through LDS, one tile row per round
     if (!((WINO24_EXP & 1) && a.relu != 12345)) {
@@ -279,6 +297,11 @@ __global__ __launch_bounds__(256) void k_conv_wino24(Wino24Args a, TileGrid tg, 
       const buf_rsrc ro = make_rsrc((char*)a.out + img);
       const buf_rsrc rk = make_rsrc((const char*)(a.skip ? a.skip : a.out) + img);
       f32x4* zl = (f32x4*)lds;
+      // SM: the tile's plane line (uniform: scalar loads) and the partials' descriptor, as in k_conv_wino
+      const int sm_b = SM ? done.n % a.sm_B : 0, sm_last = a.sm_D - 1, dq = 4 * q;
+      const float sm_lo = SM ? a.sm_planes.p[2 * sm_b] : 0.f, sm_hi = SM ? a.sm_planes.p[2 * sm_b + 1] : 0.f;
+      const float sm_step = (sm_hi - sm_lo) / (float)sm_last;   // as planes.h::plane_line
+      const buf_rsrc rp = make_rsrc((char*)a.sm_part + (size_t)done.n * a.h * a.w * (size_t)(64 * groups));      // 4 partials of 16 bytes per channel group
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         if (t) __syncthreads();                                // the previous round's readers are done
@@ -296,13 +319,37 @@ __global__ __launch_bounds__(256) void k_conv_wino24(Wino24Args a, TileGrid tg, 
         const unsigned tbase = ooff + (unsigned)((((done.r0 + 2 * t) * a.w + done.c0) * D + done.cg * MT * 16) * 4);
 #pragma unroll
         for (int bb = 0; bb < 2; ++bb) {
+          if constexpr (SM) {
+            // the softmax partial of the lane's 16 channels of pixel (oy, ox + bb): k_conv_wino's, one 16-byte store per lane, pixel
+            // and round, always issued (out-of-image pixels: BUF_OOB) so that the wait below counts right
+            float m = -INFINITY, se = 0.f, sd = 0.f;
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+              const f32x4 z0 = zl[(((oa + 0) * 4 + 2 * ob + bb) * MT + mt) * 64 + lane];
+              const f32x4 z1 = zl[(((oa + 1) * 4 + 2 * ob + bb) * MT + mt) * 64 + lane];
+              const f32x4 z2 = zl[(((oa + 2) * 4 + 2 * ob + bb) * MT + mt) * 64 + lane];
+              const f32x4 v = z0 + os * (z1 + z2);
+              const float mn = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
+              const float sc = __expf(m - mn);                   // (first tile: exp(-inf) = 0 times 0)
+              const int d = (done.cg * MT + mt) * 16 + dq;
+              const float e0 = __expf(v.x - mn), e1 = __expf(v.y - mn), e2 = __expf(v.z - mn), e3 = __expf(v.w - mn);
+              se = __fmaf_rn(se, sc, (e0 + e1) + (e2 + e3));
+              sd = sd * sc;
+              sd = __fmaf_rn(e3, plane_value(sm_lo, sm_step, min(d + 3, sm_last)), __fmaf_rn(e2, plane_value(sm_lo, sm_step, min(d + 2, sm_last)),
+                   __fmaf_rn(e1, plane_value(sm_lo, sm_step, min(d + 1, sm_last)), __fmaf_rn(e0, plane_value(sm_lo, sm_step, min(d, sm_last)), sd))));
+              m = mn;
+            }
+            const unsigned pbase = (oy < a.h && ox + bb < a.w) ? (unsigned)(((oy * a.w + ox + bb) * (4 * groups) + done.cg * 4 + q) * 16) : BUF_OOB;
+            buf_store4(rp, pbase, f32x4{m, se, sd, 0.f});
+            continue;
+          }
           const unsigned obase = (oy < a.h && ox + bb < a.w) ? tbase + (unsigned)(bb * D * 4) : BUF_OOB;
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
             const f32x4 z0 = zl[(((oa + 0) * 4 + 2 * ob + bb) * MT + mt) * 64 + lane];
             const f32x4 z1 = zl[(((oa + 1) * 4 + 2 * ob + bb) * MT + mt) * 64 + lane];
             const f32x4 z2 = zl[(((oa + 2) * 4 + 2 * ob + bb) * MT + mt) * 64 + lane];
-            f32x4 v = z0 + os * (z1 + z2) + bias4[mt];
+            f32x4 v = z0 + os * (z1 + z2);
             if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
             if (a.skip) v += buf_load4(rk, obase == BUF_OOB ? BUF_OOB : obase + mt * 64);
             buf_store4(ro, obase == BUF_OOB ? BUF_OOB : obase + mt * 64, v);
@@ -313,30 +360,46 @@ __global__ __launch_bounds__(256) void k_conv_wino24(Wino24Args a, TileGrid tg, 
     if (!more) break;
     tile = next;
     // the window chunk and the fragments were requested BEFORE the epilogue's 2 NT MT stores (vmcnt retires in order)
-    wait_vmem_but<2 * NT * MT>();
+    wait_vmem_but<SM ? 2 * NT : 2 * NT * MT>();
     __syncthreads();                                         // the epilogue's LDS readers are done: the buffers are free
   }
 }
 
-template <int MT, int NT>
-static int launch_wino24_cfg(const Wino24Args& a, int N, hipStream_t st) {
+template <int MT, int NT, int WPS, bool SM = false>
+static int launch_wino24_cfg(const WinoArgs& a, int N, hipStream_t st) {
   const int groups = a.D / (16 * MT);
-  auto kern = k_conv_wino24<MT, NT>;
-  static const int capacity = resident_blocks(kern, 256, 0);
   TileGrid tg;
   if (int rc = make_tile_grid(tg, groups * cdiv(a.w, 64), cdiv(a.h, 2 * NT), N)) return rc;
-  const int grid = tg.ntiles < capacity ? tg.ntiles : capacity;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, a, tg, groups, (unsigned)(((1ull << 32) + groups - 1) / groups));
-  ADAMVS_CHECK_LAUNCH("conv_wino24");
-  return 0;
+  return launch_resident<k_conv_wino24<MT, NT, WPS, SM>>(tg.ntiles, Wino24Geom<MT, NT>::LDS_BYTES, st, "conv_wino24", a, tg, groups,
+                                                         (unsigned)(((1ull << 32) + groups - 1) / groups));
 }
 
+// Three tilings, the same bits.  Two workgroups per CU leave a wave 24 accumulator tiles: MT 2 x NT 2 (a fragment feeds two MFMAs, six
+// channel groups per pixel block at D = 192) or MT 4 x NT 1 (one MFMA per fragment, a 4-row window per 2 output rows); one workgroup
+// per CU holds MT 4 x NT 2.  256 maps of 96 x 192 at D = 192: 10.92 / 11.01 / 11.13 ms (F(2x2, 3x3): 11.73); 64 maps 2.62 / 2.79 / 2.81
+// (2.89); 32 maps at D = 256 2.29 / 2.37 / 2.43 (2.50): MT 2 x NT 2 wherever the epilogue allows it (the softmax partials need MT 4).
+// Option wino_wps = 1 / 2 forces the one-workgroup form / MT 4 x NT 1 (A/B).
 int launch_conv_wino24(const float* in, const float* wpk, const float* bias, const float* skip, float* out, int N, int D, int h, int w,
                        int relu, hipStream_t st) {
-  const Wino24Args a{in, wpk, bias, skip, out, D, h, w, relu};
+  const WinoArgs a{in, wpk, bias, skip, out, D, h, w, relu, nullptr, PlaneSrc{nullptr, 0, 0.f}, 1, D};
   ADAMVS_CHECK_ARG(wino_depth_supported(D), "conv_wino24: D=%d unsupported (a multiple of 64 up to 512)", D);
   ADAMVS_CHECK_ARG((size_t)h * w * D * 4 < 0x7fffffffu, "conv_wino24: a map of %dx%dx%d floats exceeds the 2 GiB a buffer descriptor spans", h, w, D);
-  return launch_wino24_cfg<4, 2>(a, N, st);
+  switch (opt(OPT_WINO_WPS)) {
+    case 1: return launch_wino24_cfg<4, 2, 1>(a, N, st);
+    case 2: return launch_wino24_cfg<4, 1, 2>(a, N, st);
+    default: return launch_wino24_cfg<2, 2, 2>(a, N, st);
+  }
+}
+
+// `prob` in this form with the softmax partials behind it: launch_conv_wino_softmax's arguments and partial layout
+int launch_conv_wino24_softmax(const float* in, const float* wpk, const float* bias, float* part, const PlaneSrc& planes, float* vw, float* pd,
+                               int N, int B, int D, int n_planes, int h, int w, hipStream_t st) {
+  const WinoArgs a{in, wpk, bias, nullptr, nullptr, D, h, w, 0, part, planes, B, n_planes > 0 ? n_planes : D};
+  ADAMVS_CHECK_ARG(planes.mode == PLANES_UNIFORM && a.sm_D > 1, "conv_wino24_softmax: planes uniform per tile, at least two (mode %d, %d planes)", planes.mode, a.sm_D);
+  ADAMVS_CHECK_ARG(wino_depth_supported(D), "conv_wino24_softmax: D=%d unsupported (a multiple of 64 up to 512)", D);
+  ADAMVS_CHECK_ARG((size_t)h * w * D * 4 < 0x7fffffffu, "conv_wino24_softmax: a map of %dx%dx%d floats exceeds the 2 GiB a buffer descriptor spans", h, w, D);
+  if (int rc = opt(OPT_WINO_WPS) == 1 ? launch_wino24_cfg<4, 2, 1, true>(a, N, st) : launch_wino24_cfg<4, 1, 2, true>(a, N, st)) return rc;
+  return launch_softmax_merge(part, vw, pd, (size_t)N * h * w, D / 16, st);
 }
 
 }  // namespace adamvs
@@ -347,4 +410,18 @@ extern "C" int adamvs_conv3x3_dd_wino24(const float* in, const float* wpk, const
                                         int D, int h, int w, int relu, void* stream) {
   ADAMVS_CHECK_ARG(in && wpk && bias && out && N > 0 && h > 0 && w > 0, "conv3x3_dd_wino24: bad arguments");
   return launch_conv_wino24(in, wpk, bias, skip, out, N, D, h, w, relu, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_prob_softmax_regress_wino24(const float* in, const float* wpk, const float* bias, const float* depth_range, float* view_weight,
+                                                  float* pair_depth, int S, int B, int D, int h, int w, void* workspace,
+                                                  size_t workspace_bytes, void* stream) {
+  ADAMVS_CHECK_ARG(in && wpk && bias && depth_range && view_weight && pair_depth && workspace && S > 0 && B > 0 && h > 0 && w > 0,
+                   "prob_softmax_regress_wino24: bad arguments");
+  ADAMVS_CHECK_ARG(wino_depth_supported(D) && D > 1, "prob_softmax_regress_wino24: D=%d unsupported (a multiple of 64 up to 512)", D);
+  // the partials' layout is the F(2x2, 3x3) kernel's: the same workspace size
+  ADAMVS_CHECK_ARG(workspace_bytes >= wino_softmax_part_floats(S * B, D, h, w) * sizeof(float),
+                   "prob_softmax_regress_wino24: workspace too small (%zu < %zu bytes)", workspace_bytes,
+                   wino_softmax_part_floats(S * B, D, h, w) * sizeof(float));
+  return launch_conv_wino24_softmax(in, wpk, bias, (float*)workspace, PlaneSrc{depth_range, PLANES_UNIFORM, 0.f}, view_weight, pair_depth, S * B, B,
+                                    D, D, h, w, (hipStream_t)stream);
 }

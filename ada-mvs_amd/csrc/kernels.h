@@ -140,6 +140,12 @@ int launch_conv_wino_softmax(const float* in, const float* wpk, const float* bia
                              int N, int B, int D, int n_planes, int h, int w, hipStream_t st);
 int launch_conv_wino(const float* in, const float* wpk, const float* bias, const float* skip, float* out, int N, int D, int h, int w,
                      int relu, hipStream_t st);
+// the same two in the F(2x4, 3x3) form (costreg2d_wino24.hip; wpk from packing.pack_reg_layer_wino24)
+bool cost_reg_wino24(int D, int h, int w);        // whether conv0 / prob of a network on h x w maps take it
+int launch_conv_wino24_softmax(const float* in, const float* wpk, const float* bias, float* part, const PlaneSrc& planes, float* vw, float* pd,
+                               int N, int B, int D, int n_planes, int h, int w, hipStream_t st);
+int launch_conv_wino24(const float* in, const float* wpk, const float* bias, const float* skip, float* out, int N, int D, int h, int w,
+                       int relu, hipStream_t st);
 
 // Dw >= D: channels per pixel of sim (the width CostRegNet2D runs at); channels [D, Dw) are written as zeros
 int launch_pair_similarity(const float* feat, const float* rt, PlaneSrc planes, float* sim, int B, int S, int C, int D, int h,

@@ -164,6 +164,20 @@ def prob_softmax_regress_wino(x_cl, wino_layer, bias, depth_range, S, B, D, h, w
     return vw, pd
 
 
+def prob_softmax_regress_wino24(x_cl, wino24_layer, bias, depth_range, S, B, D, h, w):
+    """The same with `prob` in the F(2x4, 3x3) form (wino24_layer from packing.pack_reg_layer_wino24): what the fp32 stage runs on
+    wide maps at D >= 128.  Same partials, merge kernel and workspace as prob_softmax_regress_wino."""
+    vw = torch.empty(S, B, h, w, device=x_cl.device, dtype=torch.float32)
+    pd = torch.empty(S, B, h, w, device=x_cl.device, dtype=torch.float32)
+    lib = _lib.load()
+    nbytes = lib.adamvs_prob_softmax_regress_wino_workspace_bytes(S, B, D, h, w)
+    ws = torch.empty(nbytes // 4, device=x_cl.device, dtype=torch.float32)
+    check(lib.adamvs_prob_softmax_regress_wino24(_p(_dev(x_cl, "x")), _p(wino24_layer), _p(bias), _p(_dev(depth_range, "depth_range")), _p(vw),
+                                                 _p(pd), S, B, D, h, w, ctypes.c_void_p(ws.data_ptr()), nbytes, _stream()),
+          "prob_softmax_regress_wino24")
+    return vw, pd
+
+
 def aggregate_conv1(feat, rt, planes, view_weight, w1pk, B, S, C, D, h, w, precision=0, return_similarity=False):
     """-> c1 [D,B,hw,8]; return_similarity (D <= 32, one chunk): also the aggregated similarity [D,B,hw,C] the call left in
     its workspace (include/adamvs_hip.h: the workspace holds the last chunk's similarity on return)."""
@@ -353,6 +367,16 @@ def conv3x3_dd_wino(x_cl, wino_layer, bias, skip, N, D, h, w, relu, out=None):
     null = ctypes.c_void_p(0)
     check(_lib.load().adamvs_conv3x3_dd_wino(_p(_dev(x_cl, "x")), _p(wino_layer), _p(bias), _p(skip) if skip is not None else null,
                                              _p(out), N, D, h, w, int(relu), _stream()), "conv3x3_dd_wino")
+    return out
+
+
+def conv3x3_dd_wino24(x_cl, wino24_layer, bias, skip, N, D, h, w, relu, out=None):
+    """A stride-1 CostRegNet2D layer in the F(2x4, 3x3) form; wino24_layer from packing.pack_reg_layer_wino24."""
+    if out is None:
+        out = torch.empty(N, h * w, D, device=x_cl.device, dtype=torch.float32)
+    null = ctypes.c_void_p(0)
+    check(_lib.load().adamvs_conv3x3_dd_wino24(_p(_dev(x_cl, "x")), _p(wino24_layer), _p(bias), _p(skip) if skip is not None else null,
+                                               _p(out), N, D, h, w, int(relu), _stream()), "conv3x3_dd_wino24")
     return out
 
 

@@ -16,6 +16,8 @@ REG_LAYERS = ("conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "co
 REG_TRANSPOSED = ("conv7", "conv9", "conv11")
 REG_WINOGRAD = ("conv0", "conv2", "conv4", "conv6", "prob")      # stride-1 layers: also packed in the F(2x2, 3x3) form (fp32)
 WINO_WIDTHS = (64, 128, 192, 256, 384, 512)              # the widths of REG_WIDTHS that csrc/costreg2d_wino.hip takes (multiples of 64)
+REG_WINO24 = ("conv0", "prob")                           # the layers on the full-size map: also packed in the F(2x4, 3x3) form (fp32)
+WINO24_BLOB_WIDTHS = WINO_WIDTHS[1:]                     # ... at the widths at which the network can select it (not D = 64)
 # The widths CostRegNet2D's kernels are built for (csrc/costreg2d.hip::costreg_width, costreg_width_bf16x3; held equal to the
 # library's table by tests/test_host_logic.py).  The reference builds the network for any number of hypotheses
 # (models/adamvs.py:198-228): other D run at the next width, see pack_cost_reg_net_2d.
@@ -151,6 +153,23 @@ def pack_reg_layer_wino(w, scale):
     return u.reshape(4, 4, d // 16, 16, d // 4, 4).permute(4, 0, 2, 5, 3, 1).contiguous().reshape(-1)
 
 
+WINO_G4 = torch.tensor([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6],
+                        [0, 0, 1]], dtype=torch.float64)
+
+
+def pack_reg_layer_wino24(w, scale):
+    """A stride-1 CostRegNet2D layer for the F(2x4, 3x3) kernel (csrc/costreg2d_wino24.hip): U = G w G4^T, patch rows i by F(2, 3),
+    patch columns j by F(4, 3), formed in double precision and rounded once; A fragments [D/4][4 = i][D/16][64][4 = j 0..3]
+    followed by [D/4][4][D/16][64][2 = j 4, 5] (include/adamvs_hip.h): 24*D*D floats."""
+    w = (w.detach().to(torch.float64).cpu() * scale.detach().to(torch.float64).cpu().reshape(-1, 1, 1, 1))   # [co][ci][3][3]
+    d = w.shape[0]
+    assert w.shape[1] == d and d % 16 == 0
+    u = torch.einsum("ik,ockl,jl->ijoc", WINO_G, w, WINO_G4).to(torch.float32)                              # [i 4][j 6][co][ci]
+    # (i, j, tile, co16, kc, k4) -> (kc, i, tile, k4, co16, j): lane = k4*16 + co16
+    f = u.reshape(4, 6, d // 16, 16, d // 4, 4).permute(4, 0, 2, 5, 3, 1).contiguous()
+    return torch.cat([f[..., :4].reshape(-1), f[..., 4:].reshape(-1)])
+
+
 def pack_reg_layer_bf16x3(w, scale, shift, transposed):
     """One CostRegNet2D layer for the split-bf16 kernels: 9*D*D floats worth of bf16 fragments
     [hi|lo][tap][cin/32][cout/16][lane][8] (include/adamvs_hip.h) + [D] fp32 bias; same size as the fp32 packing."""
@@ -178,7 +197,9 @@ def _pad_square(w, transposed, dr):
 
 def pack_cost_reg_net_2d(sd, pre, precision="fp32"):
     """All 11 layers of `pre` (e.g. 'DepthNet.0.reg.') from a reference-keyed state dict; fp32 at the widths the F(2x2, 3x3)
-    kernel supports: followed by the five stride-1 layers in that form (16*D*D floats each, include/adamvs_hip.h).
+    kernel supports: followed by the five stride-1 layers in that form (16*D*D floats each, include/adamvs_hip.h), and at
+    WINO24_BLOB_WIDTHS by conv0 and prob in the F(2x4, 3x3) form (24*D*D floats each) -- behind everything else, so that no
+    earlier offset moves.
     A network of D hypotheses is packed at Dr = reg_width(D) channels: zero filters for the pad channels (their activations are
     ReLU(0 + 0) = 0 in every layer and no real channel reads them), PAD_SCORE as the bias of `prob`'s pad channels."""
     pack_layer = pack_reg_layer if precision == "fp32" else pack_reg_layer_bf16x3
@@ -190,7 +211,7 @@ def pack_cost_reg_net_2d(sd, pre, precision="fp32"):
         out[:d] = v.detach().float().cpu()
         return out
 
-    chunks, wino = [], []
+    chunks, wino, wino24 = [], [], []
     for name in REG_LAYERS:
         if name == "prob":
             w = sd[pre + "prob.weight"]
@@ -213,7 +234,9 @@ def pack_cost_reg_net_2d(sd, pre, precision="fp32"):
         chunks.append(pack_layer(w, scale, shift, transposed))
         if precision == "fp32" and name in REG_WINOGRAD and dr in WINO_WIDTHS:
             wino.append(pack_reg_layer_wino(w, scale))
-    return torch.cat(chunks + wino)
+        if precision == "fp32" and name in REG_WINO24 and dr in WINO24_BLOB_WIDTHS:
+            wino24.append(pack_reg_layer_wino24(w, scale))
+    return torch.cat(chunks + wino + wino24)
 
 
 FUSE_FIELDS = ("conv1", "gates1", "gates1_b", "cand1", "cand1_b", "conv2", "gates2", "gates2_b",

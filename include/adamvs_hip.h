@@ -43,7 +43,10 @@ const char* adamvs_last_error_string(void);
  *
  *   name                  default  meaning
  *   winograd                 1     CostRegNet2D (models/adamvs.py:229-238), fp32, widths that are multiples of 64: the five stride-1
- *                                  layers in the minimal-filtering form F(2x2, 3x3) (16 of 36 products); 0: direct kernels
+ *                                  layers in the minimal-filtering form F(2x2, 3x3) (16 of 36 products); 0: direct kernels.
+ *                                  On wide maps conv0 and prob take the mixed form F(2x4, 3x3) (24 products where F(2x2, 3x3) has
+ *                                  32; D >= 128, maps at least 128 pixels wide of which 64-pixel blocks waste at most an eighth); + 2
+ *                                  (value 3): F(2x2, 3x3) in every stride-1 layer, the maps of before bit for bit
  *   wino_softmax             1     ... its `prob` layer carries the softmax partials, no score volume (stage path); 0: score volume
  *   wino_wps                 0     ... 1 / 2: one / two workgroups per CU for every map size (same bits); 0: by map size
  *   fuse_softmax             1     direct `prob` kernel: softmax / max / depth regression in its epilogue; 0: k_softmax_regress
@@ -135,6 +138,9 @@ int adamvs_pair_similarity(const float* feat, const float* rt, const float* plan
  * in the minimal-filtering form F(2x2, 3x3), 16*D*D floats each, laid out as adamvs_conv3x3_dd_wino takes them; those
  * layers run on that kernel (fp32 throughout, 16 products instead of 36 per 2x2 outputs and channel pair; environment
  * ADAMVS_WINOGRAD=0: on the direct kernel).  ada-mvs_amd/packing.py::pack_cost_reg_net_2d produces exactly this.
+ * fp32 with D in {128,192,256,384,512}: behind those 11 + 5 blocks, at unchanged offsets, two more: conv0 and prob in the form
+ * F(2x4, 3x3), 24*D*D floats each, laid out as adamvs_conv3x3_dd_wino24 takes them (the two layers that run on the full-size
+ * map; option winograd says when they take that kernel).  The blob at D = 64, where that form never wins, is unchanged.
  * wpk_floats = the length of the blob, adamvs_cost_reg_net_2d_weight_floats(D, precision): a blob of another layout
  * (e.g. the 11-block blob of ABI <= 10 at a width that now carries the F(2x2, 3x3) blocks) is refused, not read past its end.
  *
@@ -173,6 +179,17 @@ int adamvs_conv3x3_dd(const float* in, const float* in2, const float* wpk, const
 int adamvs_conv3x3_dd_wino(const float* in, const float* wpk, const float* bias, const float* skip, float* out, int N, int D,
                            int h, int w, int relu, void* stream);
 
+/* The same layer in the mixed form F(2x4, 3x3): F(2, 3) down the rows as above, F(4, 3) along the columns (points 0, +-1, +-2,
+ * infinity), 24 products per 2x4 output tile and channel pair where F(2x2, 3x3) needs 32; fp32 throughout, about twice the
+ * rounding error of F(2x2, 3x3) (the column transform has the factors 4, 5, 8 and 1/24).
+ * wpk = U = G w G4^T (G as above, G4 = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1], BN scale
+ * folded in, formed in double precision and rounded once) as two arrays of A fragments, 24*D*D floats in all:
+ * [D/4][4][D/16][64][4] with element j of lane l of fragment (k-step kc, patch row i, channel tile) =
+ * U[i][j][cout = 16*tile + (l&15)][cin = 4*kc + (l>>4)] for the patch columns j = 0..3, then [D/4][4][D/16][64][2] for j = 4, 5.
+ * Everything else as adamvs_conv3x3_dd_wino. */
+int adamvs_conv3x3_dd_wino24(const float* in, const float* wpk, const float* bias, const float* skip, float* out, int N, int D,
+                             int h, int w, int relu, void* stream);
+
 /* models/adamvs.py:481-486 + module.py:617-625: softmax over D, its maximum (view
  * weight) and the expectation of the hypothesis planes (pair depth).
  * score [S*B][h*w][D], planes [B][D][h*w] -> view_weight, pair_depth [S][B][h*w]. */
@@ -198,6 +215,10 @@ size_t adamvs_prob_softmax_regress_wino_workspace_bytes(int S, int B, int D, int
 int adamvs_prob_softmax_regress_wino(const float* in, const float* wpk, const float* bias, const float* depth_range, float* view_weight,
                                      float* pair_depth, int S, int B, int D, int h, int w, void* workspace, size_t workspace_bytes,
                                      void* stream);
+/* ... and with `prob` in the form F(2x4, 3x3): wpk as adamvs_conv3x3_dd_wino24, the same partials, merge kernel and workspace. */
+int adamvs_prob_softmax_regress_wino24(const float* in, const float* wpk, const float* bias, const float* depth_range, float* view_weight,
+                                       float* pair_depth, int S, int B, int D, int h, int w, void* workspace, size_t workspace_bytes,
+                                       void* stream);
 
 /* ---- aggregation + recurrent regularisation (pass B) --------------------- */
 
