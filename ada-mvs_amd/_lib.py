@@ -199,6 +199,16 @@ SIGNATURES = {
                                ctypes.c_long, ctypes.c_void_p, c_st]),
     "adamvs_bld_label": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.POINTER(BldStats), c_st]),
     "adamvs_bld_table": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
+    "adamvs_roof_workspace_bytes": (ctypes.c_long, [c_i, c_i]),
+    "adamvs_roof_links": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                ctypes.c_void_p, c_st]),
+    "adamvs_roof_label": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.POINTER(BldStats), c_st]),
+    "adamvs_roof_moments": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_long,
+                                  ctypes.c_void_p, c_st]),
+    "adamvs_roof_grow": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_long, ctypes.c_void_p, ctypes.c_double,
+                               c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_roof_residuals": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_long, ctypes.c_void_p,
+                                    ctypes.c_double, ctypes.c_void_p, c_st]),
     "adamvs_mesh_check_views": (c_i, [ctypes.POINTER(MeshView), c_i]),
     "adamvs_tsdf_integrate": (c_i, [ctypes.POINTER(MeshBrick), ctypes.c_void_p, c_i, ctypes.c_void_p, c_i, c_f, ctypes.c_void_p,
                                     ctypes.c_void_p, c_st]),
@@ -338,6 +348,11 @@ BLD_MAX_ROUNDS = 64              # ADAMVS_BLD_MAX_ROUNDS: cap on the border roun
 BLD_NOT_CONVERGED = -2           # ADAMVS_BLD_NOT_CONVERGED
 BLD_COLUMNS = ("cells", "smooth", "rough", "undetermined", "row_min", "row_max", "col_min", "col_max", "height_sum",
                "height_max_bits")  # ADAMVS_BLD_CELLS .. ADAMVS_BLD_HEIGHT_MAX_BITS: the rows of the component table
+ROOF_MAX_SIDE = 32768            # ADAMVS_ROOF_MAX_SIDE: largest W and H of the roof stage, cells
+ROOF_MAX_GROW = 256              # ADAMVS_ROOF_MAX_GROW: cap on the growth rounds
+ROOF_Q_SCALE, ROOF_Q_MAX = 256, (1 << 19) - 1  # ADAMVS_ROOF_Q_SCALE / _Q_MAX: quantised height above z_ref, 1/256 m
+ROOF_COLUMNS = ("n", "su", "sv", "sq", "suu", "suv", "svv", "suq", "svq", "sqq_lo", "sqq_hi", "row_min", "row_max", "col_min", "col_max",
+                "q_min", "q_max", "building")  # ADAMVS_ROOF_N .. ADAMVS_ROOF_BUILDING: the rows of the moments table
 MESH_TILE = 256                  # ADAMVS_MESH_TILE: samples / cubes per workgroup of the mesh kernels
 MESH_BRICKS = (32, 64, 128)      # the brick sizes B
 MESH_MAX_VIEWS = 65535           # ADAMVS_MESH_MAX_VIEWS

@@ -573,6 +573,85 @@ extern "C" int adamvs_bld_table(int W, int H, const unsigned char* flags, const 
   return launch_bld_table(W, H, flags, ndsm, label, N, table, (hipStream_t)stream);
 }
 
+// ---- Roof planes (dsm_roofs.hip)
+static int roof_check_size(int W, int H, const char* what) {
+  ADAMVS_CHECK_ARG(W > 0 && H > 0 && W <= ADAMVS_ROOF_MAX_SIDE && H <= ADAMVS_ROOF_MAX_SIDE && (long)W * H <= ADAMVS_DSM_MAX_CELLS,
+                   "%s: grid W=%d H=%d (each <= %d, W H <= %d cells)", what, W, H, ADAMVS_ROOF_MAX_SIDE, ADAMVS_DSM_MAX_CELLS);
+  return 0;
+}
+
+static bool roof_tol_ok(double v) { return std::isfinite(v) && v >= 0.0; }
+
+extern "C" long adamvs_roof_workspace_bytes(int W, int H) {
+  if (int rc = roof_check_size(W, H, "roof_workspace_bytes")) return rc;
+  return roof_workspace_bytes(W, H);
+}
+
+extern "C" int adamvs_roof_links(int W, int H, const float* dsm, const int* building, int s, double smooth_tol, double g_tol,
+                                 double step_tol, unsigned char* link, void* stream) {
+  if (int rc = roof_check_size(W, H, "roof_links")) return rc;
+  ADAMVS_CHECK_ARG(dsm && building && link, "roof_links: null pointer");
+  ADAMVS_CHECK_ARG(s >= 1 && s <= ADAMVS_BLD_MAX_STRIDE, "roof_links: s=%d (1 .. %d)", s, ADAMVS_BLD_MAX_STRIDE);
+  ADAMVS_CHECK_ARG(roof_tol_ok(smooth_tol) && roof_tol_ok(g_tol) && roof_tol_ok(step_tol),
+                   "roof_links: smooth_tol=%g, g_tol=%g, step_tol=%g must be finite and >= 0", smooth_tol, g_tol, step_tol);
+  const long n = (long)W * H;
+  const BldBuffer b[] = {{dsm, 4 * n}, {building, 4 * n}, {link, n}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 3), "roof_links: dsm, building and link must not overlap");
+  return launch_roof_links(W, H, dsm, building, s, smooth_tol, g_tol, step_tol, link, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_roof_label(int W, int H, const unsigned char* link, void* workspace, long workspace_bytes, int* parent,
+                                 adamvs_bld_stats* stats, void* stream) {
+  if (int rc = roof_check_size(W, H, "roof_label")) return rc;
+  ADAMVS_CHECK_ARG(link && workspace && parent && stats, "roof_label: null pointer");
+  const long need = roof_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "roof_label: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{link, n}, {parent, 4 * n}, {workspace, need}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 3), "roof_label: link, parent and the workspace must not overlap");
+  return launch_roof_label(W, H, link, workspace, parent, stats, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_roof_moments(int W, int H, const float* dsm, const int* label, const int* building, double z_ref, long N,
+                                   long long* table, void* stream) {
+  if (int rc = roof_check_size(W, H, "roof_moments")) return rc;
+  const long n = (long)W * H;
+  ADAMVS_CHECK_ARG(N >= 0 && N <= n, "roof_moments: N=%ld (0 .. W H = %ld)", N, n);
+  ADAMVS_CHECK_ARG(dsm && label && building && (table || N == 0), "roof_moments: null pointer");
+  ADAMVS_CHECK_ARG(std::isfinite(z_ref), "roof_moments: z_ref=%g must be finite", z_ref);
+  const BldBuffer b[] = {{dsm, 4 * n}, {label, 4 * n}, {building, 4 * n}, {table, 8L * ADAMVS_ROOF_COLUMNS * N}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, N ? 4 : 3), "roof_moments: dsm, label, building and the table must not overlap");
+  return launch_roof_moments(W, H, dsm, label, building, z_ref, N, table, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_roof_grow(int W, int H, const float* dsm, const int* building, double z_ref, long P, const double* planes,
+                                double assign_tol, int round0, int rounds, int* label0, int* label1, unsigned* counts, void* stream) {
+  if (int rc = roof_check_size(W, H, "roof_grow")) return rc;
+  const long n = (long)W * H;
+  ADAMVS_CHECK_ARG(P >= 0 && P <= n, "roof_grow: P=%ld (0 .. W H = %ld)", P, n);
+  ADAMVS_CHECK_ARG(dsm && building && (planes || P == 0) && label0 && label1 && counts, "roof_grow: null pointer");
+  ADAMVS_CHECK_ARG(std::isfinite(z_ref), "roof_grow: z_ref=%g must be finite", z_ref);
+  ADAMVS_CHECK_ARG(roof_tol_ok(assign_tol), "roof_grow: assign_tol=%g must be finite and >= 0", assign_tol);
+  ADAMVS_CHECK_ARG(round0 >= 0 && rounds >= 0 && round0 <= ADAMVS_ROOF_MAX_GROW && rounds <= ADAMVS_ROOF_MAX_GROW - round0,
+                   "roof_grow: rounds %d .. %d + %d (at most %d in all)", round0, round0, rounds, ADAMVS_ROOF_MAX_GROW);
+  const BldBuffer b[] = {{dsm, 4 * n}, {building, 4 * n}, {label0, 4 * n}, {label1, 4 * n}, {counts, 4L * ADAMVS_ROOF_MAX_GROW},
+                         {planes, 24 * P}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, P ? 6 : 5), "roof_grow: dsm, building, the two label buffers, counts and planes must not overlap");
+  return launch_roof_grow(W, H, dsm, building, z_ref, P, planes, assign_tol, round0, rounds, label0, label1, counts, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_roof_residuals(int W, int H, const float* dsm, const int* label, double z_ref, long R, const double* planes,
+                                     double assign_tol, long long* table, void* stream) {
+  if (int rc = roof_check_size(W, H, "roof_residuals")) return rc;
+  const long n = (long)W * H;
+  ADAMVS_CHECK_ARG(R >= 0 && R <= n, "roof_residuals: R=%ld (0 .. W H = %ld)", R, n);
+  ADAMVS_CHECK_ARG(dsm && label && ((planes && table) || R == 0), "roof_residuals: null pointer");
+  ADAMVS_CHECK_ARG(std::isfinite(z_ref), "roof_residuals: z_ref=%g must be finite", z_ref);
+  ADAMVS_CHECK_ARG(roof_tol_ok(assign_tol), "roof_residuals: assign_tol=%g must be finite and >= 0", assign_tol);
+  const BldBuffer b[] = {{dsm, 4 * n}, {label, 4 * n}, {planes, 24 * R}, {table, 16 * R}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, R ? 4 : 2), "roof_residuals: dsm, label, planes and the table must not overlap");
+  return launch_roof_residuals(W, H, dsm, label, z_ref, R, planes, assign_tol, table, (hipStream_t)stream);
+}
+
 // ---- TSDF mesh (mesh.hip): every argument is checked here, before any launch
 static int mesh_check_brick(const adamvs_mesh_brick* b, const char* what) {
   ADAMVS_CHECK_ARG(b, "%s: null brick", what);

@@ -30,6 +30,7 @@
 // so flags, labels and the table are bit-identical from run to run.
 #include <math.h>
 
+#include "bld_union.h"
 #include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
@@ -37,13 +38,6 @@
 #pragma clang fp contract(off)
 
 namespace adamvs {
-
-constexpr int BLD_THREADS = 256;
-constexpr int BLD_CELLS = BLD_TILE_W * BLD_TILE_H;
-static_assert(BLD_TILE_W == 64, "a wave takes one row of a tile");
-static_assert(BLD_TILE_H % (BLD_THREADS / 64) == 0, "the waves share the rows of a tile evenly");
-
-static inline unsigned bld_blocks(long n) { return (unsigned)((n + BLD_THREADS - 1) / BLD_THREADS); }
 
 // ---- mask and flags ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BLD_THREADS) void k_bld_mask(long n, const float* __restrict__ ndsm, double min_height,
@@ -85,14 +79,6 @@ __global__ __launch_bounds__(BLD_THREADS) void k_bld_flags(int W, int H, const f
 }
 
 // ---- labels: the tile phase -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int bld_lds_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// the root of x: labels point strictly downwards until the root, which points to itself
-__device__ __forceinline__ int bld_find(const int* l, int x) {
-  for (int p = bld_lds_load(l + x); p != x; p = bld_lds_load(l + x)) x = p;
-  return x;
-}
-
 __global__ __launch_bounds__(BLD_THREADS) void k_bld_tile(int W, int H, int tiles_x, const uint8_t* __restrict__ flags,
                                                           int* __restrict__ parent) {
   __shared__ int s_l[BLD_CELLS];
@@ -141,29 +127,7 @@ __global__ __launch_bounds__(BLD_THREADS) void k_bld_tile(int W, int H, int tile
 }
 
 // ---- labels: the border rounds ----------------------------------------------------------------------------------------------
-// Pair p: first the pairs across the vertical borders (columns x - 1 | x, x a multiple of BLD_TILE_W; H per border), then
-// those across the horizontal borders (W per border).
-__device__ __forceinline__ void bld_pair_cells(long p, int W, int H, long n_vertical, long& a, long& b) {
-  if (p < n_vertical) {
-    const long border = p / H;
-    const long i = p - border * H;
-    b = i * W + (border + 1) * BLD_TILE_W;
-    a = b - 1;
-  } else {
-    const long q = p - n_vertical;
-    const long border = q / W;
-    const long jj = q - border * W;
-    b = (border + 1) * BLD_TILE_H * (long)W + jj;
-    a = b - W;
-  }
-}
-
-// the root of cell v in a forest nobody writes during this kernel (strictly downwards, so it ends)
-__device__ __forceinline__ int bld_root(const int* __restrict__ parent, int v) {
-  for (int q = parent[v]; q >= 0 && q < v; q = parent[v]) v = q;
-  return v;
-}
-
+// The pairs and their order, and the walk to a root: bld_union.h (shared with dsm_roofs.hip).
 __global__ __launch_bounds__(BLD_THREADS) void k_bld_pairs(int W, int H, long n_vertical, long n_pairs, const int* __restrict__ parent,
                                                            int2* __restrict__ pairs, unsigned* __restrict__ changed) {
   const long p = (long)blockIdx.x * BLD_THREADS + threadIdx.x;
@@ -276,12 +240,6 @@ __global__ __launch_bounds__(BLD_THREADS) void k_bld_table(int W, int H, const u
 // ---- host side --------------------------------------------------------------------------------------------------------------
 static long bld_align(long b) { return (b + 255) & ~255L; }
 
-static long bld_pairs_count(int W, int H, long* n_vertical) {
-  const long v = (long)H * (cdiv(W, BLD_TILE_W) - 1), h = (long)W * (cdiv(H, BLD_TILE_H) - 1);
-  if (n_vertical) *n_vertical = v;
-  return v + h;
-}
-
 // Workspace: a control block (256 B), then either [m0 | m | the opening's workspace] (_bld_flags) or the pairs of a round
 // (_bld_label: at most W H / 32 pairs of 8 bytes, far below the rasters).
 long bld_workspace_bytes(int W, int H) { return 256 + 2 * bld_align(4L * W * H) + dtm_workspace_bytes(W, H); }
@@ -306,23 +264,24 @@ int launch_bld_flags(int W, int H, const float* dsm, const float* ndsm, double m
   return 0;
 }
 
-// device-side stopwatch of _bld_label's three groups: four events on the stream, read after the final synchronise
-struct BldClock {
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool ok = true;
-  BldClock() {
-    for (auto& e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  }
-  ~BldClock() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  void mark(int k, hipStream_t st) { ok = ok && hipEventRecord(ev[k], st) == hipSuccess; }
-  float ms(int k) {
-    float t = 0.0f;
-    return ok && hipEventElapsedTime(&t, ev[k], ev[k + 1]) == hipSuccess ? t : -1.0f;
-  }
-};
+// one round's second and third kernel and the final walk, for both labellings (bld_union.h)
+int launch_bld_hook(long n_pairs, long n, const int2* pairs, int* parent, hipStream_t st) {
+  hipLaunchKernelGGL(k_bld_hook, dim3(bld_blocks(n_pairs)), dim3(BLD_THREADS), 0, st, n_pairs, n, pairs, parent);
+  ADAMVS_CHECK_LAUNCH("bld_hook");
+  return 0;
+}
+
+int launch_bld_compress(int W, int H, long n_vertical, long n_pairs, int* parent, hipStream_t st) {
+  hipLaunchKernelGGL(k_bld_compress, dim3(bld_blocks(n_pairs)), dim3(BLD_THREADS), 0, st, W, H, n_vertical, n_pairs, parent);
+  ADAMVS_CHECK_LAUNCH("bld_compress");
+  return 0;
+}
+
+int launch_bld_compress_all(long n, int* parent, hipStream_t st) {
+  hipLaunchKernelGGL(k_bld_compress_all, dim3(bld_blocks(n)), dim3(BLD_THREADS), 0, st, n, parent);
+  ADAMVS_CHECK_LAUNCH("bld_compress_all");
+  return 0;
+}
 
 int launch_bld_label(int W, int H, const uint8_t* flags, void* workspace, int* parent, adamvs_bld_stats* stats, hipStream_t st) {
   const long n = (long)W * H;
@@ -352,16 +311,13 @@ int launch_bld_label(int W, int H, const uint8_t* flags, void* workspace, int* p
     if (e != hipSuccess) return set_error((int)e, "bld_label: %s", hipGetErrorString(e));
     open = host != 0;
     if (!open || stats->rounds == ADAMVS_BLD_MAX_ROUNDS) break;
-    hipLaunchKernelGGL(k_bld_hook, dim3(bld_blocks(n_pairs)), dim3(BLD_THREADS), 0, st, n_pairs, n, (const int2*)pairs, parent);
-    ADAMVS_CHECK_LAUNCH("bld_hook");
-    hipLaunchKernelGGL(k_bld_compress, dim3(bld_blocks(n_pairs)), dim3(BLD_THREADS), 0, st, W, H, n_vertical, n_pairs, parent);
-    ADAMVS_CHECK_LAUNCH("bld_compress");
+    if (int rc = launch_bld_hook(n_pairs, n, pairs, parent, st)) return rc;
+    if (int rc = launch_bld_compress(W, H, n_vertical, n_pairs, parent, st)) return rc;
     ++stats->rounds;
   }
   if (open) return set_error(ADAMVS_BLD_NOT_CONVERGED, "bld_label: tile borders still open after %d rounds", ADAMVS_BLD_MAX_ROUNDS);
   clock.mark(2, st);
-  hipLaunchKernelGGL(k_bld_compress_all, dim3(bld_blocks(n)), dim3(BLD_THREADS), 0, st, n, parent);
-  ADAMVS_CHECK_LAUNCH("bld_compress_all");
+  if (int rc = launch_bld_compress_all(n, parent, st)) return rc;
   clock.mark(3, st);
   const hipError_t e = hipStreamSynchronize(st);
   if (e != hipSuccess) return set_error((int)e, "bld_label: %s", hipGetErrorString(e));

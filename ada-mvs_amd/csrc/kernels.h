@@ -196,6 +196,18 @@ int launch_bld_flags(int W, int H, const float* dsm, const float* ndsm, double m
 int launch_bld_label(int W, int H, const uint8_t* flags, void* workspace, int* parent, adamvs_bld_stats* stats, hipStream_t st);
 int launch_bld_table(int W, int H, const uint8_t* flags, const float* ndsm, const int* label, long N, long long* table, hipStream_t st);
 
+// dsm_roofs.hip: link bits, segments, integer moments, growth rounds and residuals (include/adamvs_hip.h, "Roof planes")
+long roof_workspace_bytes(int W, int H);
+int launch_roof_links(int W, int H, const float* dsm, const int* building, int s, double smooth_tol, double g_tol, double step_tol,
+                      uint8_t* link, hipStream_t st);
+int launch_roof_label(int W, int H, const uint8_t* link, void* workspace, int* parent, adamvs_bld_stats* stats, hipStream_t st);
+int launch_roof_moments(int W, int H, const float* dsm, const int* label, const int* building, double z_ref, long N, long long* table,
+                        hipStream_t st);
+int launch_roof_grow(int W, int H, const float* dsm, const int* building, double z_ref, long P, const double* planes, double assign_tol,
+                     int round0, int rounds, int* label0, int* label1, unsigned* counts, hipStream_t st);
+int launch_roof_residuals(int W, int H, const float* dsm, const int* label, double z_ref, long R, const double* planes, double assign_tol,
+                          long long* table, hipStream_t st);
+
 // mesh.hip: TSDF integration and marching-tetrahedra extraction per brick (include/adamvs_hip.h, "TSDF mesh")
 constexpr int MESH_TILE = ADAMVS_MESH_TILE;
 int launch_tsdf_integrate(const adamvs_mesh_brick& b, const adamvs_mesh_view* views, int nviews, const int* list, int nlist, float* tsdf,

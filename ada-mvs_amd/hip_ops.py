@@ -792,6 +792,91 @@ def bld_table(flags, ndsm, label, N):
     return table
 
 
+# ---- Roof planes (csrc/dsm_roofs.hip; include/adamvs_hip.h "Roof planes") -----------------------------------------------------
+def roof_links(dsm, building, s, smooth_tol, g_tol, step_tol):
+    """adamvs_roof_links: dsm [H, W] float32, building [H, W] int32 (device) -> link [H, W] uint8 (bit 0 core, bit 1 east link,
+    bit 2 south link).  Enqueued on the current stream."""
+    dsm = _bld_raster(dsm, "dsm", torch.float32)
+    building = _bld_raster(building, "building", torch.int32, dsm.shape)
+    H, W = dsm.shape
+    link = torch.empty(H, W, device=dsm.device, dtype=torch.uint8)
+    check(_lib.load().adamvs_roof_links(W, H, _p(dsm), _p(building), int(s), float(smooth_tol), float(g_tol), float(step_tol), _p(link),
+                                        _stream()), "roof_links")
+    return link
+
+
+def roof_label(link, workspace=None):
+    """adamvs_roof_label and the numbering: link [H, W] uint8 (device; any bit pattern) -> (segment [H, W] int32: 0 where bit 0
+    is clear, otherwise 1 .. S in ascending order of the segment's smallest cell index; S; parent [H, W] int32; _lib.BldStats).
+    Blocks until done."""
+    link = _bld_raster(link, "link", torch.uint8)
+    H, W = link.shape
+    need = _lib.load().adamvs_roof_workspace_bytes(W, H)
+    check(0 if need >= 0 else int(need), "roof_workspace_bytes")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=link.device, dtype=torch.uint8)
+    parent = torch.empty(H, W, device=link.device, dtype=torch.int32)
+    stats = _lib.BldStats()
+    check(_lib.load().adamvs_roof_label(W, H, _p(link), _p(workspace), workspace.numel(), _p(parent), ctypes.byref(stats), _stream()),
+          "roof_label")
+    flat = parent.view(-1)
+    root = flat == torch.arange(H * W, device=link.device, dtype=torch.int32)
+    number = torch.cumsum(root, 0, dtype=torch.int32)               # the scan over the roots: 1 .. S in ascending cell index
+    S = int(number[-1])
+    seg = torch.where(flat >= 0, number[flat.clamp(min=0).long()], torch.zeros((), device=link.device, dtype=torch.int32))
+    return seg.view(H, W), S, parent, stats
+
+
+def roof_moments(dsm, label, building, z_ref, N):
+    """adamvs_roof_moments: -> table [len(_lib.ROOF_COLUMNS), N] int64 (device), row k - 1 of each column for label k.
+    Enqueued on the current stream."""
+    dsm = _bld_raster(dsm, "dsm", torch.float32)
+    label = _bld_raster(label, "label", torch.int32, dsm.shape)
+    building = _bld_raster(building, "building", torch.int32, dsm.shape)
+    H, W = dsm.shape
+    table = torch.empty(len(_lib.ROOF_COLUMNS), int(N), device=dsm.device, dtype=torch.int64)
+    check(_lib.load().adamvs_roof_moments(W, H, _p(dsm), _p(label), _p(building), float(z_ref), int(N), _p(table), _stream()), "roof_moments")
+    return table
+
+
+def _roof_planes(planes, device):
+    planes = _dev_as(planes, "planes", torch.float64)
+    if planes.dim() != 2 or planes.shape[1] != 3:
+        raise _lib.AdaMVSHipError("planes must be [P, 3] float64, got %s" % (tuple(planes.shape),))
+    return planes
+
+
+def roof_grow(dsm, building, z_ref, planes, assign_tol, label0, label1, counts, round0, rounds):
+    """adamvs_roof_grow: the rounds round0 .. round0 + rounds - 1, round k from label[k & 1] into label[(k + 1) & 1] (label0,
+    label1 [H, W] int32, device), counts uint32-as-int32 [_lib.ROOF_MAX_GROW] (device).  Enqueued on the current stream."""
+    dsm = _bld_raster(dsm, "dsm", torch.float32)
+    building = _bld_raster(building, "building", torch.int32, dsm.shape)
+    label0 = _bld_raster(label0, "label0", torch.int32, dsm.shape)
+    label1 = _bld_raster(label1, "label1", torch.int32, dsm.shape)
+    counts = _dev_as(counts, "counts", torch.int32)
+    if counts.numel() != _lib.ROOF_MAX_GROW:
+        raise _lib.AdaMVSHipError("counts must hold %d words, got %d" % (_lib.ROOF_MAX_GROW, counts.numel()))
+    planes = _roof_planes(planes, dsm.device)
+    H, W = dsm.shape
+    check(_lib.load().adamvs_roof_grow(W, H, _p(dsm), _p(building), float(z_ref), planes.shape[0], _p(planes) if planes.shape[0] else None,
+                                       float(assign_tol), int(round0), int(rounds), _p(label0), _p(label1), _p(counts), _stream()),
+          "roof_grow")
+
+
+def roof_residuals(dsm, label, z_ref, planes, assign_tol):
+    """adamvs_roof_residuals: -> table [2, R] int64 (device): the inlier count and the largest llrint(e * 1024) per plane.
+    Enqueued on the current stream."""
+    dsm = _bld_raster(dsm, "dsm", torch.float32)
+    label = _bld_raster(label, "label", torch.int32, dsm.shape)
+    planes = _roof_planes(planes, dsm.device)
+    H, W = dsm.shape
+    R = planes.shape[0]
+    table = torch.empty(2, R, device=dsm.device, dtype=torch.int64)
+    check(_lib.load().adamvs_roof_residuals(W, H, _p(dsm), _p(label), float(z_ref), R, _p(planes) if R else None, float(assign_tol),
+                                            _p(table) if R else None, _stream()), "roof_residuals")
+    return table
+
+
 # ---- TSDF mesh (csrc/mesh.hip; driven brick by brick by ada_mvs_amd/mesh.py) ------------------------------------------------
 # Per-sample state as torch tensors of the signed type of each C type's width: weight int16 = uint16, rgba int32 = uint32
 # (little-endian r g b a), cube_code int32 = uint32, faces int32 = uint32.

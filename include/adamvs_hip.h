@@ -765,6 +765,90 @@ int adamvs_bld_label(int W, int H, const unsigned char* flags, void* workspace, 
 int adamvs_bld_table(int W, int H, const unsigned char* flags, const float* ndsm, const int* label, long N, long long* table,
                      void* stream);
 
+/* ---- Roof planes (after the building extraction): the roof of every building cut into planar faces --------------------------
+ * ada-mvs_amd/roofs.py extract(); roofs_whu.py is the CLI.  Inputs: dsm [H][W] fp32 (Z, NaN where there is no value) and
+ * building [H][W] int32 (0 = none, 1 .. B, the label raster of buildings_whu.py).  W, H <= ADAMVS_ROOF_MAX_SIDE and
+ * W H <= ADAMVS_DSM_MAX_CELLS.  A cell is c = (i, j), its index i W + j, rows running south; u = j, v = i.  Smoothness-constraint
+ * region growing (Rabbani et al. 2006) restated without a visiting order.  The caller derives s = max(1, round(smooth_span / gsd))
+ * (1 .. ADAMVS_BLD_MAX_STRIDE), g_tol = slope_tol * (2 s gsd) (metres over 2 s cells) and z_ref = floor(min finite Z).  Every
+ * floating-point operation below is fp64 on the fp32 inputs widened first, in the order written, no contraction.
+ *
+ * 1. Links (_roof_links), uint8 [H][W].  Cell c is CORE iff building(c) = b > 0, the four cells (i, j -+ s), (i -+ s, j) are inside
+ *    the grid, carry the label b and have a finite Z, Z(c) is finite, and
+ *      fabs((Z(i, j + s) + Z(i, j - s)) - 2.0 * Z(c)) <= smooth_tol   and   fabs((Z(i + s, j) + Z(i - s, j)) - 2.0 * Z(c)) <= smooth_tol.
+ *    Gradients of a core cell: gx = Z(i, j + s) - Z(i, j - s), gy = Z(i + s, j) - Z(i - s, j).  Core cell a has an EAST link to
+ *    b = (i, j + 1) iff b is inside the grid and core with the same building label, fabs(gx(a) - gx(b)) <= g_tol,
+ *    fabs(gy(a) - gy(b)) <= g_tol and fabs((Z(b) - Z(a)) - (gx(a) + gx(b)) / (4.0 * s)) <= step_tol.  The SOUTH link to
+ *    b = (i + 1, j) is the same with (gy(a) + gy(b)) in the last test.  Every test is symmetric in a and b.
+ *    link(c) = core | east << 1 | south << 2.
+ * 2. Segments (_roof_label): the connected components of the graph whose nodes are the cells with bit 0 set and whose edges
+ *    are: c - (i, j + 1) iff bit 1 of link(c) is set, c - (i + 1, j) iff bit 2 is set, and in both cases both cells are inside the
+ *    grid and have bit 0 set (a link bit on a cell without bit 0, or towards such a cell or the outside, is ignored; bits 3 .. 7
+ *    are ignored).  Two adjacent core cells without a link are NOT joined.  parent int32 [H][W]: -1 where bit 0 is clear,
+ *    otherwise the smallest cell index of the segment.  Segments are numbered 1 .. S in ascending order of that index.
+ * 3. Moments (_roof_moments), int64 [ADAMVS_ROOF_COLUMNS][N], row k - 1 for label k; any label raster (0 or outside 1 .. N =
+ *    no label).  q = llrint(min(max((Z - z_ref) * 256.0, 0.0), 524287.0)) (round to nearest, ties to even: 0 .. 2^19 - 1).  Over
+ *    the cells with label k and a finite Z: n, su, sv, sq, suu, suv, svv, suq, svq (sums of 1, u, v, q, u u, u v, v v, u q, v q),
+ *    sqq_lo = sum of (q q & 0xFFFFF), sqq_hi = sum of (q q >> 20), row_min, row_max, col_min, col_max, q_min, q_max, building
+ *    (the largest building(c)).  A label without such a cell: sums 0, minima 2^31 - 1, maxima -1.
+ *    Overflow: with u, v < 2^15, q < 2^19 and at most 2^28 cells the largest sums are suq, svq < 2^15 2^19 2^28 = 2^62,
+ *    suu, suv, svv < 2^58, sqq_lo < 2^48, sqq_hi < 2^18 2^28 = 2^46: every sum stays below 2^63.
+ * 4. Planes (host, exact integers).  With Suu = n suu - su su, Svv = n svv - sv sv, Suv = n suv - su sv, Suq = n suq - su sq,
+ *    Svq = n svq - sv sq and D = Suu Svv - Suv Suv: a segment is kept iff n gsd^2 >= min_plane_area and D != 0.  The plane
+ *    q ~ a u + b v + c is a = (Suq Svv - Svq Suv) / D, b = (Svq Suu - Suq Suv) / D, c = (sq - a su - b sv) / n as rationals, its
+ *    sse = sqq - a suq - b svq - c sq with sqq = sqq_lo + (sqq_hi << 20).  Each of a / 256, b / 256, c / 256 is rounded once to
+ *    fp64: metres per cell, metres per cell, metres above z_ref.  Kept segments are renumbered 1 .. P in order.
+ * 5. Growth (_roof_grow), rounds over two label buffers.  In a round a cell with building(c) > 0, a finite Z and label 0 looks at
+ *    its four neighbours' labels as of the previous round.  Candidates: the labels 1 <= p <= P on neighbours inside the grid with
+ *    building(neighbour) == building(c).  e_p = fabs((Z - z_ref) - ((a_p * j + b_p * i) + c_p)).  The cell takes the candidate of
+ *    least e_p, ties to the smaller p, iff that e_p <= assign_tol (a NaN e_p is never the least and never passes).  Every other
+ *    cell keeps its label.  counts[k] = the cells labelled in round k.  A round that labels nothing is a fixed point.
+ * 6. Merge (host): ada-mvs_amd/roofs.py merge_planes().  7. Residuals (_roof_residuals), int64 [2][R], row p - 1 for label p, over
+ *    the cells with label p and a finite Z: row 0 the count of cells with e_p <= assign_tol, row 1 the largest
+ *    llrint(min(e_p * 1024.0, 1048576.0)) (a NaN e_p: not counted, and the largest is 1048576); both 0 for a label without cells.
+ *
+ * Kernels (csrc/dsm_roofs.hip).  _roof_links: one pass, one lane per cell, the stride neighbours of the cell, of its east and of
+ * its south neighbour read straight from global memory (coalesced row segments served by L2, as in _bld_flags).  _roof_label:
+ * the scheme of _bld_label with the link bits in place of the mask: tiles of ADAMVS_BLD_TILE_W x ADAMVS_BLD_TILE_H in LDS (a
+ * row run starts after the nearest lane to the left whose east edge is missing; vertical unions where the upper cell's south
+ * edge exists), then rounds over the tile-border pairs whose edge exists: pairs kernel, hook kernel, compress kernel (the last
+ * two are the building stage's), at most ADAMVS_BLD_MAX_ROUNDS rounds, more is ADAMVS_BLD_NOT_CONVERGED.  No workgroup waits
+ * on another; visibility between rounds comes from the kernel boundaries; every loop is bounded.  _roof_moments and
+ * _roof_residuals: integer atomics only, one set per run of equal labels in a wave (a segmented shuffle reduction).
+ * _roof_grow runs the rounds round0 .. round0 + rounds - 1, one launch each: round k reads label[k & 1] and writes every cell of
+ * label[(k + 1) & 1], counts[k] is zeroed first; round0 + rounds <= ADAMVS_ROOF_MAX_GROW.  The caller may read counts back
+ * between calls and stop after a round that labelled nothing.  Everything is bit-identical from run to run: no floating-point
+ * atomic, no floating-point sum.  Only _roof_label blocks.
+ * All buffers device memory (planes: fp64 [P][3] = a, b, c of step 4; counts: uint32 [ADAMVS_ROOF_MAX_GROW]); workspace of at
+ * least _roof_workspace_bytes(W, H) bytes, 256-byte aligned; stats: a HOST pointer.
+ * Argument errors (<0, before any launch): a null pointer, W or H <= 0 or > ADAMVS_ROOF_MAX_SIDE or W H > ADAMVS_DSM_MAX_CELLS,
+ * s outside 1 .. ADAMVS_BLD_MAX_STRIDE, a tolerance or z_ref not finite, a tolerance < 0, N, P or R < 0 or > W H, rounds < 0,
+ * round0 < 0 or round0 + rounds > ADAMVS_ROOF_MAX_GROW, workspace_bytes below the query, any two buffers overlapping.
+ * _roof_workspace_bytes returns < 0 for a grid outside the limits. */
+#define ADAMVS_ROOF_MAX_SIDE 32768
+#define ADAMVS_ROOF_MAX_GROW 256
+#define ADAMVS_ROOF_Q_SCALE 256
+#define ADAMVS_ROOF_Q_MAX 524287 /* 2^19 - 1 */
+#define ADAMVS_ROOF_COLUMNS 18
+enum {
+  ADAMVS_ROOF_N = 0, ADAMVS_ROOF_SU = 1, ADAMVS_ROOF_SV = 2, ADAMVS_ROOF_SQ = 3, ADAMVS_ROOF_SUU = 4, ADAMVS_ROOF_SUV = 5,
+  ADAMVS_ROOF_SVV = 6, ADAMVS_ROOF_SUQ = 7, ADAMVS_ROOF_SVQ = 8, ADAMVS_ROOF_SQQ_LO = 9, ADAMVS_ROOF_SQQ_HI = 10,
+  ADAMVS_ROOF_ROW_MIN = 11, ADAMVS_ROOF_ROW_MAX = 12, ADAMVS_ROOF_COL_MIN = 13, ADAMVS_ROOF_COL_MAX = 14, ADAMVS_ROOF_Q_MIN = 15,
+  ADAMVS_ROOF_Q_MAX_COL = 16, ADAMVS_ROOF_BUILDING = 17
+};
+
+long adamvs_roof_workspace_bytes(int W, int H);
+int adamvs_roof_links(int W, int H, const float* dsm, const int* building, int s, double smooth_tol, double g_tol, double step_tol,
+                      unsigned char* link, void* stream);
+int adamvs_roof_label(int W, int H, const unsigned char* link, void* workspace, long workspace_bytes, int* parent,
+                      adamvs_bld_stats* stats, void* stream);
+int adamvs_roof_moments(int W, int H, const float* dsm, const int* label, const int* building, double z_ref, long N,
+                        long long* table, void* stream);
+int adamvs_roof_grow(int W, int H, const float* dsm, const int* building, double z_ref, long P, const double* planes,
+                     double assign_tol, int round0, int rounds, int* label0, int* label1, unsigned* counts, void* stream);
+int adamvs_roof_residuals(int W, int H, const float* dsm, const int* label, double z_ref, long R, const double* planes,
+                          double assign_tol, long long* table, void* stream);
+
 /* ---- TSDF mesh (after fuse_whu.py): the depth maps of all views integrated into a truncated signed-distance field on a voxel
  * grid, brick by brick, and its zero level set extracted as a coloured triangle mesh ---------------------------------------
  * ada-mvs_amd/mesh.py drives it per brick; mesh_whu.py is the CLI.  World axes: x east, y north, z up.
