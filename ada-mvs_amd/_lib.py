@@ -88,6 +88,12 @@ class BldStats(ctypes.Structure):
                 ("ms_tile", ctypes.c_float), ("ms_rounds", ctypes.c_float), ("ms_compress", ctypes.c_float)]
 
 
+class TreeStats(ctypes.Structure):
+    """adamvs_tree_stats"""
+    _fields_ = [("rounds", ctypes.c_int), ("converged", ctypes.c_int), ("tops", ctypes.c_long), ("candidates", ctypes.c_long),
+                ("window_cells", ctypes.c_long), ("ms_parents", ctypes.c_float), ("ms_jump", ctypes.c_float)]
+
+
 class MeshView(ctypes.Structure):
     """adamvs_mesh_view"""
     _fields_ = [("K", ctypes.c_float * 9), ("R", ctypes.c_float * 9), ("c", ctypes.c_float * 3), ("H", ctypes.c_int), ("W", ctypes.c_int),
@@ -209,6 +215,16 @@ SIGNATURES = {
                                c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
     "adamvs_roof_residuals": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_long, ctypes.c_void_p,
                                     ctypes.c_double, ctypes.c_void_p, c_st]),
+    "adamvs_tree_workspace_bytes": (ctypes.c_long, [c_i, c_i]),
+    "adamvs_tree_surface": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, c_i, ctypes.c_void_p, ctypes.c_long,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_tree_parents": (c_i, [c_i, c_i, ctypes.c_void_p, c_i, ctypes.POINTER(c_i), ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                  ctypes.POINTER(TreeStats), c_st]),
+    "adamvs_tree_roots": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.POINTER(TreeStats), c_st]),
+    "adamvs_tree_crowns": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_long, ctypes.c_void_p,
+                                 ctypes.c_void_p, c_st]),
+    "adamvs_tree_table": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                c_st]),
     "adamvs_mesh_check_views": (c_i, [ctypes.POINTER(MeshView), c_i]),
     "adamvs_tsdf_integrate": (c_i, [ctypes.POINTER(MeshBrick), ctypes.c_void_p, c_i, ctypes.c_void_p, c_i, c_f, ctypes.c_void_p,
                                     ctypes.c_void_p, c_st]),
@@ -353,6 +369,14 @@ ROOF_MAX_GROW = 256              # ADAMVS_ROOF_MAX_GROW: cap on the growth round
 ROOF_Q_SCALE, ROOF_Q_MAX = 256, (1 << 19) - 1  # ADAMVS_ROOF_Q_SCALE / _Q_MAX: quantised height above z_ref, 1/256 m
 ROOF_COLUMNS = ("n", "su", "sv", "sq", "suu", "suv", "svv", "suq", "svq", "sqq_lo", "sqq_hi", "row_min", "row_max", "col_min", "col_max",
                 "q_min", "q_max", "building")  # ADAMVS_ROOF_N .. ADAMVS_ROOF_BUILDING: the rows of the moments table
+TREE_TILE = 64                   # ADAMVS_TREE_TILE: cells of a side of a tile of the parents kernel
+TREE_MAX_RADIUS = 64             # ADAMVS_TREE_MAX_RADIUS: largest window radius of the local-maximum filter, cells
+TREE_MAX_ROUNDS = 32             # ADAMVS_TREE_MAX_ROUNDS: cap on the rounds of pointer jumping
+TREE_JUMP_HOPS = 8               # ADAMVS_TREE_JUMP_HOPS: parents followed per cell and round of pointer jumping
+TREE_NOT_CONVERGED = -2          # ADAMVS_TREE_NOT_CONVERGED
+TREE_Q_SCALE = 256               # ADAMVS_TREE_Q_SCALE: quantised height above ground, 1/256 m
+TREE_COLUMNS = ("cells", "q_sum", "q_max", "row_min", "row_max", "col_min", "col_max", "r2_max", "top",
+                "s_top")         # ADAMVS_TREE_CELLS .. ADAMVS_TREE_S_TOP: the rows of the tree table
 MESH_TILE = 256                  # ADAMVS_MESH_TILE: samples / cubes per workgroup of the mesh kernels
 MESH_BRICKS = (32, 64, 128)      # the brick sizes B
 MESH_MAX_VIEWS = 65535           # ADAMVS_MESH_MAX_VIEWS

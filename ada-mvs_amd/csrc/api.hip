@@ -652,6 +652,74 @@ extern "C" int adamvs_roof_residuals(int W, int H, const float* dsm, const int* 
   return launch_roof_residuals(W, H, dsm, label, z_ref, R, planes, assign_tol, table, (hipStream_t)stream);
 }
 
+// ---- Trees (dsm_trees.hip)
+extern "C" long adamvs_tree_workspace_bytes(int W, int H) {
+  if (int rc = dsm_fill_check_size(W, H, "tree_workspace_bytes")) return rc;
+  return tree_workspace_bytes(W, H);
+}
+
+extern "C" int adamvs_tree_surface(int W, int H, const float* ndsm, const int* building, double min_height, int smooth_passes,
+                                   void* workspace, long workspace_bytes, unsigned char* mask, int* q, int* s, int* s_max, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "tree_surface")) return rc;
+  ADAMVS_CHECK_ARG(ndsm && workspace && mask && q && s && s_max, "tree_surface: null pointer");
+  ADAMVS_CHECK_ARG(std::isfinite(min_height) && min_height > 0.0, "tree_surface: min_height=%g must be finite and > 0", min_height);
+  ADAMVS_CHECK_ARG(smooth_passes >= 0 && smooth_passes <= 2, "tree_surface: smooth_passes=%d (0 .. 2)", smooth_passes);
+  const long need = tree_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "tree_surface: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{ndsm, 4 * n}, {workspace, need}, {mask, n}, {q, 4 * n}, {s, 4 * n}, {s_max, 4}, {building, 4 * n}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, building ? 7 : 6), "tree_surface: ndsm, building, mask, q, s, s_max and the workspace must not overlap");
+  return launch_tree_surface(W, H, ndsm, building, min_height, smooth_passes, workspace, mask, q, s, s_max, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_tree_parents(int W, int H, const int* s, int r_cap, const int* thr, void* workspace, long workspace_bytes, int* parent,
+                                   adamvs_tree_stats* stats, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "tree_parents")) return rc;
+  ADAMVS_CHECK_ARG(s && thr && workspace && parent && stats, "tree_parents: null pointer");
+  ADAMVS_CHECK_ARG(r_cap >= 1 && r_cap <= ADAMVS_TREE_MAX_RADIUS, "tree_parents: r_cap=%d (1 .. %d)", r_cap, ADAMVS_TREE_MAX_RADIUS);
+  ADAMVS_CHECK_ARG(thr[0] == 0, "tree_parents: thr[1]=%d must be 0", thr[0]);
+  for (int k = 1; k < r_cap; ++k)
+    ADAMVS_CHECK_ARG(thr[k] >= thr[k - 1], "tree_parents: thr[%d]=%d is below thr[%d]=%d", k + 1, thr[k], k, thr[k - 1]);
+  const long need = tree_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "tree_parents: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{s, 4 * n}, {parent, 4 * n}, {workspace, need}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 3), "tree_parents: s, parent and the workspace must not overlap");
+  return launch_tree_parents(W, H, s, r_cap, thr, workspace, parent, stats, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_tree_roots(int W, int H, const int* parent, void* workspace, long workspace_bytes, int* root, adamvs_tree_stats* stats,
+                                 void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "tree_roots")) return rc;
+  ADAMVS_CHECK_ARG(parent && workspace && root && stats, "tree_roots: null pointer");
+  const long need = tree_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "tree_roots: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{parent, 4 * n}, {root, 4 * n}, {workspace, need}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 3), "tree_roots: parent, root and the workspace must not overlap");
+  return launch_tree_roots(W, H, parent, workspace, root, stats, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_tree_crowns(int W, int H, const int* s, const int* root, const int* number, int ratio_pm, long rc2, int* label,
+                                  long long* unassigned, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "tree_crowns")) return rc;
+  ADAMVS_CHECK_ARG(s && root && number && label && unassigned, "tree_crowns: null pointer");
+  ADAMVS_CHECK_ARG(ratio_pm >= 0 && ratio_pm <= 1000, "tree_crowns: ratio_pm=%d (0 .. 1000)", ratio_pm);
+  ADAMVS_CHECK_ARG(rc2 >= 0, "tree_crowns: rc2=%ld must be >= 0", rc2);
+  const long n = (long)W * H;
+  const BldBuffer b[] = {{s, 4 * n}, {root, 4 * n}, {number, 4 * n}, {label, 4 * n}, {unassigned, 8}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 5), "tree_crowns: s, root, number, label and unassigned must not overlap");
+  return launch_tree_crowns(W, H, s, root, number, ratio_pm, rc2, label, unassigned, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_tree_table(int W, int H, const int* label, const int* q, const int* s, const int* root, long T, long long* table,
+                                 void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "tree_table")) return rc;
+  const long n = (long)W * H;
+  ADAMVS_CHECK_ARG(T >= 0 && T <= n, "tree_table: T=%ld (0 .. W H = %ld)", T, n);
+  ADAMVS_CHECK_ARG(label && q && s && root && (table || T == 0), "tree_table: null pointer");
+  const BldBuffer b[] = {{label, 4 * n}, {q, 4 * n}, {s, 4 * n}, {root, 4 * n}, {table, 8L * ADAMVS_TREE_COLUMNS * T}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, T ? 5 : 4), "tree_table: label, q, s, root and the table must not overlap");
+  return launch_tree_table(W, H, label, q, s, root, T, table, (hipStream_t)stream);
+}
+
 // ---- TSDF mesh (mesh.hip): every argument is checked here, before any launch
 static int mesh_check_brick(const adamvs_mesh_brick* b, const char* what) {
   ADAMVS_CHECK_ARG(b, "%s: null brick", what);

@@ -208,6 +208,17 @@ int launch_roof_grow(int W, int H, const float* dsm, const int* building, double
 int launch_roof_residuals(int W, int H, const float* dsm, const int* label, double z_ref, long R, const double* planes, double assign_tol,
                           long long* table, hipStream_t st);
 
+// dsm_trees.hip: canopy surface, parents, roots, crown labels and the per-tree table (include/adamvs_hip.h, "Trees")
+long tree_workspace_bytes(int W, int H);
+int launch_tree_surface(int W, int H, const float* ndsm, const int* building, double min_height, int smooth_passes, void* workspace,
+                        uint8_t* mask, int* q, int* s, int* s_max, hipStream_t st);
+int launch_tree_parents(int W, int H, const int* s, int r_cap, const int* thr, void* workspace, int* parent, adamvs_tree_stats* stats,
+                        hipStream_t st);
+int launch_tree_roots(int W, int H, const int* parent, void* workspace, int* root, adamvs_tree_stats* stats, hipStream_t st);
+int launch_tree_crowns(int W, int H, const int* s, const int* root, const int* number, int ratio_pm, long rc2, int* label,
+                       long long* unassigned, hipStream_t st);
+int launch_tree_table(int W, int H, const int* label, const int* q, const int* s, const int* root, long T, long long* table, hipStream_t st);
+
 // mesh.hip: TSDF integration and marching-tetrahedra extraction per brick (include/adamvs_hip.h, "TSDF mesh")
 constexpr int MESH_TILE = ADAMVS_MESH_TILE;
 int launch_tsdf_integrate(const adamvs_mesh_brick& b, const adamvs_mesh_view* views, int nviews, const int* list, int nlist, float* tsdf,

@@ -877,6 +877,91 @@ def roof_residuals(dsm, label, z_ref, planes, assign_tol):
     return table
 
 
+# ---- Trees (csrc/dsm_trees.hip; include/adamvs_hip.h "Trees") -----------------------------------------------------------------
+def _tree_workspace(H, W, device, workspace):
+    need = _lib.load().adamvs_tree_workspace_bytes(W, H)
+    check(0 if need >= 0 else int(need), "tree_workspace_bytes")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=device, dtype=torch.uint8)
+    return workspace
+
+
+def tree_surface(ndsm, building, min_height, smooth_passes, workspace=None):
+    """adamvs_tree_surface: ndsm [H, W] float32, building [H, W] int32 or None (device) -> (mask uint8, q int32, s int32 (-1
+    outside the canopy), s_max int32 [1]), all on the device.  Enqueued on the current stream."""
+    ndsm = _bld_raster(ndsm, "ndsm", torch.float32)
+    if building is not None:
+        building = _bld_raster(building, "building", torch.int32, ndsm.shape)
+    H, W = ndsm.shape
+    workspace = _tree_workspace(H, W, ndsm.device, workspace)
+    mask = torch.empty(H, W, device=ndsm.device, dtype=torch.uint8)
+    q = torch.empty(H, W, device=ndsm.device, dtype=torch.int32)
+    s = torch.empty(H, W, device=ndsm.device, dtype=torch.int32)
+    s_max = torch.empty(1, device=ndsm.device, dtype=torch.int32)
+    check(_lib.load().adamvs_tree_surface(W, H, _p(ndsm), None if building is None else _p(building), float(min_height), int(smooth_passes),
+                                          _p(workspace), workspace.numel(), _p(mask), _p(q), _p(s), _p(s_max), _stream()), "tree_surface")
+    return mask, q, s, s_max
+
+
+def tree_parents(s, thr, workspace=None):
+    """adamvs_tree_parents: s [H, W] int32 (device), thr: the ascending thresholds thr[1 .. r_cap] (host integers, thr[1] = 0) ->
+    (parent [H, W] int32, _lib.TreeStats with candidates, window_cells and ms_parents set).  Blocks until done."""
+    s = _bld_raster(s, "s", torch.int32)
+    H, W = s.shape
+    thr = [int(v) for v in thr]
+    if any(v < -2 ** 31 or v >= 2 ** 31 for v in thr):
+        raise _lib.AdaMVSHipError("tree_parents: thr must hold int32 values")
+    workspace = _tree_workspace(H, W, s.device, workspace)
+    parent = torch.empty(H, W, device=s.device, dtype=torch.int32)
+    stats = _lib.TreeStats()
+    check(_lib.load().adamvs_tree_parents(W, H, _p(s), len(thr), (ctypes.c_int * max(len(thr), 1))(*thr), _p(workspace), workspace.numel(),
+                                          _p(parent), ctypes.byref(stats), _stream()), "tree_parents")
+    return parent, stats
+
+
+def tree_roots(parent, workspace=None, stats=None):
+    """adamvs_tree_roots and the numbering: parent [H, W] int32 (device) -> (root [H, W] int32, number [H, W] int32: at a top its
+    number 1 .. T in ascending cell index, T, _lib.TreeStats with rounds, converged, tops and ms_jump set; pass tree_parents'
+    stats to have both calls' fields in one).  Blocks until done."""
+    parent = _bld_raster(parent, "parent", torch.int32)
+    H, W = parent.shape
+    workspace = _tree_workspace(H, W, parent.device, workspace)
+    root = torch.empty(H, W, device=parent.device, dtype=torch.int32)
+    stats = _lib.TreeStats() if stats is None else stats
+    check(_lib.load().adamvs_tree_roots(W, H, _p(parent), _p(workspace), workspace.numel(), _p(root), ctypes.byref(stats), _stream()),
+          "tree_roots")
+    top = root.view(-1) == torch.arange(H * W, device=parent.device, dtype=torch.int32)
+    number = torch.cumsum(top, 0, dtype=torch.int32)                 # the scan over the tops: 1 .. T in ascending cell index
+    return root, number.view(H, W), int(number[-1]), stats
+
+
+def tree_crowns(s, root, number, ratio_pm, rc2):
+    """adamvs_tree_crowns: -> (label [H, W] int32: the number of the cell's top where both tests hold, else 0; unassigned int64
+    [1]: the canopy cells that fail one), on the device.  Enqueued on the current stream."""
+    s = _bld_raster(s, "s", torch.int32)
+    root = _bld_raster(root, "root", torch.int32, s.shape)
+    number = _bld_raster(number, "number", torch.int32, s.shape)
+    H, W = s.shape
+    label = torch.empty(H, W, device=s.device, dtype=torch.int32)
+    unassigned = torch.empty(1, device=s.device, dtype=torch.int64)
+    check(_lib.load().adamvs_tree_crowns(W, H, _p(s), _p(root), _p(number), int(ratio_pm), int(rc2), _p(label), _p(unassigned), _stream()),
+          "tree_crowns")
+    return label, unassigned
+
+
+def tree_table(label, q, s, root, T):
+    """adamvs_tree_table: -> table [len(_lib.TREE_COLUMNS), T] int64 (device), row k - 1 of each column for tree k.  Enqueued
+    on the current stream."""
+    label = _bld_raster(label, "label", torch.int32)
+    q = _bld_raster(q, "q", torch.int32, label.shape)
+    s = _bld_raster(s, "s", torch.int32, label.shape)
+    root = _bld_raster(root, "root", torch.int32, label.shape)
+    H, W = label.shape
+    table = torch.empty(len(_lib.TREE_COLUMNS), int(T), device=label.device, dtype=torch.int64)
+    check(_lib.load().adamvs_tree_table(W, H, _p(label), _p(q), _p(s), _p(root), int(T), _p(table) if T else None, _stream()), "tree_table")
+    return table
+
+
 # ---- TSDF mesh (csrc/mesh.hip; driven brick by brick by ada_mvs_amd/mesh.py) ------------------------------------------------
 # Per-sample state as torch tensors of the signed type of each C type's width: weight int16 = uint16, rgba int32 = uint32
 # (little-endian r g b a), cube_code int32 = uint32, faces int32 = uint32.

@@ -849,6 +849,104 @@ int adamvs_roof_grow(int W, int H, const float* dsm, const int* building, double
 int adamvs_roof_residuals(int W, int H, const float* dsm, const int* label, double z_ref, long R, const double* planes,
                           double assign_tol, long long* table, void* stream);
 
+/* ---- Trees (after the building extraction, independent of the roof planes): tree tops and their crowns from the nDSM --------
+ * ada-mvs_amd/trees.py detect(); trees_whu.py is the CLI.  Inputs: ndsm [H][W] fp32 as dtm_whu.py writes it (NaN where there is
+ * no value) and building [H][W] int32 (0 = none, the label raster of buildings_whu.py; a null pointer excludes nothing).  Outside
+ * the buildings the nDSM is a canopy height model.  W H <= ADAMVS_DSM_MAX_CELLS.  A cell is c = (i, j), its index i W + j.  The
+ * variable-window local-maximum filter (Popescu & Wynne 2004) and the marker-controlled crown growth with a height ratio and a
+ * radius limit (Dalponte & Coomes 2016), restated without a visiting order.  Every comparison below is on integers unless it
+ * says fp64.
+ *
+ * 1. Canopy.  C(c) iff ndsm(c) is finite, (double)ndsm(c) >= min_height (fp64, inclusive) and building(c) == 0.
+ *    q(c) = llrint(min((double)ndsm(c), 2047.0) * 256.0) on C (1 / ADAMVS_TREE_Q_SCALE m, round to nearest, ties to even); 0 outside C.
+ *    mask uint8 [H][W] is 1 on C, 0 elsewhere.
+ * 2. Smoothed surface s, int32 [H][W]; -1 outside C, where it is not defined.  s_0 = q; each of the smooth_passes (0 .. 2) passes
+ *    applies the 3 x 3 binomial weights w = (1 2 1) x (1 2 1) without a division:
+ *      s_k+1(c) = sum over d in {-1, 0, 1}^2 of w(d) (C(c + d) ? s_k(c + d) : s_k(c)),
+ *    a neighbour outside the grid or outside C contributing the centre's value.  s is q scaled by 16^passes: at most 2^27.
+ *    s_max = the largest s on C, -1 if C is empty.
+ * 3. Order.  c BEATS c' iff s(c) > s(c'), or s(c) == s(c') and index(c) < index(c').  A strict total order on C: plateaus need
+ *    no special case.
+ * 4. Window.  The caller passes an ascending table thr[1 .. r_cap] (int32, thr[1] = 0, 1 <= r_cap <= ADAMVS_TREE_MAX_RADIUS;
+ *    the C argument points at thr[1]).  r(c) = the largest r with s(c) >= thr[r].  ada-mvs_amd/trees.py window_table() builds it
+ *    in exact rational arithmetic: thr[r] is the smallest integer s with
+ *    floor((radius_min + radius_slope s / (256 16^passes)) / gsd) >= r, clamped below at 1; r_cap is that radius at s_max.
+ *    The window of c is the disc {c' in C : (i' - i)^2 + (j' - j)^2 <= r(c)^2}, clipped at the grid.
+ * 5. Tops.  c in C is a TOP iff no cell of its window and none of its eight neighbours beats it (from r = 2 on the window
+ *    contains the eight neighbours; the disc of r = 1 lacks the diagonal ones).
+ * 6. Parents, int32 [H][W], -1 outside C.  b(c) = the best (in the order of 3) of the up to eight neighbours of c in C.  If b(c)
+ *    exists and beats c: parent(c) = b(c).  Otherwise, if c is a top: parent(c) = c.  Otherwise parent(c) = the best cell of
+ *    c's window, which beats c because c is no top.  Every parent other than a root beats its child, so the parents form a
+ *    forest whose roots are exactly the tops; neither depends on a visiting order.
+ * 7. Roots, int32 [H][W]: root(c) = the top reached from c, -1 outside C (a parent outside 0 .. W H - 1 counts as -1), by
+ *    pointer jumping: round k writes, for every cell, next(c) = the cell ADAMVS_TREE_JUMP_HOPS parents up from c in the
+ *    previous round's buffer (a root is its own parent, so the walk stays there).  The distance to the root falls to an
+ *    eighth per round; at most ADAMVS_TREE_MAX_ROUNDS rounds, more is an error return (ADAMVS_TREE_NOT_CONVERGED), never a
+ *    longer loop.  stats.rounds = the rounds that moved a pointer.
+ * 8. Crowns.  The tops are numbered 1 .. T in ascending cell index (the caller scans the cells with root == own index into
+ *    number int32 [H][W], read at the tops only).  With t = root(c): label(c) = number(t) iff
+ *      (int64) s(c) 1000 >= ratio_pm s(t),  ratio_pm = round-half-even(crown_ratio 1000) in 0 .. 1000, and
+ *      (i - i_t)^2 + (j - j_t)^2 <= rc2,    rc2 = floor((max_crown_radius / gsd)^2) >= 0, computed exactly by the caller;
+ *    otherwise label(c) = 0, and the cells of C that fail a test are counted (unassigned, one int64).  A top always carries
+ *    its own label.  A crown may consist of several 4-connected parts (the 8-neighbour ascent, the jump at a minor maximum and
+ *    the radius test can each split it); trees.py reports the number per tree and hides nothing.
+ * 9. Table, int64 [ADAMVS_TREE_COLUMNS][T], row k - 1 for label k, over the cells with 1 <= label <= T and a root inside the
+ *    grid: cells; q_sum, q_max (of the unsmoothed q); row_min, row_max, col_min, col_max; r2_max (the largest squared cell
+ *    distance to the top); top (the cell index of root(c)); s_top (s there).  A label without a cell: sums 0, minima
+ *    2^31 - 1, maxima -1.  Integer sums, minima and maxima only.
+ * 10. Selection and vectorising run on the host (ada-mvs_amd/trees.py select(), crown_polygons()).
+ *
+ * Kernels (csrc/dsm_trees.hip, whose head gives the reasons).  _tree_surface: the mask pass and one pass per smoothing round,
+ * neighbours read straight from global memory; the last pass reduces s_max.  _tree_parents: one workgroup per tile of
+ * ADAMVS_TREE_TILE^2 cells stages s with a one-cell halo in LDS, settles every cell that a neighbour beats, compacts the others
+ * (the 8-neighbour local maxima) into an LDS list by wave ballot, and then sweeps one candidate's disc per wave, 64 cells of
+ * its bounding box at a time, the disc rows read from L2, the best key reduced by shuffles.  _tree_roots: plain double-buffered
+ * jumping, ADAMVS_TREE_JUMP_HOPS parents per round, 12 bytes per cell and round plus the later hops' gathers (the variant that first resolves every cell to its tile exit in LDS was not built); the
+ * changed words of four rounds are read back together, and the loop stops at the first round that changed nothing.
+ * _tree_table: the lanes of a wave that follow one another in a row with the same label are summed in registers and one lane
+ * issues the atomics of the run.  No floating-point atomic, no floating-point sum: every output is bit-identical from run to
+ * run.  No workgroup waits on another; visibility between rounds comes from the kernel boundaries.
+ * _tree_parents and _tree_roots block and fill their own fields of stats (a HOST pointer, as is thr); the others do not block.
+ * Everything else is device memory (s_max: one int32, unassigned: one int64); workspace of at least
+ * _tree_workspace_bytes(W, H) bytes (about 8 bytes per cell), 256-byte aligned.
+ * Argument errors (<0, before any launch): a null pointer other than building, W or H <= 0 or W H > ADAMVS_DSM_MAX_CELLS,
+ * min_height not finite or <= 0, smooth_passes outside 0 .. 2, r_cap outside 1 .. ADAMVS_TREE_MAX_RADIUS, a thr that does not
+ * ascend from 0, ratio_pm outside 0 .. 1000, rc2 < 0, T < 0 or T > W H, workspace_bytes below the query, any two of the
+ * buffers (workspace included) overlapping.  _tree_workspace_bytes returns < 0 for a grid outside the limits. */
+#define ADAMVS_TREE_TILE 64        /* cells of a side of a tile of _tree_parents: a wave takes a row */
+#define ADAMVS_TREE_MAX_RADIUS 64  /* largest window radius, cells */
+#define ADAMVS_TREE_MAX_ROUNDS 32  /* cap on the rounds of pointer jumping: 2^28 cells need 11 */
+#define ADAMVS_TREE_JUMP_HOPS 8    /* parents followed per cell and round of pointer jumping */
+#define ADAMVS_TREE_NOT_CONVERGED (-2)
+#define ADAMVS_TREE_Q_SCALE 256    /* ADAMVS_ROOF_Q_SCALE */
+#define ADAMVS_TREE_COLUMNS 10
+enum {
+  ADAMVS_TREE_CELLS = 0, ADAMVS_TREE_Q_SUM = 1, ADAMVS_TREE_Q_MAX = 2, ADAMVS_TREE_ROW_MIN = 3, ADAMVS_TREE_ROW_MAX = 4,
+  ADAMVS_TREE_COL_MIN = 5, ADAMVS_TREE_COL_MAX = 6, ADAMVS_TREE_R2_MAX = 7, ADAMVS_TREE_TOP = 8, ADAMVS_TREE_S_TOP = 9
+};
+
+typedef struct {
+  int rounds;        /* _tree_roots: rounds of jumping that moved a pointer (< ADAMVS_TREE_MAX_ROUNDS) */
+  int converged;     /* _tree_roots: 1 unless the cap was hit */
+  long tops;         /* _tree_roots: cells with parent == own index */
+  long candidates;   /* _tree_parents: 8-neighbour local maxima whose window was searched */
+  long window_cells; /* _tree_parents: cells of those windows read (inside the disc and the grid) */
+  float ms_parents;  /* _tree_parents: device time of the kernel in milliseconds; -1 if the events failed */
+  float ms_jump;     /* _tree_roots: device time of the rounds, their read-backs included */
+} adamvs_tree_stats;
+
+long adamvs_tree_workspace_bytes(int W, int H);
+int adamvs_tree_surface(int W, int H, const float* ndsm, const int* building, double min_height, int smooth_passes, void* workspace,
+                        long workspace_bytes, unsigned char* mask, int* q, int* s, int* s_max, void* stream);
+int adamvs_tree_parents(int W, int H, const int* s, int r_cap, const int* thr, void* workspace, long workspace_bytes, int* parent,
+                        adamvs_tree_stats* stats, void* stream);
+int adamvs_tree_roots(int W, int H, const int* parent, void* workspace, long workspace_bytes, int* root, adamvs_tree_stats* stats,
+                      void* stream);
+int adamvs_tree_crowns(int W, int H, const int* s, const int* root, const int* number, int ratio_pm, long rc2, int* label,
+                       long long* unassigned, void* stream);
+int adamvs_tree_table(int W, int H, const int* label, const int* q, const int* s, const int* root, long T, long long* table,
+                      void* stream);
+
 /* ---- TSDF mesh (after fuse_whu.py): the depth maps of all views integrated into a truncated signed-distance field on a voxel
  * grid, brick by brick, and its zero level set extracted as a coloured triangle mesh ---------------------------------------
  * ada-mvs_amd/mesh.py drives it per brick; mesh_whu.py is the CLI.  World axes: x east, y north, z up.
