@@ -94,6 +94,13 @@ class TreeStats(ctypes.Structure):
                 ("window_cells", ctypes.c_long), ("ms_parents", ctypes.c_float), ("ms_jump", ctypes.c_float)]
 
 
+class ContourStats(ctypes.Structure):
+    """adamvs_contour_stats"""
+    _fields_ = [("rounds", ctypes.c_int), ("rounds_min", ctypes.c_int), ("rounds_dist", ctypes.c_int), ("launched", ctypes.c_int),
+                ("converged", ctypes.c_int), ("reserved", ctypes.c_int), ("segments", ctypes.c_long), ("lines", ctypes.c_long),
+                ("ms_count", ctypes.c_float), ("ms_rank", ctypes.c_float)]
+
+
 class MeshView(ctypes.Structure):
     """adamvs_mesh_view"""
     _fields_ = [("K", ctypes.c_float * 9), ("R", ctypes.c_float * 9), ("c", ctypes.c_float * 3), ("H", ctypes.c_int), ("W", ctypes.c_int),
@@ -225,6 +232,18 @@ SIGNATURES = {
                                  ctypes.c_void_p, c_st]),
     "adamvs_tree_table": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
                                 c_st]),
+    "adamvs_contour_workspace_bytes": (ctypes.c_long, [c_i, c_i]),
+    "adamvs_contour_rank_workspace_bytes": (ctypes.c_long, [ctypes.c_long]),
+    "adamvs_contour_surface": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_double, c_i, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                     ctypes.c_void_p, c_st]),
+    "adamvs_contour_count": (c_i, [c_i, c_i, ctypes.c_void_p, c_i, ctypes.POINTER(c_i), ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                   ctypes.POINTER(ContourStats), c_st]),
+    "adamvs_contour_segments": (c_i, [c_i, c_i, ctypes.c_void_p, c_i, ctypes.POINTER(c_i), ctypes.c_long, ctypes.c_void_p, ctypes.c_long,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_contour_rank": (c_i, [ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.POINTER(ContourStats), c_st]),
+    "adamvs_contour_lines": (c_i, [c_i, c_i, ctypes.c_void_p, c_i, ctypes.POINTER(c_i), ctypes.c_long, ctypes.c_long] + [ctypes.c_void_p] * 8
+                             + [ctypes.c_long] + [ctypes.c_void_p] * 5 + [c_st]),
     "adamvs_mesh_check_views": (c_i, [ctypes.POINTER(MeshView), c_i]),
     "adamvs_tsdf_integrate": (c_i, [ctypes.POINTER(MeshBrick), ctypes.c_void_p, c_i, ctypes.c_void_p, c_i, c_f, ctypes.c_void_p,
                                     ctypes.c_void_p, c_st]),
@@ -377,6 +396,13 @@ TREE_NOT_CONVERGED = -2          # ADAMVS_TREE_NOT_CONVERGED
 TREE_Q_SCALE = 256               # ADAMVS_TREE_Q_SCALE: quantised height above ground, 1/256 m
 TREE_COLUMNS = ("cells", "q_sum", "q_max", "row_min", "row_max", "col_min", "col_max", "r2_max", "top",
                 "s_top")         # ADAMVS_TREE_CELLS .. ADAMVS_TREE_S_TOP: the rows of the tree table
+CONTOUR_TILE = 64                # ADAMVS_CONTOUR_TILE: blocks of a side of a tile of the count kernel
+CONTOUR_MAX_LEVELS = 4096        # ADAMVS_CONTOUR_MAX_LEVELS: entries of the level table
+CONTOUR_MAX_ROUNDS = 64          # ADAMVS_CONTOUR_MAX_ROUNDS: cap on the rounds of list ranking, both phases together
+CONTOUR_Q_SCALE = 256            # ADAMVS_CONTOUR_Q_SCALE: quantised height above z_ref, 1/256 m
+CONTOUR_MAX_ABS_M = 8191         # ADAMVS_CONTOUR_MAX_ABS_M: |z - z_ref| of a valid cell, metres
+CONTOUR_NOT_CONVERGED = -2       # ADAMVS_CONTOUR_NOT_CONVERGED
+CONTOUR_TOO_MANY = -3            # ADAMVS_CONTOUR_TOO_MANY
 MESH_TILE = 256                  # ADAMVS_MESH_TILE: samples / cubes per workgroup of the mesh kernels
 MESH_BRICKS = (32, 64, 128)      # the brick sizes B
 MESH_MAX_VIEWS = 65535           # ADAMVS_MESH_MAX_VIEWS

@@ -720,6 +720,100 @@ extern "C" int adamvs_tree_table(int W, int H, const int* label, const int* q, c
   return launch_tree_table(W, H, label, q, s, root, T, table, (hipStream_t)stream);
 }
 
+// ---- Contours (dsm_contours.hip)
+static int contour_check_levels(int K, const int* lev, const char* what) {
+  ADAMVS_CHECK_ARG(K >= 0 && K <= ADAMVS_CONTOUR_MAX_LEVELS, "%s: K=%d (0 .. %d)", what, K, ADAMVS_CONTOUR_MAX_LEVELS);
+  ADAMVS_CHECK_ARG(lev, "%s: null pointer", what);
+  for (int k = 1; k < K; ++k)
+    ADAMVS_CHECK_ARG(lev[k] > lev[k - 1], "%s: lev[%d]=%d does not exceed lev[%d]=%d", what, k, lev[k], k - 1, lev[k - 1]);
+  return 0;
+}
+
+static int contour_check_segments(long N, const char* what) {
+  ADAMVS_CHECK_ARG(N >= 0 && N < (1L << 31), "%s: N=%ld (0 .. 2^31 - 1)", what, N);
+  return 0;
+}
+
+extern "C" long adamvs_contour_workspace_bytes(int W, int H) {
+  if (int rc = dsm_fill_check_size(W, H, "contour_workspace_bytes")) return rc;
+  return contour_workspace_bytes(W, H);
+}
+
+extern "C" long adamvs_contour_rank_workspace_bytes(long N) {
+  if (int rc = contour_check_segments(N, "contour_rank_workspace_bytes")) return rc;
+  return contour_rank_workspace_bytes(N);
+}
+
+extern "C" int adamvs_contour_surface(int W, int H, const float* z, double z_ref, int smooth_passes, void* workspace, long workspace_bytes,
+                                      int* s, int* info, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "contour_surface")) return rc;
+  ADAMVS_CHECK_ARG(z && workspace && s && info, "contour_surface: null pointer");
+  ADAMVS_CHECK_ARG(std::isfinite(z_ref), "contour_surface: z_ref=%g must be finite", z_ref);
+  ADAMVS_CHECK_ARG(smooth_passes >= 0 && smooth_passes <= 2, "contour_surface: smooth_passes=%d (0 .. 2)", smooth_passes);
+  const long need = contour_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "contour_surface: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{z, 4 * n}, {workspace, need}, {s, 4 * n}, {info, 12}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 4), "contour_surface: z, s, info and the workspace must not overlap");
+  return launch_contour_surface(W, H, z, z_ref, smooth_passes, workspace, s, info, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_contour_count(int W, int H, const int* s, int K, const int* lev, void* workspace, long workspace_bytes, int* count,
+                                    adamvs_contour_stats* stats, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "contour_count")) return rc;
+  ADAMVS_CHECK_ARG(s && workspace && count && stats, "contour_count: null pointer");
+  if (int rc = contour_check_levels(K, lev, "contour_count")) return rc;
+  const long need = contour_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "contour_count: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{s, 4 * n}, {workspace, need}, {count, 4 * n}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 3), "contour_count: s, count and the workspace must not overlap");
+  return launch_contour_count(W, H, s, K, lev, workspace, count, stats, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_contour_segments(int W, int H, const int* s, int K, const int* lev, long N, void* workspace, long workspace_bytes,
+                                       int* seg_entry, int* seg_exit, int* seg_level, int* succ, int* pred, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "contour_segments")) return rc;
+  if (int rc = contour_check_segments(N, "contour_segments")) return rc;
+  ADAMVS_CHECK_ARG(s && workspace && (N == 0 || (seg_entry && seg_exit && seg_level && succ && pred)), "contour_segments: null pointer");
+  if (int rc = contour_check_levels(K, lev, "contour_segments")) return rc;
+  const long need = contour_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "contour_segments: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{s, 4 * n}, {workspace, need}, {seg_entry, 4 * N}, {seg_exit, 4 * N}, {seg_level, 4 * N}, {succ, 4 * N}, {pred, 4 * N}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, N ? 7 : 2), "contour_segments: s, the five segment arrays and the workspace must not overlap");
+  return launch_contour_segments(W, H, s, K, lev, N, workspace, seg_entry, seg_exit, seg_level, succ, pred, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_contour_rank(long N, const int* pred, void* workspace, long workspace_bytes, int* start, int* rank,
+                                   unsigned char* closed, adamvs_contour_stats* stats, void* stream) {
+  if (int rc = contour_check_segments(N, "contour_rank")) return rc;
+  ADAMVS_CHECK_ARG(workspace && stats && (N == 0 || (pred && start && rank && closed)), "contour_rank: null pointer");
+  const long need = contour_rank_workspace_bytes(N);
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "contour_rank: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{workspace, need}, {pred, 4 * N}, {start, 4 * N}, {rank, 4 * N}, {closed, N}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, N ? 5 : 1), "contour_rank: pred, start, rank, closed and the workspace must not overlap");
+  return launch_contour_rank(N, pred, workspace, start, rank, closed, stats, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_contour_lines(int W, int H, const int* s, int K, const int* lev, long N, long M, const int* seg_entry,
+                                    const int* seg_exit, const int* seg_level, const int* succ, const int* start, const int* rank,
+                                    const unsigned char* closed, void* workspace, long workspace_bytes, long long* line_first,
+                                    int* line_start, int* line_level, unsigned char* line_closed, long long* vertex, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "contour_lines")) return rc;
+  if (int rc = contour_check_segments(N, "contour_lines")) return rc;
+  ADAMVS_CHECK_ARG(M >= 0 && M <= N && (M > 0) == (N > 0) && N + M < (1L << 31), "contour_lines: M=%ld lines of N=%ld segments (N + M < 2^31)", M, N);
+  ADAMVS_CHECK_ARG(s && workspace && line_first, "contour_lines: null pointer");
+  ADAMVS_CHECK_ARG(N == 0 || (seg_entry && seg_exit && seg_level && succ && start && rank && closed && line_start && line_level && line_closed && vertex),
+                   "contour_lines: null pointer");
+  if (int rc = contour_check_levels(K, lev, "contour_lines")) return rc;
+  const long need = contour_rank_workspace_bytes(N), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "contour_lines: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{s, 4 * n}, {workspace, need}, {line_first, 8 * (M + 1)}, {seg_entry, 4 * N}, {seg_exit, 4 * N}, {seg_level, 4 * N},
+                         {succ, 4 * N}, {start, 4 * N}, {rank, 4 * N}, {closed, N}, {line_start, 4 * M}, {line_level, 4 * M}, {line_closed, M},
+                         {vertex, 24 * (N + M)}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, N ? 14 : 3), "contour_lines: the inputs, the outputs and the workspace must not overlap");
+  return launch_contour_lines(W, H, s, K, lev, N, M, seg_entry, seg_exit, seg_level, succ, start, rank, closed, workspace, line_first, line_start,
+                              line_level, line_closed, vertex, (hipStream_t)stream);
+}
+
 // ---- TSDF mesh (mesh.hip): every argument is checked here, before any launch
 static int mesh_check_brick(const adamvs_mesh_brick* b, const char* what) {
   ADAMVS_CHECK_ARG(b, "%s: null brick", what);

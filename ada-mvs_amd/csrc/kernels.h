@@ -219,6 +219,20 @@ int launch_tree_crowns(int W, int H, const int* s, const int* root, const int* n
                        long long* unassigned, hipStream_t st);
 int launch_tree_table(int W, int H, const int* label, const int* q, const int* s, const int* root, long T, long long* table, hipStream_t st);
 
+// dsm_contours.hip: integer surface, segments with their links, list ranking, line table and vertices (include/adamvs_hip.h, "Contours")
+long contour_workspace_bytes(int W, int H);
+long contour_rank_workspace_bytes(long N);
+int launch_contour_surface(int W, int H, const float* z, double z_ref, int smooth_passes, void* workspace, int* s, int* info, hipStream_t st);
+int launch_contour_count(int W, int H, const int* s, int K, const int* lev, void* workspace, int* count, adamvs_contour_stats* stats,
+                         hipStream_t st);
+int launch_contour_segments(int W, int H, const int* s, int K, const int* lev, long N, void* workspace, int* seg_entry, int* seg_exit,
+                            int* seg_level, int* succ, int* pred, hipStream_t st);
+int launch_contour_rank(long N, const int* pred, void* workspace, int* start, int* rank, uint8_t* closed, adamvs_contour_stats* stats,
+                        hipStream_t st);
+int launch_contour_lines(int W, int H, const int* s, int K, const int* lev, long N, long M, const int* seg_entry, const int* seg_exit,
+                         const int* seg_level, const int* succ, const int* start, const int* rank, const uint8_t* closed, void* workspace,
+                         long long* line_first, int* line_start, int* line_level, uint8_t* line_closed, long long* vertex, hipStream_t st);
+
 // mesh.hip: TSDF integration and marching-tetrahedra extraction per brick (include/adamvs_hip.h, "TSDF mesh")
 constexpr int MESH_TILE = ADAMVS_MESH_TILE;
 int launch_tsdf_integrate(const adamvs_mesh_brick& b, const adamvs_mesh_view* views, int nviews, const int* list, int nlist, float* tsdf,

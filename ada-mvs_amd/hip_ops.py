@@ -962,6 +962,125 @@ def tree_table(label, q, s, root, T):
     return table
 
 
+# ---- Contours (csrc/dsm_contours.hip; include/adamvs_hip.h "Contours") ------------------------------------------------------
+def _contour_workspace(H, W, device, workspace):
+    need = _lib.load().adamvs_contour_workspace_bytes(W, H)
+    check(0 if need >= 0 else int(need), "contour_workspace_bytes")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=device, dtype=torch.uint8)
+    return workspace
+
+
+def _contour_rank_workspace(N, device, workspace):
+    need = _lib.load().adamvs_contour_rank_workspace_bytes(int(N))
+    check(0 if need >= 0 else int(need), "contour_rank_workspace_bytes")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=device, dtype=torch.uint8)
+    return workspace
+
+
+def _contour_levels(lev, what):
+    lev = [int(v) for v in lev]
+    if any(v < -2 ** 31 or v >= 2 ** 31 for v in lev):
+        raise _lib.AdaMVSHipError("%s: lev must hold int32 values" % what)
+    return len(lev), (ctypes.c_int * max(len(lev), 1))(*lev)
+
+
+def _contour_array(t, name, dtype, n):
+    t = _dev_as(t, name, dtype)
+    if t.dim() != 1 or t.numel() != n:
+        raise _lib.AdaMVSHipError("%s must be [%d], got %s" % (name, n, tuple(t.shape)))
+    return t
+
+
+def _pn(t):
+    """the pointer of an array that may be empty (a null pointer then: the library accepts it where N or M is 0)"""
+    return _p(t) if t.numel() else None
+
+
+def contour_surface(z, z_ref, smooth_passes, workspace=None):
+    """adamvs_contour_surface: z [H, W] float32 (device) -> (s int32 [H, W], INT32_MIN outside V; info int32 [3]: s_min, s_max, the
+    finite cells out of range), on the device.  Enqueued on the current stream."""
+    z = _bld_raster(z, "z", torch.float32)
+    H, W = z.shape
+    workspace = _contour_workspace(H, W, z.device, workspace)
+    s = torch.empty(H, W, device=z.device, dtype=torch.int32)
+    info = torch.empty(3, device=z.device, dtype=torch.int32)
+    check(_lib.load().adamvs_contour_surface(W, H, _p(z), float(z_ref), int(smooth_passes), _p(workspace), workspace.numel(), _p(s), _p(info),
+                                             _stream()), "contour_surface")
+    return s, info
+
+
+def contour_count(s, lev, workspace=None):
+    """adamvs_contour_count: s [H, W] int32 (device), lev: the strictly ascending level table (host integers) -> (count int32
+    [H, W]: the segments per block, N, the workspace that holds the scanned offsets for contour_segments, _lib.ContourStats with
+    segments and ms_count set).  Blocks until done."""
+    s = _bld_raster(s, "s", torch.int32)
+    H, W = s.shape
+    K, table = _contour_levels(lev, "contour_count")
+    workspace = _contour_workspace(H, W, s.device, workspace)
+    count = torch.empty(H, W, device=s.device, dtype=torch.int32)
+    stats = _lib.ContourStats()
+    check(_lib.load().adamvs_contour_count(W, H, _p(s), K, table, _p(workspace), workspace.numel(), _p(count), ctypes.byref(stats), _stream()),
+          "contour_count")
+    return count, int(stats.segments), workspace, stats
+
+
+def contour_segments(s, lev, N, workspace):
+    """adamvs_contour_segments: `workspace` as contour_count returned it -> (entry, exit, level, succ, pred), int32 [N] each, on
+    the device.  Enqueued on the current stream."""
+    s = _bld_raster(s, "s", torch.int32)
+    H, W = s.shape
+    K, table = _contour_levels(lev, "contour_segments")
+    workspace = _dev_as(workspace, "workspace", torch.uint8)
+    out = [torch.empty(int(N), device=s.device, dtype=torch.int32) for _ in range(5)]
+    check(_lib.load().adamvs_contour_segments(W, H, _p(s), K, table, int(N), _p(workspace), workspace.numel(), *[_pn(t) for t in out], _stream()),
+          "contour_segments")
+    return tuple(out)
+
+
+def contour_rank(pred, workspace=None, stats=None):
+    """adamvs_contour_rank: pred int32 [N] (device) -> (start int32 [N], rank int32 [N], closed uint8 [N], M, the workspace,
+    _lib.ContourStats with rounds, rounds_min, rounds_dist, launched, converged, lines and ms_rank set; pass contour_count's
+    stats to have both calls' fields in one).  Blocks until done."""
+    pred = _dev_as(pred, "pred", torch.int32)
+    if pred.dim() != 1:
+        raise _lib.AdaMVSHipError("pred must be [N], got %s" % (tuple(pred.shape),))
+    N = pred.numel()
+    workspace = _contour_rank_workspace(N, pred.device, workspace)
+    start = torch.empty(N, device=pred.device, dtype=torch.int32)
+    rank = torch.empty(N, device=pred.device, dtype=torch.int32)
+    closed = torch.empty(N, device=pred.device, dtype=torch.uint8)
+    stats = _lib.ContourStats() if stats is None else stats
+    check(_lib.load().adamvs_contour_rank(N, _pn(pred), _p(workspace), workspace.numel(), _pn(start), _pn(rank), _pn(closed), ctypes.byref(stats),
+                                          _stream()), "contour_rank")
+    return start, rank, closed, int(stats.lines), workspace, stats
+
+
+def contour_lines(s, lev, segments, start, rank, closed, M, workspace=None):
+    """adamvs_contour_lines: segments = contour_segments' five arrays -> (line_first int64 [M + 1], line_start int32 [M],
+    line_level int32 [M], line_closed uint8 [M], vertex int64 [N + M, 3]), on the device.  Blocks until done."""
+    s = _bld_raster(s, "s", torch.int32)
+    H, W = s.shape
+    K, table = _contour_levels(lev, "contour_lines")
+    entry, exit_, level, succ, _ = segments
+    N, M = int(entry.numel()), int(M)
+    entry, exit_, level, succ = (_contour_array(t, name, torch.int32, N) for t, name in ((entry, "entry"), (exit_, "exit"), (level, "level"),
+                                                                                        (succ, "succ")))
+    start, rank = _contour_array(start, "start", torch.int32, N), _contour_array(rank, "rank", torch.int32, N)
+    closed = _contour_array(closed, "closed", torch.uint8, N)
+    workspace = _contour_rank_workspace(N, s.device, workspace)
+    line_first = torch.empty(M + 1, device=s.device, dtype=torch.int64)
+    line_start = torch.empty(M, device=s.device, dtype=torch.int32)
+    line_level = torch.empty(M, device=s.device, dtype=torch.int32)
+    line_closed = torch.empty(M, device=s.device, dtype=torch.uint8)
+    vertex = torch.empty(N + M, 3, device=s.device, dtype=torch.int64)
+    check(_lib.load().adamvs_contour_lines(W, H, _p(s), K, table, N, M, _pn(entry), _pn(exit_), _pn(level), _pn(succ), _pn(start), _pn(rank),
+                                           _pn(closed), _p(workspace), workspace.numel(), _p(line_first), _pn(line_start), _pn(line_level),
+                                           _pn(line_closed), _pn(vertex), _stream()), "contour_lines")
+    return line_first, line_start, line_level, line_closed, vertex
+
+
 # ---- TSDF mesh (csrc/mesh.hip; driven brick by brick by ada_mvs_amd/mesh.py) ------------------------------------------------
 # Per-sample state as torch tensors of the signed type of each C type's width: weight int16 = uint16, rgba int32 = uint32
 # (little-endian r g b a), cube_code int32 = uint32, faces int32 = uint32.

@@ -947,6 +947,118 @@ int adamvs_tree_crowns(int W, int H, const int* s, const int* root, const int* n
 int adamvs_tree_table(int W, int H, const int* label, const int* q, const int* s, const int* root, long T, long long* table,
                       void* stream);
 
+/* ---- Contours (after the ground filter, independent of the object stages): contour lines of a height raster as ordered
+ * polylines ---------------------------------------------------------------------------------------------------------------------
+ * ada-mvs_amd/contours.py trace(); contours_whu.py is the CLI.  Input: z [H][W] fp32 (the DTM as dtm_whu.py writes it, or any
+ * other height raster of the grid; NaN where there is no value).  W H <= ADAMVS_DSM_MAX_CELLS.  Marching squares and "follow
+ * the line from cell to cell", restated without a visiting order.  Samples sit at cell centres: cell (i, j) is at
+ * (x0 + (j + 0.5) gsd, y_top - (i + 0.5) gsd).  A BLOCK (i, j), 0 <= i < H - 1, 0 <= j < W - 1, is the square between the four
+ * samples A = (i, j), B = (i, j + 1), C = (i + 1, j + 1), D = (i + 1, j); its index is i W + j (the index of A: the cells of the
+ * last row and column head no block); its edges are 0 = AB, 1 = BC, 2 = CD, 3 = DA.  A grid edge has the code 2 (i W + j) + d,
+ * from sample (i, j) to its east (d = 0) or south (d = 1) neighbour.  Every comparison below is on integers.
+ *
+ * 1. Surface.  V(c) iff z(c) is finite and |(double) z(c) - z_ref| <= 8191.0.  On V: q(c) = llrint(((double) z(c) - z_ref) *
+ *    256.0) (ties to even); s = q after smooth_passes (0 .. 2) passes of the 3 x 3 binomial weights (1 2 1) x (1 2 1) without
+ *    a division, a neighbour outside the grid or outside V contributing the centre's value (the rule of Trees step 2), so s is
+ *    the height in units of 1 / S, S = 256 16^passes, |s| < 2^30.  s = INT32_MIN outside V (heights may be negative).
+ *    info int32 [3] = s_min, s_max over V (INT32_MAX, INT32_MIN if V is empty), the finite cells that failed the range test
+ *    (the caller treats any as an error).
+ * 2. Levels.  lev[0 .. K - 1], int32, strictly ascending, 0 <= K <= ADAMVS_CONTOUR_MAX_LEVELS, a HOST pointer.
+ *    contours.level_table() builds it in exact rationals: round-half-even((base + n interval - z_ref) S) for every integer n
+ *    whose level lies inside [z_ref + s_min / S, z_ref + s_max / S].  A sample is UP at level k iff s >= lev[k].
+ * 3. Segments.  A block with all four samples in V is crossed by exactly the levels with min(corners) < lev[k] <= max(corners),
+ *    one contiguous range of the table.  At such a level walk the corners A, B, C, D, A: an edge from a down corner to an up
+ *    corner is an ENTRY, from an up corner to a down corner an EXIT; there are one or two of each.  One entry, one exit: one
+ *    segment.  Two entries (the saddle; its levels are a contiguous sub-range): the centre is up iff
+ *    2 (sA + sB + sC + sD) >= 4 (2 lev[k] - 1) (int64); centre up: each entry e pairs with the exit (e - 1) mod 4 (the two down
+ *    corners are cut off); centre down: with the exit (e + 1) mod 4.  A segment runs from its entry crossing to its exit
+ *    crossing: the higher ground is on its left in world coordinates, a ring round a summit runs counter-clockwise, a ring
+ *    round a pit clockwise.  A block with a sample outside V has no segment: lines end there and at the border of the grid.
+ *    count int32 [H][W]: the segments per block (0 in the last row and column).
+ * 4. Numbering.  Segments are numbered 0 .. N - 1 by (block index, level k, entry edge), ascending.  N + (number of lines)
+ *    < 2^31, else the error return ADAMVS_CONTOUR_TOO_MANY.
+ * 5. Links.  A crossing is the pair (grid edge code, k).  seg_entry, seg_exit (edge codes), seg_level (k), int32 [N] each.
+ *    succ(n) = the segment whose entry crossing is n's exit crossing, pred its inverse, -1 where there is none.  Each crossing
+ *    is the exit of at most one segment and the entry of at most one, shared by the two blocks on its edge, which see the edge
+ *    in opposite senses: the segments form disjoint open chains and rings.
+ * 6. Lines.  An open chain starts at its segment without a pred, a ring at its smallest-numbered segment.  start(n) int32 = the
+ *    start of n's line, rank(n) int32 = the succ steps from start(n) to n, closed(n) uint8 = whether the line is a ring.  Lines
+ *    are numbered 0 .. M - 1 by ascending start.  Line m has len(m) + 1 vertices: the entry crossings of its segments in rank
+ *    order, then the exit crossing of the last one (for a ring the first vertex again).
+ * 7. Vertices.  vertex int64 [N + M][3] = (edge code, num, den): with a = s at the edge's sample (i, j) and b = s at its east or
+ *    south neighbour, num / den = (2 lev[k] - 1 - 2 a) / (2 b - 2 a), normalised to den > 0, not reduced; 0 < num < den.  The
+ *    half unit keeps every crossing strictly inside its edge: no two segments share a vertex by accident, and a plateau
+ *    exactly at a level produces nothing.  line_first int64 [M + 1] (vertex offsets, line_first[M] = N + M), line_start int32
+ *    [M], line_level int32 [M] (k), line_closed uint8 [M].
+ * 8. The host (contours.py) turns t = num / den into x = x0 + (j + 0.5 + (d == 0 ? t : 0)) gsd, y = y_top - (i + 0.5 +
+ *    (d == 1 ? t : 0)) gsd in fp64, sums the lengths, drops the short lines and writes the rest ordered by (level, line).
+ *
+ * The split into calls (csrc/dsm_contours.hip, whose head gives the reasons).  _contour_surface: the quantise pass and one pass
+ * per smoothing round; the out-of-range count and the range are reduced per workgroup before one atomic each.  _contour_count: one
+ * workgroup per tile of ADAMVS_CONTOUR_TILE^2 blocks stages its 65 x 65 samples and the level table in LDS; per block two
+ * binary searches give the level range and two more the saddle sub-range, the count is the sum of the two lengths; then the scan
+ * over the blocks (workgroup scans, k_fusion_scan over their totals, an add pass; the total also in 64 bits).  It blocks and
+ * returns N in stats.segments; the offsets stay in the workspace, which _contour_segments must be given unchanged.
+ * _contour_segments: one lane per SEGMENT (this is how (block, level) pairs are spread over the lanes: a cliff is many lanes,
+ * not one lane's loop); the lane finds its block by a binary search in the offsets, its level and entry from the two ranges,
+ * and the numbers of succ and pred in closed form from the neighbouring block's four samples (re-read from L2; no tile in LDS
+ * here): the neighbour's offset + the levels of its range below k + its saddle levels below k + the entry order inside a
+ * saddle.  No sort, no hash, no atomic.  _contour_rank: list ranking by pointer doubling over pred, double-buffered, one kernel
+ * per round, a pair (ancestor, value) per segment.  Phase 1 carries the smallest number seen; a head marks what reaches it as
+ * arrived.  It stops after a round without an arrival that lowered no minimum of a segment not yet arrived.  (While an open
+ * chain has such segments every round brings arrivals.  In a ring the window of every segment has the same length w >= the
+ * spacing gcd(w, L) of the ancestors' orbit; if no minimum fell, the minimum is constant along every orbit, and the windows of
+ * an orbit cover the ring: it is the ring's minimum.)  The rings are cut at their minimum; phase 2 carries the distance.  Each
+ * phase moves for at most ceil(log2 N) rounds and is given ADAMVS_CONTOUR_MAX_ROUNDS / 2; more is the error return
+ * ADAMVS_CONTOUR_NOT_CONVERGED, never a longer loop.  The changed words of four rounds are read back together; the result does
+ * not depend on where the loop stops.  It blocks and returns M in stats.lines.  _contour_lines: flags of the starts, their scan
+ * into line numbers, the tails scatter the vertex counts and the line table, the scan into line_first, every segment stores its
+ * entry vertex at line_first[line] + rank and the tail also its exit vertex.  It blocks.  Integer atomics only and one owner
+ * per stored word: every output is bit-identical from run to run.  No workgroup waits on another.
+ * Everything is device memory except lev and stats; workspaces of at least _contour_workspace_bytes(W, H) (surface, count,
+ * segments: about 12 bytes per cell) and _contour_rank_workspace_bytes(N) (rank, lines: about 20 bytes per segment), 256-byte
+ * aligned.  With N = 0 (no level, no block: W == 1 or H == 1) every call succeeds and the arrays of length N or M may be null.
+ * Argument errors (<0, before any launch): a null pointer, W or H <= 0 or W H > ADAMVS_DSM_MAX_CELLS, z_ref not finite,
+ * smooth_passes outside 0 .. 2, K outside 0 .. ADAMVS_CONTOUR_MAX_LEVELS, a table that does not strictly ascend, N outside
+ * 0 .. 2^31 - 1, M outside 0 .. N or zero with N > 0 or N + M >= 2^31, workspace_bytes below the query, any two of the buffers
+ * (workspace included) overlapping; after the read-back of one word, an N or M that is not the one the offsets or the starts
+ * give.  The two queries return < 0 outside the limits. */
+#define ADAMVS_CONTOUR_TILE 64           /* blocks of a side of a tile of _contour_count: a wave takes a row */
+#define ADAMVS_CONTOUR_MAX_LEVELS 4096   /* entries of the level table: 16 KB of LDS */
+#define ADAMVS_CONTOUR_MAX_ROUNDS 64     /* cap on the rounds of list ranking, both phases together */
+#define ADAMVS_CONTOUR_Q_SCALE 256       /* ADAMVS_TREE_Q_SCALE */
+#define ADAMVS_CONTOUR_MAX_ABS_M 8191    /* |z - z_ref| of a cell of V, metres */
+#define ADAMVS_CONTOUR_NOT_CONVERGED (-2)
+#define ADAMVS_CONTOUR_TOO_MANY (-3)
+
+typedef struct {
+  int rounds;        /* _contour_rank: rounds of both phases that changed a pair */
+  int rounds_min;    /* _contour_rank: those of phase 1 (heads and ring minima) */
+  int rounds_dist;   /* _contour_rank: those of phase 2 (distances) */
+  int launched;      /* _contour_rank: rounds launched (whole chunks of four per phase) */
+  int converged;     /* _contour_rank: 1 unless a phase hit its cap */
+  int reserved;
+  long segments;     /* _contour_count: N */
+  long lines;        /* _contour_rank: M */
+  float ms_count;    /* _contour_count: device time of the count and the scan in milliseconds; -1 if the events failed */
+  float ms_rank;     /* _contour_rank: device time of both phases, their read-backs included */
+} adamvs_contour_stats;
+
+long adamvs_contour_workspace_bytes(int W, int H);
+long adamvs_contour_rank_workspace_bytes(long N);
+int adamvs_contour_surface(int W, int H, const float* z, double z_ref, int smooth_passes, void* workspace, long workspace_bytes, int* s,
+                           int* info, void* stream);
+int adamvs_contour_count(int W, int H, const int* s, int K, const int* lev, void* workspace, long workspace_bytes, int* count,
+                         adamvs_contour_stats* stats, void* stream);
+int adamvs_contour_segments(int W, int H, const int* s, int K, const int* lev, long N, void* workspace, long workspace_bytes,
+                            int* seg_entry, int* seg_exit, int* seg_level, int* succ, int* pred, void* stream);
+int adamvs_contour_rank(long N, const int* pred, void* workspace, long workspace_bytes, int* start, int* rank, unsigned char* closed,
+                        adamvs_contour_stats* stats, void* stream);
+int adamvs_contour_lines(int W, int H, const int* s, int K, const int* lev, long N, long M, const int* seg_entry, const int* seg_exit,
+                         const int* seg_level, const int* succ, const int* start, const int* rank, const unsigned char* closed,
+                         void* workspace, long workspace_bytes, long long* line_first, int* line_start, int* line_level,
+                         unsigned char* line_closed, long long* vertex, void* stream);
+
 /* ---- TSDF mesh (after fuse_whu.py): the depth maps of all views integrated into a truncated signed-distance field on a voxel
  * grid, brick by brick, and its zero level set extracted as a coloured triangle mesh ---------------------------------------
  * ada-mvs_amd/mesh.py drives it per brick; mesh_whu.py is the CLI.  World axes: x east, y north, z up.
