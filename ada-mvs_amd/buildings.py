@@ -25,13 +25,12 @@ been done.
 import argparse
 import json
 import math
-import os
-import sys
 import time
 
 import numpy as np
 
-from .dsm import _check_gsd, world_file_text
+from . import raster_stage
+from .dsm import _check_gsd
 
 MAX_RADIUS = 1024                                   # ADAMVS_DTM_MAX_RADIUS: the opening, cells
 MAX_STRIDE = 64                                     # ADAMVS_BLD_MAX_STRIDE, cells
@@ -241,7 +240,7 @@ def geojson_text(polys, props):
 
 # ---- the stage ----------------------------------------------------------------------------------------------------------
 def _no_gpu():
-    return RuntimeError("buildings: needs an MI355X (there is no CPU fallback for the building-extraction kernels)")
+    return raster_stage.no_gpu("buildings", "building-extraction")
 
 
 def extract(dsm, ndsm, gsd, min_height=DEFAULTS["min_height"], min_width=DEFAULTS["min_width"], smooth_span=DEFAULTS["smooth_span"],
@@ -254,7 +253,6 @@ def extract(dsm, ndsm, gsd, min_height=DEFAULTS["min_height"], min_width=DEFAULT
     coordinates refer to (default: x0 = 0, y_top = H gsd).  Raises without a GPU: there is no CPU fallback."""
     import torch
     from . import hip_ops
-    from .dsm import Grid
     p = parameters(gsd, min_height, min_width, smooth_span, smooth_tol, min_smooth, min_area)
     simplify_tol = float(simplify_tol)
     if not (math.isfinite(simplify_tol) and simplify_tol >= 0.0):
@@ -267,7 +265,7 @@ def extract(dsm, ndsm, gsd, min_height=DEFAULTS["min_height"], min_width=DEFAULT
     H, W = dsm.shape
     gsd = float(gsd)
     if grid is None:
-        grid = Grid(0.0, H * gsd, gsd, 0.0, W, H)
+        grid = raster_stage.default_grid(H, W, gsd)
     dev = torch.device(device if device is not None else "cuda")
     d, nd = torch.from_numpy(dsm).to(dev), torch.from_numpy(ndsm).to(dev)
     torch.cuda.synchronize(dev)
@@ -281,9 +279,7 @@ def extract(dsm, ndsm, gsd, min_height=DEFAULTS["min_height"], min_width=DEFAULT
     t3 = time.time()
     table = {name: tab[k] for k, name in enumerate(COLUMNS)}
     keep, counts = select(table, gsd, p["min_area"], p["min_smooth"])
-    lut = torch.zeros(N + 1, device=dev, dtype=torch.int32)
-    lut[1:][torch.from_numpy(keep).to(dev)] = torch.arange(1, counts["buildings"] + 1, device=dev, dtype=torch.int32)
-    label = lut[comp.long()].cpu().numpy()                            # the look-up of the component numbers
+    label = raster_stage.relabel_kept(comp, keep).cpu().numpy()
     flags = flags.cpu().numpy()
     hist = np.bincount(flags.reshape(-1), minlength=5)
     counts = dict(candidate=int(hist[1:].sum()), opened_away=int(hist[1]), undetermined=int(hist[2]), smooth=int(hist[3]), rough=int(hist[4]),
@@ -304,17 +300,12 @@ def from_dsm(prefix, filled=False, min_height=DEFAULTS["min_height"], min_width=
     """The DSM of dsm_whu.py at the path prefix (its gap-filled raster if `filled`) and the nDSM of dtm_whu.py next to it ->
     extract()'s dict with `source` added; written to `out` (a path prefix) if given."""
     import torch
-    from PIL import Image
     from .ortho import read_dsm
     if not torch.cuda.is_available():
         raise _no_gpu()
     dsm, grid = read_dsm(prefix, filled)
-    npath = prefix + "_ndsm.tif"
-    if not os.path.exists(npath):
-        raise FileNotFoundError("%s: no nDSM (run dtm_whu.py --dsm %s first)" % (npath, prefix))
-    ndsm = np.array(Image.open(npath), np.float32)
-    if ndsm.shape != dsm.shape:
-        raise ValueError("%s is %s, the DSM %s" % (npath, ndsm.shape, dsm.shape))
+    ndsm = raster_stage.read_raster(prefix + "_ndsm.tif", np.float32, dsm.shape, "no nDSM (run dtm_whu.py --dsm %s first)" % prefix,
+                                    "the DSM %s" % (dsm.shape,))
     res = extract(dsm, ndsm, grid.gsd, min_height, min_width, smooth_span, smooth_tol, min_smooth, min_area, simplify_tol, grid, device)
     res["source"] = dict(prefix=prefix, filled=bool(filled))
     if out is not None:
@@ -330,37 +321,19 @@ def output_paths(out):
 
 
 def summary(res):
-    g = res["grid"]
-    return dict(grid=dict(x0=g.x0, y_top=g.y_top, gsd=g.gsd, W=g.W, H=g.H), source=res.get("source"), params=res["params"],
+    return dict(grid=raster_stage.grid_summary(res["grid"]), source=res.get("source"), params=res["params"],
                 counts=res["counts"], label_stats=res["label_stats"], seconds=res["seconds"])
 
 
 def write_outputs(out, res):
     """The GeoJSON, the label raster, its world file and the JSON summary at the path prefix `out` -> output_paths(out)."""
-    from PIL import Image
-    paths = output_paths(out)
-    if os.path.dirname(out):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-    with open(paths["geojson"], "w") as f:
-        f.write(geojson_text(res["polygons"], res["properties"]))
-    Image.fromarray(np.ascontiguousarray(res["label"], np.int32)).save(paths["label"], format="TIFF")
-    with open(paths["label_world"], "w") as f:
-        f.write(world_file_text(res["grid"]))
-    with open(paths["json"], "w") as f:
-        json.dump(summary(res), f, indent=1)
-        f.write("\n")
-    return paths
+    return raster_stage.write_outputs(output_paths(out), out, dict(geojson=geojson_text(res["polygons"], res["properties"])), summary(res),
+                                      res["label"], res["grid"])
 
 
 def read_outputs(out):
     """-> (label int32, the GeoJSON as a dict, the summary as a dict) read back from the files of write_outputs."""
-    from PIL import Image
-    paths = output_paths(out)
-    with open(paths["geojson"]) as f:
-        gj = json.load(f)
-    with open(paths["json"]) as f:
-        js = json.load(f)
-    return np.array(Image.open(paths["label"]), np.int32), gj, js
+    return raster_stage.read_outputs(output_paths(out), ("geojson",))
 
 
 def build_parser():
@@ -381,10 +354,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    print("argv:", sys.argv[1:] if argv is None else argv)
-    t0 = time.time()
-    out = args.out if args.out is not None else args.dsm
+    args, out, t0 = raster_stage.open_main(build_parser, argv)
     res = from_dsm(args.dsm, args.filled, args.min_height, args.min_width, args.smooth_span, args.smooth_tol, args.min_smooth, args.min_area,
                    args.simplify_tol, out=out)
     g, c, p, s = res["grid"], res["counts"], res["params"], res["seconds"]

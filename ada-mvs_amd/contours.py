@@ -27,13 +27,12 @@ min_length given as floats are taken as the decimal number they print as (0.1 is
 import argparse
 import json
 import math
-import os
-import sys
 import time
 from fractions import Fraction
 
 import numpy as np
 
+from . import raster_stage
 from .dsm import _check_gsd
 
 Q_SCALE = 256                                       # ADAMVS_CONTOUR_Q_SCALE
@@ -152,7 +151,7 @@ def geojson_text(feats):
 
 # ---- the stage ----------------------------------------------------------------------------------------------------------
 def _no_gpu():
-    return RuntimeError("contours: needs an MI355X (there is no CPU fallback for the contour kernels)")
+    return raster_stage.no_gpu("contours", "contour")
 
 
 def trace(z, gsd, z_ref=0.0, interval=DEFAULTS["interval"], base=DEFAULTS["base"], major_every=DEFAULTS["major_every"],
@@ -164,7 +163,6 @@ def trace(z, gsd, z_ref=0.0, interval=DEFAULTS["interval"], base=DEFAULTS["base"
     than 8191 m from z_ref, and RuntimeError without a GPU: there is no CPU fallback."""
     import torch
     from . import hip_ops
-    from .dsm import Grid
     p = parameters(interval, base, major_every, smooth_passes, min_length)
     gsd = _check_gsd(gsd)
     z = np.ascontiguousarray(z, np.float32)
@@ -176,7 +174,7 @@ def trace(z, gsd, z_ref=0.0, interval=DEFAULTS["interval"], base=DEFAULTS["base"
         raise _no_gpu()
     H, W = z.shape
     if grid is None:
-        grid = Grid(0.0, H * float(gsd), float(gsd), float(z_ref), W, H)
+        grid = raster_stage.default_grid(H, W, gsd, float(z_ref))
     dev = torch.device(device if device is not None else "cuda")
     zd = torch.from_numpy(z).to(dev)
     torch.cuda.synchronize(dev)
@@ -216,36 +214,21 @@ def trace(z, gsd, z_ref=0.0, interval=DEFAULTS["interval"], base=DEFAULTS["base"
     return res
 
 
-def _read_grid(prefix):
-    from .dsm import Grid
-    jpath = prefix + "_dsm.json"
-    if not os.path.exists(jpath):
-        raise FileNotFoundError("%s: no DSM summary (run dsm_whu.py --out %s first)" % (jpath, prefix))
-    with open(jpath) as f:
-        js = json.load(f)
-    g = js["grid"]
-    return Grid(float(g["x0"]), float(g["y_top"]), float(g["gsd"]), float(js.get("z_ref", 0.0)), int(g["W"]), int(g["H"]))
-
-
 def from_dsm(prefix, source=DEFAULTS["source"], interval=DEFAULTS["interval"], base=DEFAULTS["base"], major_every=DEFAULTS["major_every"],
              smooth_passes=DEFAULTS["smooth_passes"], min_length=DEFAULTS["min_length"], device=None, out=None):
     """The raster `<prefix>_<source>.tif` of an earlier stage -> trace()'s dict with `source` added; written to `out` (a path
     prefix) if given.  The heights are quantised about the grid's z_ref (about 0 for the nDSM, which is a height above ground)."""
     import torch
-    from PIL import Image
     if source not in SOURCES:
         raise ValueError("source=%r must be one of %s" % (source, ", ".join(SOURCES)))
     parameters(interval, base, major_every, smooth_passes, min_length)
-    grid = _read_grid(prefix)
+    grid = raster_stage.read_grid(prefix)
     path = "%s_%s.tif" % (prefix, source)
-    if not os.path.exists(path):
-        hint = {"dtm": "dtm_whu.py --dsm", "ndsm": "dtm_whu.py --dsm", "dsm": "dsm_whu.py --out", "dsm_filled": "dsm_whu.py --fill_max_dist .. --out"}
-        raise FileNotFoundError("%s: no such raster (run %s %s first)" % (path, hint[source], prefix))
+    hint = {"dtm": "dtm_whu.py --dsm", "ndsm": "dtm_whu.py --dsm", "dsm": "dsm_whu.py --out", "dsm_filled": "dsm_whu.py --fill_max_dist .. --out"}
+    raster_stage.require(path, "no such raster (run %s %s first)" % (hint[source], prefix))
     if not torch.cuda.is_available():
         raise _no_gpu()
-    z = np.array(Image.open(path), np.float32)
-    if z.shape != (grid.H, grid.W):
-        raise ValueError("%s is %s, the grid %d x %d" % (path, z.shape, grid.H, grid.W))
+    z = raster_stage.read_raster(path, np.float32, (grid.H, grid.W), says="the grid %d x %d" % (grid.H, grid.W))
     z_ref = 0.0 if source == "ndsm" else grid.z_ref
     res = trace(z, grid.gsd, z_ref, interval, base, major_every, smooth_passes, min_length, grid, device)
     res["source"] = dict(prefix=prefix, raster=source)
@@ -261,33 +244,19 @@ def output_paths(out):
 
 
 def summary(res):
-    g = res["grid"]
     params = dict(res["params"], z_ref=res["z_ref"], lev=[int(v) for v in res["lev"]], n=[int(v) for v in res["ns"]])
-    return dict(grid=dict(x0=g.x0, y_top=g.y_top, gsd=g.gsd, W=g.W, H=g.H), source=res.get("source"), params=params, counts=res["counts"],
+    return dict(grid=raster_stage.grid_summary(res["grid"]), source=res.get("source"), params=params, counts=res["counts"],
                 stats=res["stats"], seconds=res["seconds"])
 
 
 def write_outputs(out, res):
     """The GeoJSON file and the JSON summary at the path prefix `out` -> output_paths(out)."""
-    paths = output_paths(out)
-    if os.path.dirname(out):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-    with open(paths["geojson"], "w") as f:
-        f.write(geojson_text(res["features"]))
-    with open(paths["json"], "w") as f:
-        json.dump(summary(res), f, indent=1)
-        f.write("\n")
-    return paths
+    return raster_stage.write_outputs(output_paths(out), out, dict(geojson=geojson_text(res["features"])), summary(res))
 
 
 def read_outputs(out):
     """-> (the lines as a dict, the summary as a dict) read back from write_outputs' files."""
-    paths = output_paths(out)
-    with open(paths["geojson"]) as f:
-        lines = json.load(f)
-    with open(paths["json"]) as f:
-        js = json.load(f)
-    return lines, js
+    return raster_stage.read_outputs(output_paths(out), ("geojson",))
 
 
 def build_parser():
@@ -305,10 +274,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    print("argv:", sys.argv[1:] if argv is None else argv)
-    t0 = time.time()
-    out = args.out if args.out is not None else args.dsm
+    args, out, t0 = raster_stage.open_main(build_parser, argv)
     res = from_dsm(args.dsm, args.source, args.interval, args.base, args.major_every, args.smooth_passes, args.min_length, out=out)
     g, c, s, st = res["grid"], res["counts"], res["seconds"], res["stats"]
     print("contours %d x %d cells at gsd %g: %d valid cells, %d levels, %d segments in %d lines (%d closed, longest %d vertices), %d ranking "

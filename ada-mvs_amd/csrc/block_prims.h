@@ -1,5 +1,6 @@
 // The workgroup and mesh-topology primitives that fusion.hip, mesh.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_clean.hip,
-// cloud_dist.hip, cloud_knn.hip, cloud_register.hip, texture.hip and texture_level.hip share: the 256-lane tile count, ranks and
+// cloud_dist.hip, cloud_knn.hip, cloud_register.hip, texture.hip, texture_level.hip and the raster stages (dsm_buildings.hip,
+// dsm_roofs.hip, dsm_trees.hip, dsm_contours.hip; what only they share is in raster_prims.h) share: the 256-lane tile count, ranks and
 // scans over a workgroup of four waves, wave reductions in a fixed butterfly order, undirected edge keys, half-edges, the
 // run-of-one test on sorted keys and the walk to the root of a label forest.  Integer work and plain additions only: several
 // includers switch fp contraction off after their includes, and a helper that multiplies and then adds floats would round
@@ -66,6 +67,13 @@ __device__ __forceinline__ int wave_min(int x) {
   for (int m = 32; m >= 1; m >>= 1) {
     const int y = __shfl_xor(x, m);
     x = y < x ? y : x;
+  }
+  return x;
+}
+__device__ __forceinline__ int wave_max(int x) {
+  for (int m = 32; m >= 1; m >>= 1) {
+    const int y = __shfl_xor(x, m);
+    x = y > x ? y : x;
   }
   return x;
 }

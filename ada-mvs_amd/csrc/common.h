@@ -21,6 +21,8 @@ int set_error(int code, const char* fmt, ...);
        if (e_ != hipSuccess) return ::adamvs::set_error((int)e_, "%s: %s", name, hipGetErrorString(e_)); } while (0)
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// the pieces of a workspace start on 256-byte boundaries
+static inline long align256(long b) { return (b + 255) & ~255L; }
 
 // ---- device helpers -------------------------------------------------------
 // D[16 x 16] += A[16 x 4] . B[4 x 16], exact fp32 (v_mfma_f32_16x16x4_f32).

@@ -5,7 +5,7 @@
 //   k_ctr_quant         one lane per cell: q, INT32_MIN outside V; the finite cells out of range are counted, summed in LDS
 //                       and added once per workgroup (none, on a raster that passes).  The cells of V are NOT counted here:
 //                       every workgroup would add to one word.
-//   k_ctr_smooth        one binomial pass, the rule and the code of k_tree_smooth with the other sentinel.  The last kernel of
+//   k_ctr_smooth        one binomial pass (raster_prims.h binomial3x3; a hole is INT32_MIN).  The last kernel of
 //                       _contour_surface reduces the minimum and maximum of s per workgroup and issues an integer atomic only
 //                       where the word it has just read would change (dsm_trees.hip records what per-wave atomics on one
 //                       address cost).
@@ -43,6 +43,7 @@
 #include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
+#include "raster_prims.h"
 
 #pragma clang fp contract(off)
 
@@ -65,7 +66,6 @@ constexpr long CTR_OFF_LINES = 264;              // unsigned long long: the star
 constexpr long CTR_CONTROL = 512;
 
 static inline unsigned ctr_blocks(long n) { return (unsigned)((n + CTR_THREADS - 1) / CTR_THREADS); }
-static long ctr_align(long b) { return (b + 255) & ~255L; }
 
 // ---- workspaces -------------------------------------------------------------------------------------------------------------
 // grid: control | level table | two int32 rasters (the surface's intermediate passes) | offsets unsigned [n + 1] | workgroup
@@ -84,17 +84,17 @@ static CtrGridWs ctr_grid_ws(void* workspace, int W, int H) {
   CtrGridWs w;
   long o = CTR_CONTROL;
   w.lev = (int*)(p + o);
-  o += ctr_align(4L * ADAMVS_CONTOUR_MAX_LEVELS);
+  o += align256(4L * ADAMVS_CONTOUR_MAX_LEVELS);
   w.tmp[0] = (int*)(p + o);
-  o += ctr_align(4 * n);
+  o += align256(4 * n);
   w.tmp[1] = (int*)(p + o);
-  o += ctr_align(4 * n);
+  o += align256(4 * n);
   w.off = (unsigned*)(p + o);
-  o += ctr_align(4 * (n + 1));
+  o += align256(4 * (n + 1));
   w.part = (unsigned*)(p + o);
-  o += ctr_align(4 * (nb + 1));
+  o += align256(4 * (nb + 1));
   w.part_off = (unsigned*)(p + o);
-  o += ctr_align(4 * (nb + 1));
+  o += align256(4 * (nb + 1));
   w.bytes = o;
   return w;
 }
@@ -118,45 +118,30 @@ static CtrSegWs ctr_seg_ws(void* workspace, long N) {
   CtrSegWs w;
   long o = CTR_CONTROL;
   w.lev = (int*)(p + o);
-  o += ctr_align(4L * ADAMVS_CONTOUR_MAX_LEVELS);
+  o += align256(4L * ADAMVS_CONTOUR_MAX_LEVELS);
   w.buf[0] = (int2*)(p + o);
   w.count = (unsigned*)(p + o);
-  o += ctr_align(8 * (N + 1));
+  o += align256(8 * (N + 1));
   w.buf[1] = (int2*)(p + o);
   w.first = (unsigned*)(p + o);
-  o += ctr_align(8 * (N + 1));
+  o += align256(8 * (N + 1));
   w.lineno = (unsigned*)(p + o);
-  o += ctr_align(4 * (N + 1));
+  o += align256(4 * (N + 1));
   w.part = (unsigned*)(p + o);
-  o += ctr_align(4 * (nb + 1));
+  o += align256(4 * (nb + 1));
   w.part_off = (unsigned*)(p + o);
-  o += ctr_align(4 * (nb + 1));
+  o += align256(4 * (nb + 1));
   w.bytes = o;
   return w;
 }
 long contour_rank_workspace_bytes(long N) { return ctr_seg_ws(nullptr, N).bytes; }
 
 // ---- the surface ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int ctr_wave_min(int v) {
-  for (int off = 32; off; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int ctr_wave_max(int v) {
-  for (int off = 32; off; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 // info[0] = s_min, info[1] = s_max over the workgroup's cells of V (lo = INT_MAX, hi = INT_MIN for a lane without one)
 __device__ __forceinline__ void ctr_block_range(int lo, int hi, int* info) {
   __shared__ int s_lo[CTR_WAVES], s_hi[CTR_WAVES];
-  lo = ctr_wave_min(lo);
-  hi = ctr_wave_max(hi);
+  lo = wave_min(lo);
+  hi = wave_max(hi);
   if ((threadIdx.x & 63) == 0) {
     s_lo[threadIdx.x >> 6] = lo;
     s_hi[threadIdx.x >> 6] = hi;
@@ -204,30 +189,16 @@ __global__ __launch_bounds__(CTR_THREADS) void k_ctr_quant(long n, const float* 
   if (reduce) ctr_block_range(sv == CTR_NONE ? INT_MAX : sv, sv, info);      // wave-uniform: a kernel argument
 }
 
+struct CtrHole {
+  static constexpr int NONE = CTR_NONE;
+  static __device__ __forceinline__ bool is(int v) { return v == CTR_NONE; }
+};
+
 __global__ __launch_bounds__(CTR_THREADS) void k_ctr_smooth(int W, int H, const int* __restrict__ src, int* __restrict__ dst, int* info, int reduce) {
   const long n = (long)W * H;
   const long c = (long)blockIdx.x * CTR_THREADS + threadIdx.x;
   int out = CTR_NONE;
-  if (c < n) {
-    const int centre = src[c];
-    if (centre != CTR_NONE) {
-      const int i = (int)((unsigned)c / (unsigned)W), j = (int)((unsigned)c - (unsigned)i * (unsigned)W);  // n <= 2^28
-      out = 0;
-#pragma unroll
-      for (int di = -1; di <= 1; ++di)
-#pragma unroll
-        for (int dj = -1; dj <= 1; ++dj) {
-          const int ii = i + di, jj = j + dj;
-          int v = centre;
-          if (ii >= 0 && ii < H && jj >= 0 && jj < W) {
-            const int t = src[(long)ii * W + jj];
-            if (t != CTR_NONE) v = t;
-          }
-          out += (2 - (di ? 1 : 0)) * (2 - (dj ? 1 : 0)) * v;       // (1 2 1) x (1 2 1): |s| <= 8191 * 256 * 16^2 < 2^30
-        }
-    }
-    dst[c] = out;
-  }
+  if (c < n) dst[c] = out = binomial3x3<CtrHole>(W, H, src, c);      // |s| <= 8191 * 256 * 16^2 < 2^30
   if (reduce) ctr_block_range(out == CTR_NONE ? INT_MAX : out, out, info);
 }
 
@@ -395,7 +366,8 @@ __global__ __launch_bounds__(CTR_THREADS) void k_ctr_segments(int W, int H, long
     if ((long)off[mid] <= n) lo = mid;
     else hi = mid;
   }
-  const int i = (int)((unsigned)lo / (unsigned)W), j = (int)((unsigned)lo - (unsigned)i * (unsigned)W);
+  int i, j;
+  cell_ij(lo, W, i, j);
   const CtrBlock B = ctr_block(W, H, i, j, s, off, lev, K);
   const int r = (int)(n - (long)B.off);
   int out_entry = -1, out_exit = -1, out_level = -1, out_succ = -1, out_pred = -1;

@@ -142,10 +142,9 @@ __global__ __launch_bounds__(DTM_THREADS) void k_dtm_transpose(int cols, int row
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-static long dtm_align(long b) { return (b + 255) & ~255L; }
 
 // Workspace: the counters (256 B), then two rasters of fp32.
-long dtm_workspace_bytes(int W, int H) { return 256 + 2 * dtm_align(4L * W * H); }
+long dtm_workspace_bytes(int W, int H) { return 256 + 2 * align256(4L * W * H); }
 
 struct DtmWs {
   unsigned long long* counts;
@@ -154,7 +153,7 @@ struct DtmWs {
 
 static DtmWs dtm_layout(int W, int H, void* workspace) {
   char* base = (char*)workspace;
-  return DtmWs{(unsigned long long*)base, (float*)(base + 256), (float*)(base + 256 + dtm_align(4L * W * H))};
+  return DtmWs{(unsigned long long*)base, (float*)(base + 256), (float*)(base + 256 + align256(4L * W * H))};
 }
 
 static dim3 dtm_row_grid(int width, int rows) { return dim3((unsigned)cdiv(width, DTM_TILE), (unsigned)min(rows, 65535)); }

@@ -444,7 +444,6 @@ static int fill_levels(int W, int H, int* Ws, int* Hs) {
   return n + 1;
 }
 
-static long fill_align(long b) { return (b + 255) & ~255L; }
 
 // Workspace: counters (256 B), then per level its class bytes; the fine level's u (fp64) and colours (float4); the residual
 // scratch of the fine size (fp64 + float4; the column distances of the distance pass live in it first); per coarse level
@@ -461,7 +460,7 @@ static long fill_layout(int W, int H, char* base, FillWs* ws) {
   int Ws[FILL_MAX_LEVELS], Hs[FILL_MAX_LEVELS];
   const int nl = fill_levels(W, H, Ws, Hs);
   long off = 0;
-  auto take = [&](long bytes) -> char* { char* p = base ? base + off : nullptr; off += fill_align(bytes); return p; };
+  auto take = [&](long bytes) -> char* { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
   char* counts = take(256);
   if (ws) {
     ws->counts = (unsigned long long*)counts;

@@ -7,16 +7,11 @@
 //                       of a wave each offset is one contiguous 256-byte piece of another row, and the rows i - s .. i + s + 1
 //                       stay in L2 between the workgroups that share them.  What dsm_buildings.hip says of k_bld_flags against a
 //                       tile with halo in LDS holds here unchanged (at s = 64 the halo is eight times the tile).
-//   k_roof_tile         k_bld_tile with edges in place of the mask.  A wave takes a row: the ballots of the core and east bits
-//                       give the edges of the row (bit k: cells k and k + 1 are joined), and a lane's run starts after the
-//                       nearest lane to its left whose edge is missing.  The south edges of a row are kept as one ballot word
-//                       in LDS; the passes over the vertical neighbours union only where that edge exists.  The bounds of
-//                       k_bld_tile hold: every pass that changes something takes a root away.
-//   k_roof_pairs        one round's first kernel over the tile-border pairs: as k_bld_pairs, and only for pairs whose link bit is
-//                       set.  The round's hook and compress kernels and the final walk are the building stage's (bld_union.h).
-//   k_roof_moments      one lane per cell; the lanes of a wave that follow one another within a row with the same label (and a
-//                       finite Z) form a run, a segmented shuffle reduction sums the run into its first lane, which issues the
-//                       integer atomics.
+//   k_roof_tile /       bld_union.h: k_label_tile, k_label_pairs and launch_label over LinkEdges (a core cell is a node; the
+//   k_roof_pairs        east and south bits say where two core cells are joined).  The round's hook and compress kernels and
+//                       the final walk are the building stage's.
+//   k_roof_moments      one lane per cell; a run of equal labels with a finite Z (raster_prims.h wave_run) is summed into its
+//                       first lane, which issues the integer atomics.
 //   k_roof_grow         one round: every cell of the output buffer is written (the label kept, or the best neighbouring plane).
 //                       One atomicAdd per workgroup of 16 waves counts the cells labelled.
 //   k_roof_residuals    the run reduction again: inlier count and the largest quantised residual per plane.
@@ -28,6 +23,7 @@
 #include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
+#include "raster_prims.h"
 
 #pragma clang fp contract(off)
 
@@ -60,7 +56,8 @@ __global__ __launch_bounds__(BLD_THREADS) void k_roof_links(int W, int H, const 
   const long n = (long)W * H;
   const long c = (long)blockIdx.x * BLD_THREADS + threadIdx.x;
   if (c >= n) return;
-  const int i = (int)((unsigned)c / (unsigned)W), j = (int)((unsigned)c - (unsigned)i * (unsigned)W);      // n <= 2^28
+  int i, j;
+  cell_ij(c, W, i, j);
   double za = 0.0, gxa = 0.0, gya = 0.0;
   int ba = 0;
   uint8_t out = 0;
@@ -79,109 +76,7 @@ __global__ __launch_bounds__(BLD_THREADS) void k_roof_links(int W, int H, const 
   link[c] = out;
 }
 
-// ---- segments: the tile phase -----------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLD_THREADS) void k_roof_tile(int W, int H, int tiles_x, const uint8_t* __restrict__ link,
-                                                           int* __restrict__ parent) {
-  __shared__ int s_l[BLD_CELLS];
-  __shared__ unsigned long long s_south[BLD_TILE_H];                 // bit k of row r: cells (r, k) and (r + 1, k) are joined
-  __shared__ int s_changed;
-  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int j = tx * BLD_TILE_W + lane;
-  for (int r = wv; r < BLD_TILE_H; r += BLD_THREADS / 64) {          // wave-uniform: every lane takes part in the ballots
-    const int i = ty * BLD_TILE_H + r;
-    const bool in = i < H && j < W;
-    const uint8_t f = in ? link[(long)i * W + j] : (uint8_t)0;
-    const bool core = (f & 1) != 0;
-    const bool below = core && (f & 4) && r + 1 < BLD_TILE_H && i + 1 < H && (link[(long)(i + 1) * W + j] & 1);
-    const unsigned long long cb = __ballot(core);
-    const unsigned long long edges = __ballot(core && (f & 2)) & (cb >> 1);      // bit k: cells k and k + 1 of this row are joined
-    const unsigned long long sb = __ballot(below);
-    const unsigned long long gaps_below = ~edges & ((1ull << lane) - 1ull);
-    const int start = gaps_below ? 64 - __clzll((long long)gaps_below) : 0;      // the cell after the nearest missing edge on the left
-    s_l[r * BLD_TILE_W + lane] = core ? r * BLD_TILE_W + start : -1;
-    if (lane == 0) s_south[r] = sb;
-  }
-  __syncthreads();
-  for (int pass = 0; pass < BLD_CELLS; ++pass) {                     // fewer passes than cells: see the head of dsm_buildings.hip
-    if (threadIdx.x == 0) s_changed = 0;
-    __syncthreads();
-    for (int r = wv ? wv : BLD_THREADS / 64; r < BLD_TILE_H; r += BLD_THREADS / 64) {
-      const int k = r * BLD_TILE_W + lane;
-      if ((s_south[r - 1] >> lane) & 1ull) {                         // both cells are core
-        const int a = bld_find(s_l, k), b = bld_find(s_l, k - BLD_TILE_W);
-        if (a != b) {
-          atomicMin(&s_l[a > b ? a : b], a > b ? b : a);
-          s_changed = 1;
-        }
-      }
-    }
-    __syncthreads();
-    const int changed = s_changed;
-    __syncthreads();                                                 // before lane 0 clears it again
-    if (!changed) break;
-  }
-  for (int r = wv; r < BLD_TILE_H; r += BLD_THREADS / 64) {
-    const int i = ty * BLD_TILE_H + r;
-    if (i >= H || j >= W) continue;
-    const int k = r * BLD_TILE_W + lane;
-    int out = -1;
-    if (bld_lds_load(s_l + k) >= 0) {
-      const int root = bld_find(s_l, k);
-      out = (int)((long)(ty * BLD_TILE_H + root / BLD_TILE_W) * W + tx * BLD_TILE_W + root % BLD_TILE_W);
-    }
-    parent[(long)i * W + j] = out;
-  }
-}
-
-// ---- segments: the border rounds --------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLD_THREADS) void k_roof_pairs(int W, int H, long n_vertical, long n_pairs, const uint8_t* __restrict__ link,
-                                                            const int* __restrict__ parent, int2* __restrict__ pairs,
-                                                            unsigned* __restrict__ changed) {
-  const long p = (long)blockIdx.x * BLD_THREADS + threadIdx.x;
-  if (p >= n_pairs) return;
-  long a, b;
-  bld_pair_cells(p, W, H, n_vertical, a, b);
-  int2 out = make_int2(-1, -1);
-  if (link[a] & (p < n_vertical ? 2 : 4)) {
-    const int pa = parent[a], pb = parent[b];                        // both >= 0 iff both cells are core
-    if (pa >= 0 && pb >= 0) {
-      const int ra = bld_root(parent, pa), rb = bld_root(parent, pb);
-      if (ra != rb) {
-        out = make_int2(ra < rb ? ra : rb, ra < rb ? rb : ra);
-        changed[0] = 1u;
-      }
-    }
-  }
-  pairs[p] = out;
-}
-
-// ---- runs of equal labels in a wave ------------------------------------------------------------------------------------------
-// head: this lane starts a run; end: the last lane of this lane's run.  Every lane of the wave calls it.
-__device__ __forceinline__ void roof_run(int lab, int j, int lane, bool& head, int& end) {
-  const int before = __shfl_up(lab, 1, 64);
-  head = lab && (lane == 0 || before != lab || j == 0);
-  const unsigned long long breaks = __ballot(head || !lab);
-  const unsigned long long above = lane == 63 ? 0ull : breaks & ~((2ull << lane) - 1ull);
-  end = above ? __ffsll((long long)above) - 2 : 63;
-}
-
-__device__ __forceinline__ void roof_add(long long* p, long long v) {
-  if (v) atomicAdd((unsigned long long*)p, (unsigned long long)v);
-}
-
 // ---- moments ----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLD_THREADS) void k_roof_moments_init(long N, long long* __restrict__ table) {
-  const long k = (long)blockIdx.x * BLD_THREADS + threadIdx.x;
-  if (k >= N) return;
-  for (int col = 0; col < ADAMVS_ROOF_COLUMNS; ++col) {
-    long long v = 0;
-    if (col == ADAMVS_ROOF_ROW_MIN || col == ADAMVS_ROOF_COL_MIN || col == ADAMVS_ROOF_Q_MIN) v = 0x7fffffffLL;
-    if (col == ADAMVS_ROOF_ROW_MAX || col == ADAMVS_ROOF_COL_MAX || col == ADAMVS_ROOF_Q_MAX_COL || col == ADAMVS_ROOF_BUILDING) v = -1;
-    table[col * N + k] = v;
-  }
-}
-
 __global__ __launch_bounds__(BLD_THREADS) void k_roof_moments(int W, int H, const float* __restrict__ dsm, const int* __restrict__ label,
                                                               const int* __restrict__ bld, double z_ref, long N, long long* table) {
   const long n = (long)W * H;
@@ -197,8 +92,7 @@ __global__ __launch_bounds__(BLD_THREADS) void k_roof_moments(int W, int H, cons
   if (lab) {
     const float fz = dsm[c];
     if (__builtin_isfinite(fz)) {
-      i = (int)((unsigned)c / (unsigned)W);                          // n <= 2^28: 32-bit division
-      j = (int)((unsigned)c - (unsigned)i * (unsigned)W);
+      cell_ij(c, W, i, j);
       q = llrint(fmin(fmax(((double)fz - z_ref) * (double)ADAMVS_ROOF_Q_SCALE, 0.0), (double)ADAMVS_ROOF_Q_MAX));
       b = bld[c];
     } else {
@@ -207,7 +101,7 @@ __global__ __launch_bounds__(BLD_THREADS) void k_roof_moments(int W, int H, cons
   }
   bool head;
   int end;
-  roof_run(lab, j, lane, head, end);
+  wave_run(lab, j, lane, head, end);
   long long su = j, sq = q, suu = (long long)j * j, suq = (long long)j * q, lo = (q * q) & 0xFFFFF, hi = (q * q) >> 20, qmin = q, qmax = q;
   int bmax = b;
   for (int off = 1; off < 64; off <<= 1) {
@@ -225,17 +119,17 @@ __global__ __launch_bounds__(BLD_THREADS) void k_roof_moments(int W, int H, cons
   if (!head) return;
   const long k = lab - 1;
   const long long len = end - lane + 1, v = i;
-  roof_add(table + ADAMVS_ROOF_N * N + k, len);
-  roof_add(table + ADAMVS_ROOF_SU * N + k, su);
-  roof_add(table + ADAMVS_ROOF_SV * N + k, len * v);
-  roof_add(table + ADAMVS_ROOF_SQ * N + k, sq);
-  roof_add(table + ADAMVS_ROOF_SUU * N + k, suu);
-  roof_add(table + ADAMVS_ROOF_SUV * N + k, su * v);
-  roof_add(table + ADAMVS_ROOF_SVV * N + k, len * v * v);
-  roof_add(table + ADAMVS_ROOF_SUQ * N + k, suq);
-  roof_add(table + ADAMVS_ROOF_SVQ * N + k, sq * v);
-  roof_add(table + ADAMVS_ROOF_SQQ_LO * N + k, lo);
-  roof_add(table + ADAMVS_ROOF_SQQ_HI * N + k, hi);
+  add_nonzero(table + ADAMVS_ROOF_N * N + k, len);
+  add_nonzero(table + ADAMVS_ROOF_SU * N + k, su);
+  add_nonzero(table + ADAMVS_ROOF_SV * N + k, len * v);
+  add_nonzero(table + ADAMVS_ROOF_SQ * N + k, sq);
+  add_nonzero(table + ADAMVS_ROOF_SUU * N + k, suu);
+  add_nonzero(table + ADAMVS_ROOF_SUV * N + k, su * v);
+  add_nonzero(table + ADAMVS_ROOF_SVV * N + k, len * v * v);
+  add_nonzero(table + ADAMVS_ROOF_SUQ * N + k, suq);
+  add_nonzero(table + ADAMVS_ROOF_SVQ * N + k, sq * v);
+  add_nonzero(table + ADAMVS_ROOF_SQQ_LO * N + k, lo);
+  add_nonzero(table + ADAMVS_ROOF_SQQ_HI * N + k, hi);
   atomicMin(table + ADAMVS_ROOF_ROW_MIN * N + k, v);
   atomicMax(table + ADAMVS_ROOF_ROW_MAX * N + k, v);
   atomicMin(table + ADAMVS_ROOF_COL_MIN * N + k, (long long)j);
@@ -269,7 +163,8 @@ __global__ __launch_bounds__(ROOF_GROW_THREADS) void k_roof_grow(int W, int H, c
     const int b = lab == 0 ? bld[c] : 0;                             // a labelled cell is copied: 8 bytes; off the buildings: 12
     const float fz = b > 0 ? dsm[c] : 0.0f;
     if (lab == 0 && b > 0 && __builtin_isfinite(fz)) {
-      const int i = (int)((unsigned)c / (unsigned)W), j = (int)((unsigned)c - (unsigned)i * (unsigned)W);
+      int i, j;
+      cell_ij(c, W, i, j);
       const double zr = (double)fz - z_ref;
       double best_e = INFINITY;
       int best_p = 0;
@@ -312,8 +207,8 @@ __global__ __launch_bounds__(BLD_THREADS) void k_roof_residuals(int W, int H, co
   if (lab) {
     const float fz = dsm[c];
     if (__builtin_isfinite(fz)) {
-      const int i = (int)((unsigned)c / (unsigned)W);
-      j = (int)((unsigned)c - (unsigned)i * (unsigned)W);
+      int i;
+      cell_ij(c, W, i, j);
       const double e = roof_error(planes, lab, (double)fz - z_ref, i, j);
       inl = e <= assign_tol ? 1u : 0u;
       worst = e != e ? 1048576LL : llrint(fmin(e * 1024.0, 1048576.0));
@@ -323,7 +218,7 @@ __global__ __launch_bounds__(BLD_THREADS) void k_roof_residuals(int W, int H, co
   }
   bool head;
   int end;
-  roof_run(lab, j, lane, head, end);
+  wave_run(lab, j, lane, head, end);
   for (int off = 1; off < 64; off <<= 1) {
     const unsigned t_inl = __shfl_down(inl, off, 64);
     const long long t_worst = __shfl_down(worst, off, 64);
@@ -333,13 +228,13 @@ __global__ __launch_bounds__(BLD_THREADS) void k_roof_residuals(int W, int H, co
     }
   }
   if (!head) return;
-  roof_add(table + (lab - 1), (long long)inl);
+  add_nonzero(table + (lab - 1), (long long)inl);
   atomicMax(table + R + (lab - 1), worst);
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
 // Workspace of _roof_label: a control block (256 B), then the pairs of a round (at most W H / 32 pairs of 8 bytes).
-long roof_workspace_bytes(int W, int H) { return 256 + ((8 * bld_pairs_count(W, H, nullptr) + 255) & ~255L) + 256; }
+long roof_workspace_bytes(int W, int H) { return 256 + align256(8 * bld_pairs_count(W, H, nullptr)) + 256; }
 
 int launch_roof_links(int W, int H, const float* dsm, const int* building, int s, double smooth_tol, double g_tol, double step_tol,
                       uint8_t* link, hipStream_t st) {
@@ -350,55 +245,16 @@ int launch_roof_links(int W, int H, const float* dsm, const int* building, int s
 }
 
 int launch_roof_label(int W, int H, const uint8_t* link, void* workspace, int* parent, adamvs_bld_stats* stats, hipStream_t st) {
-  const long n = (long)W * H;
-  const int tiles_x = cdiv(W, BLD_TILE_W), tiles_y = cdiv(H, BLD_TILE_H);
-  long n_vertical = 0;
-  const long n_pairs = bld_pairs_count(W, H, &n_vertical);
-  unsigned* changed = (unsigned*)workspace;
-  int2* pairs = (int2*)((char*)workspace + 256);
-  memset(stats, 0, sizeof(*stats));
-  stats->tiles = (long)tiles_x * tiles_y;
-  stats->pairs = n_pairs;
-  BldClock clock;
-  clock.mark(0, st);
-  hipLaunchKernelGGL(k_roof_tile, dim3((unsigned)stats->tiles), dim3(BLD_THREADS), 0, st, W, H, tiles_x, link, parent);
-  ADAMVS_CHECK_LAUNCH("roof_tile");
-  clock.mark(1, st);
-  bool open = n_pairs > 0;                               // whether the last look found a pair with two roots
-  while (open) {
-    unsigned host = 0;
-    hipError_t e = hipMemsetAsync(changed, 0, sizeof(unsigned), st);
-    if (e != hipSuccess) return set_error((int)e, "roof_label: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(k_roof_pairs, dim3(bld_blocks(n_pairs)), dim3(BLD_THREADS), 0, st, W, H, n_vertical, n_pairs, link, (const int*)parent,
-                       pairs, changed);
-    ADAMVS_CHECK_LAUNCH("roof_pairs");
-    e = hipMemcpyAsync(&host, changed, sizeof(unsigned), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return set_error((int)e, "roof_label: %s", hipGetErrorString(e));
-    open = host != 0;
-    if (!open || stats->rounds == ADAMVS_BLD_MAX_ROUNDS) break;
-    if (int rc = launch_bld_hook(n_pairs, n, pairs, parent, st)) return rc;
-    if (int rc = launch_bld_compress(W, H, n_vertical, n_pairs, parent, st)) return rc;
-    ++stats->rounds;
-  }
-  if (open) return set_error(ADAMVS_BLD_NOT_CONVERGED, "roof_label: tile borders still open after %d rounds", ADAMVS_BLD_MAX_ROUNDS);
-  clock.mark(2, st);
-  if (int rc = launch_bld_compress_all(n, parent, st)) return rc;
-  clock.mark(3, st);
-  const hipError_t e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return set_error((int)e, "roof_label: %s", hipGetErrorString(e));
-  stats->ms_tile = clock.ms(0);
-  stats->ms_rounds = clock.ms(1);
-  stats->ms_compress = clock.ms(2);
-  stats->converged = 1;
-  return 0;
+  return launch_label<LinkEdges>(W, H, link, workspace, parent, stats, st);
 }
 
 int launch_roof_moments(int W, int H, const float* dsm, const int* label, const int* building, double z_ref, long N, long long* table,
                         hipStream_t st) {
   if (N == 0) return 0;
-  hipLaunchKernelGGL(k_roof_moments_init, dim3(bld_blocks(N)), dim3(BLD_THREADS), 0, st, N, table);
-  ADAMVS_CHECK_LAUNCH("roof_moments_init");
+  const TableStart start = TableStart(ADAMVS_ROOF_COLUMNS)
+                               .set(TABLE_MIN_START, {ADAMVS_ROOF_ROW_MIN, ADAMVS_ROOF_COL_MIN, ADAMVS_ROOF_Q_MIN})
+                               .set(-1, {ADAMVS_ROOF_ROW_MAX, ADAMVS_ROOF_COL_MAX, ADAMVS_ROOF_Q_MAX_COL, ADAMVS_ROOF_BUILDING});
+  if (int rc = launch_table_init("roof_moments_init", N, start, table, st)) return rc;
   hipLaunchKernelGGL(k_roof_moments, dim3(bld_blocks((long)W * H)), dim3(BLD_THREADS), 0, st, W, H, dsm, label, building, z_ref, N, table);
   ADAMVS_CHECK_LAUNCH("roof_moments");
   return 0;

@@ -4,8 +4,7 @@
 //
 //   k_tree_mask         one lane per cell: the canopy byte, q and s0 (s is -1 outside the canopy, so that every later kernel
 //                       reads one raster where it would read a surface and a mask).
-//   k_tree_smooth       one binomial pass, one lane per cell, the eight neighbours straight from global memory: three
-//                       coalesced row segments per wave, the rows above and below re-read from L1 / L2.  The last kernel of
+//   k_tree_smooth       one binomial pass, one lane per cell (raster_prims.h binomial3x3; a hole is s < 0).  The last kernel of
 //                       _tree_surface reduces the maximum of s per workgroup and issues an integer atomicMax only where the
 //                       word it has just read is smaller.
 //   k_tree_parents      the hot kernel; one workgroup of 16 waves per TREE_T x TREE_T tile (the candidates gather in the tiles
@@ -41,8 +40,8 @@
 //                       leaves both buffers equal, so `root` holds the result whichever buffer the last round wrote.
 //   k_tree_crowns       one lane per cell: the two tests against the cell's top, the label from the tops' numbering; the cells
 //                       that fail are counted in LDS and added once per workgroup of 16 waves.
-//   k_tree_table        as k_bld_table: the lanes of a wave that follow one another within a row and carry the same label
-//                       form a run, a segmented shuffle reduction sums the run into its first lane, which issues the atomics.
+//   k_tree_table        as k_bld_table: a run of equal labels (raster_prims.h wave_run) is summed into its first lane, which
+//                       issues the atomics.
 //
 // Every parent other than a root beats its child, so the parents are a forest whatever order the lanes ran in; integer
 // atomicMin / atomicMax / atomicAdd commute: every output is bit-identical from run to run.  No workgroup waits on another;
@@ -52,8 +51,10 @@
 #include <string.h>
 
 #include "bld_union.h"
+#include "block_prims.h"
 #include "common.h"
 #include "kernels.h"
+#include "raster_prims.h"
 
 #pragma clang fp contract(off)
 
@@ -90,20 +91,12 @@ __device__ __forceinline__ unsigned long long tree_key(int s, unsigned idx) {
 }
 __device__ __forceinline__ int tree_key_cell(unsigned long long key) { return (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull)); }
 
-__device__ __forceinline__ int tree_wave_max(int v) {
-  for (int off = 32; off; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 // The largest v of the workgroup into *s_max.  Thousands of waves hold canopy and all their atomics would hit one address, so
 // the waves are combined in LDS first, and the one lane left looks at the word before it adds: the word only grows, a stale
 // look costs an atomic that changes nothing, and after the first few workgroups hardly any is issued.
 __device__ __forceinline__ void tree_block_max(int v, int* s_max) {
   __shared__ int s_m[TREE_WAVES];
-  v = tree_wave_max(v);
+  v = wave_max(v);
   if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -130,30 +123,16 @@ __global__ __launch_bounds__(TREE_THREADS) void k_tree_mask(long n, const float*
   if (s_max) tree_block_max(sv, s_max);                             // wave-uniform: a kernel argument
 }
 
+struct TreeHole {
+  static constexpr int NONE = -1;
+  static __device__ __forceinline__ bool is(int v) { return v < 0; }
+};
+
 __global__ __launch_bounds__(TREE_THREADS) void k_tree_smooth(int W, int H, const int* __restrict__ src, int* __restrict__ dst, int* s_max) {
   const long n = (long)W * H;
   const long c = (long)blockIdx.x * TREE_THREADS + threadIdx.x;
   int out = -1;
-  if (c < n) {
-    const int centre = src[c];
-    if (centre >= 0) {
-      const int i = (int)((unsigned)c / (unsigned)W), j = (int)((unsigned)c - (unsigned)i * (unsigned)W);  // n <= 2^28
-      out = 0;
-#pragma unroll
-      for (int di = -1; di <= 1; ++di)
-#pragma unroll
-        for (int dj = -1; dj <= 1; ++dj) {
-          const int ii = i + di, jj = j + dj;
-          int v = centre;
-          if (ii >= 0 && ii < H && jj >= 0 && jj < W) {
-            const int t = src[(long)ii * W + jj];
-            if (t >= 0) v = t;
-          }
-          out += (2 - (di ? 1 : 0)) * (2 - (dj ? 1 : 0)) * v;       // (1 2 1) x (1 2 1): at most 16 * 2^23 = 2^27
-        }
-    }
-    dst[c] = out;
-  }
+  if (c < n) dst[c] = out = binomial3x3<TreeHole>(W, H, src, c);     // at most 16 * 2^23 = 2^27
   if (s_max) tree_block_max(out, s_max);
 }
 
@@ -305,8 +284,9 @@ __global__ __launch_bounds__(TREE_CROWN_THREADS) void k_tree_crowns(int W, int H
     const int t = root[c];
     int lab = 0;
     if (t >= 0 && (long)t < n) {
-      const int i = (int)((unsigned)c / (unsigned)W), j = (int)((unsigned)c - (unsigned)i * (unsigned)W);      // n <= 2^28
-      const int it = (int)((unsigned)t / (unsigned)W), jt = (int)((unsigned)t - (unsigned)it * (unsigned)W);
+      int i, j, it, jt;
+      cell_ij(c, W, i, j);
+      cell_ij(t, W, it, jt);
       const long long di = i - it, dj = j - jt;
       const bool ok = (long long)s[c] * 1000 >= (long long)ratio_pm * (long long)s[t] && di * di + dj * dj <= rc2;
       if (ok) lab = number[t];
@@ -321,17 +301,6 @@ __global__ __launch_bounds__(TREE_CROWN_THREADS) void k_tree_crowns(int W, int H
 }
 
 // ---- the table --------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TREE_THREADS) void k_tree_table_init(long T, long long* __restrict__ table) {
-  const long k = (long)blockIdx.x * TREE_THREADS + threadIdx.x;
-  if (k >= T) return;
-  for (int col = 0; col < ADAMVS_TREE_COLUMNS; ++col) {
-    long long v = -1;                                                // the maxima
-    if (col == ADAMVS_TREE_CELLS || col == ADAMVS_TREE_Q_SUM) v = 0;
-    if (col == ADAMVS_TREE_ROW_MIN || col == ADAMVS_TREE_COL_MIN) v = 0x7fffffffLL;
-    table[col * T + k] = v;
-  }
-}
-
 __global__ __launch_bounds__(TREE_THREADS) void k_tree_table(int W, int H, const int* __restrict__ label, const int* __restrict__ q,
                                                              const int* __restrict__ s, const int* __restrict__ root, long T, long long* table) {
   const long n = (long)W * H;
@@ -350,19 +319,17 @@ __global__ __launch_bounds__(TREE_THREADS) void k_tree_table(int W, int H, const
   }
   if (__ballot(lab != 0) == 0ull) return;                            // wave-uniform
   if (lab) {
-    i = (int)((unsigned)c / (unsigned)W);                            // n <= 2^28: 32-bit division
-    j = (int)((unsigned)c - (unsigned)i * (unsigned)W);
-    const int it = (int)((unsigned)t / (unsigned)W), jt = (int)((unsigned)t - (unsigned)it * (unsigned)W);
+    int it, jt;
+    cell_ij(c, W, i, j);
+    cell_ij(t, W, it, jt);
     const long long di = i - it, dj = j - jt;
     r2 = di * di + dj * dj;
     q_max = q[c];
     q_sum = (unsigned long long)(q_max > 0 ? q_max : 0);
   }
-  const int before = __shfl_up(lab, 1, 64);
-  const bool head = lab && (lane == 0 || before != lab || j == 0);
-  const unsigned long long breaks = __ballot(head || !lab);
-  const unsigned long long above = lane == 63 ? 0ull : breaks & ~((2ull << lane) - 1ull);
-  const int end = above ? __ffsll((long long)above) - 2 : 63;         // the last lane of this lane's run
+  bool head;
+  int end;
+  wave_run(lab, j, lane, head, end);
   for (int off = 1; off < 64; off <<= 1) {
     const int t_qmax = __shfl_down(q_max, off, 64);
     const unsigned long long t_qsum = (unsigned long long)__shfl_down((long long)q_sum, off, 64);
@@ -376,8 +343,8 @@ __global__ __launch_bounds__(TREE_THREADS) void k_tree_table(int W, int H, const
   if (!head) return;
   const long k = lab - 1;
   const int len = end - lane + 1;
-  atomicAdd((unsigned long long*)(table + ADAMVS_TREE_CELLS * T + k), (unsigned long long)len);
-  if (q_sum) atomicAdd((unsigned long long*)(table + ADAMVS_TREE_Q_SUM * T + k), q_sum);
+  add_nonzero(table + ADAMVS_TREE_CELLS * T + k, len);
+  add_nonzero(table + ADAMVS_TREE_Q_SUM * T + k, (long long)q_sum);
   atomicMax(table + ADAMVS_TREE_Q_MAX * T + k, (long long)q_max);
   atomicMin(table + ADAMVS_TREE_ROW_MIN * T + k, (long long)i);
   atomicMax(table + ADAMVS_TREE_ROW_MAX * T + k, (long long)i);
@@ -389,15 +356,13 @@ __global__ __launch_bounds__(TREE_THREADS) void k_tree_table(int W, int H, const
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-static long tree_align(long b) { return (b + 255) & ~255L; }
-
 // Workspace: the control block, then two int32 rasters (the surface's two intermediate passes; the jumping's second buffer).
-long tree_workspace_bytes(int W, int H) { return TREE_CONTROL + 2 * tree_align(4L * W * H); }
+long tree_workspace_bytes(int W, int H) { return TREE_CONTROL + 2 * align256(4L * W * H); }
 
 int launch_tree_surface(int W, int H, const float* ndsm, const int* building, double min_height, int smooth_passes, void* workspace,
                         uint8_t* mask, int* q, int* s, int* s_max, hipStream_t st) {
   const long n = (long)W * H;
-  int* tmp[2] = {(int*)((char*)workspace + TREE_CONTROL), (int*)((char*)workspace + TREE_CONTROL + tree_align(4 * n))};
+  int* tmp[2] = {(int*)((char*)workspace + TREE_CONTROL), (int*)((char*)workspace + TREE_CONTROL + align256(4 * n))};
   const hipError_t e = hipMemsetAsync(s_max, 0xFF, sizeof(int), st);       // -1: no canopy
   if (e != hipSuccess) return set_error((int)e, "tree_surface: %s", hipGetErrorString(e));
   int* dst = smooth_passes == 0 ? s : tmp[0];
@@ -493,8 +458,10 @@ int launch_tree_crowns(int W, int H, const int* s, const int* root, const int* n
 
 int launch_tree_table(int W, int H, const int* label, const int* q, const int* s, const int* root, long T, long long* table, hipStream_t st) {
   if (T == 0) return 0;
-  hipLaunchKernelGGL(k_tree_table_init, dim3(tree_blocks(T)), dim3(TREE_THREADS), 0, st, T, table);
-  ADAMVS_CHECK_LAUNCH("tree_table_init");
+  const TableStart start = TableStart(ADAMVS_TREE_COLUMNS, -1)       // the maxima
+                               .set(0, {ADAMVS_TREE_CELLS, ADAMVS_TREE_Q_SUM})
+                               .set(TABLE_MIN_START, {ADAMVS_TREE_ROW_MIN, ADAMVS_TREE_COL_MIN});
+  if (int rc = launch_table_init("tree_table_init", T, start, table, st)) return rc;
   hipLaunchKernelGGL(k_tree_table, dim3(tree_blocks((long)W * H)), dim3(TREE_THREADS), 0, st, W, H, label, q, s, root, T, table);
   ADAMVS_CHECK_LAUNCH("tree_table");
   return 0;

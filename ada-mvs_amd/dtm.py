@@ -18,11 +18,11 @@ import argparse
 import json
 import math
 import os
-import sys
 import time
 
 import numpy as np
 
+from . import raster_stage
 from .dsm import FILL_MAX_CYCLES, FILL_MAX_RADIUS, FillNotConverged, _check_gsd, world_file_text
 
 MAX_RADIUS = 1024                                   # ADAMVS_DTM_MAX_RADIUS, cells
@@ -75,7 +75,7 @@ def ground_filter(dsm, gsd, max_radius=DEFAULTS["max_radius"], slope=DEFAULTS["s
     radius, dh = schedule(gsd, max_radius, slope, dh0, dh_max)
     fill_m, r_fill = fill_radius_cells(fill_max_dist, max_radius, float(gsd))
     if not torch.cuda.is_available():
-        raise RuntimeError("dtm: needs an MI355X (there is no CPU fallback for the ground-filter kernels)")
+        raise raster_stage.no_gpu("dtm", "ground-filter")
     dev = torch.device(device if device is not None else "cuda")
     dsm = np.ascontiguousarray(dsm, np.float32)
     d = torch.from_numpy(dsm).to(dev)
@@ -112,7 +112,7 @@ def from_dsm(prefix, filled=False, max_radius=DEFAULTS["max_radius"], slope=DEFA
     import torch
     from .ortho import read_dsm
     if not torch.cuda.is_available():
-        raise RuntimeError("dtm: needs an MI355X (there is no CPU fallback for the ground-filter kernels)")
+        raise raster_stage.no_gpu("dtm", "ground-filter")
     dsm, grid = read_dsm(prefix, filled)
     res = ground_filter(dsm, grid.gsd, max_radius, slope, dh0, dh_max, fill_max_dist, device)
     res["grid"] = grid
@@ -149,8 +149,7 @@ def level_from_image(img):
 
 
 def summary(res):
-    g = res["grid"]
-    return dict(grid=dict(x0=g.x0, y_top=g.y_top, gsd=g.gsd, W=g.W, H=g.H), z_ref=g.z_ref, source=res.get("source"), params=res["params"],
+    return dict(grid=raster_stage.grid_summary(res["grid"]), z_ref=res["grid"].z_ref, source=res.get("source"), params=res["params"],
                 schedule=dict(radius=[int(v) for v in res["radius"]], dh=[float(v) for v in res["dh"]]), counts=res["counts"],
                 fill=res["fill"], seconds=res["seconds"])
 
@@ -198,10 +197,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    print("argv:", sys.argv[1:] if argv is None else argv)
-    t0 = time.time()
-    out = args.out if args.out is not None else args.dsm
+    args, out, t0 = raster_stage.open_main(build_parser, argv)
     res = from_dsm(args.dsm, args.filled, args.max_radius, args.slope, args.dh0, args.dh_max, args.fill_max_dist, out=out)
     g, c, f = res["grid"], res["counts"], res["fill"]
     print("dtm %d x %d cells at gsd %g: radii %s cells; %d valid cells, %d ground, %d object (per level %s), %d empty; classify %.3f s"

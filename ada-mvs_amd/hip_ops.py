@@ -692,22 +692,27 @@ def dsm_fill(dsm, rgba, r_cells, tol_height=1e-6, tol_colour=1e-3, max_cycles=20
     return dsm_out, rgba_out, dist2, filled, stats
 
 
-def _dtm_raster(dsm):
+def _workspace(entry_point, device, workspace, *args):
+    """The caller's byte workspace where it holds the adamvs_<entry_point>(*args) bytes a call needs, otherwise a new one."""
+    need = getattr(_lib.load(), "adamvs_" + entry_point)(*args)
+    check(0 if need >= 0 else int(need), entry_point)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, device=device, dtype=torch.uint8)
+    return workspace
+
+
+def _dtm_raster(dsm, workspace):
     dsm = _dev_as(dsm, "dsm", torch.float32)
     if dsm.dim() != 2:
         raise _lib.AdaMVSHipError("dsm must be [H, W], got %s" % (tuple(dsm.shape),))
     H, W = dsm.shape
-    need = _lib.load().adamvs_dtm_workspace_bytes(W, H)
-    check(0 if need >= 0 else int(need), "dtm_workspace_bytes")
-    return dsm, H, W, need
+    return dsm, H, W, _workspace("dtm_workspace_bytes", dsm.device, workspace, W, H)
 
 
 def dsm_open(dsm, r, workspace=None):
     """adamvs_dsm_open: one grey-scale opening with the square window of radius r cells (dsm [H, W] float32, device; empty
     cells NaN) -> opened [H, W] float32.  Enqueued on the current stream."""
-    dsm, H, W, need = _dtm_raster(dsm)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=dsm.device, dtype=torch.uint8)
+    dsm, H, W, workspace = _dtm_raster(dsm, workspace)
     out = torch.empty_like(dsm)
     check(_lib.load().adamvs_dsm_open(W, H, _p(dsm), int(r), _p(workspace), workspace.numel(), _p(out), _stream()), "dsm_open")
     return out
@@ -717,14 +722,12 @@ def dtm_classify(dsm, radius, dh, workspace=None):
     """adamvs_dtm_classify: the progressive morphological ground filter (dsm [H, W] float32, device; radius: ascending integer
     radii in cells, dh: one height threshold per radius, host sequences) -> (level [H, W] uint8 (0 ground, k flagged at level
     k, 255 empty), opened [H, W] float32, _lib.DtmStats).  Blocks until done."""
-    dsm, H, W, need = _dtm_raster(dsm)
+    dsm, H, W, workspace = _dtm_raster(dsm, workspace)
     radius = [int(v) for v in radius]
     dh = [float(v) for v in dh]
     if len(radius) != len(dh):
         raise _lib.AdaMVSHipError("%d radii, %d thresholds" % (len(radius), len(dh)))
     K = len(radius)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=dsm.device, dtype=torch.uint8)
     level = torch.empty(H, W, device=dsm.device, dtype=torch.uint8)
     opened = torch.empty_like(dsm)
     stats = _lib.DtmStats()
@@ -734,28 +737,34 @@ def dtm_classify(dsm, radius, dh, workspace=None):
     return level, opened, stats
 
 
-def _bld_raster(t, name, dtype, shape=None):
+def _raster(t, name, dtype, shape=None):
+    """t as an [H, W] device raster of `dtype` (of the given shape, where one is given)"""
     t = _dev_as(t, name, dtype)
     if t.dim() != 2 or (shape is not None and tuple(t.shape) != tuple(shape)):
         raise _lib.AdaMVSHipError("%s must be [H, W]%s, got %s" % (name, "" if shape is None else " = %s" % (tuple(shape),), tuple(t.shape)))
     return t
 
 
-def _bld_workspace(H, W, device, workspace):
-    need = _lib.load().adamvs_bld_workspace_bytes(W, H)
-    check(0 if need >= 0 else int(need), "bld_workspace_bytes")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=device, dtype=torch.uint8)
-    return workspace
+def _number_roots(parent, spread=True):
+    """parent [H, W] int32: a cell's root, itself at a root, negative outside -> (label [H, W] int32: 0 outside, otherwise the
+    number 1 .. N of the cell's root in ascending cell index; N).  spread=False leaves out the look-up through parent: the
+    label is then right at the roots only."""
+    flat = parent.view(-1)
+    root = flat == torch.arange(flat.numel(), device=parent.device, dtype=torch.int32)
+    number = torch.cumsum(root, 0, dtype=torch.int32)               # the scan over the roots
+    N = int(number[-1])
+    if spread:
+        number = torch.where(flat >= 0, number[flat.clamp(min=0).long()], torch.zeros((), device=parent.device, dtype=torch.int32))
+    return number.view(parent.shape), N
 
 
 def bld_flags(dsm, ndsm, min_height, r_open, s, smooth_tol, workspace=None):
     """adamvs_bld_flags: dsm, ndsm [H, W] float32 (device) -> flags [H, W] uint8 (0 not a candidate, 1 removed by the opening,
     2 undetermined, 3 smooth, 4 rough).  Enqueued on the current stream."""
-    dsm = _bld_raster(dsm, "dsm", torch.float32)
-    ndsm = _bld_raster(ndsm, "ndsm", torch.float32, dsm.shape)
+    dsm = _raster(dsm, "dsm", torch.float32)
+    ndsm = _raster(ndsm, "ndsm", torch.float32, dsm.shape)
     H, W = dsm.shape
-    workspace = _bld_workspace(H, W, dsm.device, workspace)
+    workspace = _workspace("bld_workspace_bytes", dsm.device, workspace, W, H)
     flags = torch.empty(H, W, device=dsm.device, dtype=torch.uint8)
     check(_lib.load().adamvs_bld_flags(W, H, _p(dsm), _p(ndsm), float(min_height), int(r_open), int(s), float(smooth_tol), _p(workspace),
                                        workspace.numel(), _p(flags), _stream()), "bld_flags")
@@ -765,27 +774,23 @@ def bld_flags(dsm, ndsm, min_height, r_open, s, smooth_tol, workspace=None):
 def bld_label(flags, workspace=None):
     """adamvs_bld_label and the numbering: flags [H, W] uint8 (device) -> (label [H, W] int32: 0 outside the mask flags >= 2,
     otherwise 1 .. N in ascending order of the component's smallest cell index; N; _lib.BldStats).  Blocks until done."""
-    flags = _bld_raster(flags, "flags", torch.uint8)
+    flags = _raster(flags, "flags", torch.uint8)
     H, W = flags.shape
-    workspace = _bld_workspace(H, W, flags.device, workspace)
+    workspace = _workspace("bld_workspace_bytes", flags.device, workspace, W, H)
     parent = torch.empty(H, W, device=flags.device, dtype=torch.int32)
     stats = _lib.BldStats()
     check(_lib.load().adamvs_bld_label(W, H, _p(flags), _p(workspace), workspace.numel(), _p(parent), ctypes.byref(stats), _stream()),
           "bld_label")
-    flat = parent.view(-1)
-    root = flat == torch.arange(H * W, device=flags.device, dtype=torch.int32)
-    number = torch.cumsum(root, 0, dtype=torch.int32)               # the scan over the roots: 1 .. N in ascending cell index
-    N = int(number[-1])
-    label = torch.where(flat >= 0, number[flat.clamp(min=0).long()], torch.zeros((), device=flags.device, dtype=torch.int32))
-    return label.view(H, W), N, stats
+    label, N = _number_roots(parent)
+    return label, N, stats
 
 
 def bld_table(flags, ndsm, label, N):
     """adamvs_bld_table: -> table [len(_lib.BLD_COLUMNS), N] int64 (device), row k - 1 of each column for component k.
     Enqueued on the current stream."""
-    flags = _bld_raster(flags, "flags", torch.uint8)
-    ndsm = _bld_raster(ndsm, "ndsm", torch.float32, flags.shape)
-    label = _bld_raster(label, "label", torch.int32, flags.shape)
+    flags = _raster(flags, "flags", torch.uint8)
+    ndsm = _raster(ndsm, "ndsm", torch.float32, flags.shape)
+    label = _raster(label, "label", torch.int32, flags.shape)
     H, W = flags.shape
     table = torch.empty(len(_lib.BLD_COLUMNS), int(N), device=flags.device, dtype=torch.int64)
     check(_lib.load().adamvs_bld_table(W, H, _p(flags), _p(ndsm), _p(label), int(N), _p(table), _stream()), "bld_table")
@@ -796,8 +801,8 @@ def bld_table(flags, ndsm, label, N):
 def roof_links(dsm, building, s, smooth_tol, g_tol, step_tol):
     """adamvs_roof_links: dsm [H, W] float32, building [H, W] int32 (device) -> link [H, W] uint8 (bit 0 core, bit 1 east link,
     bit 2 south link).  Enqueued on the current stream."""
-    dsm = _bld_raster(dsm, "dsm", torch.float32)
-    building = _bld_raster(building, "building", torch.int32, dsm.shape)
+    dsm = _raster(dsm, "dsm", torch.float32)
+    building = _raster(building, "building", torch.int32, dsm.shape)
     H, W = dsm.shape
     link = torch.empty(H, W, device=dsm.device, dtype=torch.uint8)
     check(_lib.load().adamvs_roof_links(W, H, _p(dsm), _p(building), int(s), float(smooth_tol), float(g_tol), float(step_tol), _p(link),
@@ -809,30 +814,23 @@ def roof_label(link, workspace=None):
     """adamvs_roof_label and the numbering: link [H, W] uint8 (device; any bit pattern) -> (segment [H, W] int32: 0 where bit 0
     is clear, otherwise 1 .. S in ascending order of the segment's smallest cell index; S; parent [H, W] int32; _lib.BldStats).
     Blocks until done."""
-    link = _bld_raster(link, "link", torch.uint8)
+    link = _raster(link, "link", torch.uint8)
     H, W = link.shape
-    need = _lib.load().adamvs_roof_workspace_bytes(W, H)
-    check(0 if need >= 0 else int(need), "roof_workspace_bytes")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=link.device, dtype=torch.uint8)
+    workspace = _workspace("roof_workspace_bytes", link.device, workspace, W, H)
     parent = torch.empty(H, W, device=link.device, dtype=torch.int32)
     stats = _lib.BldStats()
     check(_lib.load().adamvs_roof_label(W, H, _p(link), _p(workspace), workspace.numel(), _p(parent), ctypes.byref(stats), _stream()),
           "roof_label")
-    flat = parent.view(-1)
-    root = flat == torch.arange(H * W, device=link.device, dtype=torch.int32)
-    number = torch.cumsum(root, 0, dtype=torch.int32)               # the scan over the roots: 1 .. S in ascending cell index
-    S = int(number[-1])
-    seg = torch.where(flat >= 0, number[flat.clamp(min=0).long()], torch.zeros((), device=link.device, dtype=torch.int32))
-    return seg.view(H, W), S, parent, stats
+    seg, S = _number_roots(parent)
+    return seg, S, parent, stats
 
 
 def roof_moments(dsm, label, building, z_ref, N):
     """adamvs_roof_moments: -> table [len(_lib.ROOF_COLUMNS), N] int64 (device), row k - 1 of each column for label k.
     Enqueued on the current stream."""
-    dsm = _bld_raster(dsm, "dsm", torch.float32)
-    label = _bld_raster(label, "label", torch.int32, dsm.shape)
-    building = _bld_raster(building, "building", torch.int32, dsm.shape)
+    dsm = _raster(dsm, "dsm", torch.float32)
+    label = _raster(label, "label", torch.int32, dsm.shape)
+    building = _raster(building, "building", torch.int32, dsm.shape)
     H, W = dsm.shape
     table = torch.empty(len(_lib.ROOF_COLUMNS), int(N), device=dsm.device, dtype=torch.int64)
     check(_lib.load().adamvs_roof_moments(W, H, _p(dsm), _p(label), _p(building), float(z_ref), int(N), _p(table), _stream()), "roof_moments")
@@ -849,10 +847,10 @@ def _roof_planes(planes, device):
 def roof_grow(dsm, building, z_ref, planes, assign_tol, label0, label1, counts, round0, rounds):
     """adamvs_roof_grow: the rounds round0 .. round0 + rounds - 1, round k from label[k & 1] into label[(k + 1) & 1] (label0,
     label1 [H, W] int32, device), counts uint32-as-int32 [_lib.ROOF_MAX_GROW] (device).  Enqueued on the current stream."""
-    dsm = _bld_raster(dsm, "dsm", torch.float32)
-    building = _bld_raster(building, "building", torch.int32, dsm.shape)
-    label0 = _bld_raster(label0, "label0", torch.int32, dsm.shape)
-    label1 = _bld_raster(label1, "label1", torch.int32, dsm.shape)
+    dsm = _raster(dsm, "dsm", torch.float32)
+    building = _raster(building, "building", torch.int32, dsm.shape)
+    label0 = _raster(label0, "label0", torch.int32, dsm.shape)
+    label1 = _raster(label1, "label1", torch.int32, dsm.shape)
     counts = _dev_as(counts, "counts", torch.int32)
     if counts.numel() != _lib.ROOF_MAX_GROW:
         raise _lib.AdaMVSHipError("counts must hold %d words, got %d" % (_lib.ROOF_MAX_GROW, counts.numel()))
@@ -866,8 +864,8 @@ def roof_grow(dsm, building, z_ref, planes, assign_tol, label0, label1, counts, 
 def roof_residuals(dsm, label, z_ref, planes, assign_tol):
     """adamvs_roof_residuals: -> table [2, R] int64 (device): the inlier count and the largest llrint(e * 1024) per plane.
     Enqueued on the current stream."""
-    dsm = _bld_raster(dsm, "dsm", torch.float32)
-    label = _bld_raster(label, "label", torch.int32, dsm.shape)
+    dsm = _raster(dsm, "dsm", torch.float32)
+    label = _raster(label, "label", torch.int32, dsm.shape)
     planes = _roof_planes(planes, dsm.device)
     H, W = dsm.shape
     R = planes.shape[0]
@@ -878,22 +876,14 @@ def roof_residuals(dsm, label, z_ref, planes, assign_tol):
 
 
 # ---- Trees (csrc/dsm_trees.hip; include/adamvs_hip.h "Trees") -----------------------------------------------------------------
-def _tree_workspace(H, W, device, workspace):
-    need = _lib.load().adamvs_tree_workspace_bytes(W, H)
-    check(0 if need >= 0 else int(need), "tree_workspace_bytes")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=device, dtype=torch.uint8)
-    return workspace
-
-
 def tree_surface(ndsm, building, min_height, smooth_passes, workspace=None):
     """adamvs_tree_surface: ndsm [H, W] float32, building [H, W] int32 or None (device) -> (mask uint8, q int32, s int32 (-1
     outside the canopy), s_max int32 [1]), all on the device.  Enqueued on the current stream."""
-    ndsm = _bld_raster(ndsm, "ndsm", torch.float32)
+    ndsm = _raster(ndsm, "ndsm", torch.float32)
     if building is not None:
-        building = _bld_raster(building, "building", torch.int32, ndsm.shape)
+        building = _raster(building, "building", torch.int32, ndsm.shape)
     H, W = ndsm.shape
-    workspace = _tree_workspace(H, W, ndsm.device, workspace)
+    workspace = _workspace("tree_workspace_bytes", ndsm.device, workspace, W, H)
     mask = torch.empty(H, W, device=ndsm.device, dtype=torch.uint8)
     q = torch.empty(H, W, device=ndsm.device, dtype=torch.int32)
     s = torch.empty(H, W, device=ndsm.device, dtype=torch.int32)
@@ -906,12 +896,12 @@ def tree_surface(ndsm, building, min_height, smooth_passes, workspace=None):
 def tree_parents(s, thr, workspace=None):
     """adamvs_tree_parents: s [H, W] int32 (device), thr: the ascending thresholds thr[1 .. r_cap] (host integers, thr[1] = 0) ->
     (parent [H, W] int32, _lib.TreeStats with candidates, window_cells and ms_parents set).  Blocks until done."""
-    s = _bld_raster(s, "s", torch.int32)
+    s = _raster(s, "s", torch.int32)
     H, W = s.shape
     thr = [int(v) for v in thr]
     if any(v < -2 ** 31 or v >= 2 ** 31 for v in thr):
         raise _lib.AdaMVSHipError("tree_parents: thr must hold int32 values")
-    workspace = _tree_workspace(H, W, s.device, workspace)
+    workspace = _workspace("tree_workspace_bytes", s.device, workspace, W, H)
     parent = torch.empty(H, W, device=s.device, dtype=torch.int32)
     stats = _lib.TreeStats()
     check(_lib.load().adamvs_tree_parents(W, H, _p(s), len(thr), (ctypes.c_int * max(len(thr), 1))(*thr), _p(workspace), workspace.numel(),
@@ -923,24 +913,23 @@ def tree_roots(parent, workspace=None, stats=None):
     """adamvs_tree_roots and the numbering: parent [H, W] int32 (device) -> (root [H, W] int32, number [H, W] int32: at a top its
     number 1 .. T in ascending cell index, T, _lib.TreeStats with rounds, converged, tops and ms_jump set; pass tree_parents'
     stats to have both calls' fields in one).  Blocks until done."""
-    parent = _bld_raster(parent, "parent", torch.int32)
+    parent = _raster(parent, "parent", torch.int32)
     H, W = parent.shape
-    workspace = _tree_workspace(H, W, parent.device, workspace)
+    workspace = _workspace("tree_workspace_bytes", parent.device, workspace, W, H)
     root = torch.empty(H, W, device=parent.device, dtype=torch.int32)
     stats = _lib.TreeStats() if stats is None else stats
     check(_lib.load().adamvs_tree_roots(W, H, _p(parent), _p(workspace), workspace.numel(), _p(root), ctypes.byref(stats), _stream()),
           "tree_roots")
-    top = root.view(-1) == torch.arange(H * W, device=parent.device, dtype=torch.int32)
-    number = torch.cumsum(top, 0, dtype=torch.int32)                 # the scan over the tops: 1 .. T in ascending cell index
-    return root, number.view(H, W), int(number[-1]), stats
+    number, T = _number_roots(root, spread=False)                    # crowns reads it at the tops only
+    return root, number, T, stats
 
 
 def tree_crowns(s, root, number, ratio_pm, rc2):
     """adamvs_tree_crowns: -> (label [H, W] int32: the number of the cell's top where both tests hold, else 0; unassigned int64
     [1]: the canopy cells that fail one), on the device.  Enqueued on the current stream."""
-    s = _bld_raster(s, "s", torch.int32)
-    root = _bld_raster(root, "root", torch.int32, s.shape)
-    number = _bld_raster(number, "number", torch.int32, s.shape)
+    s = _raster(s, "s", torch.int32)
+    root = _raster(root, "root", torch.int32, s.shape)
+    number = _raster(number, "number", torch.int32, s.shape)
     H, W = s.shape
     label = torch.empty(H, W, device=s.device, dtype=torch.int32)
     unassigned = torch.empty(1, device=s.device, dtype=torch.int64)
@@ -952,10 +941,10 @@ def tree_crowns(s, root, number, ratio_pm, rc2):
 def tree_table(label, q, s, root, T):
     """adamvs_tree_table: -> table [len(_lib.TREE_COLUMNS), T] int64 (device), row k - 1 of each column for tree k.  Enqueued
     on the current stream."""
-    label = _bld_raster(label, "label", torch.int32)
-    q = _bld_raster(q, "q", torch.int32, label.shape)
-    s = _bld_raster(s, "s", torch.int32, label.shape)
-    root = _bld_raster(root, "root", torch.int32, label.shape)
+    label = _raster(label, "label", torch.int32)
+    q = _raster(q, "q", torch.int32, label.shape)
+    s = _raster(s, "s", torch.int32, label.shape)
+    root = _raster(root, "root", torch.int32, label.shape)
     H, W = label.shape
     table = torch.empty(len(_lib.TREE_COLUMNS), int(T), device=label.device, dtype=torch.int64)
     check(_lib.load().adamvs_tree_table(W, H, _p(label), _p(q), _p(s), _p(root), int(T), _p(table) if T else None, _stream()), "tree_table")
@@ -963,22 +952,6 @@ def tree_table(label, q, s, root, T):
 
 
 # ---- Contours (csrc/dsm_contours.hip; include/adamvs_hip.h "Contours") ------------------------------------------------------
-def _contour_workspace(H, W, device, workspace):
-    need = _lib.load().adamvs_contour_workspace_bytes(W, H)
-    check(0 if need >= 0 else int(need), "contour_workspace_bytes")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=device, dtype=torch.uint8)
-    return workspace
-
-
-def _contour_rank_workspace(N, device, workspace):
-    need = _lib.load().adamvs_contour_rank_workspace_bytes(int(N))
-    check(0 if need >= 0 else int(need), "contour_rank_workspace_bytes")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, device=device, dtype=torch.uint8)
-    return workspace
-
-
 def _contour_levels(lev, what):
     lev = [int(v) for v in lev]
     if any(v < -2 ** 31 or v >= 2 ** 31 for v in lev):
@@ -1001,9 +974,9 @@ def _pn(t):
 def contour_surface(z, z_ref, smooth_passes, workspace=None):
     """adamvs_contour_surface: z [H, W] float32 (device) -> (s int32 [H, W], INT32_MIN outside V; info int32 [3]: s_min, s_max, the
     finite cells out of range), on the device.  Enqueued on the current stream."""
-    z = _bld_raster(z, "z", torch.float32)
+    z = _raster(z, "z", torch.float32)
     H, W = z.shape
-    workspace = _contour_workspace(H, W, z.device, workspace)
+    workspace = _workspace("contour_workspace_bytes", z.device, workspace, W, H)
     s = torch.empty(H, W, device=z.device, dtype=torch.int32)
     info = torch.empty(3, device=z.device, dtype=torch.int32)
     check(_lib.load().adamvs_contour_surface(W, H, _p(z), float(z_ref), int(smooth_passes), _p(workspace), workspace.numel(), _p(s), _p(info),
@@ -1015,10 +988,10 @@ def contour_count(s, lev, workspace=None):
     """adamvs_contour_count: s [H, W] int32 (device), lev: the strictly ascending level table (host integers) -> (count int32
     [H, W]: the segments per block, N, the workspace that holds the scanned offsets for contour_segments, _lib.ContourStats with
     segments and ms_count set).  Blocks until done."""
-    s = _bld_raster(s, "s", torch.int32)
+    s = _raster(s, "s", torch.int32)
     H, W = s.shape
     K, table = _contour_levels(lev, "contour_count")
-    workspace = _contour_workspace(H, W, s.device, workspace)
+    workspace = _workspace("contour_workspace_bytes", s.device, workspace, W, H)
     count = torch.empty(H, W, device=s.device, dtype=torch.int32)
     stats = _lib.ContourStats()
     check(_lib.load().adamvs_contour_count(W, H, _p(s), K, table, _p(workspace), workspace.numel(), _p(count), ctypes.byref(stats), _stream()),
@@ -1029,7 +1002,7 @@ def contour_count(s, lev, workspace=None):
 def contour_segments(s, lev, N, workspace):
     """adamvs_contour_segments: `workspace` as contour_count returned it -> (entry, exit, level, succ, pred), int32 [N] each, on
     the device.  Enqueued on the current stream."""
-    s = _bld_raster(s, "s", torch.int32)
+    s = _raster(s, "s", torch.int32)
     H, W = s.shape
     K, table = _contour_levels(lev, "contour_segments")
     workspace = _dev_as(workspace, "workspace", torch.uint8)
@@ -1047,7 +1020,7 @@ def contour_rank(pred, workspace=None, stats=None):
     if pred.dim() != 1:
         raise _lib.AdaMVSHipError("pred must be [N], got %s" % (tuple(pred.shape),))
     N = pred.numel()
-    workspace = _contour_rank_workspace(N, pred.device, workspace)
+    workspace = _workspace("contour_rank_workspace_bytes", pred.device, workspace, int(N))
     start = torch.empty(N, device=pred.device, dtype=torch.int32)
     rank = torch.empty(N, device=pred.device, dtype=torch.int32)
     closed = torch.empty(N, device=pred.device, dtype=torch.uint8)
@@ -1060,7 +1033,7 @@ def contour_rank(pred, workspace=None, stats=None):
 def contour_lines(s, lev, segments, start, rank, closed, M, workspace=None):
     """adamvs_contour_lines: segments = contour_segments' five arrays -> (line_first int64 [M + 1], line_start int32 [M],
     line_level int32 [M], line_closed uint8 [M], vertex int64 [N + M, 3]), on the device.  Blocks until done."""
-    s = _bld_raster(s, "s", torch.int32)
+    s = _raster(s, "s", torch.int32)
     H, W = s.shape
     K, table = _contour_levels(lev, "contour_lines")
     entry, exit_, level, succ, _ = segments
@@ -1069,7 +1042,7 @@ def contour_lines(s, lev, segments, start, rank, closed, M, workspace=None):
                                                                                         (succ, "succ")))
     start, rank = _contour_array(start, "start", torch.int32, N), _contour_array(rank, "rank", torch.int32, N)
     closed = _contour_array(closed, "closed", torch.uint8, N)
-    workspace = _contour_rank_workspace(N, s.device, workspace)
+    workspace = _workspace("contour_rank_workspace_bytes", s.device, workspace, int(N))
     line_first = torch.empty(M + 1, device=s.device, dtype=torch.int64)
     line_start = torch.empty(M, device=s.device, dtype=torch.int32)
     line_level = torch.empty(M, device=s.device, dtype=torch.int32)

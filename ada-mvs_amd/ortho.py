@@ -193,19 +193,10 @@ def load_views(folder, device):
 
 def read_dsm(prefix, filled=False):
     """-> (dsm [H, W] float32, dsm.Grid) from `<prefix>_dsm.json` and `<prefix>_dsm.tif` (`_dsm_filled.tif` if filled)."""
-    from PIL import Image
-    jpath = prefix + "_dsm.json"
-    if not os.path.exists(jpath):
-        raise FileNotFoundError("%s: no DSM summary (run dsm_whu.py --out %s first)" % (jpath, prefix))
-    with open(jpath) as f:
-        js = json.load(f)
-    g = js["grid"]
-    grid = Grid(float(g["x0"]), float(g["y_top"]), float(g["gsd"]), js.get("z_ref", 0.0), int(g["W"]), int(g["H"]))
+    from . import raster_stage
+    grid = raster_stage.read_grid(prefix)
     tif = prefix + ("_dsm_filled.tif" if filled else "_dsm.tif")
-    dsm = np.array(Image.open(tif), np.float32)
-    if dsm.shape != (grid.H, grid.W):
-        raise ValueError("%s is %s, %s says %d x %d" % (tif, dsm.shape, jpath, grid.H, grid.W))
-    return dsm, grid
+    return raster_stage.read_raster(tif, np.float32, (grid.H, grid.W), says="%s_dsm.json says %d x %d" % (prefix, grid.H, grid.W)), grid
 
 
 def output_paths(out):

@@ -21,17 +21,15 @@ The defaults are conventions, not values measured on WHU scenes.  A curved roof 
 rms_m, which is reported and not hidden.  Not here: ridge and eave lines, roof-type names, right-angle regularisation, CityJSON.
 """
 import argparse
-import json
 import math
-import os
-import sys
 import time
 from fractions import Fraction
 
 import numpy as np
 
+from . import raster_stage
 from .buildings import geojson_text, polygons
-from .dsm import _check_gsd, world_file_text
+from .dsm import _check_gsd
 
 MAX_STRIDE = 64                                     # ADAMVS_BLD_MAX_STRIDE, cells
 MAX_GROW = 256                                      # ADAMVS_ROOF_MAX_GROW, rounds
@@ -206,7 +204,7 @@ def feature_properties(rows, groups, fits, residuals, grid, z_ref, flat_deg=DEFA
 
 # ---- the stage ----------------------------------------------------------------------------------------------------------
 def _no_gpu():
-    return RuntimeError("roofs: needs an MI355X (there is no CPU fallback for the roof-plane kernels)")
+    return raster_stage.no_gpu("roofs", "roof-plane")
 
 
 def reference_height(dsm):
@@ -260,7 +258,6 @@ def extract(dsm, building, gsd, smooth_span=DEFAULTS["smooth_span"], smooth_tol=
     without a GPU: there is no CPU fallback."""
     import torch
     from . import hip_ops
-    from .dsm import Grid
     p = parameters(gsd, smooth_span, smooth_tol, slope_tol, step_tol, assign_tol, min_plane_area, grow_rounds, merge_rms, flat_deg)
     dsm = np.ascontiguousarray(dsm, np.float32)
     building = np.ascontiguousarray(building)
@@ -276,7 +273,7 @@ def extract(dsm, building, gsd, smooth_span=DEFAULTS["smooth_span"], smooth_tol=
         raise _no_gpu()
     gsd = float(gsd)
     if grid is None:
-        grid = Grid(0.0, H * gsd, gsd, 0.0, W, H)
+        grid = raster_stage.default_grid(H, W, gsd)
     z_ref = reference_height(dsm)
     dev = torch.device(device if device is not None else "cuda")
     d, b = torch.from_numpy(dsm).to(dev), torch.from_numpy(building).to(dev)
@@ -292,9 +289,7 @@ def extract(dsm, building, gsd, smooth_span=DEFAULTS["smooth_span"], smooth_tol=
     keep, planes = select_planes(seg_table, gsd, p["min_plane_area"])
     P = int(keep.sum())
     t4 = time.time()
-    lut = torch.zeros(S + 1, device=dev, dtype=torch.int32)
-    lut[1:][torch.from_numpy(keep).to(dev)] = torch.arange(1, P + 1, device=dev, dtype=torch.int32)
-    seed = lut[seg.long()]
+    seed = raster_stage.relabel_kept(seg, keep)
     planes_dev = torch.from_numpy(planes).to(dev)
     grown, grow_counts, rounds_run = grow(d, b, z_ref, planes_dev, p["assign_tol"], seed, p["grow_rounds"], stop_early)
     torch.cuda.synchronize(dev)
@@ -343,17 +338,13 @@ def from_dsm(prefix, filled=False, smooth_span=DEFAULTS["smooth_span"], smooth_t
     """The DSM of dsm_whu.py at the path prefix (its gap-filled raster if `filled`) and the building labels of buildings_whu.py
     next to it -> extract()'s dict with `source` added; written to `out` (a path prefix) if given."""
     import torch
-    from PIL import Image
     from .ortho import read_dsm
     dsm, grid = read_dsm(prefix, filled)
     bpath = prefix + "_buildings.tif"
-    if not os.path.exists(bpath):
-        raise FileNotFoundError("%s: no building labels (run buildings_whu.py --dsm %s first)" % (bpath, prefix))
+    raster_stage.require(bpath, "no building labels (run buildings_whu.py --dsm %s first)" % prefix)
     if not torch.cuda.is_available():
         raise _no_gpu()
-    building = np.array(Image.open(bpath), np.int32)
-    if building.shape != dsm.shape:
-        raise ValueError("%s is %s, the DSM %s" % (bpath, building.shape, dsm.shape))
+    building = raster_stage.read_raster(bpath, np.int32, dsm.shape, says="the DSM %s" % (dsm.shape,))
     res = extract(dsm, building, grid.gsd, smooth_span, smooth_tol, slope_tol, step_tol, assign_tol, min_plane_area, grow_rounds, merge_rms,
                   flat_deg, grid, device)
     res["source"] = dict(prefix=prefix, filled=bool(filled))
@@ -369,38 +360,20 @@ def output_paths(out):
 
 
 def summary(res):
-    g = res["grid"]
-    return dict(grid=dict(x0=g.x0, y_top=g.y_top, gsd=g.gsd, W=g.W, H=g.H), source=res.get("source"), params=res["params"], z_ref=res["z_ref"],
+    return dict(grid=raster_stage.grid_summary(res["grid"]), source=res.get("source"), params=res["params"], z_ref=res["z_ref"],
                 counts=res["counts"], planes_per_building=res["per_building"], label_stats=res["label_stats"], grow_stats=res["grow_stats"],
                 seconds=res["seconds"])
 
 
 def write_outputs(out, res):
     """The GeoJSON, the label raster, its world file and the JSON summary at the path prefix `out` -> output_paths(out)."""
-    from PIL import Image
-    paths = output_paths(out)
-    if os.path.dirname(out):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-    with open(paths["geojson"], "w") as f:
-        f.write(geojson_text(res["polygons"], res["properties"]))
-    Image.fromarray(np.ascontiguousarray(res["label"], np.int32)).save(paths["label"], format="TIFF")
-    with open(paths["label_world"], "w") as f:
-        f.write(world_file_text(res["grid"]))
-    with open(paths["json"], "w") as f:
-        json.dump(summary(res), f, indent=1)
-        f.write("\n")
-    return paths
+    return raster_stage.write_outputs(output_paths(out), out, dict(geojson=geojson_text(res["polygons"], res["properties"])), summary(res),
+                                      res["label"], res["grid"])
 
 
 def read_outputs(out):
     """-> (label int32, the GeoJSON as a dict, the summary as a dict) read back from the files of write_outputs."""
-    from PIL import Image
-    paths = output_paths(out)
-    with open(paths["geojson"]) as f:
-        gj = json.load(f)
-    with open(paths["json"]) as f:
-        js = json.load(f)
-    return np.array(Image.open(paths["label"]), np.int32), gj, js
+    return raster_stage.read_outputs(output_paths(out), ("geojson",))
 
 
 def build_parser():
@@ -422,10 +395,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    print("argv:", sys.argv[1:] if argv is None else argv)
-    t0 = time.time()
-    out = args.out if args.out is not None else args.dsm
+    args, out, t0 = raster_stage.open_main(build_parser, argv)
     res = from_dsm(args.dsm, args.filled, args.smooth_span, args.smooth_tol, args.slope_tol, args.step_tol, args.assign_tol, args.min_plane_area,
                    args.grow_rounds, args.merge_rms, args.flat_deg, out=out)
     g, c, p, s = res["grid"], res["counts"], res["params"], res["seconds"]

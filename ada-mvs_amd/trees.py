@@ -30,15 +30,14 @@ Nothing is classified by species.
 import argparse
 import json
 import math
-import os
-import sys
 import time
 from fractions import Fraction
 
 import numpy as np
 
+from . import raster_stage
 from .buildings import _groups, ring_area2, trace_rings
-from .dsm import _check_gsd, world_file_text
+from .dsm import _check_gsd
 
 MAX_RADIUS = 64                                     # ADAMVS_TREE_MAX_RADIUS, cells
 Q_SCALE = 256                                       # ADAMVS_TREE_Q_SCALE
@@ -183,7 +182,7 @@ def crowns_geojson_text(polys, props):
 
 # ---- the stage ----------------------------------------------------------------------------------------------------------
 def _no_gpu():
-    return RuntimeError("trees: needs an MI355X (there is no CPU fallback for the tree-detection kernels)")
+    return raster_stage.no_gpu("trees", "tree-detection")
 
 
 def finish(label, table, keep, counts, grid, thr):
@@ -205,7 +204,6 @@ def detect(ndsm, gsd, building=None, min_height=DEFAULTS["min_height"], smooth_p
     x0 = 0, y_top = H gsd).  Raises without a GPU: there is no CPU fallback."""
     import torch
     from . import hip_ops
-    from .dsm import Grid
     p = parameters(gsd, min_height, smooth_passes, radius_min, radius_slope, crown_ratio, max_crown_radius, min_crown_area)
     ndsm = np.ascontiguousarray(ndsm, np.float32)
     if ndsm.ndim != 2:
@@ -219,7 +217,7 @@ def detect(ndsm, gsd, building=None, min_height=DEFAULTS["min_height"], smooth_p
     H, W = ndsm.shape
     gsd = float(gsd)
     if grid is None:
-        grid = Grid(0.0, H * gsd, gsd, 0.0, W, H)
+        grid = raster_stage.default_grid(H, W, gsd)
     dev = torch.device(device if device is not None else "cuda")
     nd = torch.from_numpy(ndsm).to(dev)
     bd = None if building is None else torch.from_numpy(building).to(dev)
@@ -242,9 +240,7 @@ def detect(ndsm, gsd, building=None, min_height=DEFAULTS["min_height"], smooth_p
     table = {name: tab[k] for k, name in enumerate(COLUMNS)}
     table["q_top"] = q_top
     keep, counts = select(table, gsd, p["min_crown_area"])
-    lut = torch.zeros(T + 1, device=dev, dtype=torch.int32)
-    lut[1:][torch.from_numpy(keep).to(dev)] = torch.arange(1, counts["trees"] + 1, device=dev, dtype=torch.int32)
-    label = lut[crowns.long()].cpu().numpy()                          # the look-up of the tops' numbers
+    label = raster_stage.relabel_kept(crowns, keep).cpu().numpy()
     counts = dict(canopy=int(mask.sum()), labelled=int((crowns > 0).sum()), unassigned=int(unassigned.item()), **counts)
     t5 = time.time()
     polys, props = finish(label, table, keep, counts, grid, thr)
@@ -257,41 +253,23 @@ def detect(ndsm, gsd, building=None, min_height=DEFAULTS["min_height"], smooth_p
                 seconds=dict(surface=t1 - t0, parents=t2 - t1, roots=t3 - t2, crowns_table=t4 - t3, select=t5 - t4, vectorise=t6 - t5))
 
 
-def _read_grid(prefix):
-    from .dsm import Grid
-    jpath = prefix + "_dsm.json"
-    if not os.path.exists(jpath):
-        raise FileNotFoundError("%s: no DSM summary (run dsm_whu.py --out %s first)" % (jpath, prefix))
-    with open(jpath) as f:
-        js = json.load(f)
-    g = js["grid"]
-    return Grid(float(g["x0"]), float(g["y_top"]), float(g["gsd"]), js.get("z_ref", 0.0), int(g["W"]), int(g["H"]))
-
-
 def from_dsm(prefix, no_buildings=False, min_height=DEFAULTS["min_height"], smooth_passes=DEFAULTS["smooth_passes"],
              radius_min=DEFAULTS["radius_min"], radius_slope=DEFAULTS["radius_slope"], crown_ratio=DEFAULTS["crown_ratio"],
              max_crown_radius=DEFAULTS["max_crown_radius"], min_crown_area=DEFAULTS["min_crown_area"], device=None, out=None):
     """The nDSM of dtm_whu.py at the path prefix and the building labels of buildings_whu.py next to it (none with
     `no_buildings`) -> detect()'s dict with `source` added; written to `out` (a path prefix) if given."""
     import torch
-    from PIL import Image
-    grid = _read_grid(prefix)
+    grid = raster_stage.read_grid(prefix)
     npath, bpath = prefix + "_ndsm.tif", prefix + "_buildings.tif"
-    if not os.path.exists(npath):
-        raise FileNotFoundError("%s: no nDSM (run dtm_whu.py --dsm %s first)" % (npath, prefix))
-    if not no_buildings and not os.path.exists(bpath):
-        raise FileNotFoundError("%s: no building labels (run buildings_whu.py --dsm %s first, or pass --no_buildings to exclude nothing)"
-                                % (bpath, prefix))
+    raster_stage.require(npath, "no nDSM (run dtm_whu.py --dsm %s first)" % prefix)
+    if not no_buildings:
+        raster_stage.require(bpath, "no building labels (run buildings_whu.py --dsm %s first, or pass --no_buildings to exclude nothing)" % prefix)
     if not torch.cuda.is_available():
         raise _no_gpu()
-    ndsm = np.array(Image.open(npath), np.float32)
-    if ndsm.shape != (grid.H, grid.W):
-        raise ValueError("%s is %s, the grid %d x %d" % (npath, ndsm.shape, grid.H, grid.W))
+    ndsm = raster_stage.read_raster(npath, np.float32, (grid.H, grid.W), says="the grid %d x %d" % (grid.H, grid.W))
     building = None
     if not no_buildings:
-        building = np.array(Image.open(bpath), np.int32)
-        if building.shape != ndsm.shape:
-            raise ValueError("%s is %s, the nDSM %s" % (bpath, building.shape, ndsm.shape))
+        building = raster_stage.read_raster(bpath, np.int32, ndsm.shape, says="the nDSM %s" % (ndsm.shape,))
     res = detect(ndsm, grid.gsd, building, min_height, smooth_passes, radius_min, radius_slope, crown_ratio, max_crown_radius, min_crown_area,
                  grid, device)
     res["source"] = dict(prefix=prefix, buildings=not no_buildings)
@@ -308,42 +286,20 @@ def output_paths(out):
 
 
 def summary(res):
-    g = res["grid"]
     params = dict(res["params"], thr=[int(v) for v in res["thr"]])
-    return dict(grid=dict(x0=g.x0, y_top=g.y_top, gsd=g.gsd, W=g.W, H=g.H), source=res.get("source"), params=params, counts=res["counts"],
+    return dict(grid=raster_stage.grid_summary(res["grid"]), source=res.get("source"), params=params, counts=res["counts"],
                 jump_rounds=res["stats"]["rounds"], stats=res["stats"], seconds=res["seconds"])
 
 
 def write_outputs(out, res):
     """The two GeoJSON files, the label raster, its world file and the JSON summary at the path prefix `out` -> output_paths(out)."""
-    from PIL import Image
-    paths = output_paths(out)
-    if os.path.dirname(out):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-    with open(paths["points"], "w") as f:
-        f.write(points_geojson_text(res["properties"]))
-    with open(paths["crowns"], "w") as f:
-        f.write(crowns_geojson_text(res["polygons"], res["properties"]))
-    Image.fromarray(np.ascontiguousarray(res["label"], np.int32)).save(paths["label"], format="TIFF")
-    with open(paths["label_world"], "w") as f:
-        f.write(world_file_text(res["grid"]))
-    with open(paths["json"], "w") as f:
-        json.dump(summary(res), f, indent=1)
-        f.write("\n")
-    return paths
+    texts = dict(points=points_geojson_text(res["properties"]), crowns=crowns_geojson_text(res["polygons"], res["properties"]))
+    return raster_stage.write_outputs(output_paths(out), out, texts, summary(res), res["label"], res["grid"])
 
 
 def read_outputs(out):
     """-> (label int32, the points as a dict, the crowns as a dict, the summary as a dict) read back from write_outputs' files."""
-    from PIL import Image
-    paths = output_paths(out)
-    with open(paths["points"]) as f:
-        pts = json.load(f)
-    with open(paths["crowns"]) as f:
-        crowns = json.load(f)
-    with open(paths["json"]) as f:
-        js = json.load(f)
-    return np.array(Image.open(paths["label"]), np.int32), pts, crowns, js
+    return raster_stage.read_outputs(output_paths(out), ("points", "crowns"))
 
 
 def build_parser():
@@ -363,10 +319,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    print("argv:", sys.argv[1:] if argv is None else argv)
-    t0 = time.time()
-    out = args.out if args.out is not None else args.dsm
+    args, out, t0 = raster_stage.open_main(build_parser, argv)
     res = from_dsm(args.dsm, args.no_buildings, args.min_height, args.smooth_passes, args.radius_min, args.radius_slope, args.crown_ratio,
                    args.max_crown_radius, args.min_crown_area, out=out)
     g, c, p, s, st = res["grid"], res["counts"], res["params"], res["seconds"], res["stats"]

@@ -125,6 +125,34 @@ def test_random_link_bits_over_many_tiles(density):
     print("random links %.1f at %d^2: S = %d, %d border rounds" % (density, n, S, st.rounds))
 
 
+# ---- a mask is a link raster with every edge present ------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["T+1", "2T+1", "serpentine"])
+def test_a_mask_as_link_bits_gives_the_building_labels(case):
+    """The one labelling serves both stages: over a mask written as link bits (every bit set on the mask's cells, or exactly
+    the bits of the edges that exist) adamvs_roof_label returns the label raster and the count of adamvs_bld_label over the
+    mask as flags, and both are the flood fill of the mask."""
+    import torch
+    from ada_mvs_amd import hip_ops
+    import buildings_ref as B
+    if case == "serpentine":
+        mask = B.serpentine_mask(2 * T + 3, 2 * T + 3)
+    else:
+        n = T + 1 if case == "T+1" else 2 * T + 1
+        mask = B.random_mask_raster(n, n, 0.59, seed=n)[1] > 0
+    want, N = B.components_ref(mask)
+    label, got_N, _ = hip_ops.bld_label(torch.from_numpy(np.where(mask, 3, 0).astype(np.uint8)).cuda())
+    same(label.cpu().numpy(), want, "building labels")
+    assert got_N == N and N > 0
+    exact = mask.astype(np.uint8)
+    exact[:, :-1] |= (mask[:, :-1] & mask[:, 1:]).astype(np.uint8) * 2
+    exact[:-1, :] |= (mask[:-1, :] & mask[1:, :]).astype(np.uint8) * 4
+    for what, link in (("every bit", np.where(mask, 7, 0).astype(np.uint8)), ("the edges' bits", exact)):
+        _, seg, S, _ = gpu_segments(link)
+        same(seg, want, "segments of " + what)
+        same(seg, label.cpu().numpy(), "segments against the building labels, " + what)
+        assert S == got_N
+
+
 @pytest.mark.parametrize("name", ["serpentine", "comb"])
 def test_one_segment_across_every_tile_border(name, capsys):
     """Every cell is core and adjacent rows (columns) are separated by unlinked walls: a labelling that joined adjacent core cells
