@@ -222,6 +222,17 @@ SIGNATURES = {
                                c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
     "adamvs_roof_residuals": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_long, ctypes.c_void_p,
                                     ctypes.c_double, ctypes.c_void_p, c_st]),
+    "adamvs_lod2_workspace_bytes": (ctypes.c_long, [c_i, c_i]),
+    "adamvs_lod2_corner_heights_host": (c_i, [ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p]),
+    "adamvs_lod2_fill": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_long, c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_lod2_table": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_long, ctypes.c_long,
+                                ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_lod2_transpose": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_lod2_count": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                c_st]),
+    "adamvs_lod2_runs": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long,
+                               ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
     "adamvs_tree_workspace_bytes": (ctypes.c_long, [c_i, c_i]),
     "adamvs_tree_surface": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, c_i, ctypes.c_void_p, ctypes.c_long,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
@@ -388,6 +399,15 @@ ROOF_MAX_GROW = 256              # ADAMVS_ROOF_MAX_GROW: cap on the growth round
 ROOF_Q_SCALE, ROOF_Q_MAX = 256, (1 << 19) - 1  # ADAMVS_ROOF_Q_SCALE / _Q_MAX: quantised height above z_ref, 1/256 m
 ROOF_COLUMNS = ("n", "su", "sv", "sq", "suu", "suv", "svv", "suq", "svq", "sqq_lo", "sqq_hi", "row_min", "row_max", "col_min", "col_max",
                 "q_min", "q_max", "building")  # ADAMVS_ROOF_N .. ADAMVS_ROOF_BUILDING: the rows of the moments table
+LOD2_MAX_SIDE = 32768            # ADAMVS_LOD2_MAX_SIDE: largest W and H of the LoD2 stage, cells
+LOD2_MAX_FILL = 1024             # ADAMVS_LOD2_MAX_FILL: cap on the fill rounds of the model labels
+LOD2_Z_SCALE, LOD2_XY_SCALE = 1024, 1024   # ADAMVS_LOD2_Z_SCALE / _XY_SCALE: heights in 1/1024 m, positions in 1/1024 cell
+LOD2_PLANE_BITS = 20             # ADAMVS_LOD2_PLANE_BITS: A, B, C of a plane are multiples of 2^-20 m
+LOD2_Z_MAX = 1 << 30             # ADAMVS_LOD2_Z_MAX: |zq| of every corner stays below it
+LOD2_BLOCK = 256                 # ADAMVS_LOD2_BLOCK: lattice edges per workgroup of the run kernels
+LOD2_COLUMNS = ("cells", "filled", "base", "roof_min")   # ADAMVS_LOD2_CELLS .. ADAMVS_LOD2_ROOF_MIN: the rows of the building table
+LOD2_FIELDS = ("orientation", "line", "start", "end", "L", "R", "zL_s", "zL_e", "zR_s",
+               "zR_e")           # ADAMVS_LOD2_F_ORIENTATION .. ADAMVS_LOD2_F_ZR_E: the rows of the run records
 TREE_TILE = 64                   # ADAMVS_TREE_TILE: cells of a side of a tile of the parents kernel
 TREE_MAX_RADIUS = 64             # ADAMVS_TREE_MAX_RADIUS: largest window radius of the local-maximum filter, cells
 TREE_MAX_ROUNDS = 32             # ADAMVS_TREE_MAX_ROUNDS: cap on the rounds of pointer jumping

@@ -9,6 +9,7 @@
 #include "../../include/adamvs_hip.h"
 #include "common.h"
 #include "kernels.h"
+#include "lod2_plane.h"
 
 namespace adamvs {
 
@@ -650,6 +651,92 @@ extern "C" int adamvs_roof_residuals(int W, int H, const float* dsm, const int* 
   const BldBuffer b[] = {{dsm, 4 * n}, {label, 4 * n}, {planes, 24 * R}, {table, 16 * R}};
   ADAMVS_CHECK_ARG(!bld_any_overlap(b, R ? 4 : 2), "roof_residuals: dsm, label, planes and the table must not overlap");
   return launch_roof_residuals(W, H, dsm, label, z_ref, R, planes, assign_tol, table, (hipStream_t)stream);
+}
+
+// ---- LoD2 solids (dsm_lod2.hip)
+static int lod2_check_size(int W, int H, const char* what) {
+  ADAMVS_CHECK_ARG(W > 0 && H > 0 && W <= ADAMVS_LOD2_MAX_SIDE && H <= ADAMVS_LOD2_MAX_SIDE && (long)W * H <= ADAMVS_DSM_MAX_CELLS,
+                   "%s: grid W=%d H=%d (each <= %d, W H <= %d cells)", what, W, H, ADAMVS_LOD2_MAX_SIDE, ADAMVS_DSM_MAX_CELLS);
+  return 0;
+}
+
+extern "C" long adamvs_lod2_workspace_bytes(int W, int H) {
+  if (int rc = lod2_check_size(W, H, "lod2_workspace_bytes")) return rc;
+  return lod2_workspace_bytes(W, H);
+}
+
+extern "C" int adamvs_lod2_corner_heights_host(long P, const long long* planes, long n, const int* plane, const int* row, const int* col,
+                                               long long* zq) {
+  ADAMVS_CHECK_ARG(P >= 0 && n >= 0, "lod2_corner_heights_host: P=%ld, n=%ld must be >= 0", P, n);
+  ADAMVS_CHECK_ARG(n == 0 || (planes && plane && row && col && zq), "lod2_corner_heights_host: null pointer");
+  for (long i = 0; i < n; ++i)
+    ADAMVS_CHECK_ARG(plane[i] >= 1 && plane[i] <= P && row[i] >= 0 && row[i] <= ADAMVS_LOD2_MAX_SIDE && col[i] >= 0 &&
+                         col[i] <= ADAMVS_LOD2_MAX_SIDE,
+                     "lod2_corner_heights_host: entry %ld: plane %d (1 .. %ld) at corner (%d, %d) (0 .. %d)", i, plane[i], P, row[i], col[i],
+                     ADAMVS_LOD2_MAX_SIDE);
+  for (long i = 0; i < n; ++i) zq[i] = lod2_corner_height(planes + 3 * (long)(plane[i] - 1), row[i], col[i]);
+  return 0;
+}
+
+extern "C" int adamvs_lod2_fill(int W, int H, const int* building, long P, int round0, int rounds, int* label0, int* label1,
+                                unsigned* counts, void* stream) {
+  if (int rc = lod2_check_size(W, H, "lod2_fill")) return rc;
+  const long n = (long)W * H;
+  ADAMVS_CHECK_ARG(P >= 0 && P <= ADAMVS_DSM_MAX_CELLS, "lod2_fill: P=%ld (0 .. %d)", P, ADAMVS_DSM_MAX_CELLS);
+  ADAMVS_CHECK_ARG(building && label0 && label1 && counts, "lod2_fill: null pointer");
+  ADAMVS_CHECK_ARG(round0 >= 0 && rounds >= 0 && round0 <= ADAMVS_LOD2_MAX_FILL && rounds <= ADAMVS_LOD2_MAX_FILL - round0,
+                   "lod2_fill: rounds %d .. %d + %d (at most %d in all)", round0, round0, rounds, ADAMVS_LOD2_MAX_FILL);
+  const BldBuffer b[] = {{building, 4 * n}, {label0, 4 * n}, {label1, 4 * n}, {counts, 4L * ADAMVS_LOD2_MAX_FILL}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 4), "lod2_fill: building, the two label buffers and counts must not overlap");
+  return launch_lod2_fill(W, H, building, P, round0, rounds, label0, label1, counts, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_lod2_table(int W, int H, const float* dtm, const int* building, const int* label, double z_ref, long B, long P,
+                                 const long long* planes, long long* table, void* stream) {
+  if (int rc = lod2_check_size(W, H, "lod2_table")) return rc;
+  const long n = (long)W * H;
+  ADAMVS_CHECK_ARG(B >= 0 && B <= ADAMVS_DSM_MAX_CELLS && P >= 0 && P <= ADAMVS_DSM_MAX_CELLS, "lod2_table: B=%ld, P=%ld (0 .. %d)", B, P,
+                   ADAMVS_DSM_MAX_CELLS);
+  ADAMVS_CHECK_ARG(dtm && building && label && (planes || P == 0) && (table || B == 0), "lod2_table: null pointer");
+  ADAMVS_CHECK_ARG(std::isfinite(z_ref), "lod2_table: z_ref=%g must be finite", z_ref);
+  const BldBuffer b[] = {{dtm, 4 * n}, {building, 4 * n}, {label, 4 * n}, {table, 8L * ADAMVS_LOD2_COLUMNS * B}, {planes, 24 * P}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, !B ? 3 : !P ? 4 : 5), "lod2_table: dtm, building, label, the table and planes must not overlap");
+  return launch_lod2_table(W, H, dtm, building, label, z_ref, B, P, planes, table, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_lod2_transpose(int W, int H, const int* src, int* dst, void* stream) {
+  if (int rc = lod2_check_size(W, H, "lod2_transpose")) return rc;
+  const long n = (long)W * H;
+  ADAMVS_CHECK_ARG(src && dst, "lod2_transpose: null pointer");
+  const BldBuffer b[] = {{src, 4 * n}, {dst, 4 * n}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 2), "lod2_transpose: src and dst must not overlap");
+  return launch_lod2_transpose(W, H, src, dst, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_lod2_count(int W, int H, const int* label, const int* label_t, long P, void* workspace, long workspace_bytes,
+                                 unsigned* total, void* stream) {
+  if (int rc = lod2_check_size(W, H, "lod2_count")) return rc;
+  const long n = (long)W * H, need = lod2_workspace_bytes(W, H);
+  ADAMVS_CHECK_ARG(P >= 0 && P <= ADAMVS_DSM_MAX_CELLS, "lod2_count: P=%ld (0 .. %d)", P, ADAMVS_DSM_MAX_CELLS);
+  ADAMVS_CHECK_ARG(label && label_t && workspace && total, "lod2_count: null pointer");
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "lod2_count: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{label, 4 * n}, {label_t, 4 * n}, {workspace, need}, {total, 4}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 4), "lod2_count: label, label_t, total and the workspace must not overlap");
+  return launch_lod2_count(W, H, label, label_t, P, workspace, total, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_lod2_runs(int W, int H, const int* label, const int* label_t, long P, const long long* planes, const int* plane_base,
+                                long N, void* workspace, long workspace_bytes, int* records, void* stream) {
+  if (int rc = lod2_check_size(W, H, "lod2_runs")) return rc;
+  const long n = (long)W * H, need = lod2_workspace_bytes(W, H), edges = (long)(H + 1) * W + (long)(W + 1) * H;
+  ADAMVS_CHECK_ARG(P >= 0 && P <= ADAMVS_DSM_MAX_CELLS, "lod2_runs: P=%ld (0 .. %d)", P, ADAMVS_DSM_MAX_CELLS);
+  ADAMVS_CHECK_ARG(N >= 0 && N <= edges, "lod2_runs: N=%ld (0 .. %ld lattice edges)", N, edges);
+  ADAMVS_CHECK_ARG(label && label_t && workspace && ((planes && plane_base) || P == 0) && (records || N == 0), "lod2_runs: null pointer");
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "lod2_runs: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{label, 4 * n}, {label_t, 4 * n}, {workspace, need}, {records, 4L * ADAMVS_LOD2_FIELDS * N}, {planes, 24 * P},
+                         {plane_base, 4 * P}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, !N ? 3 : !P ? 4 : 6), "lod2_runs: the inputs, the records and the workspace must not overlap");
+  return launch_lod2_runs(W, H, label, label_t, P, planes, plane_base, N, workspace, records, (hipStream_t)stream);
 }
 
 // ---- Trees (dsm_trees.hip)

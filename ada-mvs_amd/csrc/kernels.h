@@ -208,6 +208,17 @@ int launch_roof_grow(int W, int H, const float* dsm, const int* building, double
 int launch_roof_residuals(int W, int H, const float* dsm, const int* label, double z_ref, long R, const double* planes, double assign_tol,
                           long long* table, hipStream_t st);
 
+// dsm_lod2.hip: model labels, building table, transpose and the boundary runs (include/adamvs_hip.h, "LoD2 solids")
+long lod2_workspace_bytes(int W, int H);
+int launch_lod2_fill(int W, int H, const int* building, long P, int round0, int rounds, int* label0, int* label1, unsigned* counts,
+                     hipStream_t st);
+int launch_lod2_table(int W, int H, const float* dtm, const int* building, const int* label, double z_ref, long B, long P,
+                      const long long* planes, long long* table, hipStream_t st);
+int launch_lod2_transpose(int W, int H, const int* src, int* dst, hipStream_t st);
+int launch_lod2_count(int W, int H, const int* label, const int* label_t, long P, void* workspace, unsigned* total, hipStream_t st);
+int launch_lod2_runs(int W, int H, const int* label, const int* label_t, long P, const long long* planes, const int* plane_base, long N,
+                     void* workspace, int* records, hipStream_t st);
+
 // dsm_trees.hip: canopy surface, parents, roots, crown labels and the per-tree table (include/adamvs_hip.h, "Trees")
 long tree_workspace_bytes(int W, int H);
 int launch_tree_surface(int W, int H, const float* ndsm, const int* building, double min_height, int smooth_passes, void* workspace,

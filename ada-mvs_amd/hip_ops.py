@@ -875,6 +875,89 @@ def roof_residuals(dsm, label, z_ref, planes, assign_tol):
     return table
 
 
+# ---- LoD2 solids (csrc/dsm_lod2.hip; include/adamvs_hip.h "LoD2 solids") ------------------------------------------------------
+def _lod2_planes(planes):
+    planes = _dev_as(planes, "planes", torch.int64)
+    if planes.dim() != 2 or planes.shape[1] != 3:
+        raise _lib.AdaMVSHipError("planes must be [P, 3] int64, got %s" % (tuple(planes.shape),))
+    return planes
+
+
+def lod2_corner_heights_host(planes, plane, row, col):
+    """adamvs_lod2_corner_heights_host: planes int64 [P, 3], plane (1 .. P), row, col: equal-length integer sequences (host) ->
+    zq int64 (numpy): the device's own evaluation of a plane at a lattice corner, run on the host.  Needs no GPU."""
+    import numpy as np
+    planes = np.ascontiguousarray(planes, np.int64).reshape(-1, 3)
+    plane, row, col = (np.ascontiguousarray(v, np.int32).reshape(-1) for v in (plane, row, col))
+    if not plane.size == row.size == col.size:
+        raise _lib.AdaMVSHipError("plane, row and col must have one length, got %d, %d, %d" % (plane.size, row.size, col.size))
+    zq = np.empty(plane.size, np.int64)
+    check(_lib.load().adamvs_lod2_corner_heights_host(planes.shape[0], planes.ctypes.data, plane.size, plane.ctypes.data, row.ctypes.data,
+                                                      col.ctypes.data, zq.ctypes.data), "lod2_corner_heights_host")
+    return zq
+
+
+def lod2_fill(building, P, label0, label1, counts, round0, rounds):
+    """adamvs_lod2_fill: the rounds round0 .. round0 + rounds - 1, round k from label[k & 1] into label[(k + 1) & 1] (label0,
+    label1 [H, W] int32, device), counts uint32-as-int32 [_lib.LOD2_MAX_FILL] (device).  Enqueued on the current stream."""
+    building = _raster(building, "building", torch.int32)
+    label0 = _raster(label0, "label0", torch.int32, building.shape)
+    label1 = _raster(label1, "label1", torch.int32, building.shape)
+    counts = _dev_as(counts, "counts", torch.int32)
+    if counts.numel() != _lib.LOD2_MAX_FILL:
+        raise _lib.AdaMVSHipError("counts must hold %d words, got %d" % (_lib.LOD2_MAX_FILL, counts.numel()))
+    H, W = building.shape
+    check(_lib.load().adamvs_lod2_fill(W, H, _p(building), int(P), int(round0), int(rounds), _p(label0), _p(label1), _p(counts), _stream()),
+          "lod2_fill")
+
+
+def lod2_table(dtm, building, label, z_ref, B, planes):
+    """adamvs_lod2_table: -> table [len(_lib.LOD2_COLUMNS), B] int64 (device), row k - 1 of each column for building k.
+    Enqueued on the current stream."""
+    dtm = _raster(dtm, "dtm", torch.float32)
+    building = _raster(building, "building", torch.int32, dtm.shape)
+    label = _raster(label, "label", torch.int32, dtm.shape)
+    planes = _lod2_planes(planes)
+    H, W = dtm.shape
+    P = planes.shape[0]
+    table = torch.empty(len(_lib.LOD2_COLUMNS), int(B), device=dtm.device, dtype=torch.int64)
+    check(_lib.load().adamvs_lod2_table(W, H, _p(dtm), _p(building), _p(label), float(z_ref), int(B), P, _p(planes) if P else None,
+                                        _p(table) if B else None, _stream()), "lod2_table")
+    return table
+
+
+def lod2_transpose(src):
+    """adamvs_lod2_transpose: src [H, W] int32 (device) -> [W, H].  Enqueued on the current stream."""
+    src = _raster(src, "src", torch.int32)
+    H, W = src.shape
+    dst = torch.empty(W, H, device=src.device, dtype=torch.int32)
+    check(_lib.load().adamvs_lod2_transpose(W, H, _p(src), _p(dst), _stream()), "lod2_transpose")
+    return dst
+
+
+def lod2_runs(label, planes, plane_base, workspace=None):
+    """adamvs_lod2_transpose, adamvs_lod2_count, the read-back of the run count and adamvs_lod2_runs: label [H, W] int32 (device;
+    the model labels, refused buildings zeroed), planes int64 [P, 3], plane_base int32 [P] (device) -> (records
+    [len(_lib.LOD2_FIELDS), N] int32 (device) in ascending (orientation, line, start), N).  Blocks for the one word."""
+    label = _raster(label, "label", torch.int32)
+    planes = _lod2_planes(planes)
+    plane_base = _dev_as(plane_base, "plane_base", torch.int32)
+    P = planes.shape[0]
+    if plane_base.dim() != 1 or plane_base.numel() != P:
+        raise _lib.AdaMVSHipError("plane_base must be [P = %d] int32, got %s" % (P, tuple(plane_base.shape)))
+    H, W = label.shape
+    workspace = _workspace("lod2_workspace_bytes", label.device, workspace, W, H)
+    label_t = lod2_transpose(label)
+    total = torch.zeros(1, device=label.device, dtype=torch.int32)
+    lib = _lib.load()
+    check(lib.adamvs_lod2_count(W, H, _p(label), _p(label_t), P, _p(workspace), workspace.numel(), _p(total), _stream()), "lod2_count")
+    N = int(total.item())
+    records = torch.empty(len(_lib.LOD2_FIELDS), N, device=label.device, dtype=torch.int32)
+    check(lib.adamvs_lod2_runs(W, H, _p(label), _p(label_t), P, _p(planes) if P else None, _p(plane_base) if P else None, N, _p(workspace),
+                               workspace.numel(), _p(records) if N else None, _stream()), "lod2_runs")
+    return records, N
+
+
 # ---- Trees (csrc/dsm_trees.hip; include/adamvs_hip.h "Trees") -----------------------------------------------------------------
 def tree_surface(ndsm, building, min_height, smooth_passes, workspace=None):
     """adamvs_tree_surface: ndsm [H, W] float32, building [H, W] int32 or None (device) -> (mask uint8, q int32, s int32 (-1

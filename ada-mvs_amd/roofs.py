@@ -18,7 +18,8 @@ height_min, height_max), `<out>_roofs.tif` (int32 plane labels, 0 = none), `<out
 defaults to --dsm; none of the names collides with a file of an earlier stage.
 
 The defaults are conventions, not values measured on WHU scenes.  A curved roof (a dome) comes out as few planes with a large
-rms_m, which is reported and not hidden.  Not here: ridge and eave lines, roof-type names, right-angle regularisation, CityJSON.
+rms_m, which is reported and not hidden.  Not here: ridge and eave lines, roof-type names, right-angle regularisation (the solids
+and their CityJSON are the next stage's: lod2.py).
 """
 import argparse
 import math

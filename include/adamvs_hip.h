@@ -849,6 +849,99 @@ int adamvs_roof_grow(int W, int H, const float* dsm, const int* building, double
 int adamvs_roof_residuals(int W, int H, const float* dsm, const int* label, double z_ref, long R, const double* planes,
                           double assign_tol, long long* table, void* stream);
 
+/* ---- LoD2 solids (after the roof planes): footprints, roof planes and terrain joined into one watertight solid per building --
+ * ada-mvs_amd/lod2.py extract(); lod2_whu.py is the CLI.  Inputs: dtm [H][W] fp32 (terrain, NaN where there is no value),
+ * building [H][W] int32 (0 = none, 1 .. B), roof [H][W] int32 (0 = none, 1 .. P, the plane labels of roofs_whu.py) and per plane
+ * p its building bld(p) and its equation.  W, H <= ADAMVS_LOD2_MAX_SIDE and W H <= ADAMVS_DSM_MAX_CELLS.  A cell is (i, j), rows
+ * running south; a lattice CORNER is (r, c), r in 0 .. H, c in 0 .. W: the north-west corner of cell (r, c).  Everything is
+ * integer: heights in 1 / ADAMVS_LOD2_Z_SCALE m above z_ref = floor(min finite dtm), horizontal positions in
+ * 1 / ADAMVS_LOD2_XY_SCALE of a cell.  No step depends on a visiting order; every output is bit-identical from run to run.
+ *
+ * 1. Planes as integers (host).  From plane p's z = z0 + sx (x - xc) + sy (y - yc) and the grid (x0, y_top, gsd), in fp64 in the
+ *    order written: a = sx * gsd, b = -(sy * gsd) (metres per cell east and south),
+ *    c = ((z0 + sx * ((x0 + 0.5 * gsd) - xc)) + sy * ((y_top - 0.5 * gsd) - yc)) - z_ref (metres at the centre of cell (0, 0)).
+ *    A, B, C = rint(a 2^20), rint(b 2^20), rint(c 2^20) (ties to even) as int64; planes int64 [P][3].  The height of plane p at
+ *    corner (r, c) is   zq = floor((A (2 c - 1) + B (2 r - 1) + 2 C + 2^10) / 2^11)   (round half up), evaluated in int64 by the one
+ *    function lod2_corner_height() of csrc/lod2_plane.h on the device and on the host (_lod2_corner_heights_host).  The caller
+ *    refuses a plane with |A| or |B| >= 2^40, |C| >= 2^50, or |zq| >= ADAMVS_LOD2_Z_MAX at one of the four grid corners (zq is
+ *    monotonic along either axis, so it then holds at every corner); a record holds zq as an int32.
+ * 2. Model labels (_lod2_fill), rounds over two label buffers.  The caller starts from m_0(c) = roof(c) if 1 <= roof(c) <= P and
+ *    building(c) = bld(roof(c)) > 0, else 0.  In a round a cell with building(c) = b > 0 and label 0 (a label outside 1 .. P reads
+ *    as 0) takes the smallest label 1 .. P among its four neighbours inside the grid with building = b, as of the previous
+ *    round; a cell with building(c) <= 0 gets 0; every other cell keeps its label.  counts[k] = the cells labelled in round k.  A
+ *    round that labels nothing is a fixed point.  At most ADAMVS_LOD2_MAX_FILL rounds.
+ * 3. Building table (_lod2_table), int64 [ADAMVS_LOD2_COLUMNS][B], row k - 1 for building k, over the cells with building(c) = k:
+ *    cells; filled = those with a model label 1 .. P; base = the smallest
+ *    (long long)fmin(fmax(floor(((double)dtm - z_ref) * 1024.0), -2^30), 2^30) over those with a finite dtm; roof_min = the smallest
+ *    zq of the cell's plane at the cell's four corners over those with a model label.  Sums start at 0, minima at 2^31 - 1.
+ *    On the host a building gets no solid if filled = 0 ("no_plane"), else if it has no finite dtm ("no_terrain"), else if
+ *    base >= roof_min ("base_not_below_roof"); the model labels of these buildings' cells are set to 0 by a look-up.
+ * 4. Boundary runs (_lod2_count, _lod2_runs).  Horizontal line k (0 .. H) lies between the rows k - 1 and k and has the edges
+ *    pos = 0 .. W - 1 from corner (k, pos) to (k, pos + 1); vertical line k (0 .. W) lies between the columns k - 1 and k and has
+ *    the edges pos = 0 .. H - 1 from corner (pos, k) to (pos + 1, k).  A label outside the grid is 0 (outside).  Lines run east
+ *    and south; L is the label on the left of that direction, R on the right: horizontal L = m(k - 1, pos), R = m(k, pos);
+ *    vertical L = m(pos, k), R = m(pos, k - 1).  An edge is a BOUNDARY edge iff L != R.  A RUN is a maximal sequence of
+ *    consecutive boundary edges of one line with the same (L, R).  One record of ADAMVS_LOD2_FIELDS int32 per run:
+ *    orientation (0 horizontal, 1 vertical), line, start, end (the positions of its first and last corner: its edges are
+ *    start .. end - 1), L, R, zL_s, zL_e, zR_s, zR_e: the heights of the two sides at the start and the end corner.  The height
+ *    of side q > 0 is zq of plane q at that corner; the height of side 0 is plane_base[q' - 1] of the other side q' (the base of
+ *    bld(q'): the caller's table).  records int32 [ADAMVS_LOD2_FIELDS][N] in ascending order of (orientation, line, start).
+ * 5. Faces (host, exact integers): ada-mvs_amd/lod2.py faces().  Vertices are (1024 c, 1024 (H - r), z).  A run from S to E with
+ *    d = zL - zR at either end: d_s = d_e = 0 no wall; d_s d_e >= 0 one vertical polygon S_R E_R E_L S_L (repeated vertices
+ *    dropped), which faces the lower side; d_s d_e < 0 two triangles S_R X S_L and X E_R E_L with X at t = d_s / (d_s - d_e)
+ *    along the run, position and height (zL_s + t (zL_e - zL_s)) each rounded half up, the same X in the roof rings of both
+ *    sides.  On the vertical edges at S and E every other height of that corner (the side heights of all runs that end there)
+ *    strictly inside is a vertex.  One roof polygon with holes per model plane, chained from its side of its runs (S to E where
+ *    it is L, E to S where it is R; at a corner with two ways on, the left turn); one ground polygon per building at base from
+ *    the runs against label 0, reversed.  Roofs face up, the ground down, walls away from the higher side.
+ *
+ * Kernels (csrc/dsm_lod2.hip).  _lod2_fill: the rounds round0 .. round0 + rounds - 1, one launch each, round k from label[k & 1]
+ * into label[(k + 1) & 1], counts[k] zeroed first, one atomic add per workgroup; the caller may read counts back between calls
+ * and stop at a fixed point.  _lod2_table: integer atomics only, one set per run of equal building labels in a wave.
+ * _lod2_transpose: dst [W][H] = src [H][W] transposed through LDS tiles, so that the vertical lines are rows too.  _lod2_count:
+ * a workgroup takes ADAMVS_LOD2_BLOCK consecutive edges of the row-major (line, pos) order of an orientation (the horizontal
+ * lines over label, the vertical ones over label_t), reads its two rows of labels coalesced and keeps the pairs with one
+ * neighbour on either side in LDS; an edge is a HEAD if it is a boundary edge and the edge before it on its line is not one of
+ * the same pair, a TAIL likewise towards the edge after it.  The heads of a workgroup are counted, the counts of all workgroups
+ * (horizontal first) scanned; *total = N.  _lod2_runs: the same flags again; head number h writes the start half of record h,
+ * and the tail that closes it writes the end half: heads and tails alternate along the order, so a tail's number is the number
+ * of heads before its workgroup, less one if the workgroup's first edge continues a run, plus its rank among the workgroup's
+ * tails.  A tail compaction paired with the head compaction: no lane walks along a run.  The order comes from the scan alone.
+ * All buffers device memory except those of _lod2_corner_heights_host (host memory: zq[i] = the height of plane plane[i]
+ * (1 .. P) at corner (row[i], col[i])); counts: uint32 [ADAMVS_LOD2_MAX_FILL]; total: uint32 [1]; workspace of at least
+ * _lod2_workspace_bytes(W, H) bytes, 256-byte aligned, the same between _lod2_count and _lod2_runs.
+ * Argument errors (<0, before any launch): a null pointer, W or H <= 0 or > ADAMVS_LOD2_MAX_SIDE or W H > ADAMVS_DSM_MAX_CELLS,
+ * z_ref not finite, B, P or N < 0, B or P > ADAMVS_DSM_MAX_CELLS (a table may be longer than the grid has cells), N above the number of lattice edges, rounds < 0, round0 < 0 or
+ * round0 + rounds > ADAMVS_LOD2_MAX_FILL, workspace_bytes below the query, any two buffers overlapping; for the host entry a
+ * plane number outside 1 .. P or a corner outside 0 .. 32768.  _lod2_workspace_bytes returns < 0 for a grid outside the limits. */
+#define ADAMVS_LOD2_MAX_SIDE 32768
+#define ADAMVS_LOD2_MAX_FILL 1024
+#define ADAMVS_LOD2_Z_SCALE 1024
+#define ADAMVS_LOD2_XY_SCALE 1024
+#define ADAMVS_LOD2_PLANE_BITS 20      /* A, B, C are multiples of 2^-20 m */
+#define ADAMVS_LOD2_Z_MAX 1073741824   /* 2^30: |zq| of every corner stays below it */
+#define ADAMVS_LOD2_BLOCK 256          /* lattice edges per workgroup of _lod2_count and _lod2_runs */
+#define ADAMVS_LOD2_COLUMNS 4
+#define ADAMVS_LOD2_FIELDS 10
+enum { ADAMVS_LOD2_CELLS = 0, ADAMVS_LOD2_FILLED = 1, ADAMVS_LOD2_BASE = 2, ADAMVS_LOD2_ROOF_MIN = 3 };
+enum {
+  ADAMVS_LOD2_F_ORIENTATION = 0, ADAMVS_LOD2_F_LINE = 1, ADAMVS_LOD2_F_START = 2, ADAMVS_LOD2_F_END = 3, ADAMVS_LOD2_F_L = 4,
+  ADAMVS_LOD2_F_R = 5, ADAMVS_LOD2_F_ZL_S = 6, ADAMVS_LOD2_F_ZL_E = 7, ADAMVS_LOD2_F_ZR_S = 8, ADAMVS_LOD2_F_ZR_E = 9
+};
+
+long adamvs_lod2_workspace_bytes(int W, int H);
+int adamvs_lod2_corner_heights_host(long P, const long long* planes, long n, const int* plane, const int* row, const int* col,
+                                    long long* zq);
+int adamvs_lod2_fill(int W, int H, const int* building, long P, int round0, int rounds, int* label0, int* label1, unsigned* counts,
+                     void* stream);
+int adamvs_lod2_table(int W, int H, const float* dtm, const int* building, const int* label, double z_ref, long B, long P,
+                      const long long* planes, long long* table, void* stream);
+int adamvs_lod2_transpose(int W, int H, const int* src, int* dst, void* stream);
+int adamvs_lod2_count(int W, int H, const int* label, const int* label_t, long P, void* workspace, long workspace_bytes,
+                      unsigned* total, void* stream);
+int adamvs_lod2_runs(int W, int H, const int* label, const int* label_t, long P, const long long* planes, const int* plane_base,
+                     long N, void* workspace, long workspace_bytes, int* records, void* stream);
+
 /* ---- Trees (after the building extraction, independent of the roof planes): tree tops and their crowns from the nDSM --------
  * ada-mvs_amd/trees.py detect(); trees_whu.py is the CLI.  Inputs: ndsm [H][W] fp32 as dtm_whu.py writes it (NaN where there is
  * no value) and building [H][W] int32 (0 = none, the label raster of buildings_whu.py; a null pointer excludes nothing).  Outside
