@@ -86,12 +86,14 @@ template <int CA, int CB, int NT, int MODE, int EPI, bool PAIR8 = false>
 __global__ __launch_bounds__(256) void k_fconv(FConvArgs a, TileGrid tg) {
   using GM = FGeom<MODE>;
   static_assert(!PAIR8 || GM::T, "PAIR8: the transposed mode");
-  constexpr int CIN = CA + CB, KC = CIN / 4, G = CIN / 4, GA = CA / 4, GB = CB / 4;
+  constexpr int CIN = CA + CB, KC = CIN / 4, G = CIN / 4, GA = CA / 4;
   constexpr int TR = 4, TC = 16, STR = GM::STR, NTAPS = GM::NTAPS;
   constexpr int LR = GM::rows(TR), LC = GM::cols(TC), NPIX = LR * LC;
   constexpr int PLANE = (STR == 1) ? plane_pitch16(NPIX) : (NPIX | 1);
   constexpr int GP = group_pitch(PLANE, G);
-  constexpr int NA = (NPIX * GA + 255) / 256, NB = (NPIX * GB + 255) / 256, NL = NA + NB;
+  typedef TileWindow<CA, LR, LC, true, PLANE, GP> WinA;
+  typedef TileWindow<CB, LR, LC, true, PLANE, GP> WinB;
+  constexpr int NA = WinA::N, NB = WinB::N, NL = NA + NB;
   extern __shared__ float lds[];         // [G][GP]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int p = lane & 15, q = lane >> 4;
@@ -129,21 +131,11 @@ __global__ __launch_bounds__(256) void k_fconv(FConvArgs a, TileGrid tg) {
     }
   }
 
-  // ---- per-lane constants
-  unsigned goff[NL], lbyte[NL];
-  int rc[NL];
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    const bool isA = k < NA;
-    const int gs = isA ? GA : GB, cs = isA ? CA : CB;
-    int j = tid + (isA ? k : k - NA) * 256;
-    j = min(j, NPIX * gs - 1);           // surplus lanes repeat the last item
-    const int g = j % gs, pp = j / gs, r = pp / LC, c = pp % LC;
-    goff[k] = (unsigned)(((r * a.wi + c) * cs + 4 * g) * 4);
-    lbyte[k] = (unsigned)((((isA ? 0 : GA) + g) * GP + r * LC + c) * 4);
-    rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]); pin(rc[k]);
-  }
+  // ---- per-lane constants: one window per source, B's channel groups behind A's (tile_window.h)
+  WinA wa;
+  WinB wb;
+  wa.init(a.wi);
+  wb.init(a.wi);
   unsigned xbyte[KC];
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) {
@@ -164,28 +156,12 @@ __global__ __launch_bounds__(256) void k_fconv(FConvArgs a, TileGrid tg) {
 
   auto load_tile = [&](f32x4 (&stage)[NL], int n, int tx, int ty) {
     const int ix0 = tx * TC * STR + GM::ORG, iy0 = ty * TR * STR + GM::ORG;
-    const long pix0 = ((long)n * a.hi + iy0) * a.wi + ix0;
-    const buf_rsrc ra = make_rsrc((const char*)a.srcA + pix0 * (CA * 4));
-    const buf_rsrc rb = make_rsrc((const char*)a.srcB + pix0 * (CB * 4));
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + LR <= a.hi && ix0 + LC <= a.wi) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(k < NA ? ra : rb, goff[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const int iy = iy0 + (rc[k] & 0xffff), ix = ix0 + (rc[k] >> 16);
-        const bool ok = (unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi;
-        stage[k] = buf_load4(k < NA ? ra : rb, ok ? goff[k] : BUF_OOB);              // zero padding
-      }
-    }
+    wa.request(stage, a.srcA, n, a.hi, a.wi, iy0, ix0);
+    wb.request(stage + NA, a.srcB, n, a.hi, a.wi, iy0, ix0);
   };
   auto store_tile = [&](const f32x4 (&stage)[NL]) {
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      float* dl = (float*)((char*)lds + lbyte[k]);
-      f32x4 v = stage[k];
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
-    }
+    wa.store(stage, lds);
+    wb.template store<GA>(stage + NA, lds);
   };
 
   int t = blockIdx.x;
@@ -470,11 +446,13 @@ static int launch_pair_two_row(const float* srcA, const float* srcB, const adamv
 template <int CA, int CB, int NT, int EPI>
 __global__ __launch_bounds__(256, (CA + CB == 16 && NT == 1) ? 4 : 1) void k_fconv_f23(FConvArgs a, TileGrid tg) {      // (16 channels: 132 registers uncapped -- three waves per SIMD; 128: four)
   static_assert(!(EPI & (FE_CONTEXT | FE_ADD_UP)), "plain epilogues");
-  constexpr int CIN = CA + CB, KC = CIN / 4, G = CIN / 4, GA = CA / 4, GB = CB / 4;
+  constexpr int CIN = CA + CB, KC = CIN / 4, G = CIN / 4, GA = CA / 4;
   constexpr int TR = 4, TC = 32, LR = TR + 2, LC = TC + 2, NPIX = LR * LC;
   constexpr int PLANE = plane_pitch16(NPIX), GP = group_pitch(PLANE, G);
   static_assert((PLANE % 2) == 0 && (GP % 2) == 0 && (LC % 2) == 0, "8-byte aligned pair reads");
-  constexpr int NA = (NPIX * GA + 255) / 256, NB = (NPIX * GB + 255) / 256, NL = NA + NB;
+  typedef TileWindow<CA, LR, LC, true, PLANE, GP> WinA;
+  typedef TileWindow<CB, LR, LC, true, PLANE, GP> WinB;
+  constexpr int NA = WinA::N, NB = WinB::N, NL = NA + NB;
   extern __shared__ float lds[];         // [G][GP]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int p = lane & 15, q = lane >> 4;
@@ -498,21 +476,11 @@ __global__ __launch_bounds__(256, (CA + CB == 16 && NT == 1) ? 4 : 1) void k_fco
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) bias[nt] = *(const f32x4*)(a.bias + nt * 16 + 4 * q);
 
-  // ---- per-lane constants
-  unsigned goff[NL], lbyte[NL];
-  int rc[NL];
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    const bool isA = k < NA;
-    const int gs = isA ? GA : GB, cs = isA ? CA : CB;
-    int j = tid + (isA ? k : k - NA) * 256;
-    j = min(j, NPIX * gs - 1);           // surplus lanes repeat the last item
-    const int g = j % gs, pp = j / gs, r = pp / LC, c = pp % LC;
-    goff[k] = (unsigned)(((r * a.wi + c) * cs + 4 * g) * 4);
-    lbyte[k] = (unsigned)((((isA ? 0 : GA) + g) * GP + r * LC + c) * 4);
-    rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]); pin(rc[k]);
-  }
+  // ---- per-lane constants: one window per source, B's channel groups behind A's (tile_window.h)
+  WinA wa;
+  WinB wb;
+  wa.init(a.wi);
+  wb.init(a.wi);
   unsigned xbyte[KC];
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) {
@@ -529,28 +497,12 @@ __global__ __launch_bounds__(256, (CA + CB == 16 && NT == 1) ? 4 : 1) void k_fco
 
   auto load_tile = [&](f32x4 (&stage)[NL], int n, int tx, int ty) {
     const int ix0 = tx * TC - 1, iy0 = ty * TR - 1;
-    const long pix0 = ((long)n * a.hi + iy0) * a.wi + ix0;
-    const buf_rsrc ra = make_rsrc((const char*)a.srcA + pix0 * (CA * 4));
-    const buf_rsrc rb = make_rsrc((const char*)a.srcB + pix0 * (CB * 4));
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + LR <= a.hi && ix0 + LC <= a.wi) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(k < NA ? ra : rb, goff[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const int iy = iy0 + (rc[k] & 0xffff), ix = ix0 + (rc[k] >> 16);
-        const bool ok = (unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi;
-        stage[k] = buf_load4(k < NA ? ra : rb, ok ? goff[k] : BUF_OOB);              // zero padding
-      }
-    }
+    wa.request(stage, a.srcA, n, a.hi, a.wi, iy0, ix0);
+    wb.request(stage + NA, a.srcB, n, a.hi, a.wi, iy0, ix0);
   };
   auto store_tile = [&](const f32x4 (&stage)[NL]) {
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      float* dl = (float*)((char*)lds + lbyte[k]);
-      f32x4 v = stage[k];
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
-    }
+    wa.store(stage, lds);
+    wb.template store<GA>(stage + NA, lds);
   };
 
   int t = blockIdx.x;

@@ -13,6 +13,7 @@
 #include "persistent.h"
 #include "slice_roles.h"
 #include "slice_roles_wino.h"
+#include "tile_window.h"
 
 namespace adamvs {
 
@@ -145,17 +146,41 @@ static int launch_small(const SmallConvArgs& a, int B, hipStream_t st, const cha
   return launch_small_shape<CA, CB, NT, STRIDE, EPI, 4, 1>(a, B, st, name);
 }
 
+// What the four conv1 kernels share behind the chain.  conv1_out_off: byte offset of the lane's output pixel (orow, col), channels
+// 4 (q & 1).., from the first pixel of its tile in c1 [N][hw][8] (formed once).  conv1_relu_store: ReLU and the store of the lane's NP
+// horizontally adjacent pixels of tile (n, ty, tx); in a tile that is not full, the pixels outside the map take BUF_OOB.
+__device__ __forceinline__ unsigned conv1_out_off(int orow, int col, int w, int q) {
+  unsigned ooff = (unsigned)(((orow * w + col) * 8 + 4 * (q & 1)) * 4);
+  pin(ooff);
+  return ooff;
+}
+template <int TR, int TC, int NP>
+__device__ __forceinline__ void conv1_relu_store(float* c1, int n, int h, int w, int ty, int tx, int orow, int col, unsigned ooff,
+                                                 f32x4 (&o)[NP]) {
+  const int y0 = ty * TR, x0 = tx * TC;
+  const buf_rsrc ro = make_rsrc((char*)c1 + (((long)n * h + y0) * w + x0) * 32);
+  const bool full = y0 + TR <= h && x0 + TC <= w;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    unsigned oo = ooff + 32 * j;
+    if (!full) oo = (y0 + orow < h && x0 + col + j < w) ? oo : BUF_OOB;
+    o[j].x = fmaxf(o[j].x, 0.f); o[j].y = fmaxf(o[j].y, 0.f); o[j].z = fmaxf(o[j].z, 0.f); o[j].w = fmaxf(o[j].w, 0.f);
+    buf_store4(ro, oo, o[j]);
+  }
+}
+
 // conv1 (C -> 8, ReLU; reference adamvs.py:416) in two-row form: the 16 MFMA rows are 8 output channels of
 // output row y and the same 8 channels of row y+1, fed by the same input-row fragment (tap ky for the first
 // half, ky-1 for the second), so no half of the tile is zero padding: 12 fragment passes per 2 rows instead of 18.
-// src [N][hw][C] -> c1 [N][hw][8].  Persistent and pipelined like k_conv_small; tile 8 rows x 16 columns = four
+// src [N][hw][C] -> c1 [N][hw][8].  Persistent and pipelined (slice_roles.h, "Persistent workgroups"); tile 8 rows x 16 columns = four
 // row pairs, one per wave (12 * C/4 MFMAs each).
 template <int C>
 __global__ __launch_bounds__(256) void k_conv1_two_row(const float* __restrict__ src, const float* __restrict__ wpk,
                                                        float* __restrict__ c1, int h, int w, TileGrid tg) {
   constexpr int KC = C / 4, G = C / 4, TR = 8, TC = 16, LR = TR + 2, LC = TC + 2, NPIX = LR * LC;
   constexpr int PLANE = plane_pitch16(NPIX), GP = group_pitch(PLANE, G);
-  constexpr int NL = (NPIX * G + 255) / 256;
+  typedef TileWindow<C, LR, LC, true, PLANE, GP> Win;
+  constexpr int NL = Win::N;
   extern __shared__ float lds[];           // [G][GP]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform
   const int p = lane & 15, q = lane >> 4;
@@ -165,18 +190,8 @@ __global__ __launch_bounds__(256) void k_conv1_two_row(const float* __restrict__
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) wf[t][kc] = wpk[(t * KC + kc) * 64 + lane];
 
-  // ---- per-lane constants
-  unsigned goff[NL], lbyte[NL];
-  int rc[NL];
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    const int j = min(tid + k * 256, NPIX * G - 1);          // surplus lanes repeat the last item
-    const int g = j % G, pp = j / G, r = pp / LC, c = pp % LC;
-    goff[k] = (unsigned)(((r * w + c) * C + 4 * g) * 4);
-    lbyte[k] = (unsigned)((g * GP + r * LC + c) * 4);
-    rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]); pin(rc[k]);
-  }
+  Win win;                                                    // the tile window (tile_window.h)
+  win.init(w);
   unsigned xbyte[KC];                                         // B-fragment origin of the wave's row pair
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) {
@@ -184,40 +199,16 @@ __global__ __launch_bounds__(256) void k_conv1_two_row(const float* __restrict__
     pin(xbyte[kc]);
   }
   const int orow = 2 * wave + (q >> 1);                       // lane's output pixel (orow, p), channels 4*(q&1)..
-  unsigned ooff = (unsigned)(((orow * w + p) * 8 + 4 * (q & 1)) * 4);
-  pin(ooff);
-
-  auto load_tile = [&](f32x4 (&stage)[NL], int n, int tx, int ty) {
-    const int ix0 = tx * TC - 1, iy0 = ty * TR - 1;
-    const buf_rsrc rs = make_rsrc((const char*)src + (((long)n * h + iy0) * w + ix0) * (C * 4));
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + LR <= h && ix0 + LC <= w) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(rs, goff[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const int iy = iy0 + (rc[k] & 0xffff), ix = ix0 + (rc[k] >> 16);
-        stage[k] = buf_load4(rs, ((unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w) ? goff[k] : BUF_OOB);
-      }
-    }
-  };
-  auto store_tile = [&](const f32x4 (&stage)[NL]) {
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      float* dl = (float*)((char*)lds + lbyte[k]);
-      f32x4 v = stage[k];
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
-    }
-  };
+  const unsigned ooff = conv1_out_off(orow, p, w, q);
 
   int t = blockIdx.x;
   if (t >= tg.ntiles) return;
   int n, tx, ty;
   tile_coords(tg, t, n, tx, ty);
   f32x4 stage[NL];
-  load_tile(stage, n, tx, ty);
+  win.request(stage, src, n, h, w, ty * TR - 1, tx * TC - 1);
   wait_vmem_all();
-  store_tile(stage);
+  win.store(stage, lds);
   __syncthreads();
   for (;;) {
     const int tn = t + gridDim.x;
@@ -225,7 +216,7 @@ __global__ __launch_bounds__(256) void k_conv1_two_row(const float* __restrict__
     int nn = 0, txn = 0, tyn = 0;
     if (more) {
       tile_coords(tg, tn, nn, txn, tyn);
-      load_tile(stage, nn, txn, tyn);               // in flight during the MFMA chain
+      win.request(stage, src, nn, h, w, tyn * TR - 1, txn * TC - 1);               // in flight during the MFMA chain
     }
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -239,14 +230,10 @@ __global__ __launch_bounds__(256) void k_conv1_two_row(const float* __restrict__
 
     wait_vmem_all();
     __syncthreads();                                // every wave is done reading the tile
-    if (more) store_tile(stage);
+    if (more) win.store(stage, lds);
 
-    const int y0 = ty * TR, x0 = tx * TC;
-    const buf_rsrc ro = make_rsrc((char*)c1 + (((long)n * h + y0) * w + x0) * 32);
-    unsigned oo = ooff;
-    if (!(y0 + TR <= h && x0 + TC <= w)) oo = (y0 + orow < h && x0 + p < w) ? ooff : BUF_OOB;
-    acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f);
-    buf_store4(ro, oo, acc);
+    f32x4 out[1] = {acc};
+    conv1_relu_store<TR, TC>(c1, n, h, w, ty, tx, orow, p, ooff, out);
     if (!more) break;
     __syncthreads();                                // next tile visible
     t = tn; n = nn; tx = txn; ty = tyn;
@@ -278,7 +265,8 @@ __global__ __launch_bounds__(256, 3) void k_conv1_ksplit(const float* __restrict
   static_assert(C == 32, "four waves x two k-chunks");
   constexpr int KC = C / 4, G = C / 4, KW = KC / 4, TR = 8, TC = 16, LR = TR + 2, LC = TC + 2, NPIX = LR * LC;
   constexpr int PLANE = plane_pitch16(NPIX), GP = group_pitch(PLANE, G);
-  constexpr int NL = (NPIX * G + 255) / 256;
+  typedef TileWindow<C, LR, LC, true, PLANE, GP> Win;
+  constexpr int NL = Win::N;
   extern __shared__ __attribute__((aligned(16))) float lds[];           // tile [G][GP], then partials [12][64][4]
   float* red = lds + G * GP;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform
@@ -289,17 +277,8 @@ __global__ __launch_bounds__(256, 3) void k_conv1_ksplit(const float* __restrict
 #pragma unroll
     for (int kc = 0; kc < KW; ++kc) wf[t][kc] = wpk[(t * KC + wave * KW + kc) * 64 + lane];
 
-  unsigned goff[NL], lbyte[NL];
-  int rc[NL];
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    const int j = min(tid + k * 256, NPIX * G - 1);
-    const int g = j % G, pp = j / G, r = pp / LC, c = pp % LC;
-    goff[k] = (unsigned)(((r * w + c) * C + 4 * g) * 4);
-    lbyte[k] = (unsigned)((g * GP + r * LC + c) * 4);
-    rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]); pin(rc[k]);
-  }
+  Win win;                                                    // the tile window (tile_window.h)
+  win.init(w);
   unsigned xbyte[KW];                                         // B-fragment origin of row pair 0 in the wave's channels
 #pragma unroll
   for (int kc = 0; kc < KW; ++kc) {
@@ -317,40 +296,16 @@ __global__ __launch_bounds__(256, 3) void k_conv1_ksplit(const float* __restrict
   }
   pin(wbyte);
   const int orow = 2 * wave + (q >> 1);
-  unsigned ooff = (unsigned)(((orow * w + p) * 8 + 4 * (q & 1)) * 4);
-  pin(ooff);
-
-  auto load_tile = [&](f32x4 (&stage)[NL], int n, int tx, int ty) {
-    const int ix0 = tx * TC - 1, iy0 = ty * TR - 1;
-    const buf_rsrc rs = make_rsrc((const char*)src + (((long)n * h + iy0) * w + ix0) * (C * 4));
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + LR <= h && ix0 + LC <= w) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(rs, goff[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const int iy = iy0 + (rc[k] & 0xffff), ix = ix0 + (rc[k] >> 16);
-        stage[k] = buf_load4(rs, ((unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w) ? goff[k] : BUF_OOB);
-      }
-    }
-  };
-  auto store_tile = [&](const f32x4 (&stage)[NL]) {
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      float* dl = (float*)((char*)lds + lbyte[k]);
-      f32x4 v = stage[k];
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
-    }
-  };
+  const unsigned ooff = conv1_out_off(orow, p, w, q);
 
   int t = blockIdx.x;
   if (t >= tg.ntiles) return;
   int n, tx, ty;
   tile_coords(tg, t, n, tx, ty);
   f32x4 stage[NL];
-  load_tile(stage, n, tx, ty);
+  win.request(stage, src, n, h, w, ty * TR - 1, tx * TC - 1);
   wait_vmem_all();
-  store_tile(stage);
+  win.store(stage, lds);
   __syncthreads();
   for (;;) {
     const int tn = t + gridDim.x;
@@ -358,7 +313,7 @@ __global__ __launch_bounds__(256, 3) void k_conv1_ksplit(const float* __restrict
     int nn = 0, txn = 0, tyn = 0;
     if (more) {
       tile_coords(tg, tn, nn, txn, tyn);
-      load_tile(stage, nn, txn, tyn);               // in flight during the MFMA chains
+      win.request(stage, src, nn, h, w, tyn * TR - 1, txn * TC - 1);               // in flight during the MFMA chains
     }
     f32x4 acc[4];
 #pragma unroll
@@ -380,7 +335,7 @@ __global__ __launch_bounds__(256, 3) void k_conv1_ksplit(const float* __restrict
 
     wait_vmem_all();
     __syncthreads();                                // partials visible; every wave is done reading the tile
-    if (more) store_tile(stage);
+    if (more) win.store(stage, lds);
 
     f32x4 own = wave == 0 ? acc[0] : (wave == 1 ? acc[1] : (wave == 2 ? acc[2] : acc[3]));
     f32x4 part[3];
@@ -393,12 +348,8 @@ __global__ __launch_bounds__(256, 3) void k_conv1_ksplit(const float* __restrict
     else if (wave == 2) sum = ((part[0] + part[1]) + own) + part[2];
     else sum = ((part[0] + part[1]) + part[2]) + own;
 
-    const int y0 = ty * TR, x0 = tx * TC;
-    const buf_rsrc ro = make_rsrc((char*)c1 + (((long)n * h + y0) * w + x0) * 32);
-    unsigned oo = ooff;
-    if (!(y0 + TR <= h && x0 + TC <= w)) oo = (y0 + orow < h && x0 + p < w) ? ooff : BUF_OOB;
-    sum.x = fmaxf(sum.x, 0.f); sum.y = fmaxf(sum.y, 0.f); sum.z = fmaxf(sum.z, 0.f); sum.w = fmaxf(sum.w, 0.f);
-    buf_store4(ro, oo, sum);
+    f32x4 out[1] = {sum};
+    conv1_relu_store<TR, TC>(c1, n, h, w, ty, tx, orow, p, ooff, out);
     if (!more) break;
     __syncthreads();                                // next tile visible; partials consumed
     t = tn; n = nn; tx = txn; ty = tyn;
@@ -426,7 +377,8 @@ __global__ __launch_bounds__(256, 2) void k_conv1_f23(const float* __restrict__ 
   constexpr int KC = C / 4, G = C / 4, KH = KC / 2, TR = 8, TC = 32, LR = TR + 2, LC = TC + 2, NPIX = LR * LC;
   constexpr int PLANE = plane_pitch16(NPIX), GP = group_pitch(PLANE, G);
   static_assert((PLANE % 2) == 0 && (GP % 2) == 0 && (LC % 2) == 0, "8-byte aligned patch reads");
-  constexpr int NL = (NPIX * G + 255) / 256;
+  typedef TileWindow<C, LR, LC, true, PLANE, GP> Win;
+  constexpr int NL = Win::N;
   extern __shared__ __attribute__((aligned(16))) float lds[];           // tile [G][GP], then partials [4 waves][2][64] float4
   f32x4* red = (f32x4*)(lds + G * GP);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform
@@ -447,56 +399,23 @@ __global__ __launch_bounds__(256, 2) void k_conv1_f23(const float* __restrict__ 
       uf[rr][3][kc] = g2;
     }
 
-  unsigned goff[NL], lbyte[NL];
-  int rc[NL];
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    const int j = min(tid + k * 256, NPIX * G - 1);
-    const int g = j % G, pp = j / G, r = pp / LC, c = pp % LC;
-    goff[k] = (unsigned)(((r * w + c) * C + 4 * g) * 4);
-    lbyte[k] = (unsigned)((g * GP + r * LC + c) * 4);
-    rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]);
-  }
+  Win win;                                                    // the tile window (tile_window.h)
+  win.init(w);
   // the lane's patch of the wave's first row pair in the wave's first k-chunk: + k-chunk, row pair, input row as immediates
   unsigned xb = (unsigned)((kh * KH * GP + q * PLANE + (4 * rp2) * LC + 2 * p) * 4);
   pin(xb);
   const int mine = 2 * rp2 + kh;                                       // the row pair this wave finishes
   const int orow = 2 * mine + (q >> 1);                                // lane's output pixels (orow, 2 p), (orow, 2 p + 1), channels 4 (q & 1)..
-  unsigned ooff = (unsigned)(((orow * w + 2 * p) * 8 + 4 * (q & 1)) * 4);
-  pin(ooff);
-
-  auto load_tile = [&](f32x4 (&stage)[NL], int n, int tx, int ty) {
-    const int ix0 = tx * TC - 1, iy0 = ty * TR - 1;
-    const buf_rsrc rs = make_rsrc((const char*)src + (((long)n * h + iy0) * w + ix0) * (C * 4));
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + LR <= h && ix0 + LC <= w) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(rs, goff[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const int iy = iy0 + (rc[k] & 0xffff), ix = ix0 + (rc[k] >> 16);
-        stage[k] = buf_load4(rs, ((unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w) ? goff[k] : BUF_OOB);
-      }
-    }
-  };
-  auto store_tile = [&](const f32x4 (&stage)[NL]) {
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      float* dl = (float*)((char*)lds + lbyte[k]);
-      f32x4 v = stage[k];
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
-    }
-  };
+  const unsigned ooff = conv1_out_off(orow, 2 * p, w, q);
 
   int t = blockIdx.x;
   if (t >= tg.ntiles) return;
   int n, tx, ty;
   tile_coords(tg, t, n, tx, ty);
   f32x4 stage[NL];
-  load_tile(stage, n, tx, ty);
+  win.request(stage, src, n, h, w, ty * TR - 1, tx * TC - 1);
   wait_vmem_all();
-  store_tile(stage);
+  win.store(stage, lds);
   __syncthreads();
   for (;;) {
     const int tn = t + gridDim.x;
@@ -504,7 +423,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1_f23(const float* __restrict__ 
     int nn = 0, txn = 0, tyn = 0;
     if (more) {
       tile_coords(tg, tn, nn, txn, tyn);
-      load_tile(stage, nn, txn, tyn);               // in flight during the MFMA chains
+      win.request(stage, src, nn, h, w, tyn * TR - 1, txn * TC - 1);               // in flight during the MFMA chains
     }
     f32x4 m[2][4];                                  // [the wave's row pair][j]
 #pragma unroll
@@ -543,23 +462,13 @@ __global__ __launch_bounds__(256, 2) void k_conv1_f23(const float* __restrict__ 
 
     wait_vmem_all();
     __syncthreads();                                // partials visible; every wave is done reading the tile
-    if (more) store_tile(stage);
+    if (more) win.store(stage, lds);
 
     const f32x4 p0 = red[((wave ^ 1) * 2 + 0) * 64 + lane], p1 = red[((wave ^ 1) * 2 + 1) * 64 + lane];
     f32x4 o0 = kh ? p0 + y[1][0] : y[0][0] + p0;    // fixed order: channels 0-15 (kh = 0), then 16-31
     f32x4 o1 = kh ? p1 + y[1][1] : y[0][1] + p1;
-    const int y0 = ty * TR, x0 = tx * TC;
-    const buf_rsrc ro = make_rsrc((char*)c1 + (((long)n * h + y0) * w + x0) * 32);
-    unsigned oa = ooff, ob = ooff + 32;
-    if (!(y0 + TR <= h && x0 + TC <= w)) {
-      const bool rowok = y0 + orow < h;
-      oa = (rowok && x0 + 2 * p < w) ? ooff : BUF_OOB;
-      ob = (rowok && x0 + 2 * p + 1 < w) ? ooff + 32 : BUF_OOB;
-    }
-    o0.x = fmaxf(o0.x, 0.f); o0.y = fmaxf(o0.y, 0.f); o0.z = fmaxf(o0.z, 0.f); o0.w = fmaxf(o0.w, 0.f);
-    o1.x = fmaxf(o1.x, 0.f); o1.y = fmaxf(o1.y, 0.f); o1.z = fmaxf(o1.z, 0.f); o1.w = fmaxf(o1.w, 0.f);
-    buf_store4(ro, oa, o0);
-    buf_store4(ro, ob, o1);
+    f32x4 out[2] = {o0, o1};
+    conv1_relu_store<TR, TC>(c1, n, h, w, ty, tx, orow, 2 * p, ooff, out);
     if (!more) break;
     __syncthreads();                                // next tile visible; partials consumed
     t = tn; n = nn; tx = txn; ty = tyn;
@@ -575,7 +484,8 @@ __global__ __launch_bounds__(256) void k_conv1_f23_rows(const float* __restrict_
   constexpr int KC = C / 4, G = C / 4, TR = 8, TC = 32, LR = TR + 2, LC = TC + 2, NPIX = LR * LC;
   constexpr int PLANE = plane_pitch16(NPIX), GP = (group_pitch(PLANE, G) + 1) & ~1;
   static_assert((PLANE % 2) == 0 && (GP % 2) == 0 && (LC % 2) == 0, "8-byte aligned patch reads");
-  constexpr int NL = (NPIX * G + 255) / 256;
+  typedef TileWindow<C, LR, LC, true, PLANE, GP> Win;
+  constexpr int NL = Win::N;
   extern __shared__ __attribute__((aligned(16))) float lds[];           // tile [G][GP]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave = row pair
   const int p = lane & 15, q = lane >> 4;
@@ -594,54 +504,21 @@ __global__ __launch_bounds__(256) void k_conv1_f23_rows(const float* __restrict_
       uf[rr][3][kc] = g2;
     }
 
-  unsigned goff[NL], lbyte[NL];
-  int rc[NL];
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    const int j = min(tid + k * 256, NPIX * G - 1);
-    const int g = j % G, pp = j / G, r = pp / LC, c = pp % LC;
-    goff[k] = (unsigned)(((r * w + c) * C + 4 * g) * 4);
-    lbyte[k] = (unsigned)((g * GP + r * LC + c) * 4);
-    rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]); pin(rc[k]);
-  }
+  Win win;                                                    // the tile window (tile_window.h)
+  win.init(w);
   unsigned xb = (unsigned)((q * PLANE + (2 * wave) * LC + 2 * p) * 4);
   pin(xb);
   const int orow = 2 * wave + (q >> 1);                                // lane's output pixels (orow, 2 p), (orow, 2 p + 1), channels 4 (q & 1)..
-  unsigned ooff = (unsigned)(((orow * w + 2 * p) * 8 + 4 * (q & 1)) * 4);
-  pin(ooff);
-
-  auto load_tile = [&](f32x4 (&stage)[NL], int n, int tx, int ty) {
-    const int ix0 = tx * TC - 1, iy0 = ty * TR - 1;
-    const buf_rsrc rs = make_rsrc((const char*)src + (((long)n * h + iy0) * w + ix0) * (C * 4));
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + LR <= h && ix0 + LC <= w) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(rs, goff[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const int iy = iy0 + (rc[k] & 0xffff), ix = ix0 + (rc[k] >> 16);
-        stage[k] = buf_load4(rs, ((unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w) ? goff[k] : BUF_OOB);
-      }
-    }
-  };
-  auto store_tile = [&](const f32x4 (&stage)[NL]) {
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      float* dl = (float*)((char*)lds + lbyte[k]);
-      f32x4 v = stage[k];
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
-    }
-  };
+  const unsigned ooff = conv1_out_off(orow, 2 * p, w, q);
 
   int t = blockIdx.x;
   if (t >= tg.ntiles) return;
   int n, tx, ty;
   tile_coords(tg, t, n, tx, ty);
   f32x4 stage[NL];
-  load_tile(stage, n, tx, ty);
+  win.request(stage, src, n, h, w, ty * TR - 1, tx * TC - 1);
   wait_vmem_all();
-  store_tile(stage);
+  win.store(stage, lds);
   __syncthreads();
   for (;;) {
     const int tn = t + gridDim.x;
@@ -649,7 +526,7 @@ __global__ __launch_bounds__(256) void k_conv1_f23_rows(const float* __restrict_
     int nn = 0, txn = 0, tyn = 0;
     if (more) {
       tile_coords(tg, tn, nn, txn, tyn);
-      load_tile(stage, nn, txn, tyn);               // in flight during the MFMA chain
+      win.request(stage, src, nn, h, w, tyn * TR - 1, txn * TC - 1);               // in flight during the MFMA chain
     }
     f32x4 m[4];
 #pragma unroll
@@ -673,20 +550,10 @@ __global__ __launch_bounds__(256) void k_conv1_f23_rows(const float* __restrict_
 
     wait_vmem_all();
     __syncthreads();                                // every wave is done reading the tile
-    if (more) store_tile(stage);
+    if (more) win.store(stage, lds);
 
-    const int y0 = ty * TR, x0 = tx * TC;
-    const buf_rsrc ro = make_rsrc((char*)c1 + (((long)n * h + y0) * w + x0) * 32);
-    unsigned oa = ooff, ob = ooff + 32;
-    if (!(y0 + TR <= h && x0 + TC <= w)) {
-      const bool rowok = y0 + orow < h;
-      oa = (rowok && x0 + 2 * p < w) ? ooff : BUF_OOB;
-      ob = (rowok && x0 + 2 * p + 1 < w) ? ooff + 32 : BUF_OOB;
-    }
-    o0.x = fmaxf(o0.x, 0.f); o0.y = fmaxf(o0.y, 0.f); o0.z = fmaxf(o0.z, 0.f); o0.w = fmaxf(o0.w, 0.f);
-    o1.x = fmaxf(o1.x, 0.f); o1.y = fmaxf(o1.y, 0.f); o1.z = fmaxf(o1.z, 0.f); o1.w = fmaxf(o1.w, 0.f);
-    buf_store4(ro, oa, o0);
-    buf_store4(ro, ob, o1);
+    f32x4 out[2] = {o0, o1};
+    conv1_relu_store<TR, TC>(c1, n, h, w, ty, tx, orow, 2 * p, ooff, out);
     if (!more) break;
     __syncthreads();                                // next tile visible
     t = tn; n = nn; tx = txn; ty = tyn;

@@ -11,6 +11,7 @@
 #include "conv_frag.h"
 #include "kernels.h"
 #include "persistent.h"
+#include "tile_window.h"
 
 namespace adamvs {
 
@@ -66,7 +67,9 @@ struct ConvSmallRole {
   static constexpr int GP = group_pitch(PLANE, G);
   static constexpr int HC = CB;          // hidden width for the GRU epilogues
   // one load instruction covers 256 (pixel, channel group) items of ONE source, so that its base is uniform
-  static constexpr int NA = (NPIX * GA + 255) / 256, NB = (NPIX * GB + 255) / 256, NL = NA + NB;
+  typedef TileWindow<CA, LR, LC, true, PLANE, GP> WinA;
+  typedef TileWindow<CB, LR, LC, true, PLANE, GP> WinB;
+  static constexpr int NA = WinA::N, NB = WinB::N, NL = NA + NB;
   static constexpr size_t LDS_BYTES = (size_t)G * GP * sizeof(float);         // tile [G][GP]
   static constexpr int TILE_W = TC, TILE_H = TR;                               // output pixels per tile
   static int tiles_x(const Args& a) { return cdiv(a.wo, TC); }
@@ -89,22 +92,11 @@ struct ConvSmallRole {
   for (int nt = 0; nt < NT; ++nt)
     bias[nt] = (EPI == EPI_RELU) ? f32x4{0.f, 0.f, 0.f, 0.f} : *(const f32x4*)(a.bias + nt * 16 + 4 * q);
 
-  // ---- per-lane constants of the tile window
-  unsigned goff[NL];      // byte offset of the item from the window's first pixel in its source
-  unsigned lbyte[NL];     // LDS byte offset of the item's first channel plane
-  int rc[NL];             // window row | column << 16 (edge tiles only)
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    const bool isA = k < NA;
-    const int gs = isA ? GA : GB, cs = isA ? CA : CB;
-    int j = tid + (isA ? k : k - NA) * 256;
-    j = min(j, NPIX * gs - 1);           // surplus lanes repeat the last item (same value to the same place)
-    const int g = j % gs, pp = j / gs, r = pp / LC, c = pp % LC;
-    goff[k] = (unsigned)(((r * a.wi + c) * cs + 4 * g) * 4);
-    lbyte[k] = (unsigned)((((isA ? 0 : GA) + g) * GP + r * LC + c) * 4);
-    rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]); pin(rc[k]);
-  }
+  // ---- the tile window: one per source, B's channel groups behind A's (tile_window.h)
+  WinA wa;
+  WinB wb;
+  wa.init(a.wi);
+  wb.init(a.wi);
   unsigned xbyte[KC];     // B-fragment origin of the run, per k-chunk
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) {
@@ -187,60 +179,52 @@ struct ConvSmallRole {
   auto load_tile = [&](f32x4 (&stage)[NL], int b, int tx, int ty) {
     const int ix0 = tx * TC * STRIDE - 1, iy0 = ty * TR * STRIDE - 1;
     const long pix0 = ((long)b * a.hi + iy0) * a.wi + ix0;                 // may point one row/column outside
-    const buf_rsrc ra = make_rsrc((const char*)a.srcA + pix0 * (CA * 4));
-    const buf_rsrc rb = make_rsrc((const char*)a.srcB + pix0 * (CB * 4));
     if (EPI == EPI_LINEAR && pro_on) {                     // the operands of the on-the-fly srcB (zero padding is applied when it is formed)
       const buf_rsrc rf = make_rsrc((const char*)pro.f + pix0 * (2 * CB * 4));
       const buf_rsrc ro = make_rsrc((const char*)(pro.mode == GRU_PRO_OUT ? pro.o : a.srcB) + pix0 * (CB * 4));
 #pragma unroll
       for (int k = 0; k < NBP; ++k) {
-        const int iy = iy0 + (rc[NA + k] & 0xffff), ix = ix0 + (rc[NA + k] >> 16);
+        const int iy = iy0 + (wb.rc[k] & 0xffff), ix = ix0 + (wb.rc[k] >> 16);
         const bool ok = (unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi;
         stageF[k] = buf_load4(rf, ok ? foff[k] : BUF_OOB);
-        if (pro.mode == GRU_PRO_OUT) stageO[k] = buf_load4(ro, ok ? goff[NA + k] : BUF_OOB);
+        if (pro.mode == GRU_PRO_OUT) stageO[k] = buf_load4(ro, ok ? wb.goff[k] : BUF_OOB);
       }
     }
-    const bool interior = iy0 >= 0 && ix0 >= 0 && iy0 + LR <= a.hi && ix0 + LC <= a.wi;
-    if (interior) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(k < NA ? ra : rb, goff[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const int iy = iy0 + (rc[k] & 0xffff), ix = ix0 + (rc[k] >> 16);
-        const bool ok = (unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi;
-        stage[k] = buf_load4(k < NA ? ra : rb, ok ? goff[k] : BUF_OOB);              // zero padding
-      }
-    }
+    wa.request(stage, a.srcA, b, a.hi, a.wi, iy0, ix0);
+    wb.request(stage + NA, a.srcB, b, a.hi, a.wi, iy0, ix0);
   };
   auto store_tile = [&](const f32x4 (&stage)[NL], int b, int tx, int ty) {
+    wa.store(stage, lds);
+    if constexpr (EPI != EPI_LINEAR) {
+      wb.template store<GA>(stage + NA, lds);
+    } else {                                               // MS-REDNet: srcB may be formed on the fly (GruPro) on its way into the tile
 #pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      float* dl = (float*)((char*)lds + lbyte[k]);
-      f32x4 v = stage[k];
-      if (EPI == EPI_LINEAR && k >= NA && pro_on) {
-        const int kb = k - NA < NBP ? k - NA : 0;
-        const int wr = rc[k] & 0xffff, wc = rc[k] >> 16;
-        const int iy = ty * TR - 1 + wr, ix = tx * TC - 1 + wc;
-        const bool ok = (unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi;
-        const f32x4 fn = (stageF[kb] - pst[0]) * pst[1] * gfw[kb] + gfb[kb];
-        const f32x4 sg = {sigmoidf_(fn.x), sigmoidf_(fn.y), sigmoidf_(fn.z), sigmoidf_(fn.w)};
-        if (pro.mode == GRU_PRO_GATES) {
-          v = sg * v;                                        // r * h
-        } else {
-          const f32x4 on = (stageO[kb] - pst[2]) * pst[3] * gow[kb] + gob[kb];
-          const f32x4 y = {tanhf(on.x), tanhf(on.y), tanhf(on.z), tanhf(on.w)};
-          v = sg * v + (1.0f - sg) * y;                      // h' = u h + (1 - u) y
+      for (int kb = 0; kb < NB; ++kb) {
+        f32x4 v = stage[NA + kb];
+        if (pro_on) {
+          const int wr = wb.rc[kb] & 0xffff, wc = wb.rc[kb] >> 16;
+          const int iy = ty * TR - 1 + wr, ix = tx * TC - 1 + wc;
+          const bool ok = (unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi;
+          const f32x4 fn = (stageF[kb] - pst[0]) * pst[1] * gfw[kb] + gfb[kb];
+          const f32x4 sg = {sigmoidf_(fn.x), sigmoidf_(fn.y), sigmoidf_(fn.z), sigmoidf_(fn.w)};
+          if (pro.mode == GRU_PRO_GATES) {
+            v = sg * v;                                        // r * h
+          } else {
+            const f32x4 on = (stageO[kb] - pst[2]) * pst[3] * gow[kb] + gob[kb];
+            const f32x4 y = {tanhf(on.x), tanhf(on.y), tanhf(on.z), tanhf(on.w)};
+            v = sg * v + (1.0f - sg) * y;                      // h' = u h + (1 - u) y
+          }
+          if (!ok) v = f32x4{0.f, 0.f, 0.f, 0.f};              // zero padding
+          if (pro.mode == GRU_PRO_OUT && ok && tid + kb * 256 < NPIX * GB && wr >= 1 && wr <= TR && wc >= 1 && wc <= TC) {
+            const size_t pix = ((size_t)b * a.hi + iy) * a.wi + ix;      // the tile's own pixels: the new state (and R)
+            const int c4 = 4 * ((tid + kb * 256) % GBP);
+            *(f32x4*)(pro.state_out + pix * CB + c4) = v;
+            if (pro.R) *(f32x4*)(pro.R + pix * pro.RW + c4) = v;
+          }
         }
-        if (!ok) v = f32x4{0.f, 0.f, 0.f, 0.f};              // zero padding
-        if (pro.mode == GRU_PRO_OUT && ok && tid + kb * 256 < NPIX * GB && wr >= 1 && wr <= TR && wc >= 1 && wc <= TC) {
-          const size_t pix = ((size_t)b * a.hi + iy) * a.wi + ix;      // the tile's own pixels: the new state (and R)
-          const int c4 = 4 * ((tid + kb * 256) % GBP);
-          *(f32x4*)(pro.state_out + pix * CB + c4) = v;
-          if (pro.R) *(f32x4*)(pro.R + pix * pro.RW + c4) = v;
-        }
+        float* dl = (float*)((char*)lds + wb.lbyte[kb]) + GA * GP;
+        dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
       }
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
     }
   };
 
@@ -386,7 +370,9 @@ struct Conv2Gates2Role {
   static constexpr int PLANE_A = NH | 1, GP_A = group_pitch(PLANE_A, 2);
   static constexpr int PLANE = plane_pitch16(NW), G = 8, GP = group_pitch(PLANE, G);
   static constexpr int LDS_A = 2 * GP_A;                                                    // floats
-  static constexpr int NA = (NH * 2 + 255) / 256, NB = (NW * 4 + 255) / 256, NL = NA + NB;
+  typedef TileWindow<8, HR, HC, true, PLANE_A, GP_A> WinA;
+  typedef TileWindow<16, LR, LC, true, PLANE, GP> WinB;
+  static constexpr int NA = WinA::N, NB = WinB::N, NL = NA + NB;
   static constexpr int NRUN = 2;                                                            // conv2 runs per wave (7 runs of 16 window pixels)
   static constexpr size_t LDS_BYTES = (size_t)(LDS_A + G * GP) * sizeof(float);
   static constexpr int TILE_W = TC, TILE_H = TR;
@@ -404,27 +390,11 @@ struct Conv2Gates2Role {
   load_wfrag<1, 8>(wf, a.wgates + HALF * 9 * 8 * 64, lane);                 // fragment stream [nt][tap][kc][64]: nt = HALF
   const f32x4 bias = *(const f32x4*)(a.bgates + HALF * 16 + 4 * q);
 
-  // ---- per-lane constants: the two windows
-  unsigned goff[NL], lbyte[NL];
-  int rc[NL];
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    const bool isA = k < NA;
-    if (isA) {
-      const int j = min(tid + k * 256, NH * 2 - 1);
-      const int g = j % 2, pp = j / 2, r = pp / HC, c = pp % HC;
-      goff[k] = (unsigned)(((r * a.w + c) * 8 + 4 * g) * 4);
-      lbyte[k] = (unsigned)((g * GP_A + r * HC + c) * 4);
-      rc[k] = r | (c << 16);
-    } else {
-      const int j = min(tid + (k - NA) * 256, NW * 4 - 1);
-      const int g = j % 4, pp = j / 4, r = pp / LC, c = pp % LC;
-      goff[k] = (unsigned)(((r * a.w2 + c) * 16 + 4 * g) * 4);
-      lbyte[k] = (unsigned)((LDS_A + (4 + g) * GP + r * LC + c) * 4);
-      rc[k] = r | (c << 16);
-    }
-    pin(goff[k]); pin(lbyte[k]); pin(rc[k]);
-  }
+  // ---- per-lane constants: the two windows (tile_window.h)
+  WinA wa;                                                                      // h1, full resolution, at the start of the tile
+  WinB wb;                                                                      // h2, behind the four groups that conv2 fills
+  wa.init(a.w);
+  wb.init(a.w2);
   // conv2: run j of the wave covers window pixels 16 (wave + 4 j) .. + 15 (runs past the 108 pixels repeat the last one)
   unsigned xa[NRUN][2], cbyte[NRUN], coff[NRUN];
   int wrc[NRUN];
@@ -457,30 +427,18 @@ struct Conv2Gates2Role {
   auto load_tile = [&](f32x4 (&stage)[NL], int b, int tx, int ty) {
     const int j0 = tx * TC - 1, i0 = ty * TR - 1;                       // window origin, half resolution
     const int ix0 = 2 * j0 - 1, iy0 = 2 * i0 - 1;                       // h1 window origin
-    const buf_rsrc ra = make_rsrc((const char*)a.st1 + (((long)b * a.h + iy0) * a.w + ix0) * 32);
-    const buf_rsrc rb = make_rsrc((const char*)a.st2 + (((long)b * a.h2 + i0) * a.w2 + j0) * 64);
-    const bool interior = iy0 >= 0 && ix0 >= 0 && iy0 + HR <= a.h && ix0 + HC <= a.w && i0 + LR <= a.h2 && j0 + LC <= a.w2;
-    if (interior) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(k < NA ? ra : rb, goff[k]);
+    const buf_rsrc ra = WinA::origin(a.st1, b, a.h, a.w, iy0, ix0), rb = WinB::origin(a.st2, b, a.h2, a.w2, i0, j0);
+    if (WinA::interior(a.h, a.w, iy0, ix0) && WinB::interior(a.h2, a.w2, i0, j0)) {      // one test for both windows
+      wa.template load<false>(stage, ra, a.h, a.w, iy0, ix0);
+      wb.template load<false>(stage + NA, rb, a.h2, a.w2, i0, j0);
     } else {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const bool isA = k < NA;
-        const int iy = (isA ? iy0 : i0) + (rc[k] & 0xffff), ix = (isA ? ix0 : j0) + (rc[k] >> 16);
-        const bool ok = (unsigned)iy < (unsigned)(isA ? a.h : a.h2) && (unsigned)ix < (unsigned)(isA ? a.w : a.w2);
-        stage[k] = buf_load4(isA ? ra : rb, ok ? goff[k] : BUF_OOB);              // zero padding
-      }
+      wa.template load<true>(stage, ra, a.h, a.w, iy0, ix0);
+      wb.template load<true>(stage + NA, rb, a.h2, a.w2, i0, j0);
     }
   };
   auto store_tile = [&](const f32x4 (&stage)[NL]) {
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      float* dl = (float*)((char*)lds + lbyte[k]);
-      const int pl = k < NA ? PLANE_A : PLANE;
-      f32x4 v = stage[k];
-      dl[0] = v.x; dl[pl] = v.y; dl[2 * pl] = v.z; dl[3 * pl] = v.w;
-    }
+    wa.store(stage, lds);
+    wb.template store<4>(stage + NA, lds + LDS_A);
   };
 
   int t = tr.begin + wg;
@@ -599,8 +557,7 @@ __device__ __forceinline__ f32x4 upconv1_class(const float (&wf)[1][9][4], const
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// Persistent, software-pipelined like k_conv_small (same reasoning: uniform descriptors + pinned lane offsets,
-// no bounds checks on interior tiles, one wait per tile).  A tile is 8 x 30 pixels of s (full resolution h x w; round 4: 6 x 30
+// Persistent and pipelined: see "Persistent workgroups" above ConvSmallRole.  A tile is 8 x 30 pixels of s (full resolution h x w; round 4: 6 x 30
 // until then -- phase 2, the larger half of the kernel's vector work, ran 180 of 256 lanes, now 240);
 // its s region is 10 x 32 (one pixel of halo each side), fed by a 6 x 17 region of h2.
 //   phase 1  upconv1 on the matrix cores: 20 runs = 4 parity classes x 5 rows; wave k takes row k of every
@@ -918,7 +875,8 @@ struct TwoRowPairRole {
   typedef SmallConvArgs Args;
   static constexpr int CA = 8, CB = 8, C = 16, KC = C / 4, G = C / 4, GA = CA / 4, TR = 8, TC = 16 * RW, LR = TR + 2, LC = TC + 2;
   static constexpr int NPIX = LR * LC, PLANE = plane_pitch16(NPIX), GP = group_pitch(PLANE, G);
-  static constexpr int NA = (NPIX * GA + 255) / 256, NL = 2 * NA;     // loads per source: a load's base must be uniform
+  typedef TileWindow<CA, LR, LC, RW == 1, PLANE, GP> Win;              // one source's window (tile_window.h)
+  static constexpr int NA = Win::N, NL = 2 * NA;                       // loads per source: a load's base must be uniform
   static constexpr size_t LDS_BYTES = (size_t)(G * GP + (RW > 1 ? 8 : 0)) * sizeof(float);         // tile [G][GP] (RW > 1: + the bias)
   static constexpr int TILE_W = TC, TILE_H = TR;
   static int tiles_x(const Args& a) { return cdiv(a.wo, TC); }
@@ -945,20 +903,11 @@ struct TwoRowPairRole {
   //  address GA groups further on, and the k-chunks of a B fragment are immediates from the first: the registers that the second
   //  run's accumulator and epilogue operands take, at the same four workgroups per CU)
   constexpr bool SHARE = RW > 1;
-  constexpr int NI = SHARE ? NA : NL, NX = SHARE ? 1 : KC;
-  unsigned goff[NL], lbyte[NL];
-  int rc[NL];
+  constexpr int NX = SHARE ? 1 : KC;
+  Win win[SHARE ? 1 : 2];                                    // (SHARE: one window serves both sources, its edge coordinates formed again on edge tiles)
 #pragma unroll
-  for (int k = 0; k < NI; ++k) {
-    const bool isA = k < NA;
-    const int j = min(tid + (isA ? k : k - NA) * 256, NPIX * GA - 1);          // surplus lanes repeat the last item
-    const int g = j % GA, pp = j / GA, r = pp / LC, c = pp % LC;
-    goff[k] = (unsigned)(((r * w + c) * CA + 4 * g) * 4);
-    lbyte[k] = (unsigned)((((isA ? 0 : GA) + g) * GP + r * LC + c) * 4);
-    rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]);
-    if (!SHARE) pin(rc[k]);                                                    // (SHARE: formed again on edge tiles)
-  }
+  for (int i = 0; i < (SHARE ? 1 : 2); ++i) win[i].init(w);
+  const Win& wb = win[SHARE ? 0 : 1];
   unsigned xbyte[KC];
 #pragma unroll
   for (int kc = 0; kc < NX; ++kc) {
@@ -970,29 +919,16 @@ struct TwoRowPairRole {
   pin(ooff);
 
   auto load_tile = [&](f32x4 (&stage)[NL], int n, int tx, int ty) {
-    const int ix0 = tx * TC - 1, iy0 = ty * TR - 1;
-    const long pix0 = ((long)n * h + iy0) * w + ix0;
-    const buf_rsrc ra = make_rsrc((const char*)a.srcA + pix0 * (CA * 4));
-    const buf_rsrc rb = make_rsrc((const char*)a.srcB + pix0 * (CB * 4));
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + LR <= h && ix0 + LC <= w) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(k < NA ? ra : rb, goff[k % NI]);
+    if constexpr (SHARE) {
+      win[0].request(stage, a.srcA, stage + NA, a.srcB, n, h, w, ty * TR - 1, tx * TC - 1);
     } else {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const int pp = min(tid + (k % NA) * 256, NPIX * GA - 1) / GA;
-        const int iy = iy0 + (SHARE ? pp / LC : rc[k] & 0xffff), ix = ix0 + (SHARE ? pp % LC : rc[k] >> 16);
-        stage[k] = buf_load4(k < NA ? ra : rb, ((unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w) ? goff[k % NI] : BUF_OOB);
-      }
+      win[0].request(stage, a.srcA, n, h, w, ty * TR - 1, tx * TC - 1);
+      wb.request(stage + NA, a.srcB, n, h, w, ty * TR - 1, tx * TC - 1);
     }
   };
   auto store_tile = [&](const f32x4 (&stage)[NL]) {
-#pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      float* dl = (float*)((char*)lds + lbyte[k % NI] + (SHARE && k >= NA ? GA * GP * 4 : 0));
-      f32x4 v = stage[k];
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
-    }
+    win[0].store(stage, lds);
+    wb.template store<GA>(stage + NA, lds);
   };
 
   int t = tr.begin + wg;

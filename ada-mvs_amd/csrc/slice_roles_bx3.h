@@ -4,6 +4,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "persistent.h"
+#include "tile_window.h"
 #include "slice_roles.h"
 
 namespace adamvs {
@@ -86,9 +87,8 @@ struct SmallConvArgsBx {
   const float* hin;       // CAND: the state that is blended; null = dst0 (update in place)
 };
 
-// Persistent and pipelined exactly like k_conv_small in slice_red.hip (uniform buffer descriptors + pinned lane
-// offsets, interior tiles without bounds checks, one wait per tile, requests before the MFMA chain, stores after
-// it); what differs is the tile in LDS (pixel-major bf16, hi and lo images, written through split_store), the
+// Persistent and pipelined: see "Persistent workgroups" above ConvSmallRole (slice_roles.h), the window's loads: tile_window.h.
+// What differs is the tile in LDS (pixel-major bf16, hi and lo images, written through split_store), the
 // chain (flattened k, three MFMAs per k-block) and the GRU state of the lane's own pixel, which the reset gate
 // multiplies in full fp32 and therefore comes from global memory with the other epilogue operands.
 // Tile = 4 rows x 16 columns, one run per wave; the two-row conv1 takes 8 x 16 (a run = 2 output rows).
@@ -106,7 +106,9 @@ struct ConvSmallBx3Role {
   static constexpr int NPIX = LR * LC;
   static constexpr int PP = bx_pixel_pitch(CIN);      // bf16 per pixel
   static constexpr int LO = NPIX * PP * 2;            // byte offset of the lo image
-  static constexpr int NA = (NPIX * GA + 255) / 256, NB = (NPIX * GB + 255) / 256, NL = NA + NB;
+  typedef TileWindow<CA, LR, LC> WinA;
+  typedef TileWindow<CB, LR, LC> WinB;
+  static constexpr int NA = WinA::N, NB = WinB::N, NL = NA + NB;
   static constexpr size_t LDS_BYTES = (size_t)2 * NPIX * PP * sizeof(__bf16);         // [hi|lo][NPIX][PP]
   static constexpr int TILE_W = TC, TILE_H = TR;
   static int tiles_x(const Args& a) { return cdiv(a.wo, TC); }
@@ -132,21 +134,11 @@ struct ConvSmallBx3Role {
   for (int nt = 0; nt < NT; ++nt)
     bias[nt] = (EPI == BXE_GATES || EPI == BXE_CAND) ? *(const f32x4*)(a.bias + nt * 16 + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // ---- per-lane constants
-  unsigned goff[NL], lbyte[NL];
-  int rc[NL];
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    const bool isA = k < NA;
-    const int gs = isA ? GA : GB, cs = isA ? CA : CB;
-    int j = tid + (isA ? k : k - NA) * 256;
-    j = min(j, NPIX * gs - 1);                        // surplus lanes repeat the last item
-    const int g = j % gs, pp = j / gs, r = pp / LC, c = pp % LC;
-    goff[k] = (unsigned)(((r * a.wi + c) * cs + 4 * g) * 4);
-    lbyte[k] = (unsigned)((pp * PP + (isA ? 0 : CA) + 4 * g) * 2);
-    rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]); pin(rc[k]);
-  }
+  // ---- per-lane constants: one window per source (tile_window.h) into the pixel-major hi image, B's channels behind A's
+  WinA wa;
+  WinB wb;
+  wa.init(a.wi, [](int r, int c, int g) { return ((r * LC + c) * PP + 4 * g) * 2; });
+  wb.init(a.wi, [](int r, int c, int g) { return ((r * LC + c) * PP + CA + 4 * g) * 2; });
   unsigned xoff[NKB];                                 // B fragment of k-block kb: 8 channels of one position
 #pragma unroll
   for (int kb = 0; kb < NKB; ++kb) {
@@ -174,27 +166,18 @@ struct ConvSmallBx3Role {
 
   auto load_tile = [&](f32x4 (&stage)[NL], int b, int tx, int ty) {
     const int ix0 = tx * TC * STRIDE - 1, iy0 = ty * TR * STRIDE - 1;
-    const long pix0 = ((long)b * a.hi + iy0) * a.wi + ix0;
-    const buf_rsrc ra = make_rsrc((const char*)a.srcA + pix0 * (CA * 4));
-    const buf_rsrc rb = make_rsrc((const char*)a.srcB + pix0 * (CB * 4));
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + LR <= a.hi && ix0 + LC <= a.wi) {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) stage[k] = buf_load4(k < NA ? ra : rb, goff[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < NL; ++k) {
-        const int iy = iy0 + (rc[k] & 0xffff), ix = ix0 + (rc[k] >> 16);
-        const bool ok = (unsigned)iy < (unsigned)a.hi && (unsigned)ix < (unsigned)a.wi;
-        stage[k] = buf_load4(k < NA ? ra : rb, ok ? goff[k] : BUF_OOB);
-      }
-    }
+    wa.request(stage, a.srcA, b, a.hi, a.wi, iy0, ix0);
+    wb.request(stage + NA, a.srcB, b, a.hi, a.wi, iy0, ix0);
   };
   auto store_tile = [&](const f32x4 (&stage)[NL]) {
+    auto put = [&](unsigned lbyte, const f32x4& v) {
+      __bf16* hi = (__bf16*)((char*)ldsb + lbyte);
+      split_store(hi, (__bf16*)((char*)hi + LO), v);
+    };
 #pragma unroll
-    for (int k = 0; k < NL; ++k) {
-      __bf16* hi = (__bf16*)((char*)ldsb + lbyte[k]);
-      split_store(hi, (__bf16*)((char*)hi + LO), stage[k]);
-    }
+    for (int k = 0; k < NA; ++k) put(wa.lbyte[k], stage[k]);
+#pragma unroll
+    for (int k = 0; k < NB; ++k) put(wb.lbyte[k], stage[NA + k]);
   };
 
   int t = tr.begin + wg;
@@ -334,7 +317,8 @@ struct Gru1FusedBx3Role {
   // -DBX3_CAND_TWO_ROW=0: one-row runs (cand1 then packed by pack_small_conv_bf16x3; A/B).
   static constexpr bool C2R = BX3_CAND_TWO_ROW != 0;
   static constexpr int NKC = C2R ? 6 : 5, NC = C2R ? 2 : 4;      // candidate: k-blocks, runs per wave
-  static constexpr int NITEM = NPIXW * 2, NS = (NITEM + 255) / 256;      // 4-channel groups per source, loads per thread
+  typedef TileWindow<8, WR, WC> Win;
+  static constexpr int NS = Win::N;                  // loads per source and thread
   static constexpr size_t LDS_BYTES = (size_t)2 * 12 * 34 * 32 + 10 * 32 * 32;
   static constexpr int TILE_W = TC, TILE_H = TR;
   static int tiles_x(const Args& a) { return cdiv(a.w, TC); }
@@ -354,17 +338,8 @@ struct Gru1FusedBx3Role {
   const f32x4 bias_g = *(const f32x4*)(a.bg + 4 * q);
   const f32x4 bias_c = *(const f32x4*)(a.bc + 4 * (C2R ? (q & 1) : q));
 
-  unsigned goff[NS], lbyte[NS];
-  int rc[NS];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    int j = min(tid + k * 256, NITEM - 1);
-    const int g = j & 1, pp = j >> 1, r = pp / WC, c = pp % WC;
-    goff[k] = (unsigned)(((r * a.w + c) * 8 + 4 * g) * 4);
-    lbyte[k] = (unsigned)(pp * PB + 8 * g);
-    rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]); pin(rc[k]);
-  }
+  Win win;                                             // the window of x and of the state (tile_window.h), pixel-major in LDS
+  win.init(a.w, [](int r, int c, int g) { return (r * WC + c) * PB + 8 * g; });
   unsigned xoff[NKB];                                  // gate run 0 of the wave; candidate runs add (WC + 1) * PB
 #pragma unroll
   for (int kb = 0; kb < NKB; ++kb) {
@@ -404,27 +379,12 @@ struct Gru1FusedBx3Role {
   }
 
   auto load_tile = [&](f32x4 (&sx)[NS], f32x4 (&sh)[NS], int b, int tx, int ty) {
-    const int ix0 = tx * TC - 2, iy0 = ty * TR - 2;
-    const long pix0 = ((long)b * a.h + iy0) * a.w + ix0;
-    const buf_rsrc rx = make_rsrc((const char*)a.x + pix0 * 32);
-    const buf_rsrc rh = make_rsrc((const char*)a.hin + pix0 * 32);
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + WR <= a.h && ix0 + WC <= a.w) {
-#pragma unroll
-      for (int k = 0; k < NS; ++k) { sx[k] = buf_load4(rx, goff[k]); sh[k] = buf_load4(rh, goff[k]); }
-    } else {
-#pragma unroll
-      for (int k = 0; k < NS; ++k) {
-        const int iy = iy0 + (rc[k] & 0xffff), ix = ix0 + (rc[k] >> 16);
-        const bool ok = (unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w;
-        const unsigned o = ok ? goff[k] : BUF_OOB;
-        sx[k] = buf_load4(rx, o); sh[k] = buf_load4(rh, o);
-      }
-    }
+    win.request(sx, a.x, sh, a.hin, b, a.h, a.w, ty * TR - 2, tx * TC - 2);
   };
   auto store_tile = [&](const f32x4 (&sx)[NS], const f32x4 (&sh)[NS]) {
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
-      __bf16* hi = (__bf16*)(lds + lbyte[k]);
+      __bf16* hi = (__bf16*)(lds + win.lbyte[k]);
       split_store(hi, (__bf16*)((char*)hi + LO), sx[k]);
       split_store(hi + 8, (__bf16*)((char*)hi + LO) + 8, sh[k]);
     }
@@ -590,7 +550,8 @@ struct Gru2FusedBx3Role {
   static constexpr int RH0 = U0 + 10 * 16 * 64;        // r*h buffer
   static constexpr int RC = 18, RPB = 2 * bx_pixel_pitch(16), RLO = 10 * RC * RPB;      // its row length, pixel pitch, lo image
   static constexpr int NKB = 9, NG = 5, NC = 2;        // k-blocks (9 taps x 32 channels), gate / candidate runs per wave
-  static constexpr int NITEM = NPIXW * 4, NS = (NITEM + 255) / 256;      // 4-channel groups per source, loads per thread
+  typedef TileWindow<16, WR, WC, false> Win;           // (edge coordinates formed again on edge tiles: not worth a register per item)
+  static constexpr int NS = Win::N;                  // loads per source and thread
   static constexpr int BIAS0 = RH0 + 2 * RLO;          // gate bias [32], candidate bias [16] (fp32): read where they are used
   static constexpr size_t LDS_BYTES = (size_t)BIAS0 + 48 * 4;
   static_assert(LDS_BYTES <= 64 * 1024, "default dynamic LDS limit");
@@ -613,15 +574,8 @@ struct Gru2FusedBx3Role {
   if (tid < 48) ((float*)(lds + BIAS0))[tid] = tid < 32 ? a.bg[tid] : a.bc[tid - 32];      // visible after the first barrier
   const unsigned bgbyte = (unsigned)(BIAS0 + (half * 16 + 4 * q) * 4), bcbyte = (unsigned)(BIAS0 + (32 + 4 * q) * 4);
 
-  unsigned goff[NS], lbyte[NS];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    int j = min(tid + k * 256, NITEM - 1);
-    const int g = j & 3, pp = j >> 2, r = pp / WC, c = pp % WC;
-    goff[k] = (unsigned)(((r * a.w + c) * 16 + 4 * g) * 4);
-    lbyte[k] = (unsigned)(pp * PB + 8 * g);
-    pin(goff[k]); pin(lbyte[k]);
-  }
+  Win win;                                             // the window of c2 and of the state (tile_window.h), pixel-major in LDS
+  win.init(a.w, [](int r, int c, int g) { return (r * WC + c) * PB + 8 * g; });
   // B fragments: k-block = tap, lane q: channels 8q .. 8q+7 of cat(c2, state).  Gate run 0 of the wave reads the window;
   // candidate run 0 (inner row `wave`) reads c2 (q < 2) from the window and r*h (q >= 2) from its buffer.
   // All lanes of a k-block share its tap (32 channels = one k-block per tap), so a fragment address is a lane base plus a
@@ -639,28 +593,12 @@ struct Gru2FusedBx3Role {
   pin(ooff);
 
   auto load_tile = [&](f32x4 (&sx)[NS], f32x4 (&sh)[NS], int b, int tx, int ty) {
-    const int ix0 = tx * TC - 2, iy0 = ty * TR - 2;
-    const long pix0 = ((long)b * a.h + iy0) * a.w + ix0;
-    const buf_rsrc rx = make_rsrc((const char*)a.x + pix0 * 64);
-    const buf_rsrc rh = make_rsrc((const char*)a.hin + pix0 * 64);
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + WR <= a.h && ix0 + WC <= a.w) {
-#pragma unroll
-      for (int k = 0; k < NS; ++k) { sx[k] = buf_load4(rx, goff[k]); sh[k] = buf_load4(rh, goff[k]); }
-    } else {
-#pragma unroll
-      for (int k = 0; k < NS; ++k) {
-        const int pp = min(tid + k * 256, NITEM - 1) >> 2;          // (edge tiles only: not worth a register per item)
-        const int iy = iy0 + pp / WC, ix = ix0 + pp % WC;
-        const bool ok = (unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w;
-        const unsigned o = ok ? goff[k] : BUF_OOB;
-        sx[k] = buf_load4(rx, o); sh[k] = buf_load4(rh, o);
-      }
-    }
+    win.request(sx, a.x, sh, a.hin, b, a.h, a.w, ty * TR - 2, tx * TC - 2);
   };
   auto store_tile = [&](const f32x4 (&sx)[NS], const f32x4 (&sh)[NS]) {
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
-      __bf16* hi = (__bf16*)(lds + lbyte[k]);
+      __bf16* hi = (__bf16*)(lds + win.lbyte[k]);
       split_store(hi, (__bf16*)((char*)hi + LO), sx[k]);
       split_store(hi + 16, (__bf16*)((char*)hi + LO) + 16, sh[k]);
     }

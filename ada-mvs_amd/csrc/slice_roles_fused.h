@@ -43,7 +43,8 @@ struct Gru1FusedRole {
   static constexpr int RS = 4 / NRW;                                   // region rows (row pairs) between a wave's consecutive runs
   static constexpr int NGR = RR * NRW, NG = (NGR + 3) / 4;             // gate runs in all / per wave
   static constexpr int NCR = (TR / 2) * NRW, NC = (NCR + 3) / 4;       // candidate pair-runs in all / per wave
-  static constexpr int NS = (NPIX * 2 + 255) / 256;                    // float4 items per source and thread
+  typedef TileWindow<8, WR, WC, false, PLANE, GP> Win;                 // (edge coordinates formed again on edge tiles: not worth a register per item)
+  static constexpr int NS = Win::N;                                    // float4 items per source and thread
   static constexpr size_t LDS_BYTES = (size_t)(U0 + RR * RCOLS * 8) * sizeof(float);
   static constexpr int TILE_W = TC, TILE_H = TR;
   static int tiles_x(const Args& a) { return cdiv(a.w, TC); }
@@ -65,15 +66,8 @@ struct Gru1FusedRole {
   const f32x4 bias_c = *(const f32x4*)(a.bc + 4 * (q & 1));
 
   // ---- per-lane constants
-  unsigned goff[NS], lbyte[NS];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    const int j = min(tid + k * 256, NPIX * 2 - 1);                    // surplus lanes repeat the last item
-    const int g = j & 1, pp = j >> 1, r = pp / WC, c = pp % WC;
-    goff[k] = (unsigned)(((r * a.w + c) * 8 + 4 * g) * 4);
-    lbyte[k] = (unsigned)((g * GP + r * WC + c) * 4);                  // x group g; h group g: + 2 GP
-    pin(goff[k]); pin(lbyte[k]);
-  }
+  Win win;                                                             // the window of x (groups 0, 1) and of h (groups 2, 3): tile_window.h
+  win.init(a.w);
   unsigned xg[KC], xc[KC];                                             // B-fragment origins of the wave's first gate / candidate run
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) {
@@ -95,31 +89,11 @@ struct Gru1FusedRole {
   pin(ooff);
 
   auto load_tile = [&](f32x4 (&sx)[NS], f32x4 (&sh)[NS], int b, int tx, int ty) {
-    const int ix0 = tx * TC - 2, iy0 = ty * TR - 2;
-    const long pix0 = ((long)b * a.h + iy0) * a.w + ix0;
-    const buf_rsrc rx = make_rsrc((const char*)a.x + pix0 * 32);
-    const buf_rsrc rh = make_rsrc((const char*)a.hin + pix0 * 32);
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + WR <= a.h && ix0 + WC <= a.w) {
-#pragma unroll
-      for (int k = 0; k < NS; ++k) { sx[k] = buf_load4(rx, goff[k]); sh[k] = buf_load4(rh, goff[k]); }
-    } else {
-#pragma unroll
-      for (int k = 0; k < NS; ++k) {
-        const int pp = min(tid + k * 256, NPIX * 2 - 1) >> 1;          // (edge tiles only: not worth a register per item)
-        const int iy = iy0 + pp / WC, ix = ix0 + pp % WC;
-        const unsigned o = ((unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w) ? goff[k] : BUF_OOB;      // zero padding
-        sx[k] = buf_load4(rx, o); sh[k] = buf_load4(rh, o);
-      }
-    }
+    win.request(sx, a.x, sh, a.hin, b, a.h, a.w, ty * TR - 2, tx * TC - 2);
   };
   auto store_tile = [&](const f32x4 (&sx)[NS], const f32x4 (&sh)[NS]) {
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-      float* dx = (float*)((char*)lds + lbyte[k]);
-      float* dh = dx + 2 * GP;
-      dx[0] = sx[k].x; dx[PLANE] = sx[k].y; dx[2 * PLANE] = sx[k].z; dx[3 * PLANE] = sx[k].w;
-      dh[0] = sh[k].x; dh[PLANE] = sh[k].y; dh[2 * PLANE] = sh[k].z; dh[3 * PLANE] = sh[k].w;
-    }
+    win.store(sx, lds);
+    win.template store<2>(sh, lds);
   };
 
   int t = tr.begin + wg;
@@ -232,7 +206,8 @@ struct Gru2FusedRole {
   static constexpr int KC = 8, G = 12, PLANE = plane_pitch16(NPIX), GP = group_pitch(PLANE, G);
   static constexpr int U0 = (G * GP + 3) & ~3;                         // floats (16-byte aligned): u [RR * 16][16]
   static constexpr int NG = (RR + 1) / 2, NC = (TR + 3) / 4;           // gate runs per wave (rows w & 1, + 2, ...), candidate runs per wave
-  static constexpr int NS = (NPIX * 4 + 255) / 256;
+  typedef TileWindow<16, WR, WC, true, PLANE, GP> Win;
+  static constexpr int NS = Win::N;
   static constexpr size_t LDS_BYTES = (size_t)(U0 + RR * RCOLS * 16) * sizeof(float);
   static_assert(LDS_BYTES <= 64 * 1024, "default dynamic LDS limit");
   static constexpr int TILE_W = TC, TILE_H = TR;
@@ -251,17 +226,8 @@ struct Gru2FusedRole {
   const f32x4 bias_g = *(const f32x4*)(a.bg + half * 16 + 4 * q);
   const f32x4 bias_c = *(const f32x4*)(a.bc + 4 * q);
 
-  unsigned goff[NS], lbyte[NS];
-  int rc[NS];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    const int j = min(tid + k * 256, NPIX * 4 - 1);
-    const int g = j & 3, pp = j >> 2, r = pp / WC, c = pp % WC;
-    goff[k] = (unsigned)(((r * a.w + c) * 16 + 4 * g) * 4);
-    lbyte[k] = (unsigned)((g * GP + r * WC + c) * 4);                  // c2 group g; h group g: + 4 GP
-    rc[k] = r | (c << 16);
-    pin(goff[k]); pin(lbyte[k]); pin(rc[k]);
-  }
+  Win win;                                                             // the window of c2 (groups 0-3) and of h (groups 4-7): tile_window.h
+  win.init(a.w);
   unsigned xg[KC], xc[KC];
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) {
@@ -280,30 +246,11 @@ struct Gru2FusedRole {
   pin(ooff);
 
   auto load_tile = [&](f32x4 (&sx)[NS], f32x4 (&sh)[NS], int b, int tx, int ty) {
-    const int ix0 = tx * TC - 2, iy0 = ty * TR - 2;
-    const long pix0 = ((long)b * a.h + iy0) * a.w + ix0;
-    const buf_rsrc rx = make_rsrc((const char*)a.x + pix0 * 64);
-    const buf_rsrc rh = make_rsrc((const char*)a.hin + pix0 * 64);
-    if (iy0 >= 0 && ix0 >= 0 && iy0 + WR <= a.h && ix0 + WC <= a.w) {
-#pragma unroll
-      for (int k = 0; k < NS; ++k) { sx[k] = buf_load4(rx, goff[k]); sh[k] = buf_load4(rh, goff[k]); }
-    } else {
-#pragma unroll
-      for (int k = 0; k < NS; ++k) {
-        const int iy = iy0 + (rc[k] & 0xffff), ix = ix0 + (rc[k] >> 16);
-        const unsigned o = ((unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w) ? goff[k] : BUF_OOB;
-        sx[k] = buf_load4(rx, o); sh[k] = buf_load4(rh, o);
-      }
-    }
+    win.request(sx, a.x, sh, a.hin, b, a.h, a.w, ty * TR - 2, tx * TC - 2);
   };
   auto store_tile = [&](const f32x4 (&sx)[NS], const f32x4 (&sh)[NS]) {
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-      float* dx = (float*)((char*)lds + lbyte[k]);
-      float* dh = dx + 4 * GP;
-      dx[0] = sx[k].x; dx[PLANE] = sx[k].y; dx[2 * PLANE] = sx[k].z; dx[3 * PLANE] = sx[k].w;
-      dh[0] = sh[k].x; dh[PLANE] = sh[k].y; dh[2 * PLANE] = sh[k].z; dh[3 * PLANE] = sh[k].w;
-    }
+    win.store(sx, lds);
+    win.template store<4>(sh, lds);
   };
 
   int t = tr.begin + wg;

@@ -117,6 +117,7 @@ struct ConvWinoRole {
   }
 
   // ---- window fill: as ConvSmallRole (two sources, planar groups)
+  // (its own code, not tile_window.h: on the helper k_conv_small_wino<16, 16, 1, EPI_CAND> came out at 241 VGPRs for 242 and <16, 16, 2, EPI_GATES> at 252 for 254)
   // (CONV2: the two sources have the same shape, so item k of the state half has the offsets of item k - NA of the input half, its
   //  LDS address GA groups further on: six registers the conv2 fragments need, or the kernel loses a workgroup per CU)
   constexpr bool SHARE = CONV2 && CA == CB;

@@ -438,7 +438,8 @@ def test_slice_reg_step_bf16x3(hip, k):
     assert rel_l1(reg, g["reg"]) < 2e-4, "decoder"
 
 
-@pytest.mark.parametrize("k,h,w", [(0, 22, 38), (1, 30, 18), (2, 26, 50), (0, 4, 6)])
+@pytest.mark.parametrize("k,h,w", [(0, 22, 38), (1, 30, 18), (2, 26, 50), (0, 4, 6),
+                                   (0, 18, 66), (1, 18, 66)])     # one interior 8 x 32 tile (iy0 = 7, ix0 = 31)
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
 def test_slice_reg_step_ragged_shapes(hip, O, precision, k, h, w):
     """Sizes that are no multiple of any tile (4 x 16 GRU tiles, 6 x 30 decoder tiles, 8 x 16 conv1 tiles): every
@@ -458,7 +459,8 @@ def test_slice_reg_step_ragged_shapes(hip, O, precision, k, h, w):
     assert rel_l1(n1, r1) < tol and rel_l1(n2, r2) < tol and rel_l1(reg, ref) < tol
 
 
-@pytest.mark.parametrize("k,h,w", [(0, 22, 38), (1, 30, 18), (2, 26, 50), (0, 4, 6)])
+@pytest.mark.parametrize("k,h,w", [(0, 22, 38), (1, 30, 18), (2, 26, 50), (0, 4, 6),
+                                   (0, 18, 66), (1, 18, 66)])     # one interior 8 x 32 tile (iy0 = 7, ix0 = 31)
 @pytest.mark.parametrize("form", ["gru_wino=0", "gru_wino=7", "gru_wino=15", "bf16x3"])
 def test_slice_reg_step_every_form_against_float64(hip, O, set_option, form, k, h, w):
     """One recurrent step (launch_slice_step: conv1, gates and candidate of both ConvGRU levels, conv2, the decoder) per element
@@ -533,7 +535,8 @@ def _check_sweep(sim, c1, sim64, c164, c1_bars=SWEEP):
                                               (32, 24, 40, 24, 8.0),        # narrow sweep: one LDS-resident chunk
                                               (32, 24, 40, 16, 400.0),      # wide sweep: chunks split, patches leave the image
                                               (16, 40, 24, 10, 2500.0),     # extreme: per-plane patches / global fallback
-                                              (32, 16, 40, 33, 8.0), (8, 24, 70, 40, 80.0)])    # two chunks of 32 planes
+                                              (32, 16, 40, 33, 8.0), (8, 24, 70, 40, 80.0),     # two chunks of 32 planes
+                                              (32, 18, 66, 2, 80.0), (16, 18, 66, 2, 80.0)])    # one interior 8 x 32 tile (iy0 = 7, ix0 = 31)
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
 def test_aggregate_conv1(hip, O, C, h, w, D, baseline, precision):
     """Weighted aggregation (register-resident taps, arbitrary planes) + two-row conv1 (fp32 and split-bf16 MFMA).  Every plane
