@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
+#include "chunk_window.h"
 #include "common.h"
 #include "conv_frag.h"
 #include "costreg_softmax.h"
@@ -59,16 +60,7 @@ template <int BR> struct TileGeom<CONV_T2, BR> { static constexpr int LR = BR + 
 // Block = 8 rows x 16 columns of output positions x all D output channels.
 // Waves: WM along output channels (MT tiles of 16 each), WN = 4/WM along rows.
 // PY/PX: output parity class, CONV_T2 only (ConvTranspose2d k3 s2 p1 op1).
-//
-// fp32 MFMA shares the vector lanes (tools/microbench/mfma_issue.hip: every extra VALU instruction per MFMA costs
-// 3-6 cycles of matrix time, at any occupancy), and at this register budget there is one wave per SIMD, so the
-// chunk loop is written to contain matrix instructions and nothing else that needs the vector ALU:
-//  * global accesses are buffer loads: uniform descriptor, per-lane byte offset computed once (bounds folded in
-//    as BUF_OOB -> zero fill), the chunk enters as the scalar offset operand;
-//  * LDS addresses of the tile fill and of the B-fragment reads are per-lane constants, pinned in registers;
-//  * two named register sets for the A fragments and two chunks per loop trip: the fragments and the activation
-//    tile of chunk k+1 are requested before the MFMAs of chunk k and waited for once, after them (vmcnt retires
-//    in order; a single explicit wait keeps the compiler from scheduling its own in the middle of the chain).
+// Window, fragment fetch, chunk loop (and why it holds one explicit wait per chunk) and epilogue: chunk_window.h.
 template <int MT, int WM, int MODE, int KB, int PY, int PX, int BR = 8, bool TWO = false, bool SOFTMAX = false>
 __device__ __forceinline__ void conv_dd_body(const ConvDDArgs& a, float* lds, int n, int by, int bx) {
   using TG = TileGeom<MODE, BR>;
@@ -86,21 +78,14 @@ __device__ __forceinline__ void conv_dd_body(const ConvDDArgs& a, float* lds, in
   const int iy0 = (MODE == CONV_T2) ? r0 : r0 * STR - 1;
   const int ix0 = (MODE == CONV_T2) ? c0 : c0 * STR - 1;
   constexpr int NTAP = NTY * NTX;
-  constexpr int NITEMS = LR * LC * (KB / 4), NITA = (NITEMS + 255) / 256;
+  using Win = ChunkWindow<LR, LC, LC, KB / 4, PLANE, GP>;
+  constexpr int NITA = Win::N;
 
   // ---- per-lane constants
   // activation tile: item = (pixel of the window, group of 4 channels); out-of-image pixels read as zero
-  const buf_rsrc rx = make_rsrc((const char*)a.in + (((long)n * a.hi + iy0) * a.wi + ix0) * (long)D * 4);
-  unsigned xoff[NITA], xlds[NITA];
-#pragma unroll
-  for (int it = 0; it < NITA; ++it) {
-    const int i = min(tid + it * 256, NITEMS - 1);           // surplus lanes repeat the last item
-    const int g = i % (KB / 4), pp = i / (KB / 4), r = pp / LC, c = pp % LC;
-    const bool ok = (unsigned)(iy0 + r) < (unsigned)a.hi && (unsigned)(ix0 + c) < (unsigned)a.wi;
-    xoff[it] = ok ? (unsigned)(((r * a.wi + c) * D + 4 * g) * 4) : BUF_OOB;
-    xlds[it] = (unsigned)((g * GP + r * LC + c) * 4);
-    pin(xoff[it]); pin(xlds[it]);
-  }
+  const buf_rsrc rx = Win::origin(a.in, n, a.hi, a.wi, D, iy0, ix0);
+  Win win;
+  win.init(a.hi, a.wi, D, iy0, ix0);
   // A fragments: [tap][D/4][D/16][64]; lane offset only, the rest is uniform
   const buf_rsrc rw = make_rsrc(a.wpk);
   unsigned woff = (unsigned)(lane * 4);
@@ -130,32 +115,12 @@ __device__ __forceinline__ void conv_dd_body(const ConvDDArgs& a, float* lds, in
         for (int kc = 0; kc < KB / 4; ++kc)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
-            const unsigned frag = (unsigned)(((ky * 3 + kx) * KCT + ch / 4 + kc) * NTILES + wm * MT + mt) * 256u;   // uniform
-            wf[ty * NTX + tx][kc][mt] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, woff, frag, 0));
+            wf[ty * NTX + tx][kc][mt] = load_afrag(rw, woff, ky * 3 + kx, ch / 4 + kc, wm * MT + mt, KCT, NTILES);
           }
       }
   };
   constexpr bool two = TWO;          // the layer convolves in + in2 (a separate instantiation: the plain chunk loop stays as it was)
-  const buf_rsrc rx2 = make_rsrc((const char*)(two ? a.in2 : a.in) + (((long)n * a.hi + iy0) * a.wi + ix0) * (long)D * 4);
-  f32x4 xs2[two ? NITA : 1];
-  auto load_x = [&](f32x4 (&st)[NITA], int ch) {
-#pragma unroll
-    for (int it = 0; it < NITA; ++it)
-      st[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xoff[it], (unsigned)ch * 4u, 0));
-    if (two) {
-#pragma unroll
-      for (int it = 0; it < NITA; ++it)
-        xs2[two ? it : 0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx2, xoff[it], (unsigned)ch * 4u, 0));
-    }
-  };
-  auto store_x = [&](const f32x4 (&st)[NITA]) {
-#pragma unroll
-    for (int it = 0; it < NITA; ++it) {
-      float* dl = (float*)((char*)lds + xlds[it]);
-      const f32x4 v = two ? st[it] + xs2[two ? it : 0] : st[it];
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
-    }
-  };
+  const buf_rsrc rx2 = Win::origin(two ? a.in2 : a.in, n, a.hi, a.wi, D, iy0, ix0);
   auto mfma_chunk = [&](const float (&wf)[NTAP][KB / 4][MT]) {
 #pragma unroll
     for (int ty = 0; ty < NTY; ++ty)
@@ -174,28 +139,11 @@ __device__ __forceinline__ void conv_dd_body(const ConvDDArgs& a, float* lds, in
   };
 
   float wfA[NTAP][KB / 4][MT], wfB[NTAP][KB / 4][MT];
-  f32x4 xs[NITA];
-  load_w(wfA, 0);
-  load_x(xs, 0);
-  for (int ch = 0; ch < D; ch += 2 * KB) {       // D / KB is even for every supported D
-    wait_vmem_all();
-    __syncthreads();                    // previous chunk's readers are done
-    store_x(xs);
-    __syncthreads();
-    load_w(wfB, ch + KB);
-    load_x(xs, ch + KB);
-    mfma_chunk(wfA);
-
-    wait_vmem_all();
-    __syncthreads();
-    store_x(xs);
-    __syncthreads();
-    if (ch + 2 * KB < D) {
-      load_w(wfA, ch + 2 * KB);
-      load_x(xs, ch + 2 * KB);
-    }
-    mfma_chunk(wfB);
-  }
+  f32x4 xs[NITA], xs2[NITA];
+  auto request = [&](auto& wf, int ch) { load_w(wf, ch); win.request(xs, rx, xs2, rx2, ch, two); };
+  request(wfA, 0);
+  auto store_x = [&] { win.store(xs, xs2, two, lds); };
+  for (int ch = 0; ch < D; ch += 2 * KB) chunk_trip<KB>(D, ch, wfA, wfB, request, store_x, mfma_chunk);
 
   if (SOFTMAX) {
     __syncthreads();                                   // the last chunk's readers are done: the tile space is reused
@@ -205,20 +153,9 @@ __device__ __forceinline__ void conv_dd_body(const ConvDDArgs& a, float* lds, in
   // epilogue: lane owns channels co4..co4+3 of the pixel in column p
 #pragma unroll
   for (int r = 0; r < NTR; ++r) {
-    int row = r0 + wn * NTR + r, col = c0 + p;
-    int oy = (MODE == CONV_T2) ? 2 * row + PY : row;
-    int ox = (MODE == CONV_T2) ? 2 * col + PX : col;
-    bool valid = (MODE == CONV_T2) ? (row < a.hi && col < a.wi) : (oy < a.ho && ox < a.wo);
-    if (!valid) continue;
-    size_t opix = ((size_t)n * a.ho + oy) * a.wo + ox;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-      int co4 = (wm * MT + mt) * 16 + 4 * q;
-      f32x4 v = acc[mt][r] + *(const f32x4*)(a.bias + co4);
-      if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-      if (a.skip) v += *(const f32x4*)(a.skip + opix * D + co4);
-      *(f32x4*)(a.out + opix * D + co4) = v;
-    }
+    const int row = r0 + wn * NTR + r, col = c0 + p;
+    epilogue_pixel<MT>(a, D, n, (MODE == CONV_T2) ? 2 * row + PY : row, (MODE == CONV_T2) ? 2 * col + PX : col, wm * MT, q,
+                       [&](int mt) { return acc[mt][r]; });
   }
 }
 
@@ -237,21 +174,14 @@ __device__ __forceinline__ void conv_dd_t2_all(const ConvDDArgs& a, float* lds, 
   const int p = lane & 15, q = lane >> 4;
   const int D = a.D, KCT = D / 4, NTILES = D / 16;
   const int r0 = by * 8, c0 = bx * 16;                       // block origin: input positions (i, j)
-  constexpr int NITEMS = LR * LC * (KB / 4), NITA = (NITEMS + 255) / 256;
+  using Win = ChunkWindow<LR, LC, LC, KB / 4, PLANE, GP>;
+  constexpr int NITA = Win::N;
 
-  const buf_rsrc rx = make_rsrc((const char*)a.in + (((long)n * a.hi + r0) * a.wi + c0) * (long)D * 4);
+  const buf_rsrc rx = Win::origin(a.in, n, a.hi, a.wi, D, r0, c0);
   const bool two = a.in2 != nullptr;                         // uniform: the layer convolves in + in2
-  const buf_rsrc rx2 = make_rsrc((const char*)(two ? a.in2 : a.in) + (((long)n * a.hi + r0) * a.wi + c0) * (long)D * 4);
-  unsigned xoff[NITA], xlds[NITA];
-#pragma unroll
-  for (int it = 0; it < NITA; ++it) {
-    const int i = min(tid + it * 256, NITEMS - 1);           // surplus lanes repeat the last item
-    const int g = i % (KB / 4), pp = i / (KB / 4), r = pp / LC, c = pp % LC;
-    const bool ok = r0 + r < a.hi && c0 + c < a.wi;
-    xoff[it] = ok ? (unsigned)(((r * a.wi + c) * D + 4 * g) * 4) : BUF_OOB;
-    xlds[it] = (unsigned)((g * GP + r * LC + c) * 4);
-    pin(xoff[it]); pin(xlds[it]);
-  }
+  const buf_rsrc rx2 = Win::origin(two ? a.in2 : a.in, n, a.hi, a.wi, D, r0, c0);
+  Win win;
+  win.init(a.hi, a.wi, D, r0, c0);
   const buf_rsrc rw = make_rsrc(a.wpk);
   unsigned woff = (unsigned)(lane * 4);
   pin(woff);
@@ -278,24 +208,8 @@ __device__ __forceinline__ void conv_dd_t2_all(const ConvDDArgs& a, float* lds, 
   f32x4 xs[NITA], xs2[NITA];
   f32x4 acc[MT][NTR];
 
-  auto load_x = [&](int ch) {
-#pragma unroll
-    for (int it = 0; it < NITA; ++it)
-      xs[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xoff[it], (unsigned)ch * 4u, 0));
-    if (two) {
-#pragma unroll
-      for (int it = 0; it < NITA; ++it)
-        xs2[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx2, xoff[it], (unsigned)ch * 4u, 0));
-    }
-  };
-  auto store_x = [&]() {
-#pragma unroll
-    for (int it = 0; it < NITA; ++it) {
-      float* dl = (float*)((char*)lds + xlds[it]);
-      const f32x4 v = two ? xs[it] + xs2[it] : xs[it];
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
-    }
-  };
+  auto load_x = [&](int ch) { win.request(xs, rx, xs2, rx2, ch, two); };
+  auto store_x = [&] { win.store(xs, xs2, two, lds); };
   auto load_w = [&](auto pyc, auto pxc, float (&wf)[4][KB / 4][MT], int ch) {
     constexpr int PY = decltype(pyc)::value, PX = decltype(pxc)::value;
 #pragma unroll
@@ -307,8 +221,7 @@ __device__ __forceinline__ void conv_dd_t2_all(const ConvDDArgs& a, float* lds, 
         for (int kc = 0; kc < KB / 4; ++kc)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
-            const unsigned frag = (unsigned)(((ky * 3 + kx) * KCT + ch / 4 + kc) * NTILES + wm * MT + mt) * 256u;   // uniform
-            wf[ty * (1 + PX) + tx][kc][mt] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, woff, frag, 0));
+            wf[ty * (1 + PX) + tx][kc][mt] = load_afrag(rw, woff, ky * 3 + kx, ch / 4 + kc, wm * MT + mt, KCT, NTILES);
           }
       }
   };
@@ -338,7 +251,7 @@ __device__ __forceinline__ void conv_dd_t2_all(const ConvDDArgs& a, float* lds, 
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
       for (int r = 0; r < NTR; ++r) acc[mt][r] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int ch = 0; ch < D; ch += 2 * KB) {
+    for (int ch = 0; ch < D; ch += 2 * KB) {            // chunk_trip (chunk_window.h) with the two class-chaining rules
       if (decltype(first)::value || ch > 0) wait_vmem_all();
       __syncthreads();
       store_x();
@@ -365,8 +278,7 @@ __device__ __forceinline__ void conv_dd_t2_all(const ConvDDArgs& a, float* lds, 
     for (int r = 0; r < NTR; ++r)
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
-        f32x4 v = acc[mt][r] + *(const f32x4*)(a.bias + (wm * MT + mt) * 16 + 4 * q);
-        if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        f32x4 v = bias_act(acc[mt][r], *(const f32x4*)(a.bias + (wm * MT + mt) * 16 + 4 * q), a.relu);
         const unsigned o = ooff[r] == BUF_OOB ? BUF_OOB : ooff[r] + cls + (unsigned)(mt * 64);
         if (a.skip) v += buf_load4(rk, o);
         buf_store4(ro, o, v);
@@ -404,19 +316,12 @@ __device__ __forceinline__ void conv_dd_t2_fused(const ConvDDArgs& a, float* lds
   const int p = lane & 15, q = lane >> 4;
   const int D = a.D, KCT = D / 4, NTILES = D / 16;
   const int r0 = by * BR, c0 = bx * 16;                      // block origin: input positions (i, j)
-  constexpr int NITEMS = LR * LC * (KB / 4), NITA = (NITEMS + 255) / 256;
+  using Win = ChunkWindow<LR, LC, LC, KB / 4, PLANE, GP>;
+  constexpr int NITA = Win::N;
 
-  const buf_rsrc rx = make_rsrc((const char*)a.in + (((long)n * a.hi + r0) * a.wi + c0) * (long)D * 4);
-  unsigned xoff[NITA], xlds[NITA];
-#pragma unroll
-  for (int it = 0; it < NITA; ++it) {
-    const int i = min(tid + it * 256, NITEMS - 1);           // surplus lanes repeat the last item
-    const int g = i % (KB / 4), pp = i / (KB / 4), r = pp / LC, c = pp % LC;
-    const bool ok = r0 + r < a.hi && c0 + c < a.wi;
-    xoff[it] = ok ? (unsigned)(((r * a.wi + c) * D + 4 * g) * 4) : BUF_OOB;
-    xlds[it] = (unsigned)((g * GP + r * LC + c) * 4);
-    pin(xoff[it]); pin(xlds[it]);
-  }
+  const buf_rsrc rx = Win::origin(a.in, n, a.hi, a.wi, D, r0, c0);
+  Win win;
+  win.init(a.hi, a.wi, D, r0, c0);
   const buf_rsrc rw = make_rsrc(a.wpk);
   unsigned woff = (unsigned)(lane * 4);
   pin(woff);
@@ -442,31 +347,11 @@ __device__ __forceinline__ void conv_dd_t2_fused(const ConvDDArgs& a, float* lds
       for (int kc = 0; kc < KB / 4; ++kc)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-          const unsigned frag = (unsigned)((t * KCT + ch / 4 + kc) * NTILES + wm * MT + mt) * 256u;   // uniform
-          wf[t][kc][mt] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, woff, frag, 0));
+          wf[t][kc][mt] = load_afrag(rw, woff, t, ch / 4 + kc, wm * MT + mt, KCT, NTILES);
         }
   };
   const bool two = a.in2 != nullptr;                         // uniform: the layer convolves in + in2
-  const buf_rsrc rx2 = make_rsrc((const char*)(two ? a.in2 : a.in) + (((long)n * a.hi + r0) * a.wi + c0) * (long)D * 4);
-  f32x4 xs2[NITA];
-  auto load_x = [&](f32x4 (&st)[NITA], int ch) {
-#pragma unroll
-    for (int it = 0; it < NITA; ++it)
-      st[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xoff[it], (unsigned)ch * 4u, 0));
-    if (two) {
-#pragma unroll
-      for (int it = 0; it < NITA; ++it)
-        xs2[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx2, xoff[it], (unsigned)ch * 4u, 0));
-    }
-  };
-  auto store_x = [&](const f32x4 (&st)[NITA]) {
-#pragma unroll
-    for (int it = 0; it < NITA; ++it) {
-      float* dl = (float*)((char*)lds + xlds[it]);
-      const f32x4 v = two ? st[it] + xs2[it] : st[it];
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
-    }
-  };
+  const buf_rsrc rx2 = Win::origin(two ? a.in2 : a.in, n, a.hi, a.wi, D, r0, c0);
   auto mfma_chunk = [&](const float (&wf)[9][KB / 4][MT]) {
 #pragma unroll
     for (int ty = 0; ty < 2; ++ty)
@@ -492,45 +377,18 @@ __device__ __forceinline__ void conv_dd_t2_fused(const ConvDDArgs& a, float* lds
   };
 
   float wfA[9][KB / 4][MT], wfB[9][KB / 4][MT];
-  f32x4 xs[NITA];
-  load_w(wfA, 0);
-  load_x(xs, 0);
-  for (int ch = 0; ch < D; ch += 2 * KB) {       // D / KB is even for every supported D
-    wait_vmem_all();
-    __syncthreads();                    // previous chunk's readers are done
-    store_x(xs);
-    __syncthreads();
-    load_w(wfB, ch + KB);
-    load_x(xs, ch + KB);
-    mfma_chunk(wfA);
-
-    wait_vmem_all();
-    __syncthreads();
-    store_x(xs);
-    __syncthreads();
-    if (ch + 2 * KB < D) {
-      load_w(wfA, ch + 2 * KB);
-      load_x(xs, ch + 2 * KB);
-    }
-    mfma_chunk(wfB);
-  }
+  f32x4 xs[NITA], xs2[NITA];
+  auto request = [&](auto& wf, int ch) { load_w(wf, ch); win.request(xs, rx, xs2, rx2, ch, two); };
+  request(wfA, 0);
+  auto store_x = [&] { win.store(xs, xs2, two, lds); };
+  for (int ch = 0; ch < D; ch += 2 * KB) chunk_trip<KB>(D, ch, wfA, wfB, request, store_x, mfma_chunk);
 
 #pragma unroll
   for (int c = 0; c < 4; ++c)
 #pragma unroll
-    for (int r = 0; r < NTR; ++r) {
-      const int row = r0 + wn * NTR + r, col = c0 + p;
-      if (!(row < a.hi && col < a.wi)) continue;
-      const size_t opix = ((size_t)n * a.ho + 2 * row + (c >> 1)) * a.wo + 2 * col + (c & 1);
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) {
-        const int co4 = (wm * MT + mt) * 16 + 4 * q;
-        f32x4 v = acc[c][mt][r] + *(const f32x4*)(a.bias + co4);
-        if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        if (a.skip) v += *(const f32x4*)(a.skip + opix * D + co4);
-        *(f32x4*)(a.out + opix * D + co4) = v;
-      }
-    }
+    for (int r = 0; r < NTR; ++r)
+      epilogue_pixel<MT>(a, D, n, 2 * (r0 + wn * NTR + r) + (c >> 1), 2 * (c0 + p) + (c & 1), wm * MT, q,
+                         [&](int mt) { return acc[c][mt][r]; });
 }
 
 // Stride-2 layer (conv1, conv3, conv5 of the hourglass: reference models/adamvs.py:206-211, 229-232) with the minimal-filtering
@@ -551,24 +409,17 @@ template <int MT, int WM>
 __device__ __forceinline__ void conv_dd_s2_pairs(const ConvDDArgs& a, float* lds, int n, int by, int bx) {
   static_assert(WM == 4, "every wave takes all rows of the block");
   constexpr int BR = S2P_ROWS, LR = 2 * BR + 1, WCOLS = 65, LC = 68, PLANE = ((LR * LC + 31) / 32) * 32 + 16;
-  constexpr int NITEMS = LR * WCOLS, NITA = (NITEMS + 255) / 256;
+  using Win = ChunkWindow<LR, WCOLS, LC, 1, PLANE, 4 * PLANE>;     // one channel group per chunk
+  constexpr int NITA = Win::N;
   const int tid = threadIdx.x, lane = tid & 63, wm = __builtin_amdgcn_readfirstlane(tid >> 6);    // wave = channel slice
   const int p = lane & 15, q = lane >> 4;
   const int D = a.D, KCT = D / 4, NTILES = D / 16;
   const int r0 = by * BR, c0 = bx * 32;
   const int iy0 = 2 * r0 - 1, ix0 = 2 * c0 - 1;
 
-  const buf_rsrc rx = make_rsrc((const char*)a.in + (((long)n * a.hi + iy0) * a.wi + ix0) * (long)D * 4);
-  unsigned xoff[NITA], xlds[NITA];
-#pragma unroll
-  for (int it = 0; it < NITA; ++it) {
-    const int i = min(tid + it * 256, NITEMS - 1);           // surplus lanes repeat the last item
-    const int r = i / WCOLS, c = i % WCOLS;
-    const bool ok = (unsigned)(iy0 + r) < (unsigned)a.hi && (unsigned)(ix0 + c) < (unsigned)a.wi;
-    xoff[it] = ok ? (unsigned)(((r * a.wi + c) * D) * 4) : BUF_OOB;
-    xlds[it] = (unsigned)((r * LC + c) * 4);
-    pin(xoff[it]); pin(xlds[it]);
-  }
+  const buf_rsrc rx = Win::origin(a.in, n, a.hi, a.wi, D, iy0, ix0);
+  Win win;
+  win.init(a.hi, a.wi, D, iy0, ix0);
   const buf_rsrc rw = make_rsrc(a.wpk);
   unsigned woff = (unsigned)(lane * 4);
   pin(woff);
@@ -588,21 +439,8 @@ __device__ __forceinline__ void conv_dd_s2_pairs(const ConvDDArgs& a, float* lds
     for (int t = 0; t < 9; ++t)
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
-        const unsigned frag = (unsigned)((t * KCT + ch / 4) * NTILES + wm * MT + mt) * 256u;   // uniform
-        wf[t][mt] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, woff, frag, 0));
+        wf[t][mt] = load_afrag(rw, woff, t, ch / 4, wm * MT + mt, KCT, NTILES);
       }
-  };
-  auto load_x = [&](f32x4 (&st)[NITA], int ch) {
-#pragma unroll
-    for (int it = 0; it < NITA; ++it)
-      st[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, xoff[it], (unsigned)ch * 4u, 0));
-  };
-  auto store_x = [&](const f32x4 (&st)[NITA]) {
-#pragma unroll
-    for (int it = 0; it < NITA; ++it) {
-      float* dl = (float*)((char*)lds + xlds[it]);
-      dl[0] = st[it].x; dl[PLANE] = st[it].y; dl[2 * PLANE] = st[it].z; dl[3 * PLANE] = st[it].w;
-    }
   };
   auto mfma_chunk = [&](const float (&wf)[9][MT]) {
     float w02[3][MT];
@@ -631,27 +469,10 @@ __device__ __forceinline__ void conv_dd_s2_pairs(const ConvDDArgs& a, float* lds
 
   float wfA[9][MT], wfB[9][MT];
   f32x4 xs[NITA];
-  load_w(wfA, 0);
-  load_x(xs, 0);
-  for (int ch = 0; ch < D; ch += 8) {            // two chunks of 4 input channels per trip (D / 4 is even for every supported D)
-    wait_vmem_all();
-    __syncthreads();                    // previous chunk's readers are done
-    store_x(xs);
-    __syncthreads();
-    load_w(wfB, ch + 4);
-    load_x(xs, ch + 4);
-    mfma_chunk(wfA);
-
-    wait_vmem_all();
-    __syncthreads();
-    store_x(xs);
-    __syncthreads();
-    if (ch + 8 < D) {
-      load_w(wfA, ch + 8);
-      load_x(xs, ch + 8);
-    }
-    mfma_chunk(wfB);
-  }
+  auto request = [&](auto& wf, int ch) { load_w(wf, ch); win.request(xs, rx, ch); };
+  request(wfA, 0);
+  auto store_x = [&] { win.store(xs, lds); };
+  for (int ch = 0; ch < D; ch += 8) chunk_trip<4>(D, ch, wfA, wfB, request, store_x, mfma_chunk);      // one k-step per chunk
   // epilogue: lane owns channels co4 .. co4 + 3 of the output pair (c0 + 2 p, c0 + 2 p + 1) of every row
 #pragma unroll
   for (int r = 0; r < BR; ++r) {
@@ -662,11 +483,7 @@ __device__ __forceinline__ void conv_dd_s2_pairs(const ConvDDArgs& a, float* lds
     for (int mt = 0; mt < MT; ++mt) {
       const int co4 = (wm * MT + mt) * 16 + 4 * q;
       const f32x4 b = *(const f32x4*)(a.bias + co4);
-      f32x4 v0 = (acc[0][mt][r] + acc[2][mt][r]) + b, v1 = (acc[1][mt][r] + acc[2][mt][r]) + b;
-      if (a.relu) {
-        v0.x = fmaxf(v0.x, 0.f); v0.y = fmaxf(v0.y, 0.f); v0.z = fmaxf(v0.z, 0.f); v0.w = fmaxf(v0.w, 0.f);
-        v1.x = fmaxf(v1.x, 0.f); v1.y = fmaxf(v1.y, 0.f); v1.z = fmaxf(v1.z, 0.f); v1.w = fmaxf(v1.w, 0.f);
-      }
+      const f32x4 v0 = bias_act(acc[0][mt][r] + acc[2][mt][r], b, a.relu), v1 = bias_act(acc[1][mt][r] + acc[2][mt][r], b, a.relu);
       *(f32x4*)(a.out + opix * D + co4) = v0;
       if (ox + 1 < a.wo) *(f32x4*)(a.out + (opix + 1) * D + co4) = v1;
     }
@@ -707,7 +524,10 @@ template <int MT, int NR, int KB1, int KB0>
 __device__ __forceinline__ void conv_dd_t2_pairs(const ConvDDArgs& a, float* lds, int n, int by, int bx) {
   using G = T2PGeom<NR>;
   constexpr int WCOLS = G::WCOLS, LC = G::LC, PLANE = G::PLANE;
-  constexpr int NI1 = ((NR + 1) * WCOLS * (KB1 / 4) + 255) / 256, NI0 = KB0 == KB1 ? NI1 : (NR * WCOLS * (KB0 / 4) + 255) / 256, NIM = NI1 > NI0 ? NI1 : NI0;
+  constexpr bool SAME = KB0 == KB1;                            // one window for both classes: py = 0 loads (and ignores) the row below its own
+  using Win1 = ChunkWindow<NR + 1, WCOLS, LC, KB1 / 4, PLANE, group_pitch(PLANE, KB1 / 4)>;
+  using Win0 = ChunkWindow<NR, WCOLS, LC, KB0 / 4, PLANE, group_pitch(PLANE, KB0 / 4)>;
+  constexpr int NI0 = SAME ? Win1::N : Win0::N, NIM = Win1::N > NI0 ? Win1::N : NI0;
   constexpr int NW = (6 * (KB1 / 4) > 3 * (KB0 / 4) ? 6 * (KB1 / 4) : 3 * (KB0 / 4)) * MT;
   static_assert(192 % (2 * KB1) == 0 && 192 % (2 * KB0) == 0, "an even number of chunks per class at D = 192, 384");
   const int tid = threadIdx.x, lane = tid & 63, wm = __builtin_amdgcn_readfirstlane(tid >> 6);    // wave = channel slice
@@ -715,30 +535,21 @@ __device__ __forceinline__ void conv_dd_t2_pairs(const ConvDDArgs& a, float* lds
   const int D = a.D, KCT = D / 4, NTILES = D / 16;
   const int r0 = by * NR, c0 = bx * T2P_COLS;                  // block origin: input positions (i, j)
 
-  const buf_rsrc rx = make_rsrc((const char*)a.in + (((long)n * a.hi + r0) * a.wi + c0) * (long)D * 4);
+  const buf_rsrc rx = Win1::origin(a.in, n, a.hi, a.wi, D, r0, c0);
   const bool two = a.in2 != nullptr;                           // uniform: the layer convolves in + in2
-  const buf_rsrc rx2 = make_rsrc((const char*)(two ? a.in2 : a.in) + (((long)n * a.hi + r0) * a.wi + c0) * (long)D * 4);
+  const buf_rsrc rx2 = Win1::origin(two ? a.in2 : a.in, n, a.hi, a.wi, D, r0, c0);
   // window fill, per class: item = (pixel of the window, group of 4 channels); pixels outside the map read as zero
-  unsigned xoff1[NI1], xlds1[NI1], xoff0[NI0], xlds0[NI0];
-  auto fill_consts = [&](auto pyc, auto kbc, auto& xoff, auto& xlds) {
-    constexpr int PY = decltype(pyc)::value, NG = decltype(kbc)::value / 4, NITEMS = (NR + PY) * WCOLS * NG, GP = group_pitch(PLANE, NG);
-#pragma unroll
-    for (int it = 0; it < (NITEMS + 255) / 256; ++it) {
-      const int i = min(tid + it * 256, NITEMS - 1);           // surplus lanes repeat the last item
-      const int g = i % NG, pp = i / NG, r = pp / WCOLS, c = pp % WCOLS;
-      const bool ok = r0 + r < a.hi && c0 + c < a.wi;
-      xoff[it] = ok ? (unsigned)(((r * a.wi + c) * D + 4 * g) * 4) : BUF_OOB;
-      xlds[it] = (unsigned)((g * GP + r * LC + c) * 4);
-      pin(xoff[it]); pin(xlds[it]);
-    }
+  Win1 win1;
+  Win0 win0;
+  win1.init(a.hi, a.wi, D, r0, c0);
+  if (!SAME) win0.init(a.hi, a.wi, D, r0, c0);
+  auto window = [&](auto pyc) -> const auto& {
+    if constexpr (decltype(pyc)::value || SAME) return win1; else return win0;
   };
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
   using K0 = std::integral_constant<int, KB0>;
   using K1 = std::integral_constant<int, KB1>;
-  constexpr bool SAME = KB0 == KB1;                            // one fill for both classes: py = 0 loads (and ignores) the row below its own
-  fill_consts(I1{}, K1{}, xoff1, xlds1);
-  if (!SAME) fill_consts(I0{}, K0{}, xoff0, xlds0);
   const buf_rsrc rw = make_rsrc(a.wpk);
   unsigned woff = (unsigned)(lane * 4);
   pin(woff);
@@ -760,30 +571,8 @@ __device__ __forceinline__ void conv_dd_t2_pairs(const ConvDDArgs& a, float* lds
   f32x4 xs[NIM], xs2[NIM];
   f32x4 acc[5][MT][NR];                                        // even outputs E0 | E1, then A1 | A2 | A3
 
-  auto load_x = [&](auto pyc, auto kbc, int ch) {
-    constexpr int PY = decltype(pyc)::value, NI = PY ? NI1 : NI0;
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const unsigned o = PY || SAME ? xoff1[it < NI1 ? it : 0] : xoff0[it < NI0 ? it : 0];
-      xs[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, o, (unsigned)ch * 4u, 0));
-    }
-    if (two) {
-#pragma unroll
-      for (int it = 0; it < NI; ++it) {
-        const unsigned o = PY || SAME ? xoff1[it < NI1 ? it : 0] : xoff0[it < NI0 ? it : 0];
-        xs2[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx2, o, (unsigned)ch * 4u, 0));
-      }
-    }
-  };
-  auto store_x = [&](auto pyc) {
-    constexpr int PY = decltype(pyc)::value, NI = PY ? NI1 : NI0;
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      float* dl = (float*)((char*)lds + (PY || SAME ? xlds1[it < NI1 ? it : 0] : xlds0[it < NI0 ? it : 0]));
-      const f32x4 v = two ? xs[it] + xs2[it] : xs[it];
-      dl[0] = v.x; dl[PLANE] = v.y; dl[2 * PLANE] = v.z; dl[3 * PLANE] = v.w;
-    }
-  };
+  auto load_x = [&](auto pyc, auto kbc, int ch) { window(pyc).request(xs, rx, xs2, rx2, ch, two); };
+  auto store_x = [&](auto pyc) { window(pyc).store(xs, xs2, two, lds); };
   auto load_w = [&](auto pyc, auto kbc, float (&wf)[NW], int ch) {
     constexpr int PY = decltype(pyc)::value, NG = decltype(kbc)::value / 4;
 #pragma unroll
@@ -795,8 +584,7 @@ __device__ __forceinline__ void conv_dd_t2_pairs(const ConvDDArgs& a, float* lds
         for (int kc = 0; kc < NG; ++kc)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
-            const unsigned frag = (unsigned)(((ky * 3 + kx) * KCT + ch / 4 + kc) * NTILES + wm * MT + mt) * 256u;   // uniform
-            wf[((ty * 3 + kx) * NG + kc) * MT + mt] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, woff, frag, 0));
+            wf[((ty * 3 + kx) * NG + kc) * MT + mt] = load_afrag(rw, woff, ky * 3 + kx, ch / 4 + kc, wm * MT + mt, KCT, NTILES);
           }
       }
   };
@@ -864,16 +652,16 @@ __device__ __forceinline__ void conv_dd_t2_pairs(const ConvDDArgs& a, float* lds
       const f32x4 b = *(const f32x4*)(a.bias + (wm * MT + mt) * 16 + 4 * q);
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
-        f32x4 v[4] = {acc[0][mt][r] + b, (acc[2][mt][r] + acc[3][mt][r]) + b, acc[1][mt][r] + b, (acc[4][mt][r] + acc[3][mt][r]) + b};
+        const f32x4 sum[4] = {acc[0][mt][r], acc[2][mt][r] + acc[3][mt][r], acc[1][mt][r], acc[4][mt][r] + acc[3][mt][r]};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          if (a.relu) { v[k].x = fmaxf(v[k].x, 0.f); v[k].y = fmaxf(v[k].y, 0.f); v[k].z = fmaxf(v[k].z, 0.f); v[k].w = fmaxf(v[k].w, 0.f); }
+          f32x4 v = bias_act(sum[k], b, a.relu);
           // BUF_OOB plus these terms (< 2^31) is still out of range.  The sum is a lane offset, not the scalar offset operand: a 16-byte
           // store with a scalar offset gets no wait state before the next write of its data registers, and the last store of the
           // class lost its fourth channel in lanes 12 - 15 to the next class's window sum
           const unsigned o = ooff[r] + (cls + (unsigned)(mt * 64) + (unsigned)(k * D * 4));
-          if (a.skip) v[k] += buf_load4(rk, o);
-          buf_store4(ro, o, v[k]);
+          if (a.skip) v += buf_load4(rk, o);
+          buf_store4(ro, o, v);
         }
       }
     }
@@ -968,18 +756,37 @@ static int t2_form(int MT, int WM, int N, int hi, int wi) {
   if (MT == 3 && WM == 4 && s2_pairs() && t2_pairs_pay(wi)) return 2;
   return 0;
 }
+// The tiling of a layer of width D: MT channel tiles per wave x WM waves along the channels = `chunk` output channels per launch,
+// `parts` launches over output-channel slices.  Read by conv_t2_form (adamvs_conv_t2_form: which kernel a transposed layer takes)
+// and by launch_conv_dd_z, so that the two agree.
+struct WidthTiling { int D, MT, WM, parts, chunk; };
+static const WidthTiling kWidthTilings[] = {
+    {16, 1, 1, 1, 16}, {32, 2, 1, 1, 32}, {48, 3, 1, 1, 48}, {64, 4, 1, 1, 64}, {96, 3, 2, 1, 96}, {128, 4, 2, 1, 128}, {192, 3, 4, 1, 192},
+    // 16 output tiles per block need 256 accumulator registers: one wave per SIMD, which feeds the matrix pipe at 83 % (DESIGN
+    // section 4, lesson 2; measured 74.5 % of the fp32 MFMA peak for the whole network at cfg5 against 88.5 % at D = 192).  The
+    // 128-channel tiling (two waves per SIMD) run twice instead: the second launch sees the weights, bias, skip and output
+    // moved by 8 channel tiles and contracts over all 256 input channels like the first.  Measured at cfg5 (8 tiles): 291.9 ->
+    // 279.5 ms per step.
+    {256, 4, 2, 2, 128},
+    // the 192-channel tiling twice (as 256 = 2 x 128 above): each launch contracts over all 384 input channels into its half
+    // of the output channels
+    {384, 3, 4, 2, 192},
+    // the 128-channel tiling four times (round 5; the class default of the reference is num_depth = 384, adamvs.py:538, and
+    // ndepths[0] is unconstrained): each launch contracts over all 512 input channels into its quarter of the output channels
+    {512, 4, 2, 4, 128},
+};
+// D = 256 in one launch: the softmax epilogue needs all the channels of a pixel in one workgroup and keeps the wide tiling;
+// ADAMVS_CONV256_SPLIT=0: the wide tiling everywhere
+static const WidthTiling kWide256 = {256, 4, 4, 1, 256};
+static const WidthTiling* width_tiling(int D, bool softmax_epilogue) {
+  if (D == 256 && (softmax_epilogue || !conv256_split())) return &kWide256;
+  for (const WidthTiling& t : kWidthTilings)
+    if (t.D == D) return &t;
+  return nullptr;
+}
 static int conv_t2_form(int N, int D, int hi, int wi) {
-  switch (D) {
-    case 16: return t2_form(1, 1, N, hi, wi);
-    case 32: return t2_form(2, 1, N, hi, wi);
-    case 48: return t2_form(3, 1, N, hi, wi);
-    case 64: return t2_form(4, 1, N, hi, wi);
-    case 96: return t2_form(3, 2, N, hi, wi);
-    case 128: case 512: return t2_form(4, 2, N, hi, wi);
-    case 192: case 384: return t2_form(3, 4, N, hi, wi);
-    case 256: return conv256_split() ? t2_form(4, 2, N, hi, wi) : t2_form(4, 4, N, hi, wi);
-  }
-  return -1;
+  const WidthTiling* t = width_tiling(D, false);
+  return t ? t2_form(t->MT, t->WM, N, hi, wi) : -1;
 }
 
 template <int MT, int WM>
@@ -1087,7 +894,8 @@ __global__ __launch_bounds__(DUAL ? 512 : 256) void k_conv_dd_resident(ConvDDArg
   constexpr int WM = D / 16, WN = 4 / WM, TR = NTR * WN, KCT = D / 4, NTILES = D / 16;
   constexpr int LR = TR + 2, LC = 18, PLANE = plane_pitch16(LR * LC);
   constexpr int NTHR = DUAL ? 512 : 256;
-  constexpr int NITEMS = LR * LC * KCT, NIT = (NITEMS + NTHR - 1) / NTHR;
+  using Win = ChunkWindow<LR, LC, LC, KCT, PLANE, 4 * PLANE, NTHR>;      // one chunk: all D channels
+  constexpr int NIT = Win::N;
   __shared__ float lds[D * PLANE];
   const int tid = threadIdx.x, lane = tid & 63, wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = DUAL ? wave8 >> 2 : 0, wave = wave8 & 3;
@@ -1103,33 +911,25 @@ __global__ __launch_bounds__(DUAL ? 512 : 256) void k_conv_dd_resident(ConvDDArg
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
-    for (int kc = 0; kc < KCT; ++kc)
-      wf[t][kc] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-          rw, (unsigned)(lane * 4), (unsigned)(((t * KCT + kc) * NTILES + wm) * 256), 0));
-  const long wbase = (((long)n * a.hi + iy0) * a.wi + ix0) * (long)D * 4;
-  const buf_rsrc rx = make_rsrc((const char*)a0.in + wbase);
+    for (int kc = 0; kc < KCT; ++kc) wf[t][kc] = load_afrag(rw, (unsigned)(lane * 4), t, kc, wm, KCT, NTILES);
+  Win win;
+  win.init(a.hi, a.wi, D, iy0, ix0);
   f32x4 xs[NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = min(tid + it * NTHR, NITEMS - 1);
-    const int g = i % KCT, pp = i / KCT, r = pp / LC, c = pp % LC;
-    const bool ok = (unsigned)(iy0 + r) < (unsigned)a.hi && (unsigned)(ix0 + c) < (unsigned)a.wi;
-    xs[it] = buf_load4(rx, ok ? (unsigned)(((r * a.wi + c) * D + 4 * g) * 4) : BUF_OOB);
-  }
+  win.request(xs, Win::origin(a0.in, n, a.hi, a.wi, D, iy0, ix0), 0);
   if (pro.mode != GRU_PRO_NONE) {                            // uniform: the window is formed from the previous kernels' maps
     __shared__ double wsum[NTHR / 64][2];
     __shared__ float st[2][2];
     gru_pro_stats<NTHR>(pro.part_f + ((size_t)n * 2 + pro.group_f) * pro.parts_f * 2, pro.parts_f, pro.count, pro.eps, wsum, st[0]);
     if (pro.mode == GRU_PRO_OUT) gru_pro_stats<NTHR>(pro.part_o + (size_t)n * pro.parts_o * 2, pro.parts_o, pro.count, pro.eps, wsum, st[1]);
-    const buf_rsrc rf = make_rsrc((const char*)pro.f + wbase);
-    const buf_rsrc ro_ = make_rsrc((const char*)(pro.mode == GRU_PRO_OUT ? pro.o : pro.f) + wbase);
+    const buf_rsrc rf = Win::origin(pro.f, n, a.hi, a.wi, D, iy0, ix0);
+    const buf_rsrc ro_ = Win::origin(pro.mode == GRU_PRO_OUT ? pro.o : pro.f, n, a.hi, a.wi, D, iy0, ix0);
     const float mf = st[0][0], rf_ = st[0][1], mo = st[1][0], ro2 = st[1][1];
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      const int i = min(tid + it * NTHR, NITEMS - 1);
-      const int g = i % KCT, pp = i / KCT, r = pp / LC, c = pp % LC;
-      const bool ok = (unsigned)(iy0 + r) < (unsigned)a.hi && (unsigned)(ix0 + c) < (unsigned)a.wi && 4 * g < pro.hc;
-      const unsigned off = ok ? (unsigned)(((r * a.wi + c) * D + 4 * g) * 4) : BUF_OOB;
+      const auto item = Win::item(it);
+      const int g = item.g, r = item.r, c = item.c;
+      const bool ok = win.goff[it] != BUF_OOB && 4 * g < pro.hc;
+      const unsigned off = ok ? win.goff[it] : BUF_OOB;
       const int c4 = min(4 * g, pro.hc - 4);
       const f32x4 fv = buf_load4(rf, off);
       const f32x4 gw = *(const f32x4*)(pro.gn_f + c4), gb = *(const f32x4*)(pro.gn_f + pro.hc + c4);
@@ -1147,7 +947,7 @@ __global__ __launch_bounds__(DUAL ? 512 : 256) void k_conv_dd_resident(ConvDDArg
       }
       xs[it] = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};           // zero padding / padding channels
       // the block's own pixels: the new state (and R)
-      if (pro.mode == GRU_PRO_OUT && ok && tid + it * NTHR < NITEMS && r >= 1 && r <= TR && c >= 1 && c <= 16) {
+      if (pro.mode == GRU_PRO_OUT && ok && item.own && r >= 1 && r <= TR && c >= 1 && c <= 16) {
         const size_t pix = ((size_t)n * a.hi + (iy0 + r)) * a.wi + (ix0 + c);
         *(f32x4*)(pro.state_out + pix * D + 4 * g) = xs[it];
         if (pro.R) *(f32x4*)(pro.R + pix * pro.RW + 4 * g) = xs[it];
@@ -1155,22 +955,12 @@ __global__ __launch_bounds__(DUAL ? 512 : 256) void k_conv_dd_resident(ConvDDArg
     }
   }
   if (a0.in2) {                                              // uniform: the layer convolves in + in2
-    const buf_rsrc rx2 = make_rsrc((const char*)a0.in2 + (((long)n * a.hi + iy0) * a.wi + ix0) * (long)D * 4);
+    f32x4 xs2[NIT];
+    win.request(xs2, Win::origin(a0.in2, n, a.hi, a.wi, D, iy0, ix0), 0);
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int i = min(tid + it * NTHR, NITEMS - 1);
-      const int g = i % KCT, pp = i / KCT, r = pp / LC, c = pp % LC;
-      const bool ok = (unsigned)(iy0 + r) < (unsigned)a.hi && (unsigned)(ix0 + c) < (unsigned)a.wi;
-      xs[it] += buf_load4(rx2, ok ? (unsigned)(((r * a.wi + c) * D + 4 * g) * 4) : BUF_OOB);
-    }
+    for (int it = 0; it < NIT; ++it) xs[it] += xs2[it];
   }
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int i = min(tid + it * NTHR, NITEMS - 1);
-    const int g = i % KCT, pp = i / KCT;
-    float* d = lds + 4 * g * PLANE + pp;
-    d[0] = xs[it].x; d[PLANE] = xs[it].y; d[2 * PLANE] = xs[it].z; d[3 * PLANE] = xs[it].w;
-  }
+  win.store(xs, lds);
   __syncthreads();
 
   f32x4 acc[NTR];
@@ -1192,19 +982,17 @@ __global__ __launch_bounds__(DUAL ? 512 : 256) void k_conv_dd_resident(ConvDDArg
     const int oy = r0 + wn * NTR + r, ox = c0 + p;
     if (oy >= a.ho || ox >= a.wo) continue;
     const size_t opix = ((size_t)n * a.ho + oy) * a.wo + ox;
-    f32x4 v = acc[r] + bias;
-    if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    f32x4 v = bias_act(acc[r], bias, a.relu);
     if (a.skip) v += *(const f32x4*)(a.skip + opix * D + co4);
     *(f32x4*)(a.out + opix * D + co4) = v;
   }
-  if (a.gn_part) {                                           // uniform
+  if (a.gn_part) {                                           // uniform: the stored values formed again (the same text: chunk_window.h says why)
     double gs = 0.0, gq = 0.0;
 #pragma unroll
     for (int r = 0; r < NTR; ++r) {
       const int oy = r0 + wn * NTR + r, ox = c0 + p;
       if (oy < a.ho && ox < a.wo && co4 < a.gn_n) {
-        f32x4 v = acc[r] + bias;
-        if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        f32x4 v = bias_act(acc[r], bias, a.relu);
         if (a.skip) v += *(const f32x4*)(a.skip + (((size_t)n * a.ho + oy) * a.wo + ox) * D + co4);
         gs += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
         gq += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
@@ -1284,62 +1072,31 @@ static int launch_conv_dd_z(const ConvDDArgs& a, int N, int mode, hipStream_t st
     const int rc = a.D == 32 ? launch_conv_dd_resident<32>(a, N, st) : launch_conv_dd_resident<64>(a, N, st);
     if (rc >= 0) return rc;
   }
-  switch (a.D) {
-    case 16: return launch_conv_dd_cfg<1, 1>(a, N, mode, st);
-    case 32: return launch_conv_dd_cfg<2, 1>(a, N, mode, st);
-    case 48: return launch_conv_dd_cfg<3, 1>(a, N, mode, st);
-    case 64: return launch_conv_dd_cfg<4, 1>(a, N, mode, st);
-    case 96: return launch_conv_dd_cfg<3, 2>(a, N, mode, st);
-    case 128: return launch_conv_dd_cfg<4, 2>(a, N, mode, st);
-    case 192: return launch_conv_dd_cfg<3, 4>(a, N, mode, st);
-    case 256:
-      // 16 output tiles per block need 256 accumulator registers: one wave per SIMD, which feeds the matrix pipe at 83 % (DESIGN
-      // section 4, lesson 2; measured 74.5 % of the fp32 MFMA peak for the whole network at cfg5 against 88.5 % at D = 192).  The
-      // 128-channel tiling (two waves per SIMD) run twice instead: the second launch sees the weights, bias, skip and output
-      // moved by 8 channel tiles and contracts over all 256 input channels like the first.  The softmax epilogue needs all the
-      // channels of a pixel in one workgroup and keeps the wide tiling.  ADAMVS_CONV256_SPLIT=0: the wide tiling everywhere.
-      // Measured at cfg5 (8 tiles): 291.9 -> 279.5 ms per step.
-      if (!a.sm_vw && conv256_split()) {
-        ConvDDArgs h = a;
-        for (int half = 0; half < 2; ++half) {
-          h.wpk = a.wpk + (size_t)half * 8 * 64;       // fragment index = (... * D/16 + tile) * 64 floats
-          h.bias = a.bias + half * 128;
-          h.out = a.out + half * 128;
-          h.skip = a.skip ? a.skip + half * 128 : nullptr;
-          if (int rc = launch_conv_dd_cfg<4, 2>(h, N, mode, st)) return rc;
-        }
-        return 0;
+  const WidthTiling* t = width_tiling(a.D, a.sm_vw != nullptr);
+  if (t) {
+    // No softmax epilogue where a width runs as several launches (it needs a pixel's channels in one workgroup): the scores go
+    // through the score volume to k_softmax_regress.
+    ADAMVS_CHECK_ARG(t->parts == 1 || !a.sm_vw, "conv_dd: no softmax epilogue at D=%d", a.D);
+    ConvDDArgs h = a;
+    for (int part = 0; part < t->parts; ++part) {
+      h.wpk = a.wpk + (size_t)part * (t->chunk / 16) * 64;       // fragment index = (... * D/16 + tile) * 64 floats
+      h.bias = a.bias + part * t->chunk;
+      h.out = a.out + part * t->chunk;
+      h.skip = a.skip ? a.skip + part * t->chunk : nullptr;
+      int rc = -1;
+      switch (t->MT * 10 + t->WM) {
+        case 11: rc = launch_conv_dd_cfg<1, 1>(h, N, mode, st); break;
+        case 21: rc = launch_conv_dd_cfg<2, 1>(h, N, mode, st); break;
+        case 31: rc = launch_conv_dd_cfg<3, 1>(h, N, mode, st); break;
+        case 41: rc = launch_conv_dd_cfg<4, 1>(h, N, mode, st); break;
+        case 32: rc = launch_conv_dd_cfg<3, 2>(h, N, mode, st); break;
+        case 42: rc = launch_conv_dd_cfg<4, 2>(h, N, mode, st); break;
+        case 34: rc = launch_conv_dd_cfg<3, 4>(h, N, mode, st); break;
+        case 44: rc = launch_conv_dd_cfg<4, 4>(h, N, mode, st); break;
       }
-      return launch_conv_dd_cfg<4, 4>(a, N, mode, st);
-    case 384: {
-      // the 192-channel tiling twice (as 256 = 2 x 128 above): each launch contracts over all 384 input channels into its half
-      // of the output channels.  No softmax epilogue at this width (it needs a pixel's channels in one workgroup): the scores
-      // go through the score volume to k_softmax_regress.
-      ADAMVS_CHECK_ARG(!a.sm_vw, "conv_dd: no softmax epilogue at D=384");
-      ConvDDArgs h = a;
-      for (int half = 0; half < 2; ++half) {
-        h.wpk = a.wpk + (size_t)half * 12 * 64;
-        h.bias = a.bias + half * 192;
-        h.out = a.out + half * 192;
-        h.skip = a.skip ? a.skip + half * 192 : nullptr;
-        if (int rc = launch_conv_dd_cfg<3, 4>(h, N, mode, st)) return rc;
-      }
-      return 0;
+      if (rc) return rc;
     }
-    case 512: {
-      // the 128-channel tiling four times (round 5; the class default of the reference is num_depth = 384, adamvs.py:538, and
-      // ndepths[0] is unconstrained): each launch contracts over all 512 input channels into its quarter of the output channels
-      ADAMVS_CHECK_ARG(!a.sm_vw, "conv_dd: no softmax epilogue at D=512");
-      ConvDDArgs h = a;
-      for (int part = 0; part < 4; ++part) {
-        h.wpk = a.wpk + (size_t)part * 8 * 64;
-        h.bias = a.bias + part * 128;
-        h.out = a.out + part * 128;
-        h.skip = a.skip ? a.skip + part * 128 : nullptr;
-        if (int rc = launch_conv_dd_cfg<4, 2>(h, N, mode, st)) return rc;
-      }
-      return 0;
-    }
+    return 0;
   }
   return set_error(-1, "cost_reg_net_2d: D=%d unsupported (16, 32, 48, 64, 96, 128, 192, 256, 384 or 512)", a.D);
 }
