@@ -2,6 +2,7 @@
 (tests/accuracy_ref.py).  The bar is the header's derived bound |d - d_fp64| <= 1e-6 c: the kept flags must agree outside
 |d - D| <= 1e-6 c, the indices unless the second-nearest target lies within 2e-6 c of the nearest, and each set-aside share is at
 most 1e-3.  Where every fp32 operation is exact (the hand-made input on a dyadic lattice) d2 and index are equal bit for bit.
+tests/test_cloud_edges_gpu.py holds the search at every slice and tile edge of its walk.
 
 Measured with the same inline functions on the host (adamvs_cloud_nearest_host, random clouds of test 2): largest |d - d_fp64| =
 0.126 of the bound, no query of 30 000 set aside at D or as a tie, 85.4 % within D, the fullest cell holds 14 targets."""

@@ -3,6 +3,7 @@
 both).  Where every fp32 operation is exact (the hand-made cloud on a dyadic lattice) d2, index and count equal the brute force
 bit for bit; on the random clouds the header's bound |d - d_fp64| <= 1e-6 c holds, with at most 1e-3 of the queries set aside
 at R or as ties; everywhere the device's bytes equal the host twin's.
+tests/test_cloud_edges_gpu.py holds the search at every slice, tile, pass and chunk edge.
 
 Measured on an MI355X (and, the bytes being equal, through the host twins): cloud T at k = 8: largest |d - d_fp64| = 0.135 of the
 bound, 0 queries at R and 9 ties set aside of 30 000; cloud Q at k = 16: 0.129 of the bound, 0 at R, 3 ties.  Normals against
