@@ -343,6 +343,11 @@ SIGNATURES = {
                                    ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
     "adamvs_ortho_finalize": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_ortho_observe": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.POINTER(OrthoView), ctypes.c_void_p, c_i,
+                                   ctypes.c_float, ctypes.c_float, ctypes.c_void_p, c_st]),
+    "adamvs_ortho_pair_stats": (c_i, [ctypes.c_void_p, c_i, ctypes.c_long, ctypes.c_void_p, c_i, c_i, ctypes.c_void_p, c_st]),
+    "adamvs_ortho_adjust_image": (c_i, [ctypes.c_void_p, c_i, c_i, ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, c_st]),
+    "adamvs_ortho_seam_stats": (c_i, [ctypes.POINTER(OrthoGrid), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_st]),
     "adamvs_texture_project": (c_i, [ctypes.POINTER(OrthoView), ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, c_st]),
     "adamvs_texture_zbuf": (c_i, [ctypes.POINTER(OrthoView), ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, c_st]),
@@ -443,6 +448,9 @@ ICP_TERMS = 32                   # ADAMVS_ICP_TERMS: sums of one accumulation of
 ORTHO_BEST, ORTHO_FEATHER = 0, 1 # ADAMVS_ORTHO_BEST / ADAMVS_ORTHO_FEATHER
 ORTHO_MAX_CELLS = 1 << 28        # ADAMVS_ORTHO_MAX_CELLS
 ORTHO_MAX_UPSAMPLE = 8           # ADAMVS_ORTHO_MAX_UPSAMPLE
+ORTHO_BAL_MAX_SAMPLES = 1 << 20  # ADAMVS_ORTHO_BAL_MAX_SAMPLES: most cells of the balance's observation lattice
+ORTHO_BAL_CHUNK = 8192           # ADAMVS_ORTHO_BAL_CHUNK: lattice cells per workgroup of the pair statistics
+ORTHO_BAL_MAX_Q = 16320          # ADAMVS_ORTHO_BAL_MAX_Q: 64 x 255, the largest quantised colour
 TEXTURE_TILE = 256               # ADAMVS_TEXTURE_TILE: faces per workgroup of the texture kernels
 TEXTURE_PAGES = (1024, 16384)    # ADAMVS_TEXTURE_MIN_PAGE, ADAMVS_TEXTURE_MAX_PAGE
 TEXTURE_MAX_FACES = (1 << 31) - 1 # ADAMVS_TEXTURE_MAX_FACES

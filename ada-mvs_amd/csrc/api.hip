@@ -1440,6 +1440,56 @@ extern "C" int adamvs_ortho_finalize(const adamvs_ortho_grid* grid, const float*
   return launch_ortho_finalize(*grid, acc, view_state, nvis, rgba, view_out, nvis_out, (hipStream_t)stream);
 }
 
+// ---- image orthophoto, radiometric balance (ortho_balance.hip): every argument is checked here, before any launch
+extern "C" int adamvs_ortho_observe(const adamvs_ortho_grid* grid, const float* dsm, const adamvs_ortho_view* view, const unsigned* zbuf,
+                                    int S, float border, float occlusion_tol, unsigned short* obs, void* stream) {
+  ADAMVS_CHECK_ARG(grid, "ortho_observe: null grid");
+  adamvs_ortho_grid g = *grid;
+  g.K = 1;                                                          // the lattice samples the DSM's own cells
+  if (int rc = ortho_check_grid(&g, "ortho_observe")) return rc;
+  if (int rc = ortho_check_view(view, "ortho_observe")) return rc;
+  ADAMVS_CHECK_ARG(dsm && zbuf && obs, "ortho_observe: null pointer");
+  ADAMVS_CHECK_ARG(S >= 1, "ortho_observe: stride S=%d (>= 1)", S);
+  const long ns = (long)((g.W + (long)S - 1) / S) * ((g.H + (long)S - 1) / S);
+  ADAMVS_CHECK_ARG(ns <= ADAMVS_ORTHO_BAL_MAX_SAMPLES, "ortho_observe: %ld lattice cells at S=%d exceed %ld", ns, S,
+                   (long)ADAMVS_ORTHO_BAL_MAX_SAMPLES);
+  ADAMVS_CHECK_ARG(std::isfinite(border) && border >= 0.f, "ortho_observe: border=%g (finite, >= 0)", (double)border);
+  ADAMVS_CHECK_ARG(std::isfinite(occlusion_tol) && occlusion_tol >= 0.f, "ortho_observe: occlusion_tol=%g (finite, >= 0)",
+                   (double)occlusion_tol);
+  return launch_ortho_observe(g, dsm, *view, zbuf, S, border, occlusion_tol, obs, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_ortho_pair_stats(const unsigned short* obs, int V, long N_s, const int* pairs, int P, int max_diff_q,
+                                       long long* stats, void* stream) {
+  ADAMVS_CHECK_ARG(V >= 1 && P >= 0, "ortho_pair_stats: V=%d (>= 1), P=%d (>= 0)", V, P);
+  ADAMVS_CHECK_ARG(N_s >= 1 && N_s <= ADAMVS_ORTHO_BAL_MAX_SAMPLES, "ortho_pair_stats: N_s=%ld (1 .. %ld)", N_s,
+                   (long)ADAMVS_ORTHO_BAL_MAX_SAMPLES);
+  ADAMVS_CHECK_ARG(max_diff_q >= 0 && max_diff_q <= ADAMVS_ORTHO_BAL_MAX_Q, "ortho_pair_stats: max_diff_q=%d (0 .. %d)", max_diff_q,
+                   ADAMVS_ORTHO_BAL_MAX_Q);
+  const long nchunk = (N_s + ADAMVS_ORTHO_BAL_CHUNK - 1) / ADAMVS_ORTHO_BAL_CHUNK;
+  ADAMVS_CHECK_ARG(nchunk * P < (1L << 31), "ortho_pair_stats: %d pairs of %ld chunks exceed 2^31 workgroups", P, nchunk);
+  if (P == 0) return 0;
+  ADAMVS_CHECK_ARG(obs && pairs && stats, "ortho_pair_stats: null pointer");
+  return launch_ortho_pair_stats(obs, N_s, pairs, P, max_diff_q, stats, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_ortho_adjust_image(const unsigned char* rgba_in, int H, int W, const float* gain, unsigned char* rgba_out,
+                                         void* stream) {
+  ADAMVS_CHECK_ARG(rgba_in && gain && rgba_out, "ortho_adjust_image: null pointer");
+  ADAMVS_CHECK_ARG(rgba_in != rgba_out, "ortho_adjust_image: rgba_out may not alias rgba_in");
+  ADAMVS_CHECK_ARG(H >= 1 && W >= 1 && (long)H * W <= ADAMVS_ORTHO_MAX_CELLS, "ortho_adjust_image: image %d x %d", H, W);
+  for (int k = 0; k < 3; ++k)
+    ADAMVS_CHECK_ARG(std::isfinite(gain[k]) && gain[k] > 0.f, "ortho_adjust_image: gain[%d]=%g (finite, > 0)", k, (double)gain[k]);
+  return launch_ortho_adjust_image(rgba_in, (long)H * W, gain, rgba_out, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_ortho_seam_stats(const adamvs_ortho_grid* grid, const int* view_out, const unsigned char* rgba, long long* stats,
+                                       void* stream) {
+  if (int rc = ortho_check_grid(grid, "ortho_seam_stats")) return rc;
+  ADAMVS_CHECK_ARG(view_out && rgba && stats, "ortho_seam_stats: null pointer");
+  return launch_ortho_seam_stats(*grid, view_out, rgba, stats, (hipStream_t)stream);
+}
+
 // ---- mesh texturing (texture.hip): every argument is checked here, before any launch
 static int texture_check_mesh(long nv, long nf, const char* what) {
   ADAMVS_CHECK_ARG(nv >= 1, "%s: nv=%ld (>= 1)", what, nv);

@@ -356,6 +356,15 @@ int launch_ortho_compose(const adamvs_ortho_grid& g, const adamvs_ortho_view& v,
 int launch_ortho_finalize(const adamvs_ortho_grid& g, const float* acc, const int* view, const int* nvis, uint8_t* rgba, int* view_out,
                           uint16_t* nvis_out, hipStream_t st);
 
+// ortho_balance.hip: per-view gains for the mosaic (include/adamvs_hip.h, "Image orthophoto: radiometric balance";
+// ortho_sample.h holds the visibility test and bilinear sample it shares with ortho.hip)
+constexpr int ORTHO_BAL_CHUNK = ADAMVS_ORTHO_BAL_CHUNK;
+int launch_ortho_observe(const adamvs_ortho_grid& g, const float* dsm, const adamvs_ortho_view& v, const unsigned* zbuf, int S, float border,
+                         float tol, uint16_t* obs, hipStream_t st);
+int launch_ortho_pair_stats(const uint16_t* obs, long Ns, const int* pairs, int P, int max_diff_q, long long* stats, hipStream_t st);
+int launch_ortho_adjust_image(const uint8_t* rgba_in, long npx, const float* gain, uint8_t* rgba_out, hipStream_t st);
+int launch_ortho_seam_stats(const adamvs_ortho_grid& g, const int* view_out, const uint8_t* rgba, long long* stats, hipStream_t st);
+
 // texture.hip: mesh texture from the source views (include/adamvs_hip.h, "Mesh texturing"; raster.h holds the rasteriser it
 // shares with ortho.hip)
 constexpr int TEX_TILE = ADAMVS_TEXTURE_TILE;

@@ -6,7 +6,8 @@
 //   k_ortho_zbuf_small   per view: one lane per DSM quad, its two triangles; a triangle whose pixel box holds at most
 //                        ORTHO_SMALL_PX pixel centres is rasterised by the lane, a larger one is appended to a list
 //   k_ortho_zbuf_large   per view: one wave per listed triangle, the lanes stride over its pixel box
-//   k_ortho_compose      per view: one lane per cell, visibility against the depth buffer and the cell's state update
+//   k_ortho_compose      per view: one lane per cell, visibility against the depth buffer and the cell's state update (the
+//                        visibility test and the bilinear sample are ortho_sample.h's, shared with ortho_balance.hip)
 //   k_ortho_finalize     once: RGBA, chosen view and visible-view count
 //
 // The only atomics are the depth buffer's 32-bit unsigned min on the bits of positive floats (order-independent) and the
@@ -15,6 +16,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "persistent.h"
+#include "ortho_sample.h"
 #include "raster.h"
 
 // The header states the arithmetic operation by operation: no contraction into fma in this file.
@@ -23,13 +25,6 @@
 namespace adamvs {
 
 static_assert(ORTHO_TILE == 256, "kernels below assume workgroups of four waves");
-
-struct OrthoArgs {
-  double x0, y_top, gsd;        // the DSM grid
-  int W, H, K;                  // DSM cells, upsample
-};
-
-static OrthoArgs ortho_args(const adamvs_ortho_grid& g) { return OrthoArgs{g.x0, g.y_top, g.gsd, g.W, g.H, g.K}; }
 
 // ---- surface --------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_ortho_surface(const OrthoArgs a, const float* __restrict__ dsm, double* __restrict__ height) {
@@ -134,26 +129,11 @@ __global__ __launch_bounds__(256) void k_ortho_compose(const OrthoArgs a, const 
   if (isnan(h)) return;
   const int i = (int)(n % Wo), j = (int)(n / Wo);
   const double g = a.gsd / (double)a.K;
-  const Proj p = project(c, a.x0 + ((double)i + 0.5) * g, a.y_top - ((double)j + 0.5) * g, h);
-  if (!(p.z > 0.f)) return;
-  const float umax = (float)(c.W - 1) - border, vmax = (float)(c.H - 1) - border;
-  if (!(p.u >= border && p.u <= umax && p.v >= border && p.v <= vmax)) return;       // NaN fails too
-  const int pu = (int)floorf(p.u + 0.5f), pv = (int)floorf(p.v + 0.5f);
-  const float zb = __uint_as_float(zbuf[(long)pv * c.W + pu]);
-  if (!(p.z <= zb + tol)) return;
+  Proj p;
+  if (!ortho_visible(c, zbuf, border, tol, a.x0 + ((double)i + 0.5) * g, a.y_top - ((double)j + 0.5) * g, h, p)) return;
   const float s = -p.dz / sqrtf(p.dx * p.dx + p.dy * p.dy + p.dz * p.dz);
-  // bilinear sample
-  const int xa = (int)floorf(p.u), ya = (int)floorf(p.v);
-  const float fx = p.u - (float)xa, fy = p.v - (float)ya;
-  const int xb = xa + 1 < c.W ? xa + 1 : c.W - 1, yb = ya + 1 < c.H ? ya + 1 : c.H - 1;
-  const unsigned p00 = *(const unsigned*)(rgba + 4 * ((long)ya * c.W + xa)), p10 = *(const unsigned*)(rgba + 4 * ((long)ya * c.W + xb));
-  const unsigned p01 = *(const unsigned*)(rgba + 4 * ((long)yb * c.W + xa)), p11 = *(const unsigned*)(rgba + 4 * ((long)yb * c.W + xb));
   float col[3];
-  for (int ch = 0; ch < 3; ++ch) {
-    const float c00 = (float)((p00 >> (8 * ch)) & 255u), c10 = (float)((p10 >> (8 * ch)) & 255u);
-    const float c01 = (float)((p01 >> (8 * ch)) & 255u), c11 = (float)((p11 >> (8 * ch)) & 255u);
-    col[ch] = (1.f - fy) * ((1.f - fx) * c00 + fx * c10) + fy * ((1.f - fx) * c01 + fx * c11);
-  }
+  ortho_bilinear(c, rgba, p, col);
   nvis[n] = nvis[n] + 1;
   if (FEATHER) {
     const float e = fminf(fminf(p.u, (float)(c.W - 1) - p.u), fminf(p.v, (float)(c.H - 1) - p.v));

@@ -1932,6 +1932,95 @@ def ortho_finalize(grid, acc, vstate, nvis):
     return rgba, view_out, nvis_out
 
 
+# ---- image orthophoto, radiometric balance (csrc/ortho_balance.hip; driven by ada_mvs_amd/ortho.py) --------------------------
+# obs is int16 holding uint16 (q_r, q_g, q_b, flag) per lattice cell; the statistics are int64.
+def ortho_lattice(grid, S):
+    """(W_s, H_s) of the observation lattice of stride S over the DSM grid; raises unless S >= 1 and N_s is within the cap."""
+    if isinstance(S, bool) or int(S) != S or int(S) < 1:
+        raise _lib.AdaMVSHipError("balance stride %r: an integer >= 1" % (S,))
+    S = int(S)
+    Ws, Hs = -(-int(grid.W) // S), -(-int(grid.H) // S)
+    if Ws * Hs > _lib.ORTHO_BAL_MAX_SAMPLES:
+        raise _lib.AdaMVSHipError("balance stride %d: %d x %d lattice cells exceed the cap of %d" % (S, Ws, Hs, _lib.ORTHO_BAL_MAX_SAMPLES))
+    return Ws, Hs
+
+
+def ortho_observe(grid, dsm, view, zbuf, S, border, occlusion_tol, obs):
+    """adamvs_ortho_observe: the view's samples on the lattice of stride S into obs (device int16 [N_s, 4], one plane)."""
+    dsm = _dev(dsm, "dsm")
+    zbuf = _dev_as(zbuf, "zbuf", torch.int32)
+    Ws, Hs = ortho_lattice(grid, S)
+    if tuple(dsm.shape) != (grid.H, grid.W) or zbuf.numel() != view.H * view.W:
+        raise _lib.AdaMVSHipError("ortho_observe: dsm %s, grid %d x %d, zbuf %d, image %d x %d"
+                                  % (tuple(dsm.shape), grid.H, grid.W, zbuf.numel(), view.H, view.W))
+    if (not isinstance(obs, torch.Tensor) or not obs.is_cuda or obs.dtype != torch.int16 or not obs.is_contiguous()
+            or tuple(obs.shape) != (Ws * Hs, 4)):
+        raise _lib.AdaMVSHipError("ortho_observe: obs must be a contiguous GPU int16 [%d, 4] (it is written in place)" % (Ws * Hs))
+    check(_lib.load().adamvs_ortho_observe(ctypes.byref(grid), _p(dsm), ctypes.byref(view), _p(zbuf), int(S), float(border),
+                                           float(occlusion_tol), _p(obs), _stream()), "ortho_observe")
+
+
+class OrthoPairs:
+    """Pairs of views checked on the host (0 <= a < b < V) and uploaded: .host int32 [P, 2], .dev the same on the device."""
+
+    def __init__(self, pairs, V, device):
+        host = pairs.cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+        host = host.reshape(-1, 2) if host.size == 0 else host
+        if host.ndim != 2 or host.shape[1] != 2 or (host.size and not np.issubdtype(host.dtype, np.integer)):
+            raise _lib.AdaMVSHipError("ortho_pair_stats: pairs must be an integer [P, 2], got %s %s" % (host.dtype, host.shape))
+        host = host.astype(np.int64)
+        bad = (host[:, 0] < 0) | (host[:, 0] >= host[:, 1]) | (host[:, 1] >= V)
+        if bad.any():
+            raise _lib.AdaMVSHipError("ortho_pair_stats: pair %s is not 0 <= a < b < V = %d" % (tuple(host[np.nonzero(bad)[0][0]]), V))
+        self.V, self.host = int(V), np.ascontiguousarray(host, np.int32)
+        self.dev = torch.from_numpy(self.host).to(device)
+
+
+def ortho_pair_stats(obs, pairs, max_diff_q):
+    """adamvs_ortho_pair_stats: obs device int16 [V, N_s, 4]; pairs [P, 2] (any integer array, or an OrthoPairs made for V views:
+    0 <= a < b < V is checked on the host, the kernel does not check it) -> stats device int64 [P, 7] = (n, Sa_0..2, Sb_0..2)."""
+    obs = _dev_as(obs, "obs", torch.int16)
+    if obs.dim() != 3 or obs.shape[2] != 4 or obs.shape[0] < 1 or obs.shape[1] < 1:
+        raise _lib.AdaMVSHipError("ortho_pair_stats: obs must be [V, N_s, 4], got %s" % (tuple(obs.shape),))
+    V, Ns = int(obs.shape[0]), int(obs.shape[1])
+    if not isinstance(pairs, OrthoPairs):
+        pairs = OrthoPairs(pairs, V, obs.device)
+    if pairs.V != V or pairs.dev.device != obs.device:
+        raise _lib.AdaMVSHipError("ortho_pair_stats: the pairs were checked for %d views on %s, obs has %d on %s"
+                                  % (pairs.V, pairs.dev.device, V, obs.device))
+    P = int(pairs.host.shape[0])
+    stats = torch.empty(P, 7, device=obs.device, dtype=torch.int64)
+    check(_lib.load().adamvs_ortho_pair_stats(_p(obs), V, Ns, _p(pairs.dev), P, int(max_diff_q), _p(stats), _stream()), "ortho_pair_stats")
+    return stats
+
+
+def ortho_adjust_image(rgba, gain, out=None):
+    """adamvs_ortho_adjust_image: rgba device [H, W, 4] uint8, gain [3] (host) -> the adjusted image (into `out` if given)."""
+    rgba = _dev_as(rgba, "rgba", torch.uint8)
+    if rgba.dim() != 3 or rgba.shape[2] != 4:
+        raise _lib.AdaMVSHipError("rgba must be [H, W, 4], got %s" % (tuple(rgba.shape),))
+    if out is None:
+        out = torch.empty_like(rgba)
+    elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous()
+          or out.shape != rgba.shape or out.data_ptr() == rgba.data_ptr()):
+        raise _lib.AdaMVSHipError("ortho_adjust_image: out must be another contiguous GPU uint8 tensor of the image's shape")
+    g = (ctypes.c_float * 3)(*[float(x) for x in np.asarray(gain, np.float64).reshape(3)])
+    check(_lib.load().adamvs_ortho_adjust_image(_p(rgba), int(rgba.shape[0]), int(rgba.shape[1]), g, _p(out), _stream()),
+          "ortho_adjust_image")
+    return out
+
+
+def ortho_seam_stats(grid, view_out, rgba):
+    """adamvs_ortho_seam_stats over the mosaic of ortho_finalize -> stats device int64 [4] = (pairs, sum d_r^2, d_g^2, d_b^2)."""
+    view_out, rgba = _dev_as(view_out, "view", torch.int32), _dev_as(rgba, "rgba", torch.uint8)
+    n = grid.H * grid.K * grid.W * grid.K
+    if view_out.numel() != n or rgba.numel() != 4 * n:
+        raise _lib.AdaMVSHipError("ortho_seam_stats: sizes do not match %d cells" % n)
+    stats = torch.empty(4, device=rgba.device, dtype=torch.int64)
+    check(_lib.load().adamvs_ortho_seam_stats(ctypes.byref(grid), _p(view_out), _p(rgba), _p(stats), _stream()), "ortho_seam_stats")
+    return stats
+
+
 # ---- mesh texturing (csrc/texture.hip; driven by ada_mvs_amd/texture.py) ------------------------------------------------------
 # Views are _lib.OrthoView (ortho_view above).  faces: device int32 [nf, 3] holding uint32 indices; the depth buffer is int32
 # holding uint32 float bits; every per-face state tensor is updated in place and must be contiguous.

@@ -1802,6 +1802,54 @@ int adamvs_ortho_compose(const adamvs_ortho_grid* grid, const adamvs_ortho_view*
 int adamvs_ortho_finalize(const adamvs_ortho_grid* grid, const float* acc, const int* view_state, const int* nvis, unsigned char* rgba,
                           int* view_out, unsigned short* nvis_out, void* stream);
 
+/* ---- Image orthophoto: radiometric balance (ortho_whu.py --balance gain) ---------------------------------------------------
+ * ada-mvs_amd/ortho.py drives it.  One gain per view and channel, from the pairwise statistics of the views over the cells
+ * they both see (the block adjustment of Brown & Lowe 2007; OpenCV's GainCompensator); the V x V solve is the host's.  Every
+ * device result of this section is an integer.
+ *
+ * Observation lattice.  For a stride S (integer >= 1) the lattice is the DSM cells (a S, b S), a < W_s = ceil(W / S),
+ * b < H_s = ceil(H / S); N_s = W_s H_s <= ADAMVS_ORTHO_BAL_MAX_SAMPLES = 2^20; lattice cell (a, b) is entry b W_s + a.  Its
+ * sample is the K = 1 sample of DSM cell (a S, b S): x = x0 + (a S + 1/2) gsd, y = y_top - (b S + 1/2) gsd, height
+ * dsm[b S][a S] as fp64 (not finite: no surface).  No height array is needed, and the balance does not depend on the upsample.
+ *
+ * adamvs_ortho_observe, per view: one lane per lattice cell; grid.K is ignored.  obs [N_s][4] uint16 (8-byte aligned) is written
+ * completely by the call.  Where the sample is visible in the view, by exactly the visibility rule of "Image orthophoto" (zbuf
+ * is the view's buffer from adamvs_ortho_zbuf), with c its bilinear sample:  obs = (q_r, q_g, q_b, 1),
+ * q_k = floor(64 c_k + 1/2) in fp32 (64 c_k is exact; at most 16320).  Elsewhere obs = (0, 0, 0, 0).
+ *
+ * adamvs_ortho_pair_stats: obs [V][N_s][4] uint16 (the views' planes, 8-byte aligned), pairs [P][2] int32 (device) with
+ * 0 <= a < b < V (NOT checked on the device: the caller checks them), stats [P][7] int64, zeroed by the call with a kernel.
+ * For pair p = (a, b), over every lattice cell where both flags are 1 and |q_a,k - q_b,k| <= max_diff_q for k = 0, 1, 2:
+ * n += 1, Sa_k += q_a,k, Sb_k += q_b,k; the layout is (n, Sa_0, Sa_1, Sa_2, Sb_0, Sb_1, Sb_2).  All sums are integers (at most
+ * 2^20 x 16320 < 2^34) and are added with integer atomics, so the result does not depend on the order of the reduction: it is
+ * bit-identical from run to run and equal to any exact restatement.  One workgroup per (chunk of ADAMVS_ORTHO_BAL_CHUNK lattice
+ * cells, pair), P ceil(N_s / chunk) < 2^31 of them; it adds its seven sums with one 64-bit atomic each.  P = 0 returns 0
+ * without a launch (and before the pointers are looked at).
+ *
+ * adamvs_ortho_adjust_image: rgba_in, rgba_out [H][W][4] uint8 (device; they may not alias), gain [3] a HOST pointer.  One lane
+ * per pixel:  out_k = min(255, floor(gain_k * (float)in_k + 0.5f)) for k = 0 .. 2 (one fp32 product, one fp32 sum, no
+ * contraction); alpha is copied.
+ *
+ * adamvs_ortho_seam_stats: over the W_o x H_o mosaic adamvs_ortho_finalize wrote (view_out [N] int32, rgba [N][4] uint8), every
+ * horizontally and every vertically adjacent pair of cells with both view_out >= 0 and different views:  stats[0] += 1,
+ * stats[1 + k] += d_k d_k with d_k the integer difference of channel k.  stats [4] int64, zeroed by the call; integer atomics,
+ * one set per workgroup.  The rms colour step across seams is sqrt((s1 + s2 + s3) / (3 s0)).
+ *
+ * Argument errors (<0, before any launch), beyond those of the calls above: S < 1 or N_s > ADAMVS_ORTHO_BAL_MAX_SAMPLES;
+ * V < 1, N_s < 1 or N_s over the cap, P < 0 or 2^31 workgroups or more; max_diff_q outside 0 .. ADAMVS_ORTHO_BAL_MAX_Q; a gain
+ * that is not finite or <= 0; H or W < 1 (H W at most ADAMVS_ORTHO_MAX_CELLS); a null pointer; rgba_out == rgba_in. */
+#define ADAMVS_ORTHO_BAL_MAX_SAMPLES (1L << 20)
+#define ADAMVS_ORTHO_BAL_CHUNK 8192
+#define ADAMVS_ORTHO_BAL_MAX_Q 16320
+
+int adamvs_ortho_observe(const adamvs_ortho_grid* grid, const float* dsm, const adamvs_ortho_view* view, const unsigned* zbuf, int S,
+                         float border, float occlusion_tol, unsigned short* obs, void* stream);
+int adamvs_ortho_pair_stats(const unsigned short* obs, int V, long N_s, const int* pairs, int P, int max_diff_q, long long* stats,
+                            void* stream);
+int adamvs_ortho_adjust_image(const unsigned char* rgba_in, int H, int W, const float* gain, unsigned char* rgba_out, void* stream);
+int adamvs_ortho_seam_stats(const adamvs_ortho_grid* grid, const int* view_out, const unsigned char* rgba, long long* stats,
+                            void* stream);
+
 /* ---- Mesh texturing (after mesh_whu.py): a triangle mesh textured from the source images ----------------------------------
  * ada-mvs_amd/texture.py drives it; texture_whu.py is the CLI.  Views are adamvs_ortho_view structs (a HOST pointer, copied into the
  * arguments; projection exactly as "Image orthophoto" states it).  Mesh: xyz [nv][3] fp64 (device), faces [nf][3] uint32,

@@ -1,11 +1,16 @@
 """Image orthophoto timing (csrc/ortho.hip): z-buffers and compose for the 5-view scene over an analytic DSM.
-    python tools/ortho_bench.py [--H 2752 --W 1856] [--gsd 0.16] [--steps 3] [--crop 192]
+    python tools/ortho_bench.py [--H 2752 --W 1856] [--gsd 0.16] [--steps 3] [--crop 192] [--balance 1]
 The 5-view scene of tools/fusion_bench.py (ada_mvs_amd/fusion_synth.py: one nadir and four 40-degree obliques) with images
 textured by world position and face class (tests/ortho_scene.py), and its DSM cast analytically at gsd (the DSM is this
 step's input).  Per (K, mode) in {1, 2} x {best, feather}: one warm-up run, then `steps` timed runs of OrthoBuilder over all
 views; device events around each view's z-buffer and compose (the medians of their sums are reported), and the host round
 trip of ortho.from_dsm (host DSM in, host rasters out).  The byte model below is priced against 6.3 TB/s.  The CPU baseline is
 the numpy restatement (tests/ortho_ref.py) on a crop of crop x crop DSM cells, scaled to the whole grid.  One JSON line.
+
+--balance 1 adds a `balance` block: the images scaled by the exposures 0.85, 1.10, 1.00, 0.92, 1.18, then in one run the K = 1
+`best` mosaic without the option (the yardstick: device_ms and its seam_rms) and with --balance gain (the whole stage, the
+observe and pair_stats passes by device events, P, N_s, the bytes 16 P N_s pair_stats reads and their rate next to the
+6.3 TB/s copy rate, and the seam_rms of the balanced mosaic).
 """
 import argparse
 import json
@@ -35,6 +40,76 @@ def model_bytes(W, H, K, img_px, covered_px):
     return sum(per_view) + n * (28 + 10) + 4 * W * H + 8 * n
 
 
+BALANCE_EXPOSURES = (0.85, 1.10, 1.00, 0.92, 1.18)
+
+
+def pair_stats_ms(ortho, views, z, g, stride, max_diff_q, reps=50):
+    """adamvs_ortho_pair_stats alone on the scene's observations: the mean of `reps` back-to-back calls between two device
+    events (each call zeroes its sums and reduces every candidate pair), after a warm-up call."""
+    import torch
+    from ada_mvs_amd import hip_ops
+    b = ortho.OrthoBuilder(g, 1, "best", z)
+    Ws, Hs = ortho.lattice_shape(g, stride)
+    obs = torch.zeros(len(views), Ws * Hs, 4, device=b.device, dtype=torch.int16)
+    for k, view in enumerate(views):
+        if b.sees(view):
+            v, zbuf = b.view_zbuf(view)
+            hip_ops.ortho_observe(b.cgrid, b.dsm, v, zbuf, stride, b.border_px, b.occlusion_tol, obs[k])
+    pairs = hip_ops.OrthoPairs(ortho.candidate_pairs(obs), len(views), b.device)
+    first = hip_ops.ortho_pair_stats(obs, pairs, max_diff_q)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        stats = hip_ops.ortho_pair_stats(obs, pairs, max_diff_q)
+    e1.record()
+    torch.cuda.synchronize()
+    assert torch.equal(first, stats)
+    return e0.elapsed_time(e1) / reps
+
+
+def balance_block(ortho, views, z, g, steps):
+    """The K = 1 `best` mosaic of exposure-scaled images without and with --balance gain, in the same run."""
+    import torch
+    scaled = []
+    for v, gam in zip(views, BALANCE_EXPOSURES):
+        img = v["rgba"].to(torch.float32)
+        img[..., :3] = torch.clamp(torch.floor(gam * img[..., :3] + 0.5), 0.0, 255.0)
+        scaled.append(dict(v, rgba=img.to(torch.uint8).contiguous()))
+    plain_ms, stage_ms, obs_ms, pair_ms, adj_ms, wall_plain, wall_bal = [], [], [], [], [], [], []
+    for step in range(steps + 1):
+        torch.cuda.synchronize()
+        t1 = time.time()
+        plain = ortho.from_dsm(z, g, scaled, 1, "best")
+        torch.cuda.synchronize()
+        t2 = time.time()
+        bal = ortho.from_dsm(z, g, scaled, 1, "best", balance="gain")
+        torch.cuda.synchronize()
+        t3 = time.time()
+        if step == 0:
+            continue
+        b = bal["balance"]
+        plain_ms.append(plain["device_seconds"] * 1e3)
+        obs_ms.append(b["observe_seconds"] * 1e3)
+        pair_ms.append(b["pair_stats_seconds"] * 1e3)
+        adj_ms.append(b["adjust_seconds"] * 1e3)
+        stage_ms.append((bal["device_seconds"] + b["observe_seconds"] + b["pair_stats_seconds"] + b["adjust_seconds"]) * 1e3)
+        wall_plain.append((t2 - t1) * 1e3)
+        wall_bal.append((t3 - t2) * 1e3)
+    b = bal["balance"]
+    P, Ns = b["pairs_candidate"], b["samples"]
+    pair = pair_stats_ms(ortho, scaled, z, g, b["stride"], b["max_diff_q"])
+    nbytes = 16 * P * Ns
+    return dict(exposures=list(BALANCE_EXPOSURES), stride=b["stride"], N_s=Ns, P=P, pairs_used=b["pairs_used"],
+                pair_stats_in_stage_ms=round(float(np.median(pair_ms)), 4),
+                plain_device_ms=round(float(np.median(plain_ms)), 3), plain_roundtrip_ms=round(float(np.median(wall_plain)), 1),
+                balanced_device_ms=round(float(np.median(stage_ms)), 3), balanced_roundtrip_ms=round(float(np.median(wall_bal)), 1),
+                observe_ms=round(float(np.median(obs_ms)), 3), pair_stats_ms=round(pair, 4), adjust_ms=round(float(np.median(adj_ms)), 3),
+                pair_stats_mb=round(nbytes / 1e6, 2), pair_stats_tbs=round(nbytes / (pair * 1e9), 3) if pair > 0 else None,
+                copy_rate_tbs=HBM_GBS / 1e3, gains=b["gains"], overlap_rms_before=b["overlap_rms_before"],
+                overlap_rms_after=b["overlap_rms_after"], seam_rms_plain=round(ortho.seam_rms(plain)[0], 3),
+                seam_rms_balanced=round(b["seam_rms"], 3), seam_pairs=b["seam_pairs"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--H", type=int, default=2752)
@@ -42,6 +117,7 @@ def main():
     ap.add_argument("--gsd", type=float, default=0.16)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--crop", type=int, default=192)
+    ap.add_argument("--balance", type=int, default=0, help="1: also time the mosaic with --balance gain on exposure-scaled images")
     args = ap.parse_args()
     import torch
     from ada_mvs_amd import ortho
@@ -86,6 +162,8 @@ def main():
                                     device_ms=round(dev_ms, 3), roundtrip_ms=round(float(np.median(rts)), 1),
                                     model_mb=round(nbytes / 1e6, 1), model_ms_at_hbm=round(nbytes / (HBM_GBS * 1e6), 3),
                                     cells_coloured=coloured))
+    if args.balance:
+        res["balance"] = balance_block(ortho, views, z, g, args.steps)
     # CPU baseline: the restatement on a crop, scaled by cells
     c = args.crop
     zc = np.ascontiguousarray(z[H // 2 - c // 2:H // 2 + c // 2, W // 2 - c // 2:W // 2 + c // 2])
