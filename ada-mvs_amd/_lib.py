@@ -163,6 +163,12 @@ SIGNATURES = {
     "adamvs_depth_stage_workspace_bytes": (c_sz, [ctypes.POINTER(StageDesc)]),
     "adamvs_recurrence_schedule": (c_i, [c_i, ctypes.c_longlong]),
     "adamvs_conv_t2_form": (c_i, [c_i, c_i, c_i, c_i]),
+    "adamvs_conv_wino24_fold": (c_i, [c_i, c_i, c_i]),
+    "adamvs_conv_s2_form": (c_i, [c_i, c_i, c_i, c_i, c_i]),
+    "adamvs_conv3x3_dd_wino24_blocks": (c_i, [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "adamvs_conv3x3_dd_s2_blocks": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "adamvs_cost_reg_net_2d_blocks": (c_i, [c_f, c_f, c_sz, c_f, c_i, c_i, c_i, c_i, c_i, ctypes.c_void_p, c_sz, c_st]),
+    "adamvs_cost_reg_fold": (c_i, [c_i, c_i, c_i, c_i]),
     "adamvs_gru_wino_mask": (c_i, []),
     "adamvs_depth_stage_forward": (c_i, [ctypes.POINTER(StageDesc), c_f, c_f, c_f, c_f, c_f, c_sz, ctypes.POINTER(FuseWeights),
                                          c_f, c_f, c_f, c_f, c_i, ctypes.c_void_p, c_sz, c_st]),

@@ -404,17 +404,34 @@ __device__ __forceinline__ void conv_dd_t2_fused(const ConvDDArgs& a, float* lds
 // two differences (2 vector instructions per 15 MFMAs) and W0 + W2 once per chunk from the fragments it streams anyway (9 adds):
 // the blob keeps its nine taps.  Block = 3 output rows x 32 columns x all channels: three accumulator sets of 3 x 3 tiles = 108
 // registers, two waves per SIMD as in conv_dd_body; one k-step per chunk, chunks double-buffered the same way.
+//
+// FOLD = F: the 16 columns of an MFMA are 16 / F output pairs of each of F row groups -- lane p holds pair
+// p % (16 / F) of the output rows (p / (16 / F)) 3 + r -- so a block is 3 F output rows x 32 / F columns with the same accumulators,
+// fragments and MFMAs, and per output the same sums in the same order: conv3's 24 x 48 outputs are blocks of 6 x 16 (F = 2), conv5's
+// 12 x 24 blocks of 12 x 8 (F = 4), where the 32-column block pads a row by a third and the layer stayed on the direct kernel.
+// The window's row pitch and plane pitch put the 16 lanes of every ds_read_b128 group on 16 different bank quadruples (row groups
+// 6 LC floats apart: LC = 48 gives 8 quadruples (mod 16) for F = 2, LC = 24 gives 4 for F = 4; planes a multiple of 64 floats).
 constexpr int S2P_ROWS = 3;      // output rows per block (4: 144 accumulator registers next to 63 of fragments: spills; the hourglass's 48 / 24 / 12 rows divide by 3)
-template <int MT, int WM>
+template <int FOLD>
+struct S2PGeom {
+  static_assert(FOLD == 1 || FOLD == 2 || FOLD == 4, "16 / FOLD pairs of FOLD row groups");
+  static constexpr int BR = S2P_ROWS, PPR = 16 / FOLD, BC = 2 * PPR;              // pairs per row, output columns per block
+  static constexpr int LR = 2 * BR * FOLD + 1, WCOLS = 2 * BC + 1, LC = FOLD == 1 ? 68 : (FOLD == 2 ? 48 : 24);
+  static constexpr int PLANE = FOLD == 1 ? ((LR * LC + 31) / 32) * 32 + 16 : ((LR * LC + 63) / 64) * 64;
+  static_assert(LC >= WCOLS && LC % 4 == 0 && PLANE >= LR * LC, "16-byte reads at column 4 p of a row");
+};
+template <int MT, int WM, int FOLD = 1>
 __device__ __forceinline__ void conv_dd_s2_pairs(const ConvDDArgs& a, float* lds, int n, int by, int bx) {
   static_assert(WM == 4, "every wave takes all rows of the block");
-  constexpr int BR = S2P_ROWS, LR = 2 * BR + 1, WCOLS = 65, LC = 68, PLANE = ((LR * LC + 31) / 32) * 32 + 16;
+  using G = S2PGeom<FOLD>;
+  constexpr int BR = G::BR, LR = G::LR, WCOLS = G::WCOLS, LC = G::LC, PLANE = G::PLANE;
   using Win = ChunkWindow<LR, WCOLS, LC, 1, PLANE, 4 * PLANE>;     // one channel group per chunk
   constexpr int NITA = Win::N;
   const int tid = threadIdx.x, lane = tid & 63, wm = __builtin_amdgcn_readfirstlane(tid >> 6);    // wave = channel slice
   const int p = lane & 15, q = lane >> 4;
   const int D = a.D, KCT = D / 4, NTILES = D / 16;
-  const int r0 = by * BR, c0 = bx * 32;
+  const int fr = FOLD == 1 ? 0 : p / G::PPR, fp = FOLD == 1 ? p : p % G::PPR;   // the lane's row group and pair of the row
+  const int r0 = by * BR * FOLD, c0 = bx * G::BC;
   const int iy0 = 2 * r0 - 1, ix0 = 2 * c0 - 1;
 
   const buf_rsrc rx = Win::origin(a.in, n, a.hi, a.wi, D, iy0, ix0);
@@ -423,7 +440,7 @@ __device__ __forceinline__ void conv_dd_s2_pairs(const ConvDDArgs& a, float* lds
   const buf_rsrc rw = make_rsrc(a.wpk);
   unsigned woff = (unsigned)(lane * 4);
   pin(woff);
-  unsigned xb = (unsigned)((q * PLANE + 4 * p) * 4);           // the lane's k-row and first window column of its pair
+  unsigned xb = (unsigned)((q * PLANE + 2 * BR * fr * LC + 4 * fp) * 4);   // the lane's k-row, first window row of its row group and first column of its pair
   pin(xb);
 
   f32x4 acc[3][MT][BR];                                        // A0 | A1 | A2
@@ -476,7 +493,7 @@ __device__ __forceinline__ void conv_dd_s2_pairs(const ConvDDArgs& a, float* lds
   // epilogue: lane owns channels co4 .. co4 + 3 of the output pair (c0 + 2 p, c0 + 2 p + 1) of every row
 #pragma unroll
   for (int r = 0; r < BR; ++r) {
-    const int oy = r0 + r, ox = c0 + 2 * p;
+    const int oy = r0 + fr * BR + r, ox = c0 + 2 * fp;
     if (oy >= a.ho || ox >= a.wo) continue;
     const size_t opix = ((size_t)n * a.ho + oy) * a.wo + ox;
 #pragma unroll
@@ -490,11 +507,11 @@ __device__ __forceinline__ void conv_dd_s2_pairs(const ConvDDArgs& a, float* lds
   }
 }
 
-// grid: (ceil(wo/32), ceil(ho/S2P_ROWS), N); block 256
-template <int MT, int WM>
+// grid: (ceil(wo / (32 / FOLD)), ceil(ho / (S2P_ROWS FOLD)), N); block 256
+template <int MT, int WM, int FOLD = 1>
 __global__ __launch_bounds__(256, 2) void k_conv_dd_s2p(ConvDDArgs a) {
-  __shared__ __attribute__((aligned(16))) float lds[4 * ((((2 * S2P_ROWS + 1) * 68 + 31) / 32) * 32 + 16)];
-  conv_dd_s2_pairs<MT, WM>(a, lds, blockIdx.z, blockIdx.y, blockIdx.x);
+  __shared__ __attribute__((aligned(16))) float lds[4 * S2PGeom<FOLD>::PLANE];
+  conv_dd_s2_pairs<MT, WM, FOLD>(a, lds, blockIdx.z, blockIdx.y, blockIdx.x);
 }
 
 // Transposed layer (conv7, conv9, conv11 of the hourglass) with the same minimal-filtering form along x.  The odd output columns of a
@@ -751,6 +768,20 @@ static bool conv256_split() { return opt(OPT_CONV256_SPLIT) != 0; }
 // and conv7 (24: less than a block) no; cfg5: conv11 (192) and conv9 (96).  Odd widths would split a pair at the border.
 constexpr int T2P_NR = 2, T2P_KB1 = 8, T2P_KB0 = 8;      // input rows per block; input channels per chunk of the odd- / even-row class
 static bool t2_pairs_pay(int wi) { return wi % 2 == 0 && wi >= T2P_COLS && 5 * 2 * cdiv(wi, T2P_COLS) < 6 * cdiv(wi, 16); }
+// Which blocks the stride-2 pair form takes for ho x wo outputs: 1 = 3 rows x 32 columns (where a row divides into them, or from 256
+// columns), 2 / 4 = the folded blocks of 6 x 16 / 12 x 8 where the 32-column block does not fit and these tile the map exactly
+// (blocks = -1, what every caller but the A/B entry points passes; 2 / 4: that fold wherever the width is a multiple of its block's,
+// any height; 0: the selection of before, no folded blocks), 0 = none: the direct kernel.
+static int s2_pairs_fold(int ho, int wo, int blocks) {
+  if (!s2_pairs()) return 0;
+  if (blocks == -1 && (opt(OPT_WINOGRAD) & 4)) blocks = 0;   // option winograd + 4: no folded blocks in any layer (A/B of the whole pipeline)
+  if ((blocks == 2 || blocks == 4) && wo % (32 / blocks) == 0) return blocks;
+  if (wo % 32 == 0 || wo >= 256) return 1;
+  if (blocks != -1) return 0;
+  if (wo % 16 == 0 && ho % (2 * S2P_ROWS) == 0) return 2;
+  if (wo % 8 == 0 && ho % (4 * S2P_ROWS) == 0) return 4;
+  return 0;
+}
 static int t2_form(int MT, int WM, int N, int hi, int wi) {
   if (WM >= 2 && t2_fused((long)cdiv(wi, 16) * cdiv(hi, 8) * N)) return 1;
   if (MT == 3 && WM == 4 && s2_pairs() && t2_pairs_pay(wi)) return 2;
@@ -784,13 +815,22 @@ static const WidthTiling* width_tiling(int D, bool softmax_epilogue) {
     if (t.D == D) return &t;
   return nullptr;
 }
+// Which kernel a stride-2 layer without skip or second input takes (adamvs_conv_s2_form): 0 a direct kernel (8-row blocks, or 2-row
+// blocks on a small grid), 1 / 2 / 4 the pair form on blocks of 3 x 32, 6 x 16, 12 x 8 outputs (s2_pairs_fold)
+static int conv_s2_form(int N, int D, int hi, int wi, int blocks) {
+  const WidthTiling* t = width_tiling(D, false);
+  if (!t) return -1;
+  const int ho = hi / 2, wo = wi / 2;
+  if (t->WM >= 2 && small_grid_rows2((long)cdiv(wo, 16) * cdiv(ho, 8) * N)) return 0;
+  return t->MT == 3 && t->WM == 4 ? s2_pairs_fold(ho, wo, blocks) : 0;
+}
 static int conv_t2_form(int N, int D, int hi, int wi) {
   const WidthTiling* t = width_tiling(D, false);
   return t ? t2_form(t->MT, t->WM, N, hi, wi) : -1;
 }
 
 template <int MT, int WM>
-static int launch_conv_dd_cfg(const ConvDDArgs& a_, int N, int mode, hipStream_t st) {
+static int launch_conv_dd_cfg(const ConvDDArgs& a_, int N, int mode, hipStream_t st, int s2_blocks) {
   const ConvDDArgs& a = a_;
   constexpr int KB = (WM == 4 || (MT == 4 && WM == 2)) ? 4 : 8;
   const bool rows2 = WM >= 2 && mode != CONV_T2 && small_grid_rows2((long)cdiv(a.wo, 16) * cdiv(a.ho, 8) * N);
@@ -811,8 +851,13 @@ static int launch_conv_dd_cfg(const ConvDDArgs& a_, int N, int mode, hipStream_t
     hipLaunchKernelGGL((k_conv_dd<MT, WM, CONV_S1, KB>), dim3(cdiv(a.wo, 16), cdiv(a.ho, 8), N), dim3(256), 0, st, a);
   // D = 192 (and 384 as two launches): 15 / 18 of the products.  Blocks are 32 output columns wide: taken where a row divides into
   // them (cfg2 at 128 tiles: conv1, 48 x 96 outputs, 11.47 -> 10.10 ms; conv3, 24 x 48 -- a block and a half per row -- 2.88 -> 3.31)
-  else if (mode == CONV_S2 && MT == 3 && WM == 4 && !a.skip && !a.in2 && (a.wo % 32 == 0 || a.wo >= 256) && s2_pairs())
+  else if (mode == CONV_S2 && MT == 3 && WM == 4 && !a.skip && !a.in2 && s2_pairs_fold(a.ho, a.wo, s2_blocks) == 1)
     hipLaunchKernelGGL((k_conv_dd_s2p<MT, (WM == 4 ? 4 : 4)>), dim3(cdiv(a.wo, 32), cdiv(a.ho, S2P_ROWS), N), dim3(256), 0, st, a);
+  // ... and on the folded blocks where those tile the map and the 32-column block does not (cfg2: conv3 on 6 x 16, conv5 on 12 x 8)
+  else if (mode == CONV_S2 && MT == 3 && WM == 4 && !a.skip && !a.in2 && s2_pairs_fold(a.ho, a.wo, s2_blocks) == 2)
+    hipLaunchKernelGGL((k_conv_dd_s2p<MT, (WM == 4 ? 4 : 4), 2>), dim3(cdiv(a.wo, 16), cdiv(a.ho, 2 * S2P_ROWS), N), dim3(256), 0, st, a);
+  else if (mode == CONV_S2 && MT == 3 && WM == 4 && !a.skip && !a.in2 && s2_pairs_fold(a.ho, a.wo, s2_blocks) == 4)
+    hipLaunchKernelGGL((k_conv_dd_s2p<MT, (WM == 4 ? 4 : 4), 4>), dim3(cdiv(a.wo, 8), cdiv(a.ho, 4 * S2P_ROWS), N), dim3(256), 0, st, a);
   else if (mode == CONV_S2)
     hipLaunchKernelGGL((k_conv_dd<MT, WM, CONV_S2, KB>), dim3(cdiv(a.wo, 16), cdiv(a.ho, 8), N), dim3(256), 0, st, a);
   else if (WM >= 2 && t2_form(MT, WM, N, a.hi, a.wi) == 1)      // small grids: 2-row blocks, all classes per chunk
@@ -1043,13 +1088,14 @@ static int launch_conv_dd_resident(const ConvDDArgs& a, int N, hipStream_t st) {
   return -1;
 }
 
-static int launch_conv_dd_z(const ConvDDArgs& a, int N, int mode, hipStream_t st);
+static int launch_conv_dd_z(const ConvDDArgs& a, int N, int mode, hipStream_t st, int s2_blocks);
 
 // The kernels below take the image index from blockIdx.z (at most 65535): more images run as several launches over
 // sub-batches, every pointer moved by whole images (the softmax epilogue's tile index is n % sm_B: sub-batches of whole tiles).
-static int launch_conv_dd(const ConvDDArgs& a, int N, int mode, hipStream_t st) {
+// s2_blocks: the blocks of the stride-2 pair form (s2_pairs_fold; -1 by the map)
+static int launch_conv_dd(const ConvDDArgs& a, int N, int mode, hipStream_t st, int s2_blocks = -1) {
   constexpr int ZMAX = 65535;
-  if (N <= ZMAX) return launch_conv_dd_z(a, N, mode, st);
+  if (N <= ZMAX) return launch_conv_dd_z(a, N, mode, st, s2_blocks);
   ADAMVS_CHECK_ARG(!a.gn_part, "conv_dd: GroupNorm partials with N=%d images (at most %d)", N, ZMAX);
   const int unit = a.sm_vw ? a.sm_B : 1;
   ADAMVS_CHECK_ARG(unit <= ZMAX, "conv_dd: softmax epilogue with %d tiles per view (at most %d)", unit, ZMAX);
@@ -1062,12 +1108,12 @@ static int launch_conv_dd(const ConvDDArgs& a, int N, int mode, hipStream_t st) 
     if (a.out) b.out = a.out + n0 * out_img;
     if (a.skip) b.skip = a.skip + n0 * out_img;
     if (a.sm_vw) { b.sm_vw = a.sm_vw + n0 * map; b.sm_pd = a.sm_pd + n0 * map; }
-    if (int rc = launch_conv_dd_z(b, N - n0 < step ? N - n0 : step, mode, st)) return rc;
+    if (int rc = launch_conv_dd_z(b, N - n0 < step ? N - n0 : step, mode, st, s2_blocks)) return rc;
   }
   return 0;
 }
 
-static int launch_conv_dd_z(const ConvDDArgs& a, int N, int mode, hipStream_t st) {
+static int launch_conv_dd_z(const ConvDDArgs& a, int N, int mode, hipStream_t st, int s2_blocks) {
   if (mode == CONV_S1 && (a.D == 32 || a.D == 64) && !a.sm_vw) {
     const int rc = a.D == 32 ? launch_conv_dd_resident<32>(a, N, st) : launch_conv_dd_resident<64>(a, N, st);
     if (rc >= 0) return rc;
@@ -1085,14 +1131,14 @@ static int launch_conv_dd_z(const ConvDDArgs& a, int N, int mode, hipStream_t st
       h.skip = a.skip ? a.skip + part * t->chunk : nullptr;
       int rc = -1;
       switch (t->MT * 10 + t->WM) {
-        case 11: rc = launch_conv_dd_cfg<1, 1>(h, N, mode, st); break;
-        case 21: rc = launch_conv_dd_cfg<2, 1>(h, N, mode, st); break;
-        case 31: rc = launch_conv_dd_cfg<3, 1>(h, N, mode, st); break;
-        case 41: rc = launch_conv_dd_cfg<4, 1>(h, N, mode, st); break;
-        case 32: rc = launch_conv_dd_cfg<3, 2>(h, N, mode, st); break;
-        case 42: rc = launch_conv_dd_cfg<4, 2>(h, N, mode, st); break;
-        case 34: rc = launch_conv_dd_cfg<3, 4>(h, N, mode, st); break;
-        case 44: rc = launch_conv_dd_cfg<4, 4>(h, N, mode, st); break;
+        case 11: rc = launch_conv_dd_cfg<1, 1>(h, N, mode, st, s2_blocks); break;
+        case 21: rc = launch_conv_dd_cfg<2, 1>(h, N, mode, st, s2_blocks); break;
+        case 31: rc = launch_conv_dd_cfg<3, 1>(h, N, mode, st, s2_blocks); break;
+        case 41: rc = launch_conv_dd_cfg<4, 1>(h, N, mode, st, s2_blocks); break;
+        case 32: rc = launch_conv_dd_cfg<3, 2>(h, N, mode, st, s2_blocks); break;
+        case 42: rc = launch_conv_dd_cfg<4, 2>(h, N, mode, st, s2_blocks); break;
+        case 34: rc = launch_conv_dd_cfg<3, 4>(h, N, mode, st, s2_blocks); break;
+        case 44: rc = launch_conv_dd_cfg<4, 4>(h, N, mode, st, s2_blocks); break;
       }
       if (rc) return rc;
     }
@@ -1255,7 +1301,7 @@ __global__ __launch_bounds__(256) void k_softmax_regress(const float* __restrict
 // Layer plan.  Packed weights: 11 layers x (9*D*D fragment floats + D bias floats), in the order
 // conv0..conv6, conv7, conv9, conv11, prob; fp32 with D in {64, 128, 192, 256}: followed by the five stride-1 layers
 // (conv0, conv2, conv4, conv6, prob) in the F(2x2, 3x3) form, 16*D*D floats each (costreg2d_wino.hip); D >= 128: then conv0 and
-// prob in the F(2x4, 3x3) form, 24*D*D floats each (costreg2d_wino24.hip).
+// prob in the F(2x4, 3x3) form, 24*D*D floats each (costreg2d_wino24.hip); D >= 192: then conv2 and conv4 in that form.
 // Workspace: 3 * N*h*w*D floats.
 // sm_vw != null: the `prob` layer reduces its scores over D in its epilogue (costreg_softmax.h) and writes the view
 // weights / pair depths of softmax_max_regress directly (score is not written); the caller skips launch_softmax_regress.
@@ -1279,8 +1325,24 @@ bool cost_reg_wino24(int D, int h, int w) {
   return !(opt(OPT_WINOGRAD) & 2) && wino24_depth_supported(D) && w >= 128 && cdiv(w, 64) * 64 * 8 <= w * 9;
 }
 
+// conv2 and conv4 -- the stride-1 layers of the two inner levels, 96 and 48 pixels wide at cfg2 -- in the F(2x4, 3x3) form on folded
+// blocks (costreg2d_wino24.hip: 8 x 32 or 8 x 16 pixels), where those tile the map and the unfolded 64-pixel blocks do not.  From
+// D = 192 (the blob carries the blocks from there).  By the map's shape alone, like cost_reg_wino24: the two forms round differently,
+// and a tile must give the same bits alone and in a batch (tests/test_full_size_parity.py::test_cfg4_rank_share_against_oracle); the
+// folded blocks are the faster ones down to the smallest grid of the cascade (16 maps of 24 x 48: 0.111 -> 0.051 ms; 48 x 96:
+// 0.220 -> 0.190; profiles/r10_fold_ab.txt).  Option winograd + 2: F(2x2, 3x3) in every stride-1 layer, as before; + 4: no folded blocks
+// in any layer, here and in s2_pairs_fold (value 5: the selection of before round 10, the maps of then bit for bit).
+bool wino24_inner_depth_supported(int D) { return wino24_depth_supported(D) && D >= 192; }
+int cost_reg_wino24_fold(int N, int D, int h, int w) {
+  (void)N;
+  if ((opt(OPT_WINOGRAD) & (2 | 4)) || !wino24_inner_depth_supported(D)) return 0;
+  const int f = conv_wino24_fold(h, w);
+  return f > 1 ? f : 0;
+}
+
 int launch_cost_reg_net_2d(const float* x, const float* wpk, float* ws, float* score, int N, int D, int h, int w,
-                           int precision, hipStream_t st, float* sm_vw, float* sm_pd, const PlaneSrc* sm_planes, int sm_B, int n_planes) {
+                           int precision, hipStream_t st, float* sm_vw, float* sm_pd, const PlaneSrc* sm_planes, int sm_B, int n_planes, int blocks) {
+  // blocks = 0 (adamvs_cost_reg_net_2d_blocks: A/B, tests): no folded blocks, the selection of before; -1: by the maps
   // D = the width the network runs at; n_planes <= D hypothesis planes for the softmax (0: D)
   const bool fuse_softmax = sm_vw != nullptr;
   // the softmax epilogue of the direct kernels needs a pixel's channels in one workgroup: not at D = 384 (two launches)
@@ -1336,15 +1398,18 @@ int launch_cost_reg_net_2d(const float* x, const float* wpk, float* ws, float* s
       // a pixel are different workgroups there, so the softmax behind the last layer is every lane's partial + a merge kernel
       // (uniform planes: stage 1); with per-pixel planes, or ADAMVS_WINO_SOFTMAX=0, the scores go through the score volume to
       // k_softmax_regress
-      const bool w24 = (i == 0 || i == 10) && cost_reg_wino24(D, h, w);
-      const float* ww = w24 ? wpk + (size_t)11 * LW + (size_t)5 * 16 * D * D + (size_t)(i == 10) * 24 * D * D
+      const bool folded = blocks != 0 && (i == 2 || i == 4) && cost_reg_wino24_fold(N, D, plan[i].hi, plan[i].wi) > 0;
+      const bool w24 = ((i == 0 || i == 10) && cost_reg_wino24(D, h, w)) || folded;
+      // the F(2x4, 3x3) blocks of the blob: conv0, prob, then (D >= 192) conv2, conv4
+      const float* ww = w24 ? wpk + (size_t)11 * LW + (size_t)5 * 16 * D * D + (size_t)(i == 0 ? 0 : (i == 10 ? 1 : 1 + i / 2)) * 24 * D * D
                             : wpk + (size_t)11 * LW + (size_t)(i == 10 ? 4 : i / 2) * 16 * D * D;
       if (i == 10 && fuse_softmax && wino_softmax_fused() && sm_planes->mode == PLANES_UNIFORM && (n_planes > 0 ? n_planes : D) > 1) {
         // every lane's softmax partial instead of the scores (D bytes per pixel instead of 4 D), in the score volume's place
         rc = (w24 ? launch_conv_wino24_softmax : launch_conv_wino_softmax)(plan[i].in, ww, wl + (size_t)9 * D * D, score, *sm_planes, sm_vw, sm_pd, N,
                                                                            sm_B, D, n_planes, h, w, st);
       } else {
-        rc = (w24 ? launch_conv_wino24 : launch_conv_wino)(plan[i].in, ww, wl + (size_t)9 * D * D, nullptr, plan[i].out, N, D, plan[i].hi, plan[i].wi, plan[i].relu, st);
+        rc = w24 ? launch_conv_wino24(plan[i].in, ww, wl + (size_t)9 * D * D, nullptr, plan[i].out, N, D, plan[i].hi, plan[i].wi, plan[i].relu, st)
+                 : launch_conv_wino(plan[i].in, ww, wl + (size_t)9 * D * D, nullptr, plan[i].out, N, D, plan[i].hi, plan[i].wi, plan[i].relu, st);
         if (!rc && i == 10 && fuse_softmax) rc = launch_softmax_regress(score, *sm_planes, sm_vw, sm_pd, N / sm_B, sm_B, D, h, w, st, n_planes);
       }
     } else {
@@ -1354,7 +1419,7 @@ int launch_cost_reg_net_2d(const float* x, const float* wpk, float* ws, float* s
                    plan[i].hi, plan[i].wi, plan[i].ho, plan[i].wo, plan[i].relu, nullptr, nullptr, PlaneSrc{nullptr, 0, 0.f}, 1,
                    take ? plan[i - 1].skip : nullptr};
       if (i == 10 && epilogue_sm) { a.sm_vw = sm_vw; a.sm_pd = sm_pd; a.sm_planes = *sm_planes; a.sm_B = sm_B; a.sm_D = n_planes; }
-      rc = launch_conv_dd(a, N, plan[i].mode, st);
+      rc = launch_conv_dd(a, N, plan[i].mode, st, blocks);
       if (!rc && i == 10 && fuse_softmax && !epilogue_sm)
         rc = launch_softmax_regress(score, *sm_planes, sm_vw, sm_pd, N / sm_B, sm_B, D, h, w, st, n_planes);
     }
@@ -1403,6 +1468,10 @@ static int check_precision(int precision, int D, const char* who) {
 
 extern "C" int adamvs_conv_t2_form(int N, int D, int hi, int wi) { return N > 0 && hi > 0 && wi > 0 ? conv_t2_form(N, D, hi, wi) : -1; }
 
+extern "C" int adamvs_conv_s2_form(int N, int D, int hi, int wi, int blocks) { return N > 0 && hi > 1 && wi > 1 ? conv_s2_form(N, D, hi, wi, blocks) : -1; }
+extern "C" int adamvs_cost_reg_fold(int N, int D, int h, int w) { return N > 0 && h > 0 && w > 0 ? cost_reg_wino24_fold(N, D, h, w) : -1; }
+extern "C" int adamvs_conv_wino24_fold(int h, int w, int blocks) { return h > 0 && w > 0 ? conv_wino24_fold(h, w, blocks) : -1; }
+
 extern "C" int adamvs_cost_reg_width(int D, int precision) {
   return D < 1 ? 0 : (precision == PRECISION_BF16X3 ? costreg_width_bf16x3(D) : costreg_width(D));
 }
@@ -1410,7 +1479,8 @@ extern "C" int adamvs_cost_reg_width(int D, int precision) {
 size_t adamvs::cost_reg_weight_floats(int D, int precision) {
   if (!(precision == PRECISION_BF16X3 ? costreg_bf16x3_depth_supported(D) : costreg_depth_supported(D))) return 0;
   return (size_t)11 * ((size_t)9 * D * D + D) + (precision == PRECISION_FP32 && wino_depth_supported(D) ? (size_t)5 * 16 * D * D : 0) +
-         (precision == PRECISION_FP32 && wino24_depth_supported(D) ? (size_t)2 * 24 * D * D : 0);
+         (precision == PRECISION_FP32 && wino24_depth_supported(D) ? (size_t)2 * 24 * D * D : 0) +
+         (precision == PRECISION_FP32 && wino24_inner_depth_supported(D) ? (size_t)2 * 24 * D * D : 0);
 }
 extern "C" size_t adamvs_cost_reg_net_2d_weight_floats(int D, int precision) { return cost_reg_weight_floats(D, precision); }
 
@@ -1427,6 +1497,29 @@ extern "C" int adamvs_cost_reg_net_2d(const float* x, const float* wpk, size_t w
                    "cost_reg_net_2d: workspace too small (%zu < %zu bytes)", workspace_bytes,
                    adamvs_cost_reg_net_2d_workspace_bytes(N, D, h, w));
   return launch_cost_reg_net_2d(x, wpk, (float*)workspace, score, N, D, h, w, precision, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_cost_reg_net_2d_blocks(const float* x, const float* wpk, size_t wpk_floats, float* score, int N, int D, int h, int w,
+                                             int blocks, void* workspace, size_t workspace_bytes, void* stream) {
+  ADAMVS_CHECK_ARG(x && wpk && score && workspace && N > 0 && h > 0 && w > 0, "cost_reg_net_2d_blocks: bad arguments");
+  ADAMVS_CHECK_ARG(blocks == -1 || blocks == 0, "cost_reg_net_2d_blocks: blocks=%d (-1 by the maps, 0 no folded blocks)", blocks);
+  ADAMVS_CHECK_ARG(costreg_depth_supported(D), "cost_reg_net_2d_blocks: D=%d unsupported", D);
+  ADAMVS_CHECK_ARG(wpk_floats == cost_reg_weight_floats(D, PRECISION_FP32), "cost_reg_net_2d_blocks: wpk holds %zu floats, the layout for D=%d has %zu",
+                   wpk_floats, D, cost_reg_weight_floats(D, PRECISION_FP32));
+  ADAMVS_CHECK_ARG((h % 8) == 0 && (w % 8) == 0, "cost_reg_net_2d_blocks: h=%d w=%d must be multiples of 8", h, w);
+  ADAMVS_CHECK_ARG(workspace_bytes >= adamvs_cost_reg_net_2d_workspace_bytes(N, D, h, w), "cost_reg_net_2d_blocks: workspace too small (%zu bytes)",
+                   workspace_bytes);
+  return launch_cost_reg_net_2d(x, wpk, (float*)workspace, score, N, D, h, w, PRECISION_FP32, (hipStream_t)stream, nullptr, nullptr, nullptr, 1, 0, blocks);
+}
+
+extern "C" int adamvs_conv3x3_dd_s2_blocks(const float* in, const float* wpk, const float* bias, float* out, int N, int D, int hi, int wi,
+                                           int relu, int blocks, void* stream) {
+  ADAMVS_CHECK_ARG(in && wpk && bias && out && N > 0 && hi > 0 && wi > 0, "conv3x3_dd_s2_blocks: bad arguments");
+  ADAMVS_CHECK_ARG(costreg_depth_supported(D), "conv3x3_dd_s2_blocks: D=%d unsupported", D);
+  ADAMVS_CHECK_ARG((hi % 2) == 0 && (wi % 2) == 0, "conv3x3_dd_s2_blocks: stride 2 needs even hi, wi");
+  ADAMVS_CHECK_ARG(blocks == -1 || blocks == 0 || blocks == 2 || blocks == 4, "conv3x3_dd_s2_blocks: blocks=%d (-1 by the map, 0, 2, 4)", blocks);
+  ConvDDArgs a{in, wpk, bias, nullptr, out, D, hi, wi, hi / 2, wi / 2, relu, nullptr, nullptr, PlaneSrc{nullptr, 0, 0.f}, 1, nullptr};
+  return launch_conv_dd(a, N, CONV_S2, (hipStream_t)stream, blocks);
 }
 
 extern "C" int adamvs_conv3x3_dd(const float* in, const float* in2, const float* wpk, const float* bias, const float* skip,

@@ -24,6 +24,10 @@
 // against 2.89.  conv0 and prob of the network take this form on maps at least 128 wide (costreg2d.hip::cost_reg_wino24): cfg2's step
 // 385.7 -> 376.9 ms.  Timing builds of round 4 (-DWINO24_EXP, of 5.84 ms per 128 maps, one workgroup per CU): no epilogue -0.53, no
 // fragment loads -0.68, no transform -0.71, no window fill and barrier -0.97, no raw-row reads -0.57 -- every part a tenth, none dominant.
+// Round 10: folded blocks (FOLD, below) tile the 96- and 48-pixel levels; 1024 maps at D = 192: 48 x 96 10.66 ms on 8 x 32 blocks against
+// 11.54 for F(2x2, 3x3) (13.43 on 64-pixel blocks), 24 x 48 2.51 on 8 x 16 against 3.79 (3.33); conv2 and conv4 of the network take them:
+// cfg2's step 373.2 -> 368.3 ms together with the folded stride-2 pair form (costreg2d.hip).  The FOLD 1 instantiations are the
+// instruction streams of before.
 //
 // Mapping (as costreg2d_wino.hip unless said): workgroup = 4 waves = patch rows i; a tile = NT tile rows x 16 tiles x
 // MT channel tiles = 2 NT x 64 output pixels x 16 MT channels; LDS window (2 NT + 2) x 66 pixels x 16 input channels, double-buffered,
@@ -36,6 +40,11 @@
 // from two arrays.  Epilogue: Z_i[b] = sum_j At4[b][j] M[i][j] (b = 0..3) in registers, through LDS (4 rows x 4 b x MT x 1 KB),
 // wave (a, b') forms Y[a][b] = sum_i At2[a][i] Z_i[b] for b = 2 b', 2 b' + 1, applies ReLU / skip and stores (the bias came through
 // accumulator position (1, 1)); SM: the softmax partial of the lane's 16 MT channels instead, as k_conv_wino<..., SM>.
+// FOLD (Wino24Geom): an MFMA column is an independent tile, and nothing above needs the 16 of an instruction in one tile row.  With
+// FOLD = F they are 16 / F tiles of each of F tile rows: the block is 2 NT F rows x 64 / F columns, the window (2 NT F + 2) x (64 / F + 2)
+// pixels at a row pitch that keeps the raw-row reads on 16 different bank quadruples; the lane's tile row and tile enter the pinned
+// read bases and the epilogue's lane offset once, the loop is the unfolded one.  conv2 / conv4 of the network (96 and 48 columns:
+// 3 x 32, 3 x 16) take FOLD 2 (MT 2 x NT 2: 8 x 32) and FOLD 4 (MT 4 x NT 1: 8 x 16) (costreg2d.hip::cost_reg_wino24_fold).
 #include <stdlib.h>
 #include <type_traits>
 
@@ -57,10 +66,25 @@ namespace adamvs {
 // WinoArgs (costreg_wino.h); wpk: [D/4][4][D/16][64][4] (patch columns 0-3) then [D/4][4][D/16][64][2] (columns 4, 5): k-step, patch
 // row i, channel tile, lane (A-fragment order) -- 24 bytes per lane and (k-step, channel tile), fetched as 16 + 8
 
-template <int MT, int NT>
+// FOLD = F: the 16 MFMA columns are 16 / F tiles of each of F tile rows -- a block F times narrower and F times taller, the same
+// accumulators, fragments and MFMAs (levels of the hourglass whose width is no multiple of 64: 96 = 3 x 32, 48 = 3 x 16).  Lane p
+// holds tile p % (16 / F) of the tile rows (p / (16 / F)) NT + t, t = 0 .. NT - 1.
+template <int MT, int NT, int FOLD = 1>
 struct Wino24Geom {
+  static_assert(FOLD == 1 || FOLD == 2 || FOLD == 4, "16 / FOLD tiles of FOLD tile rows");
   static constexpr int KC = 16, KS = KC / 4;                 // input channels per LDS chunk, k-steps per chunk
-  static constexpr int LR = 2 * NT + 2, LC = 66, NPIX = LR * LC;
+  static constexpr int TPR = 16 / FOLD, BW = 4 * TPR, BH = 2 * NT * FOLD;   // tiles per tile row; the block's columns and rows
+  static constexpr int LR = BH + 2, LCW = BW + 2;            // the window
+  // Row pitch: the 16 lanes p of a ds_read_b64 start at pixel (p / TPR) 2 NT LC + 4 (p % TPR) of their plane and must take 16
+  // different bank quadruples, as the pixels 4 p of the unfolded form do: the smallest pitch from the window's width up that does it
+  // (FOLD 1: 66, the window; FOLD 2, NT 2: 40 for 34; FOLD 4, NT 1: 24 for 18).  The pad columns are filled with zeros and never read.
+  static constexpr bool pitch_ok(int lc) {
+    unsigned seen = 0;
+    for (int p = 0; p < 16; ++p) seen |= 1u << ((((p / TPR) * 2 * NT * lc + 4 * (p % TPR)) & 63) >> 2);
+    return seen == 0xffffu && lc % 2 == 0;                   // (even: the 8-byte reads at pixel 4 t + 2 j stay aligned)
+  }
+  static constexpr int pitch() { int lc = LCW; while (!pitch_ok(lc)) ++lc; return lc; }
+  static constexpr int LC = pitch(), NPIX = LR * LC;
   // == 2 (mod 4): a lane reads 8 bytes at pixel 4 p -- banks 4p, 4p+1 -- and the k-rows q, q + 1 of a 32-lane ds_read_b64 group take the other two of every four
   static constexpr int PLANE = (NPIX + 3) / 4 * 4 + 2;
   static constexpr int GP = (4 * PLANE + 63) / 64 * 64 + 16; // channel-group pitch: the 4 groups of 16 neighbouring pixels of a fill on 64 different banks
@@ -71,15 +95,16 @@ struct Wino24Geom {
   static_assert(PLANE >= NPIX, "plane pitch");
 };
 
-template <int MT, int NT, int WPS, bool SM>
+template <int MT, int NT, int WPS, bool SM, int FOLD = 1>
 __global__ __launch_bounds__(256, WPS) void k_conv_wino24(WinoArgs a, TileGrid tg, int groups, unsigned mgroups) {
-  using G = Wino24Geom<MT, NT>;
+  using G = Wino24Geom<MT, NT, FOLD>;
   static_assert(!SM || MT == 4, "k_softmax_merge reads four partials per channel group of 64");
-  constexpr int KC = G::KC, KS = G::KS, LC = G::LC, NPIX = G::NPIX, PLANE = G::PLANE, GP = G::GP, CHUNK = G::CHUNK;
+  constexpr int KC = G::KC, KS = G::KS, LC = G::LC, LCW = G::LCW, TPR = G::TPR, NPIX = G::NPIX, PLANE = G::PLANE, GP = G::GP, CHUNK = G::CHUNK;
   constexpr int NITEMS = NPIX * (KC / 4), NITA = (NITEMS + 255) / 256;
   extern __shared__ __attribute__((aligned(16))) float lds[];   // G::LDS_BYTES: the buffers / the epilogue's exchange + the layer's bias vector (D <= 512)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave = patch row i
   const int p = lane & 15, q = lane >> 4;
+  const int fr = FOLD == 1 ? 0 : p / TPR, ft = FOLD == 1 ? p : p % TPR;   // the lane's tile: tile rows fr NT + t, tile ft of the row
   const int D = a.D, NTILES = D / 16, NC = D / KC;
 
   // ---- per-lane constants (tile-independent)
@@ -99,7 +124,7 @@ __global__ __launch_bounds__(256, WPS) void k_conv_wino24(WinoArgs a, TileGrid t
   const f32x2 sgn2 = {sgn, sgn};
   f32x2 k41 = {-4.0f, -1.0f}, kpm = {1.0f, -1.0f}, kpm2 = {2.0f, -2.0f}, k4 = {4.0f, 4.0f}, k5 = {-5.0f, -5.0f};
   // three separately pinned bases per row: merged into ds_read2_b64 the pairs would need a vector add per read for the address
-  unsigned pa0 = (unsigned)((q * PLANE + rowA * LC + 4 * p) * 4), pb0 = (unsigned)((q * PLANE + rowB * LC + 4 * p) * 4);
+  unsigned pa0 = (unsigned)((q * PLANE + (2 * NT * fr + rowA) * LC + 4 * ft) * 4), pb0 = (unsigned)((q * PLANE + (2 * NT * fr + rowB) * LC + 4 * ft) * 4);
   unsigned pa1 = pa0 + 8, pa2 = pa0 + 16, pb1 = pb0 + 8, pb2 = pb0 + 16;
   pin(pa0); pin(pa1); pin(pa2); pin(pb0); pin(pb1); pin(pb2);
   const buf_rsrc rw = make_rsrc(a.wpk);
@@ -109,7 +134,7 @@ __global__ __launch_bounds__(256, WPS) void k_conv_wino24(WinoArgs a, TileGrid t
   // epilogue: wave (oa, ob) stores output pixels (2 ty + oa, 4 tx + 2 ob + {0, 1}) of every 2 x 4 tile
   const int oa = wave >> 1, ob = wave & 1;
   const float os = oa ? -1.0f : 1.0f;
-  unsigned ooff = (unsigned)(((oa * a.w + 4 * p + 2 * ob) * D + 4 * q) * 4);   // + the tile's origin and the tile row
+  unsigned ooff = (unsigned)((((2 * NT * fr + oa) * a.w + 4 * ft + 2 * ob) * D + 4 * q) * 4);   // + the tile's origin and the tile row
   pin(ooff);
 
   struct Tile { int n, r0, c0, cg; };
@@ -117,7 +142,7 @@ __global__ __launch_bounds__(256, WPS) void k_conv_wino24(WinoArgs a, TileGrid t
     int n, tx, ty;
     tile_coords(tg, t, n, tx, ty);                           // tx runs over (block column, channel group)
     const int bx = groups == 1 ? tx : (int)__umulhi((unsigned)tx, mgroups);
-    return Tile{n, ty * 2 * NT, bx * 64, tx - bx * groups};
+    return Tile{n, ty * G::BH, bx * G::BW, tx - bx * groups};
   };
   buf_rsrc rx;
   unsigned xoff[NITA];
@@ -126,7 +151,7 @@ __global__ __launch_bounds__(256, WPS) void k_conv_wino24(WinoArgs a, TileGrid t
 #pragma unroll
     for (int it = 0; it < NITA; ++it) {
       const int pp = it + 1 < NITA ? pp0 + 64 * it : ppl, r = pp / LC, c = pp - r * LC;
-      const bool ok = (unsigned)(t.r0 - 1 + r) < (unsigned)a.h && (unsigned)(t.c0 - 1 + c) < (unsigned)a.w;
+      const bool ok = (unsigned)(t.r0 - 1 + r) < (unsigned)a.h && (unsigned)(t.c0 - 1 + c) < (unsigned)a.w && (LC == LCW || c < LCW);
       xoff[it] = ok ? (unsigned)((r * a.w + c) * D * 4) + (it + 1 < NITA ? (unsigned)(fg * 16) : gch) : BUF_OOB;
     }
   };
@@ -315,7 +340,7 @@ __global__ __launch_bounds__(256, WPS) void k_conv_wino24(WinoArgs a, TileGrid t
           zl[((wave * 4 + 3) * MT + mt) * 64 + lane] = (d12 + 8.0f * d34) + acc[5][mt][t];
         }
         __syncthreads();
-        const int oy = done.r0 + 2 * t + oa, ox = done.c0 + 4 * p + 2 * ob;
+        const int oy = done.r0 + 2 * (NT * fr + t) + oa, ox = done.c0 + 4 * ft + 2 * ob;
         const unsigned tbase = ooff + (unsigned)((((done.r0 + 2 * t) * a.w + done.c0) * D + done.cg * MT * 16) * 4);
 #pragma unroll
         for (int bb = 0; bb < 2; ++bb) {
@@ -365,13 +390,14 @@ __global__ __launch_bounds__(256, WPS) void k_conv_wino24(WinoArgs a, TileGrid t
   }
 }
 
-template <int MT, int NT, int WPS, bool SM = false>
+template <int MT, int NT, int WPS, bool SM = false, int FOLD = 1>
 static int launch_wino24_cfg(const WinoArgs& a, int N, hipStream_t st) {
+  using G = Wino24Geom<MT, NT, FOLD>;
   const int groups = a.D / (16 * MT);
   TileGrid tg;
-  if (int rc = make_tile_grid(tg, groups * cdiv(a.w, 64), cdiv(a.h, 2 * NT), N)) return rc;
-  return launch_resident<k_conv_wino24<MT, NT, WPS, SM>>(tg.ntiles, Wino24Geom<MT, NT>::LDS_BYTES, st, "conv_wino24", a, tg, groups,
-                                                         (unsigned)(((1ull << 32) + groups - 1) / groups));
+  if (int rc = make_tile_grid(tg, groups * cdiv(a.w, G::BW), cdiv(a.h, G::BH), N)) return rc;
+  return launch_resident<k_conv_wino24<MT, NT, WPS, SM, FOLD>>(tg.ntiles, G::LDS_BYTES, st, "conv_wino24", a, tg, groups,
+                                                               (unsigned)(((1ull << 32) + groups - 1) / groups));
 }
 
 // Three tilings, the same bits.  Two workgroups per CU leave a wave 24 accumulator tiles: MT 2 x NT 2 (a fragment feeds two MFMAs, six
@@ -379,11 +405,30 @@ static int launch_wino24_cfg(const WinoArgs& a, int N, hipStream_t st) {
 // per CU holds MT 4 x NT 2.  256 maps of 96 x 192 at D = 192: 10.92 / 11.01 / 11.13 ms (F(2x2, 3x3): 11.73); 64 maps 2.62 / 2.79 / 2.81
 // (2.89); 32 maps at D = 256 2.29 / 2.37 / 2.43 (2.50): MT 2 x NT 2 wherever the epilogue allows it (the softmax partials need MT 4).
 // Option wino_wps = 1 / 2 forces the one-workgroup form / MT 4 x NT 1 (A/B).
+//
+// Folded blocks (Wino24Geom): FOLD 2 with MT 2 x NT 2 covers 8 x 32 pixels, FOLD 4 with MT 4 x NT 1 covers 8 x 16 -- the widths 96 and
+// 48 of the inner hourglass levels tile exactly, where the 64-pixel blocks pad a quarter.  Per pixel the same sums in the same order:
+// every form gives the same bits.  conv_wino24_fold: the FOLD a map takes.  blocks = -1 (what every caller but the A/B entry point
+// passes): a folded form where the unfolded blocks would pad the width and the folded ones tile the map in both directions; 2 / 4: that
+// FOLD wherever the width is a multiple of its block's (adamvs_conv3x3_dd_wino24_blocks: A/B, tests, any height); 1: the 64-pixel
+// blocks.  A forced wino_wps keeps the unfolded blocks.
+int conv_wino24_fold(int h, int w, int blocks) {
+  if (opt(OPT_WINO_WPS) == 1 || opt(OPT_WINO_WPS) == 2) return 1;
+  if (blocks == 2 || blocks == 4) return w % (64 / blocks) == 0 ? blocks : 1;
+  if (blocks != -1 || w % 64 == 0 || h % 8 != 0) return 1;
+  return w % 32 == 0 ? 2 : (w % 16 == 0 ? 4 : 1);
+}
+
 int launch_conv_wino24(const float* in, const float* wpk, const float* bias, const float* skip, float* out, int N, int D, int h, int w,
-                       int relu, hipStream_t st) {
+                       int relu, hipStream_t st, int blocks) {
   const WinoArgs a{in, wpk, bias, skip, out, D, h, w, relu, nullptr, PlaneSrc{nullptr, 0, 0.f}, 1, D};
   ADAMVS_CHECK_ARG(wino_depth_supported(D), "conv_wino24: D=%d unsupported (a multiple of 64 up to 512)", D);
   ADAMVS_CHECK_ARG((size_t)h * w * D * 4 < 0x7fffffffu, "conv_wino24: a map of %dx%dx%d floats exceeds the 2 GiB a buffer descriptor spans", h, w, D);
+  switch (conv_wino24_fold(h, w, blocks)) {
+    case 2: return launch_wino24_cfg<2, 2, 2, false, 2>(a, N, st);
+    case 4: return launch_wino24_cfg<4, 1, 2, false, 4>(a, N, st);
+    default: break;
+  }
   switch (opt(OPT_WINO_WPS)) {
     case 1: return launch_wino24_cfg<4, 2, 1>(a, N, st);
     case 2: return launch_wino24_cfg<4, 1, 2>(a, N, st);
@@ -410,6 +455,13 @@ extern "C" int adamvs_conv3x3_dd_wino24(const float* in, const float* wpk, const
                                         int D, int h, int w, int relu, void* stream) {
   ADAMVS_CHECK_ARG(in && wpk && bias && out && N > 0 && h > 0 && w > 0, "conv3x3_dd_wino24: bad arguments");
   return launch_conv_wino24(in, wpk, bias, skip, out, N, D, h, w, relu, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_conv3x3_dd_wino24_blocks(const float* in, const float* wpk, const float* bias, const float* skip, float* out, int N,
+                                               int D, int h, int w, int relu, int blocks, void* stream) {
+  ADAMVS_CHECK_ARG(in && wpk && bias && out && N > 0 && h > 0 && w > 0, "conv3x3_dd_wino24_blocks: bad arguments");
+  ADAMVS_CHECK_ARG(blocks == -1 || blocks == 1 || blocks == 2 || blocks == 4, "conv3x3_dd_wino24_blocks: blocks=%d (-1 by the map, 1, 2, 4)", blocks);
+  return launch_conv_wino24(in, wpk, bias, skip, out, N, D, h, w, relu, (hipStream_t)stream, blocks);
 }
 
 extern "C" int adamvs_prob_softmax_regress_wino24(const float* in, const float* wpk, const float* bias, const float* depth_range, float* view_weight,

@@ -123,7 +123,7 @@ int launch_sweep_variance(const float* feat, const float* rt, const float* plane
 size_t sweep_workspace_floats(int B, int C, int D, int h, int w);
 int launch_cost_reg_net_2d(const float* x, const float* wpk, float* ws, float* score, int N, int D, int h, int w,
                            int precision, hipStream_t st, float* sm_vw = nullptr, float* sm_pd = nullptr,
-                           const PlaneSrc* sm_planes = nullptr, int sm_B = 1, int n_planes = 0);
+                           const PlaneSrc* sm_planes = nullptr, int sm_B = 1, int n_planes = 0, int blocks = -1);
 size_t cost_reg_weight_floats(int D, int precision);        // floats of the packed weight blob at width D (0: unsupported)
 int costreg_width(int D);            // the width CostRegNet2D runs at for D hypotheses (next supported; 0: none)
 int costreg_width_bf16x3(int D);
@@ -142,10 +142,12 @@ int launch_conv_wino(const float* in, const float* wpk, const float* bias, const
                      int relu, hipStream_t st);
 // the same two in the F(2x4, 3x3) form (costreg2d_wino24.hip; wpk from packing.pack_reg_layer_wino24)
 bool cost_reg_wino24(int D, int h, int w);        // whether conv0 / prob of a network on h x w maps take it
+int conv_wino24_fold(int h, int w, int blocks = -1);   // the FOLD (1, 2, 4) of the blocks a layer on h x w maps takes; blocks: -1 by the map, or forced
+int cost_reg_wino24_fold(int N, int D, int h, int w);   // conv2 / conv4 of a network on h x w maps at that level: the FOLD, 0 = F(2x2, 3x3)
 int launch_conv_wino24_softmax(const float* in, const float* wpk, const float* bias, float* part, const PlaneSrc& planes, float* vw, float* pd,
                                int N, int B, int D, int n_planes, int h, int w, hipStream_t st);
 int launch_conv_wino24(const float* in, const float* wpk, const float* bias, const float* skip, float* out, int N, int D, int h, int w,
-                       int relu, hipStream_t st);
+                       int relu, hipStream_t st, int blocks = -1);
 
 // Dw >= D: channels per pixel of sim (the width CostRegNet2D runs at); channels [D, Dw) are written as zeros
 int launch_pair_similarity(const float* feat, const float* rt, PlaneSrc planes, float* sim, int B, int S, int C, int D, int h,

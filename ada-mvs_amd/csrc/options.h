@@ -12,7 +12,7 @@ namespace adamvs {
 // X(enumerator, "name", default)
 #define ADAMVS_OPTION_LIST(X)                                                                                                     \
   X(OPT_WINOGRAD, "winograd", 1)                     /* CostRegNet2D: stride-1 layers in the F(2x2, 3x3) form (fp32, D % 64 == 0) */ \
-                                                     /* (conv0 / prob on wide maps in F(2x4, 3x3); + 2: F(2x2, 3x3) everywhere) */    \
+                                                     /* (conv0 / prob on wide maps in F(2x4, 3x3); + 2: F(2x2, 3x3) everywhere; + 4: no folded blocks) */ \
   X(OPT_WINO_SOFTMAX, "wino_softmax", 1)             /* ... `prob` carries the softmax partials (no score volume) */                 \
   X(OPT_WINO_WPS, "wino_wps", 0)                     /* ... 1 / 2 workgroups per CU; 0 = by map size */                              \
   X(OPT_FUSE_SOFTMAX, "fuse_softmax", 1)             /* direct `prob` kernel: softmax / max / regression in its epilogue */           \

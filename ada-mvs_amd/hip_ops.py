@@ -119,14 +119,20 @@ def pair_similarity(feat, rt, planes, B, S, C, D, h, w):
     return sim
 
 
-def cost_reg_net_2d(x_cl, wpk, h, w, precision=0):
-    """x_cl [N,hw,D] channel-last -> score [N,hw,D]   (adamvs.py:229-238)"""
+def cost_reg_net_2d(x_cl, wpk, h, w, precision=0, blocks=None):
+    """x_cl [N,hw,D] channel-last -> score [N,hw,D]   (adamvs.py:229-238).  blocks (fp32; A/B, tests): -1 as None, 0 no folded
+    blocks in any layer (adamvs_cost_reg_net_2d_blocks)."""
     x_cl = _dev(x_cl, "x")
     N, hw, D = x_cl.shape
     lib = _lib.load()
     nbytes = lib.adamvs_cost_reg_net_2d_workspace_bytes(N, D, h, w)
     ws = torch.empty(nbytes // 4, device=x_cl.device, dtype=torch.float32)
     score = torch.empty_like(x_cl)
+    if blocks is not None:
+        assert int(precision) == 0
+        check(lib.adamvs_cost_reg_net_2d_blocks(_p(x_cl), _p(wpk), wpk.numel(), _p(score), N, D, h, w, int(blocks), _p(ws), nbytes, _stream()),
+              "cost_reg_net_2d_blocks")
+        return score
     check(lib.adamvs_cost_reg_net_2d(_p(x_cl), _p(wpk), wpk.numel(), _p(score), N, D, h, w, int(precision), _p(ws), nbytes, _stream()),
           "cost_reg_net_2d")
     return score
@@ -370,13 +376,28 @@ def conv3x3_dd_wino(x_cl, wino_layer, bias, skip, N, D, h, w, relu, out=None):
     return out
 
 
-def conv3x3_dd_wino24(x_cl, wino24_layer, bias, skip, N, D, h, w, relu, out=None):
-    """A stride-1 CostRegNet2D layer in the F(2x4, 3x3) form; wino24_layer from packing.pack_reg_layer_wino24."""
+def conv3x3_dd_wino24(x_cl, wino24_layer, bias, skip, N, D, h, w, relu, out=None, blocks=None):
+    """A stride-1 CostRegNet2D layer in the F(2x4, 3x3) form; wino24_layer from packing.pack_reg_layer_wino24.  blocks (A/B, tests):
+    1 the 64-pixel blocks, 2 / 4 the folded ones where the width allows, -1 as None (adamvs_conv3x3_dd_wino24_blocks)."""
     if out is None:
         out = torch.empty(N, h * w, D, device=x_cl.device, dtype=torch.float32)
     null = ctypes.c_void_p(0)
+    if blocks is not None:
+        check(_lib.load().adamvs_conv3x3_dd_wino24_blocks(_p(_dev(x_cl, "x")), _p(wino24_layer), _p(bias), _p(skip) if skip is not None else null,
+                                                          _p(out), N, D, h, w, int(relu), int(blocks), _stream()), "conv3x3_dd_wino24_blocks")
+        return out
     check(_lib.load().adamvs_conv3x3_dd_wino24(_p(_dev(x_cl, "x")), _p(wino24_layer), _p(bias), _p(skip) if skip is not None else null,
                                                _p(out), N, D, h, w, int(relu), _stream()), "conv3x3_dd_wino24")
+    return out
+
+
+def conv3x3_dd_s2_blocks(x_cl, wpk_layer, bias, N, D, hi, wi, relu, blocks, out=None):
+    """A stride-2 CostRegNet2D layer (fp32, no skip) with the blocks of its pair form given (A/B, tests): -1 by the map, as
+    conv3x3_dd(mode=1); 0 no folded blocks; 2 / 4 the folded ones where the width allows (adamvs_conv3x3_dd_s2_blocks)."""
+    if out is None:
+        out = torch.empty(N, (hi // 2) * (wi // 2), D, device=x_cl.device, dtype=torch.float32)
+    check(_lib.load().adamvs_conv3x3_dd_s2_blocks(_p(_dev(x_cl, "x")), _p(wpk_layer), _p(bias), _p(out), N, D, hi, wi, int(relu), int(blocks),
+                                                  _stream()), "conv3x3_dd_s2_blocks")
     return out
 
 

@@ -18,6 +18,8 @@ REG_WINOGRAD = ("conv0", "conv2", "conv4", "conv6", "prob")      # stride-1 laye
 WINO_WIDTHS = (64, 128, 192, 256, 384, 512)              # the widths of REG_WIDTHS that csrc/costreg2d_wino.hip takes (multiples of 64)
 REG_WINO24 = ("conv0", "prob")                           # the layers on the full-size map: also packed in the F(2x4, 3x3) form (fp32)
 WINO24_BLOB_WIDTHS = WINO_WIDTHS[1:]                     # ... at the widths at which the network can select it (not D = 64)
+REG_WINO24_INNER = ("conv2", "conv4")                    # the inner levels' stride-1 layers: in that form on folded blocks
+WINO24_INNER_BLOB_WIDTHS = WINO_WIDTHS[2:]               # ... from D = 192, behind conv0 and prob
 # The widths CostRegNet2D's kernels are built for (csrc/costreg2d.hip::costreg_width, costreg_width_bf16x3; held equal to the
 # library's table by tests/test_host_logic.py).  The reference builds the network for any number of hypotheses
 # (models/adamvs.py:198-228): other D run at the next width, see pack_cost_reg_net_2d.
@@ -198,8 +200,8 @@ def _pad_square(w, transposed, dr):
 def pack_cost_reg_net_2d(sd, pre, precision="fp32"):
     """All 11 layers of `pre` (e.g. 'DepthNet.0.reg.') from a reference-keyed state dict; fp32 at the widths the F(2x2, 3x3)
     kernel supports: followed by the five stride-1 layers in that form (16*D*D floats each, include/adamvs_hip.h), and at
-    WINO24_BLOB_WIDTHS by conv0 and prob in the F(2x4, 3x3) form (24*D*D floats each) -- behind everything else, so that no
-    earlier offset moves.
+    WINO24_BLOB_WIDTHS by conv0 and prob in the F(2x4, 3x3) form (24*D*D floats each), at WINO24_INNER_BLOB_WIDTHS by conv2 and
+    conv4 in that form -- each addition behind everything else, so that no earlier offset moves.
     A network of D hypotheses is packed at Dr = reg_width(D) channels: zero filters for the pad channels (their activations are
     ReLU(0 + 0) = 0 in every layer and no real channel reads them), PAD_SCORE as the bias of `prob`'s pad channels."""
     pack_layer = pack_reg_layer if precision == "fp32" else pack_reg_layer_bf16x3
@@ -211,7 +213,7 @@ def pack_cost_reg_net_2d(sd, pre, precision="fp32"):
         out[:d] = v.detach().float().cpu()
         return out
 
-    chunks, wino, wino24 = [], [], []
+    chunks, wino, wino24, inner24 = [], [], [], []
     for name in REG_LAYERS:
         if name == "prob":
             w = sd[pre + "prob.weight"]
@@ -236,7 +238,9 @@ def pack_cost_reg_net_2d(sd, pre, precision="fp32"):
             wino.append(pack_reg_layer_wino(w, scale))
         if precision == "fp32" and name in REG_WINO24 and dr in WINO24_BLOB_WIDTHS:
             wino24.append(pack_reg_layer_wino24(w, scale))
-    return torch.cat(chunks + wino + wino24)
+        if precision == "fp32" and name in REG_WINO24_INNER and dr in WINO24_INNER_BLOB_WIDTHS:
+            inner24.append(pack_reg_layer_wino24(w, scale))
+    return torch.cat(chunks + wino + wino24 + inner24)
 
 
 FUSE_FIELDS = ("conv1", "gates1", "gates1_b", "cand1", "cand1_b", "conv2", "gates2", "gates2_b",

@@ -46,7 +46,9 @@ const char* adamvs_last_error_string(void);
  *                                  layers in the minimal-filtering form F(2x2, 3x3) (16 of 36 products); 0: direct kernels.
  *                                  On wide maps conv0 and prob take the mixed form F(2x4, 3x3) (24 products where F(2x2, 3x3) has
  *                                  32; D >= 128, maps at least 128 pixels wide of which 64-pixel blocks waste at most an eighth); + 2
- *                                  (value 3): F(2x2, 3x3) in every stride-1 layer, the maps of before bit for bit
+ *                                  (value 3): F(2x2, 3x3) in every stride-1 layer, the maps of before bit for bit; + 4 (value 5): no
+ *                                  folded blocks in any layer ("Folded blocks" below: conv2 / conv4 stay in F(2x2, 3x3), conv3 / conv5
+ *                                  on the direct kernel), the maps of before those bit for bit -- the run-time A/B of the whole pipeline
  *   wino_softmax             1     ... its `prob` layer carries the softmax partials, no score volume (stage path); 0: score volume
  *   wino_wps                 0     ... 1 / 2: one / two workgroups per CU for every map size (same bits); 0: by map size
  *   fuse_softmax             1     direct `prob` kernel: softmax / max / depth regression in its epilogue; 0: k_softmax_regress
@@ -141,6 +143,8 @@ int adamvs_pair_similarity(const float* feat, const float* rt, const float* plan
  * fp32 with D in {128,192,256,384,512}: behind those 11 + 5 blocks, at unchanged offsets, two more: conv0 and prob in the form
  * F(2x4, 3x3), 24*D*D floats each, laid out as adamvs_conv3x3_dd_wino24 takes them (the two layers that run on the full-size
  * map; option winograd says when they take that kernel).  The blob at D = 64, where that form never wins, is unchanged.
+ * fp32 with D in {192,256,384,512}: behind those, again at unchanged offsets, conv2 and conv4 in the same form and layout (the inner
+ * levels' stride-1 layers; adamvs_cost_reg_fold says when they take that kernel).  The blobs at D = 64 and 128 are unchanged.
  * wpk_floats = the length of the blob, adamvs_cost_reg_net_2d_weight_floats(D, precision): a blob of another layout
  * (e.g. the 11-block blob of ABI <= 10 at a width that now carries the F(2x2, 3x3) blocks) is refused, not read past its end.
  *
@@ -380,6 +384,34 @@ int adamvs_gru_wino_mask(void);
  * the current options: 0 class by class, 1 the four parity classes per chunk (small grids: option t2_fused), 2 the pair form along x
  * (15 of 18 products: D = 192 / 384, even widths whose rows fill blocks of 32 input columns; option s2_pairs).  -1: unsupported D. */
 int adamvs_conv_t2_form(int N, int D, int hi, int wi);
+
+/* Folded blocks (no option: the choice rounds differently in the network, so it goes by the maps alone and a tile gives the same bits
+ * alone and in a batch).  The 16 matrix columns of an instruction need not lie in one row of the map: with a fold F they are 16 / F
+ * pixel groups of each of F rows, and a block is F times narrower and taller with the same sums per pixel.
+ *  - F(2x4, 3x3) (adamvs_conv3x3_dd_wino24): blocks of 8 x 32 pixels (F = 2) or 8 x 16 (F = 4) where they tile the map exactly and the
+ *    64-pixel blocks do not.  Every block shape gives the same bits.  In adamvs_cost_reg_net_2d, fp32, D >= 192: conv2 and conv4 take
+ *    the form on such blocks (widths 96, 48 of cfg2's inner levels); they stay in F(2x2, 3x3) elsewhere and under winograd = 3.
+ *  - the stride-2 pair form (option s2_pairs; D = 192, 384): blocks of 6 x 16 (F = 2) or 12 x 8 outputs (F = 4) where they tile the map
+ *    and the 32-column block does not divide the row (conv3, conv5 of cfg2), behind the small-grid rule of conv_rows2.
+ * adamvs_conv_wino24_fold: the blocks a layer on h x w maps takes, 1 (64 pixels wide), 2 or 4.  adamvs_cost_reg_fold: conv2 / conv4 of
+ * the network on h x w maps at that level: 2 or 4, 0 where the layer stays in F(2x2, 3x3) (N does not enter).  adamvs_conv_s2_form:
+ * a stride-2 layer (mode 1, no skip) of N maps of hi x wi inputs: 0 a direct kernel, 1 the pair form on blocks of 3 x 32 outputs, 2 / 4
+ * on folded blocks.  `blocks` = -1 asks what the plain entry points do; another value what the *_blocks entry points below do with
+ * it.  -1: bad arguments / unsupported D.
+ * The *_blocks entry points exist for A/B timing and tests: the plain entry point's arguments plus `blocks` --
+ * adamvs_conv3x3_dd_wino24_blocks: -1 by the map, 1 the 64-pixel blocks, 2 / 4 that fold wherever the width is a multiple of 32 / 16;
+ * adamvs_conv3x3_dd_s2_blocks (fp32, stride 2, no skip): -1 by the map, 0 the selection of before (no folded blocks), 2 / 4 that fold
+ * wherever the output width is a multiple of 16 / 8; adamvs_cost_reg_net_2d_blocks (fp32): -1 as adamvs_cost_reg_net_2d, 0 no folded
+ * blocks in any layer: the kernels of before, bit for bit. */
+int adamvs_conv_wino24_fold(int h, int w, int blocks);
+int adamvs_conv_s2_form(int N, int D, int hi, int wi, int blocks);
+int adamvs_cost_reg_fold(int N, int D, int h, int w);
+int adamvs_conv3x3_dd_wino24_blocks(const float* in, const float* wpk, const float* bias, const float* skip, float* out, int N, int D,
+                                    int h, int w, int relu, int blocks, void* stream);
+int adamvs_conv3x3_dd_s2_blocks(const float* in, const float* wpk, const float* bias, float* out, int N, int D, int hi, int wi, int relu,
+                                int blocks, void* stream);
+int adamvs_cost_reg_net_2d_blocks(const float* x, const float* wpk, size_t wpk_floats, float* score, int N, int D, int h, int w, int blocks,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* phases of a stage.  VIEW_WEIGHTS may run in a call of its own: its results are the view_weight / pair_depth OUTPUT
  * tensors, which a later call reads back.  AGGREGATE, RECURRENCE and SOFT_ARGMIN form one chain over chunks of 32
