@@ -101,6 +101,12 @@ class ContourStats(ctypes.Structure):
                 ("ms_count", ctypes.c_float), ("ms_rank", ctypes.c_float)]
 
 
+class DrainStats(ctypes.Structure):
+    """adamvs_drain_stats"""
+    _fields_ = [("rounds", ctypes.c_int), ("launched", ctypes.c_int), ("converged", ctypes.c_int), ("reserved", ctypes.c_int),
+                ("links", ctypes.c_long), ("vertices", ctypes.c_long), ("ms", ctypes.c_float), ("reserved2", ctypes.c_float)]
+
+
 class MeshView(ctypes.Structure):
     """adamvs_mesh_view"""
     _fields_ = [("K", ctypes.c_float * 9), ("R", ctypes.c_float * 9), ("c", ctypes.c_float * 3), ("H", ctypes.c_int), ("W", ctypes.c_int),
@@ -261,6 +267,16 @@ SIGNATURES = {
                                   ctypes.c_void_p, ctypes.POINTER(ContourStats), c_st]),
     "adamvs_contour_lines": (c_i, [c_i, c_i, ctypes.c_void_p, c_i, ctypes.POINTER(c_i), ctypes.c_long, ctypes.c_long] + [ctypes.c_void_p] * 8
                              + [ctypes.c_long] + [ctypes.c_void_p] * 5 + [c_st]),
+    "adamvs_drain_workspace_bytes": (ctypes.c_long, [c_i, c_i]),
+    "adamvs_drain_fill": (c_i, [c_i, c_i, ctypes.c_void_p, c_i, c_i, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.POINTER(DrainStats), c_st]),
+    "adamvs_drain_direction": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, c_st]),
+    "adamvs_drain_accumulate": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.POINTER(DrainStats), c_st]),
+    "adamvs_drain_streams": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(DrainStats), c_st]),
+    "adamvs_drain_links": (c_i, [c_i, c_i] + [ctypes.c_void_p] * 4 + [ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_long]
+                           + [ctypes.c_void_p] * 5 + [c_st]),
     "adamvs_mesh_check_views": (c_i, [ctypes.POINTER(MeshView), c_i]),
     "adamvs_tsdf_integrate": (c_i, [ctypes.POINTER(MeshBrick), ctypes.c_void_p, c_i, ctypes.c_void_p, c_i, c_f, ctypes.c_void_p,
                                     ctypes.c_void_p, c_st]),
@@ -434,6 +450,9 @@ CONTOUR_Q_SCALE = 256            # ADAMVS_CONTOUR_Q_SCALE: quantised height abov
 CONTOUR_MAX_ABS_M = 8191         # ADAMVS_CONTOUR_MAX_ABS_M: |z - z_ref| of a valid cell, metres
 CONTOUR_NOT_CONVERGED = -2       # ADAMVS_CONTOUR_NOT_CONVERGED
 CONTOUR_TOO_MANY = -3            # ADAMVS_CONTOUR_TOO_MANY
+DRAIN_TILE = 32                  # ADAMVS_DRAIN_TILE: cells of a side of a tile of the fill
+DRAIN_UNITS = 65536              # ADAMVS_DRAIN_UNITS: units of r and F per metre
+DRAIN_NOT_A_FOREST = -2          # ADAMVS_DRAIN_NOT_A_FOREST
 MESH_TILE = 256                  # ADAMVS_MESH_TILE: samples / cubes per workgroup of the mesh kernels
 MESH_BRICKS = (32, 64, 128)      # the brick sizes B
 MESH_MAX_VIEWS = 65535           # ADAMVS_MESH_MAX_VIEWS

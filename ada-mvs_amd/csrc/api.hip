@@ -901,6 +901,73 @@ extern "C" int adamvs_contour_lines(int W, int H, const int* s, int K, const int
                               line_level, line_closed, vertex, (hipStream_t)stream);
 }
 
+// ---- Drainage (dsm_drainage.hip)
+extern "C" long adamvs_drain_workspace_bytes(int W, int H) {
+  if (int rc = dsm_fill_check_size(W, H, "drain_workspace_bytes")) return rc;
+  return drain_workspace_bytes(W, H);
+}
+
+extern "C" int adamvs_drain_fill(int W, int H, const int* s, int smooth_passes, int max_rounds, void* workspace, long workspace_bytes, int* r,
+                                 int* F, adamvs_drain_stats* stats, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "drain_fill")) return rc;
+  ADAMVS_CHECK_ARG(s && workspace && r && F && stats, "drain_fill: null pointer");
+  ADAMVS_CHECK_ARG(smooth_passes >= 0 && smooth_passes <= 2, "drain_fill: smooth_passes=%d (0 .. 2)", smooth_passes);
+  ADAMVS_CHECK_ARG(max_rounds >= 1, "drain_fill: max_rounds=%d must be >= 1", max_rounds);
+  const long need = drain_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "drain_fill: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{s, 4 * n}, {workspace, need}, {r, 4 * n}, {F, 4 * n}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 4), "drain_fill: s, r, F and the workspace must not overlap");
+  return launch_drain_fill(W, H, s, smooth_passes, max_rounds, workspace, r, F, stats, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_drain_direction(int W, int H, const int* F, unsigned char* dir, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "drain_direction")) return rc;
+  ADAMVS_CHECK_ARG(F && dir, "drain_direction: null pointer");
+  const long n = (long)W * H;
+  const BldBuffer b[] = {{F, 4 * n}, {dir, n}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 2), "drain_direction: F and dir must not overlap");
+  return launch_drain_direction(W, H, F, dir, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_drain_accumulate(int W, int H, const unsigned char* dir, const int* value, void* workspace, long workspace_bytes,
+                                       int* acc, int* root, adamvs_drain_stats* stats, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "drain_accumulate")) return rc;
+  ADAMVS_CHECK_ARG(dir && workspace && acc && root && stats, "drain_accumulate: null pointer");
+  const long need = drain_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "drain_accumulate: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{dir, n}, {workspace, need}, {acc, 4 * n}, {root, 4 * n}, {value, 4 * n}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, value ? 5 : 4), "drain_accumulate: dir, value, acc, root and the workspace must not overlap");
+  return launch_drain_accumulate(W, H, dir, value, workspace, acc, root, stats, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_drain_streams(int W, int H, const unsigned char* dir, const int* acc, int min_cells, void* workspace, long workspace_bytes,
+                                    unsigned char* nd, int* link, int* pos, adamvs_drain_stats* stats, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "drain_streams")) return rc;
+  ADAMVS_CHECK_ARG(dir && acc && workspace && nd && link && pos && stats, "drain_streams: null pointer");
+  ADAMVS_CHECK_ARG(min_cells >= 1, "drain_streams: min_cells=%d must be >= 1", min_cells);
+  const long need = drain_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "drain_streams: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{dir, n}, {acc, 4 * n}, {workspace, need}, {nd, n}, {link, 4 * n}, {pos, 4 * n}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 6), "drain_streams: dir, acc, nd, link, pos and the workspace must not overlap");
+  return launch_drain_streams(W, H, dir, acc, min_cells, workspace, nd, link, pos, stats, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_drain_links(int W, int H, const unsigned char* dir, const unsigned char* nd, const int* link, const int* pos, long L,
+                                  long P, void* workspace, long workspace_bytes, int* link_first, int* link_head, int* link_end, int* link_to,
+                                  int* vertex, void* stream) {
+  if (int rc = dsm_fill_check_size(W, H, "drain_links")) return rc;
+  const long need = drain_workspace_bytes(W, H), n = (long)W * H;
+  ADAMVS_CHECK_ARG(L >= 0 && L <= n && P >= 2 * L && P < (1L << 31) && (L > 0 || P == 0), "drain_links: L=%ld links with P=%ld vertices (L <= W H, 2 L <= P < 2^31)",
+                   L, P);
+  ADAMVS_CHECK_ARG(dir && nd && link && pos && workspace && link_first, "drain_links: null pointer");
+  ADAMVS_CHECK_ARG(L == 0 || (link_head && link_end && link_to && vertex), "drain_links: null pointer");
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "drain_links: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{dir, n}, {nd, n}, {link, 4 * n}, {pos, 4 * n}, {workspace, need}, {link_first, 4 * (L + 1)}, {link_head, 4 * L},
+                         {link_end, 4 * L}, {link_to, 4 * L}, {vertex, 4 * P}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, L ? 10 : 6), "drain_links: the inputs, the outputs and the workspace must not overlap");
+  return launch_drain_links(W, H, dir, nd, link, pos, L, P, workspace, link_first, link_head, link_end, link_to, vertex, (hipStream_t)stream);
+}
+
 // ---- TSDF mesh (mesh.hip): every argument is checked here, before any launch
 static int mesh_check_brick(const adamvs_mesh_brick* b, const char* what) {
   ADAMVS_CHECK_ARG(b, "%s: null brick", what);

@@ -12,10 +12,9 @@
 //   k_ctr_count         one workgroup per tile of CTR_T x CTR_T blocks: the (CTR_T + 1)^2 samples and the level table go to LDS,
 //                       a lane takes a block, two binary searches give the range of levels that cross it and two more the
 //                       saddle sub-range; the count is the sum of the two lengths.
-//   k_ctr_scan_*        the exclusive scan used three times (block counts -> offsets, start flags -> line numbers, vertex counts
-//                       -> line_first): workgroups of 256 scan their elements with block_exclusive_scan, k_fusion_scan scans
-//                       the workgroup totals, a third kernel adds them.  The total is also summed in 64 bits, so an overflow of
-//                       the 32-bit offsets is seen on the host before anything reads them.
+//   raster_scan         the exclusive scan of raster_prims.h, used three times (block counts -> offsets, start flags -> line
+//                       numbers, vertex counts -> line_first).  The total is also summed in 64 bits, so an overflow of the
+//                       32-bit offsets is seen on the host before anything reads them.
 //   k_ctr_segments      one lane per SEGMENT, not per block: the lane finds its block by a binary search in the scanned offsets
 //                       (23 steps for 2^23 cells, the upper ones shared by the whole wave and the lower ones a few cache lines
 //                       apart), its level and entry edge from the block's two ranges.  A cliff with hundreds of levels in one
@@ -58,6 +57,8 @@ constexpr int CTR_PHASE_ROUNDS = ADAMVS_CONTOUR_MAX_ROUNDS / 2;
 constexpr int CTR_NONE = INT_MIN;                // s outside V
 static_assert(CTR_T == 64, "a wave takes one row of a tile");
 static_assert(CTR_PHASE_ROUNDS % CTR_RANK_CHUNK == 0 && CTR_PHASE_ROUNDS >= 32, "2^31 segments need 31 rounds and one that changes nothing");
+static_assert(CTR_THREADS == RASTER_THREADS && CTR_PHASE_ROUNDS == RASTER_RANK_ROUNDS && CTR_RANK_CHUNK == RASTER_RANK_CHUNK,
+              "the scan and the ranking phases of raster_prims.h");
 
 // the control block at the head of either workspace
 constexpr long CTR_OFF_CHANGED = 0;              // unsigned [ADAMVS_CONTOUR_MAX_ROUNDS]: phase 1, then phase 2
@@ -276,45 +277,10 @@ __global__ __launch_bounds__(CTR_THREADS) void k_ctr_count(int W, int H, int til
   }
 }
 
-// ---- the scan ---------------------------------------------------------------------------------------------------------------
-// exclusive scan of a workgroup's 256 elements into `out`, its total into part[blockIdx.x] and into the 64-bit total
-__global__ __launch_bounds__(CTR_THREADS) void k_ctr_scan_local(long n, const unsigned* __restrict__ in, unsigned* __restrict__ out,
-                                                                unsigned* __restrict__ part, unsigned long long* total64) {
-  const long c = (long)blockIdx.x * CTR_THREADS + threadIdx.x;
-  const unsigned v = c < n ? in[c] : 0u;
-  unsigned total;
-  const unsigned ex = block_exclusive_scan(v, &total);
-  if (c < n) out[c] = ex;
-  if (threadIdx.x == 0) {
-    part[blockIdx.x] = total;
-    if (total) atomicAdd(total64, (unsigned long long)total);
-  }
-}
-
-// out[c] += part_off[workgroup of c]; out[n] = the total
-__global__ __launch_bounds__(CTR_THREADS) void k_ctr_scan_add(long n, const unsigned* __restrict__ part_off, unsigned nb, unsigned* __restrict__ out) {
-  const long c = (long)blockIdx.x * CTR_THREADS + threadIdx.x;
-  if (c < n) out[c] += part_off[blockIdx.x];
-  if (c == n) out[n] = part_off[nb];
-}
-
+// ---- the scan: raster_prims.h raster_scan ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(CTR_THREADS) void k_ctr_widen(long n, const unsigned* __restrict__ in, long long* __restrict__ out) {
   const long c = (long)blockIdx.x * CTR_THREADS + threadIdx.x;
   if (c < n) out[c] = (long long)in[c];
-}
-
-// in [n] -> out [n + 1] (another buffer), 1 <= n < 2^31.  Enqueues only; *total64 (device) holds the sum afterwards, and the
-// caller compares it with 2^31 before anything trusts the 32-bit offsets.
-static int ctr_scan(long n, const unsigned* in, unsigned* out, unsigned* part, unsigned* part_off, unsigned long long* total64, hipStream_t st) {
-  const unsigned nb = ctr_blocks(n);
-  const hipError_t e = hipMemsetAsync(total64, 0, 8, st);
-  if (e != hipSuccess) return set_error((int)e, "contour scan: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(k_ctr_scan_local, dim3(nb), dim3(CTR_THREADS), 0, st, n, in, out, part, total64);
-  ADAMVS_CHECK_LAUNCH("contour_scan_local");
-  if (int rc = launch_fusion_scan(part, part_off, (int)nb, st)) return rc;
-  hipLaunchKernelGGL(k_ctr_scan_add, dim3(ctr_blocks(n + 1)), dim3(CTR_THREADS), 0, st, n, part_off, nb, out);
-  ADAMVS_CHECK_LAUNCH("contour_scan_add");
-  return 0;
 }
 
 // ---- the segments -----------------------------------------------------------------------------------------------------------
@@ -469,21 +435,7 @@ __global__ __launch_bounds__(CTR_THREADS) void k_ctr_rank_cut(long N, const int2
   if (threadIdx.x == 0 && s_n) atomicAdd(lines, (unsigned long long)s_n);
 }
 
-// phase 2: y = the succ steps from the ancestor to the segment
-__global__ __launch_bounds__(CTR_THREADS) void k_ctr_rank_dist(long N, const int2* __restrict__ cur, int2* __restrict__ nxt, unsigned* changed) {
-  const long n = (long)blockIdx.x * CTR_THREADS + threadIdx.x;
-  bool moved = false;
-  if (n < N) {
-    int2 v = cur[n];
-    if (v.x >= 0 && (long)v.x < N) {
-      const int2 a = cur[v.x];
-      v = make_int2(a.x, v.y + a.y);
-      moved = true;
-    }
-    nxt[n] = v;
-  }
-  if (__ballot(moved) != 0ull && (threadIdx.x & 63) == 0) changed[0] = 1u;
-}
+// phase 2, y = the succ steps from the ancestor to the segment: raster_prims.h k_raster_rank_dist
 
 __global__ __launch_bounds__(CTR_THREADS) void k_ctr_rank_store(long N, const int2* __restrict__ res, int* __restrict__ rank) {
   const long n = (long)blockIdx.x * CTR_THREADS + threadIdx.x;
@@ -593,7 +545,7 @@ int launch_contour_count(int W, int H, const int* s, int K, const int* lev, void
   const int tiles_x = cdiv(W, CTR_T), tiles_y = cdiv(H, CTR_T);
   hipLaunchKernelGGL(k_ctr_count, dim3((unsigned)((long)tiles_x * tiles_y)), dim3(CTR_THREADS), 0, st, W, H, tiles_x, s, w.lev, K, count);
   ADAMVS_CHECK_LAUNCH("contour_count");
-  if (int rc = ctr_scan(n, (const unsigned*)count, w.off, w.part, w.part_off, total64, st)) return rc;
+  if (int rc = raster_scan("contour", n, (const unsigned*)count, w.off, w.part, w.part_off, total64, st)) return rc;
   clock.mark(1, st);
   unsigned long long total = 0;
   hipError_t e = hipMemcpyAsync(&total, total64, 8, hipMemcpyDeviceToHost, st);
@@ -621,31 +573,6 @@ int launch_contour_segments(int W, int H, const int* s, int K, const int* lev, l
   return 0;
 }
 
-// One phase: rounds base .. base + CTR_PHASE_ROUNDS - 1 of the changed words; the result is in buf[*where] afterwards.
-template <typename Kernel>
-static int ctr_rank_phase(Kernel kernel, const char* name, long N, int2* const buf[2], int* where, unsigned* changed, int base, int* moved,
-                          int* launched, bool* converged, hipStream_t st) {
-  unsigned host[CTR_PHASE_ROUNDS];
-  *moved = 0;
-  *converged = false;
-  for (int done = 0; done < CTR_PHASE_ROUNDS && !*converged; done += CTR_RANK_CHUNK) {
-    for (int k = done; k < done + CTR_RANK_CHUNK; ++k) {
-      hipLaunchKernelGGL(kernel, dim3(ctr_blocks(N)), dim3(CTR_THREADS), 0, st, N, (const int2*)buf[*where], buf[*where ^ 1], changed + base + k);
-      ADAMVS_CHECK_LAUNCH(name);
-      *where ^= 1;
-      ++*launched;
-    }
-    hipError_t e = hipMemcpyAsync(host, changed + base, sizeof(host), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return set_error((int)e, "%s: %s", name, hipGetErrorString(e));
-    for (int k = done; k < done + CTR_RANK_CHUNK && !*converged; ++k) {
-      if (host[k]) *moved = k + 1;
-      else *converged = true;        // a round that changes nothing leaves every later one without a change: the result stands
-    }
-  }
-  return 0;
-}
-
 int launch_contour_rank(long N, const int* pred, void* workspace, int* start, int* rank, uint8_t* closed, adamvs_contour_stats* stats,
                         hipStream_t st) {
   stats->rounds = stats->rounds_min = stats->rounds_dist = stats->launched = 0;
@@ -665,13 +592,13 @@ int launch_contour_rank(long N, const int* pred, void* workspace, int* start, in
   bool ok = false;
   hipLaunchKernelGGL(k_ctr_rank_init, dim3(ctr_blocks(N)), dim3(CTR_THREADS), 0, st, N, pred, w.buf[0]);
   ADAMVS_CHECK_LAUNCH("contour_rank_init");
-  if (int rc = ctr_rank_phase(k_ctr_rank_min, "contour_rank_min", N, w.buf, &where, changed, 0, &stats->rounds_min, &stats->launched, &ok, st)) return rc;
+  if (int rc = raster_rank_phase(k_ctr_rank_min, "contour_rank_min", N, w.buf, &where, changed, 0, &stats->rounds_min, &stats->launched, &ok, st)) return rc;
   if (!ok) return set_error(ADAMVS_CONTOUR_NOT_CONVERGED, "contour_rank: minima still moving after %d rounds", CTR_PHASE_ROUNDS);
   hipLaunchKernelGGL(k_ctr_rank_cut, dim3(ctr_blocks(N)), dim3(CTR_THREADS), 0, st, N, (const int2*)w.buf[where], pred, w.buf[where ^ 1], start, closed,
                      lines);
   ADAMVS_CHECK_LAUNCH("contour_rank_cut");
   where ^= 1;
-  if (int rc = ctr_rank_phase(k_ctr_rank_dist, "contour_rank_dist", N, w.buf, &where, changed, CTR_PHASE_ROUNDS, &stats->rounds_dist, &stats->launched,
+  if (int rc = raster_rank_phase(k_raster_rank_dist, "contour_rank_dist", N, w.buf, &where, changed, CTR_PHASE_ROUNDS, &stats->rounds_dist, &stats->launched,
                               &ok, st))
     return rc;
   if (!ok) return set_error(ADAMVS_CONTOUR_NOT_CONVERGED, "contour_rank: distances still moving after %d rounds", CTR_PHASE_ROUNDS);
@@ -705,7 +632,7 @@ int launch_contour_lines(int W, int H, const int* s, int K, const int* lev, long
   unsigned* flag = (unsigned*)w.buf[0];                              // the ranking's buffers are free again
   hipLaunchKernelGGL(k_ctr_line_flag, dim3(ctr_blocks(N)), dim3(CTR_THREADS), 0, st, N, start, flag);
   ADAMVS_CHECK_LAUNCH("contour_line_flag");
-  if (int rc = ctr_scan(N, flag, w.lineno, w.part, w.part_off, total64, st)) return rc;
+  if (int rc = raster_scan("contour", N, flag, w.lineno, w.part, w.part_off, total64, st)) return rc;
   unsigned long long total = 0;
   hipError_t e = hipMemcpyAsync(&total, total64, 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -717,7 +644,7 @@ int launch_contour_lines(int W, int H, const int* s, int K, const int* lev, long
   hipLaunchKernelGGL(k_ctr_line_tails, dim3(ctr_blocks(N)), dim3(CTR_THREADS), 0, st, N, M, succ, start, rank, closed, seg_level, (const unsigned*)w.lineno,
                      w.count, line_start, line_level, line_closed);
   ADAMVS_CHECK_LAUNCH("contour_line_tails");
-  if (int rc = ctr_scan(M, w.count, w.first, w.part, w.part_off, total64, st)) return rc;
+  if (int rc = raster_scan("contour", M, w.count, w.first, w.part, w.part_off, total64, st)) return rc;
   e = hipMemcpyAsync(&total, total64, 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return set_error((int)e, "contour_lines: %s", hipGetErrorString(e));

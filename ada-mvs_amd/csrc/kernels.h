@@ -246,6 +246,18 @@ int launch_contour_lines(int W, int H, const int* s, int K, const int* lev, long
                          const int* seg_level, const int* succ, const int* start, const int* rank, const uint8_t* closed, void* workspace,
                          long long* line_first, int* line_start, int* line_level, uint8_t* line_closed, long long* vertex, hipStream_t st);
 
+// dsm_drainage.hip: fill, D8 directions, accumulation with roots, stream links (include/adamvs_hip.h, "Drainage")
+long drain_workspace_bytes(int W, int H);
+int launch_drain_fill(int W, int H, const int* s, int smooth_passes, int max_rounds, void* workspace, int* r, int* F, adamvs_drain_stats* stats,
+                      hipStream_t st);
+int launch_drain_direction(int W, int H, const int* F, uint8_t* dir, hipStream_t st);
+int launch_drain_accumulate(int W, int H, const uint8_t* dir, const int* value, void* workspace, int* acc, int* root, adamvs_drain_stats* stats,
+                            hipStream_t st);
+int launch_drain_streams(int W, int H, const uint8_t* dir, const int* acc, int min_cells, void* workspace, uint8_t* nd, int* link, int* pos,
+                         adamvs_drain_stats* stats, hipStream_t st);
+int launch_drain_links(int W, int H, const uint8_t* dir, const uint8_t* nd, const int* link, const int* pos, long L, long P, void* workspace,
+                       int* link_first, int* link_head, int* link_end, int* link_to, int* vertex, hipStream_t st);
+
 // mesh.hip: TSDF integration and marching-tetrahedra extraction per brick (include/adamvs_hip.h, "TSDF mesh")
 constexpr int MESH_TILE = ADAMVS_MESH_TILE;
 int launch_tsdf_integrate(const adamvs_mesh_brick& b, const adamvs_mesh_view* views, int nviews, const int* list, int nlist, float* tsdf,

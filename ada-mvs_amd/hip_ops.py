@@ -1158,6 +1158,83 @@ def contour_lines(s, lev, segments, start, rank, closed, M, workspace=None):
     return line_first, line_start, line_level, line_closed, vertex
 
 
+# ---- Drainage (csrc/dsm_drainage.hip; include/adamvs_hip.h "Drainage") ------------------------------------------------------
+def _drain_stats(st):
+    return dict(rounds=int(st.rounds), launched=int(st.launched), converged=int(st.converged), ms=float(st.ms))
+
+
+def drain_fill(s, smooth_passes, max_rounds, workspace=None):
+    """adamvs_drain_fill: s [H, W] int32 (device; contour_surface's, of the same smooth_passes) -> (r int32 [H, W], F int32
+    [H, W], stats dict(rounds, launched, converged, ms), the workspace).  Blocks until done.  F is the fill only if converged."""
+    s = _raster(s, "s", torch.int32)
+    H, W = s.shape
+    workspace = _workspace("drain_workspace_bytes", s.device, workspace, W, H)
+    r, F = torch.empty_like(s), torch.empty_like(s)
+    st = _lib.DrainStats()
+    check(_lib.load().adamvs_drain_fill(W, H, _p(s), int(smooth_passes), int(max_rounds), _p(workspace), workspace.numel(), _p(r), _p(F),
+                                        ctypes.byref(st), _stream()), "drain_fill")
+    return r, F, _drain_stats(st), workspace
+
+
+def drain_direction(F):
+    """adamvs_drain_direction: F [H, W] int32 (device) -> dir uint8 [H, W].  Enqueued on the current stream."""
+    F = _raster(F, "F", torch.int32)
+    H, W = F.shape
+    d = torch.empty(H, W, device=F.device, dtype=torch.uint8)
+    check(_lib.load().adamvs_drain_direction(W, H, _p(F), _p(d), _stream()), "drain_direction")
+    return d
+
+
+def drain_accumulate(direction, value=None, workspace=None):
+    """adamvs_drain_accumulate: dir [H, W] uint8 (device), value [H, W] int32 or None (1 per valid cell) -> (acc int32 [H, W],
+    root int32 [H, W], stats, the workspace).  Blocks until done."""
+    direction = _raster(direction, "dir", torch.uint8)
+    H, W = direction.shape
+    if value is not None:
+        value = _raster(value, "value", torch.int32, direction.shape)
+    workspace = _workspace("drain_workspace_bytes", direction.device, workspace, W, H)
+    acc = torch.empty(H, W, device=direction.device, dtype=torch.int32)
+    root = torch.empty_like(acc)
+    st = _lib.DrainStats()
+    check(_lib.load().adamvs_drain_accumulate(W, H, _p(direction), None if value is None else _p(value), _p(workspace), workspace.numel(),
+                                              _p(acc), _p(root), ctypes.byref(st), _stream()), "drain_accumulate")
+    return acc, root, _drain_stats(st), workspace
+
+
+def drain_streams(direction, acc, min_cells, workspace=None):
+    """adamvs_drain_streams: -> (nd uint8 [H, W], link int32 [H, W], pos int32 [H, W], L, P, stats, the workspace that holds the
+    vertex offsets for drain_links).  Blocks until done."""
+    direction = _raster(direction, "dir", torch.uint8)
+    acc = _raster(acc, "acc", torch.int32, direction.shape)
+    H, W = direction.shape
+    workspace = _workspace("drain_workspace_bytes", direction.device, workspace, W, H)
+    nd = torch.empty_like(direction)
+    link, pos = torch.empty_like(acc), torch.empty_like(acc)
+    st = _lib.DrainStats()
+    check(_lib.load().adamvs_drain_streams(W, H, _p(direction), _p(acc), int(min_cells), _p(workspace), workspace.numel(), _p(nd), _p(link),
+                                           _p(pos), ctypes.byref(st), _stream()), "drain_streams")
+    return nd, link, pos, int(st.links), int(st.vertices), _drain_stats(st), workspace
+
+
+def drain_links(direction, nd, link, pos, L, P, workspace):
+    """adamvs_drain_links: `workspace` as drain_streams returned it -> (link_first int32 [L + 1], link_head, link_end, link_to
+    int32 [L], vertex int32 [P]), on the device.  Enqueued on the current stream after one read-back."""
+    direction = _raster(direction, "dir", torch.uint8)
+    nd = _raster(nd, "nd", torch.uint8, direction.shape)
+    link = _raster(link, "link", torch.int32, direction.shape)
+    pos = _raster(pos, "pos", torch.int32, direction.shape)
+    workspace = _dev_as(workspace, "workspace", torch.uint8)
+    H, W = direction.shape
+    L, P = int(L), int(P)
+    dev = direction.device
+    link_first = torch.empty(L + 1, device=dev, dtype=torch.int32)
+    link_head, link_end, link_to = (torch.empty(L, device=dev, dtype=torch.int32) for _ in range(3))
+    vertex = torch.empty(P, device=dev, dtype=torch.int32)
+    check(_lib.load().adamvs_drain_links(W, H, _p(direction), _p(nd), _p(link), _p(pos), L, P, _p(workspace), workspace.numel(), _p(link_first),
+                                         _pn(link_head), _pn(link_end), _pn(link_to), _pn(vertex), _stream()), "drain_links")
+    return link_first, link_head, link_end, link_to, vertex
+
+
 # ---- TSDF mesh (csrc/mesh.hip; driven brick by brick by ada_mvs_amd/mesh.py) ------------------------------------------------
 # Per-sample state as torch tensors of the signed type of each C type's width: weight int16 = uint16, rgba int32 = uint32
 # (little-endian r g b a), cube_code int32 = uint32, faces int32 = uint32.

@@ -1184,6 +1184,95 @@ int adamvs_contour_lines(int W, int H, const int* s, int K, const int* lev, long
                          void* workspace, long workspace_bytes, long long* line_first, int* line_start, int* line_level,
                          unsigned char* line_closed, long long* vertex, void* stream);
 
+/* ---- Drainage (after the ground filter, next to the contours): the depression-free surface, D8 flow directions, flow
+ * accumulation, catchments and the stream links of a height raster ------------------------------------------------------------
+ * ada-mvs_amd/drainage.py route(); drainage_whu.py is the CLI.  Input: the surface s of _contour_surface (step 1 of Contours:
+ * the heights above z_ref in 1 / (256 16^passes) m, INT32_MIN outside V, refused beyond 8191 m).  W H <= ADAMVS_DSM_MAX_CELLS
+ * (< 2^30).  A cell is c = (i, j), its index i W + j, rows running south.  The eight neighbours in the order of the tie rule, with
+ * their ESRI codes: E 1, SE 2, S 4, SW 8, W 16, NW 32, N 64, NE 128.  Priority-flood, the topological walk of the accumulation and
+ * "follow the stream", restated without a visiting order.  Every step is on integers.
+ *
+ * 1. Routing surface.  r(c) = s(c) 2^(8 - 4 passes) on V: ADAMVS_DRAIN_UNITS = 65536 units per metre whatever the smoothing,
+ *    |r| < 2^29; INT32_MIN outside V.
+ * 2. Edge cells.  A cell of V is an EDGE cell iff it lies in the first or last row or column or one of its eight neighbours is
+ *    outside V.  Edge cells are the outlets.  Every other cell of V has eight neighbours in V.
+ * 3. Fill.  F int32 [H][W]: F = r at the edge cells, INT32_MIN outside V, and at every other cell of V
+ *    F(c) = max(r(c), min over the eight neighbours n of F(n) + 1): one unit per step, so no flat survives and every such cell
+ *    has a neighbour with a smaller F.  The solution is unique (induct over the cells in ascending F) and equals priority-flood
+ *    with an epsilon of one unit.  |F| < 2^30.
+ * 4. Directions.  dir uint8 [H][W]: 255 outside V, 0 at an edge cell; elsewhere the code of the neighbour with the steepest
+ *    positive drop d = F(c) - F(n), an orthogonal drop a against a diagonal drop b compared as 2 a^2 against b^2 in int64, ties
+ *    to the first neighbour in the order above.  The RECEIVER of c is that neighbour.  F falls strictly along receivers: a forest
+ *    rooted at the edge cells.
+ * 5. Accumulation.  acc int32 [H][W]: acc(c) = the sum of value over the cells whose path along the receivers passes through c, c
+ *    included; value = 1 on V for a null pointer (the cell count), and with value = "a stream cell without a stream donor" the
+ *    Shreve magnitude.  0 outside V.  root int32 [H][W]: the outlet that c's path ends at, -1 outside V.
+ * 6. Streams.  The stream cells are the cells of V with acc >= min_cells; the receiver of a stream cell is one.  nd uint8 [H][W]:
+ *    the stream cells among the eight neighbours whose receiver is c, 255 where c is no stream cell.  HEADS are the stream cells
+ *    with nd != 1: sources and junctions.  A head with a receiver heads a LINK: itself, the stream cells with nd = 1 below it (its
+ *    OWN cells, one chain along the receivers) and, as the last vertex, the receiver of its last own cell if that cell has one: a
+ *    head again, shared with the other links that end there and the first vertex of its own link if it has a receiver.  A head
+ *    that is an outlet heads no link.  Links are numbered 0 .. L - 1 by ascending head index.  link int32 [H][W]: the link that
+ *    owns the cell, pos int32 [H][W]: its receiver steps below the head; -1 both where no link owns the cell.
+ * 7. Link table.  link_first int32 [L + 1] (vertex offsets, link_first[L] = P), link_head, link_end (the last vertex), link_to
+ *    (the link that link_end heads, -1 if none: an outlet) int32 [L]; vertex int32 [P]: the cells of link l at link_first[l] + pos
+ *    and link_end after them, running downstream.  P < 2^31.
+ * 8. The host (drainage.py) takes the cell centres as coordinates in fp64, the length and drop of every link, its
+ *    upstream_cells (acc of its last own cell), Strahler orders in one pass over the links by ascending acc(head), numbers the
+ *    outlets with acc >= min_cells 1 .. K by cell index for the basin raster, drops short links and writes the files.
+ *
+ * The split into calls (csrc/dsm_drainage.hip, whose head gives the reasons).  _drain_fill: r, the edge test and the start of F
+ * (r at the edge cells, INT32_MAX elsewhere on V), then ROUNDS: in a round one workgroup per tile of ADAMVS_DRAIN_TILE^2 cells
+ * loads its tile with a one-cell halo into LDS (34 x 34 words, 4.6 KB per workgroup), lowers its cells in place to a standstill
+ * and writes back those that fell.  The sweeps race; the operator is monotone and no value is ever below the fixed point, so
+ * every schedule ends at the same integers.  The schedule's bound: let t(c) = 0 at an edge cell and otherwise
+ * t(c) = max(1, min over the neighbours n with F(n) < F(c) of t(n) + [n lies in another tile]).  Cell c holds F(c) after round
+ * t(c) at the latest (a cell is final in the round in which a lower neighbour of its tile is, and one round after a lower
+ * neighbour of another tile), so at most max t rounds change a word and round max t + 1 changes none.  It runs until a round
+ * changes nothing or max_rounds have been launched and returns stats.rounds (the rounds that changed a word, <= max t),
+ * stats.launched (whole chunks of four while the cap allows; one read-back of the changed words, a stream synchronise, per chunk)
+ * and stats.converged; without convergence F still holds INT32_MAX or values above the fixed point and must not be used.
+ * _drain_direction: one lane per cell.  _drain_accumulate: pointer doubling, a pair (2^k-th ancestor or ~root, sum over the
+ * descendants nearer than 2^k) per cell, double-buffered; a round adds every pair's sum to its ancestor's with an integer atomic;
+ * ceil(log2(longest path + 1)) rounds and one that moves nothing, at most 32, else (dir holds a cycle: not one of
+ * _drain_direction's) the error return ADAMVS_DRAIN_NOT_A_FOREST.  It blocks.  _drain_streams: nd and the donors in closed form,
+ * the scan of the link heads, list ranking upstream by the distance rounds of the contours, link and pos, the tails' vertex
+ * counts and their scan.  It blocks and returns L in stats.links and P in stats.vertices; the offsets stay in the workspace,
+ * which _drain_links must be given unchanged.  _drain_links: the table and the vertices, every word stored by the one cell that
+ * owns it.  Integer atomics only: every output is bit-identical from run to run.  No workgroup waits on another.
+ * Everything is device memory except stats; a workspace of at least _drain_workspace_bytes(W, H) (about 20 bytes per cell),
+ * 256-byte aligned.  With L = 0 _drain_links succeeds and the arrays of length L or P may be null.  Argument errors (<0, before
+ * any launch): a null pointer other than value, W or H <= 0 or W H > ADAMVS_DSM_MAX_CELLS, smooth_passes outside 0 .. 2,
+ * max_rounds < 1, min_cells < 1, L outside 0 .. W H, P outside 2 L .. 2^31 - 1 (0 with L = 0), workspace_bytes below the query,
+ * any two of the buffers (workspace included) overlapping; after the read-back of one word, a P that is not the one the offsets
+ * give.  The query returns < 0 outside the limits. */
+#define ADAMVS_DRAIN_TILE 32             /* cells of a side of a tile of the fill */
+#define ADAMVS_DRAIN_UNITS 65536         /* units of r and F per metre */
+#define ADAMVS_DRAIN_NOT_A_FOREST (-2)
+
+typedef struct {
+  int rounds;        /* rounds that changed a word (fill), moved a pair (accumulate, streams) */
+  int launched;      /* rounds launched */
+  int converged;     /* 1 once a round changed nothing; 0: the cap was hit */
+  int reserved;
+  long links;        /* _drain_streams: L */
+  long vertices;     /* _drain_streams: P */
+  float ms;          /* device time of the call in milliseconds, its read-backs included; -1 if the events failed */
+  float reserved2;
+} adamvs_drain_stats;
+
+long adamvs_drain_workspace_bytes(int W, int H);
+int adamvs_drain_fill(int W, int H, const int* s, int smooth_passes, int max_rounds, void* workspace, long workspace_bytes, int* r, int* F,
+                      adamvs_drain_stats* stats, void* stream);
+int adamvs_drain_direction(int W, int H, const int* F, unsigned char* dir, void* stream);
+int adamvs_drain_accumulate(int W, int H, const unsigned char* dir, const int* value, void* workspace, long workspace_bytes, int* acc,
+                            int* root, adamvs_drain_stats* stats, void* stream);
+int adamvs_drain_streams(int W, int H, const unsigned char* dir, const int* acc, int min_cells, void* workspace, long workspace_bytes,
+                         unsigned char* nd, int* link, int* pos, adamvs_drain_stats* stats, void* stream);
+int adamvs_drain_links(int W, int H, const unsigned char* dir, const unsigned char* nd, const int* link, const int* pos, long L, long P,
+                       void* workspace, long workspace_bytes, int* link_first, int* link_head, int* link_end, int* link_to, int* vertex,
+                       void* stream);
+
 /* ---- TSDF mesh (after fuse_whu.py): the depth maps of all views integrated into a truncated signed-distance field on a voxel
  * grid, brick by brick, and its zero level set extracted as a coloured triangle mesh ---------------------------------------
  * ada-mvs_amd/mesh.py drives it per brick; mesh_whu.py is the CLI.  World axes: x east, y north, z up.
