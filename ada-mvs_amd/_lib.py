@@ -107,6 +107,12 @@ class DrainStats(ctypes.Structure):
                 ("links", ctypes.c_long), ("vertices", ctypes.c_long), ("ms", ctypes.c_float), ("reserved2", ctypes.c_float)]
 
 
+class SolarStats(ctypes.Structure):
+    """adamvs_solar_stats"""
+    _fields_ = [("lines", ctypes.c_long), ("spills", ctypes.c_long), ("deepest", ctypes.c_int), ("reserved", ctypes.c_int),
+                ("ms", ctypes.c_float), ("reserved2", ctypes.c_float)]
+
+
 class MeshView(ctypes.Structure):
     """adamvs_mesh_view"""
     _fields_ = [("K", ctypes.c_float * 9), ("R", ctypes.c_float * 9), ("c", ctypes.c_float * 3), ("H", ctypes.c_int), ("W", ctypes.c_int),
@@ -277,6 +283,17 @@ SIGNATURES = {
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(DrainStats), c_st]),
     "adamvs_drain_links": (c_i, [c_i, c_i] + [ctypes.c_void_p] * 4 + [ctypes.c_long, ctypes.c_long, ctypes.c_void_p, ctypes.c_long]
                            + [ctypes.c_void_p] * 5 + [c_st]),
+    "adamvs_solar_workspace_bytes": (ctypes.c_long, [c_i, c_i, c_i]),
+    "adamvs_solar_horizon": (c_i, [c_i, c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.POINTER(SolarStats), c_st]),
+    "adamvs_solar_svf": (c_i, [c_i, c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
+                               ctypes.c_double, ctypes.c_void_p, c_st]),
+    "adamvs_solar_expose": (c_i, [c_i, c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i, ctypes.POINTER(c_i),
+                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.POINTER(c_i),
+                                  ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
+                                  ctypes.c_void_p, c_st]),
+    "adamvs_solar_plane_sums": (c_i, [c_i, c_i, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, c_st]),
     "adamvs_mesh_check_views": (c_i, [ctypes.POINTER(MeshView), c_i]),
     "adamvs_tsdf_integrate": (c_i, [ctypes.POINTER(MeshBrick), ctypes.c_void_p, c_i, ctypes.c_void_p, c_i, c_f, ctypes.c_void_p,
                                     ctypes.c_void_p, c_st]),
@@ -453,6 +470,11 @@ CONTOUR_TOO_MANY = -3            # ADAMVS_CONTOUR_TOO_MANY
 DRAIN_TILE = 32                  # ADAMVS_DRAIN_TILE: cells of a side of a tile of the fill
 DRAIN_UNITS = 65536              # ADAMVS_DRAIN_UNITS: units of r and F per metre
 DRAIN_NOT_A_FOREST = -2          # ADAMVS_DRAIN_NOT_A_FOREST
+SOLAR_STACK_WINDOW = 16          # ADAMVS_SOLAR_STACK_WINDOW: stack entries per line kept in LDS
+SOLAR_MAX_SAMPLES = 8192         # ADAMVS_SOLAR_MAX_SAMPLES: rows of the sample table
+SOLAR_MAX_SIDE = 32768           # ADAMVS_SOLAR_MAX_SIDE
+SOLAR_HEAD_BYTES = 262656        # ADAMVS_SOLAR_HEAD_BYTES: the workspace of the exposure
+SOLAR_BAD_LABEL = -2             # ADAMVS_SOLAR_BAD_LABEL
 MESH_TILE = 256                  # ADAMVS_MESH_TILE: samples / cubes per workgroup of the mesh kernels
 MESH_BRICKS = (32, 64, 128)      # the brick sizes B
 MESH_MAX_VIEWS = 65535           # ADAMVS_MESH_MAX_VIEWS

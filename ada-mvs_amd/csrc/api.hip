@@ -968,6 +968,85 @@ extern "C" int adamvs_drain_links(int W, int H, const unsigned char* dir, const 
   return launch_drain_links(W, H, dir, nd, link, pos, L, P, workspace, link_first, link_head, link_end, link_to, vertex, (hipStream_t)stream);
 }
 
+// ---- Solar (dsm_solar.hip)
+static int solar_check_size(int W, int H, int K, const char* what) {
+  if (int rc = dsm_fill_check_size(W, H, what)) return rc;
+  ADAMVS_CHECK_ARG(W <= ADAMVS_SOLAR_MAX_SIDE && H <= ADAMVS_SOLAR_MAX_SIDE, "%s: grid W=%d H=%d (a side of at most %d cells)", what, W, H,
+                   ADAMVS_SOLAR_MAX_SIDE);
+  ADAMVS_CHECK_ARG(K == 8 || K == 16 || K == 32, "%s: K=%d directions (8, 16 or 32)", what, K);
+  return 0;
+}
+
+extern "C" long adamvs_solar_workspace_bytes(int W, int H, int K) {
+  if (int rc = solar_check_size(W, H, K, "solar_workspace_bytes")) return rc;
+  return solar_workspace_bytes(W, H, K);
+}
+
+extern "C" int adamvs_solar_horizon(int W, int H, int K, const int* s, void* workspace, long workspace_bytes, int* hz_n, int* hz_h,
+                                    adamvs_solar_stats* stats, void* stream) {
+  if (int rc = solar_check_size(W, H, K, "solar_horizon")) return rc;
+  ADAMVS_CHECK_ARG(s && workspace && hz_n && hz_h && stats, "solar_horizon: null pointer");
+  const long need = solar_workspace_bytes(W, H, K), n = (long)W * H;
+  ADAMVS_CHECK_ARG(workspace_bytes >= need, "solar_horizon: workspace of %ld bytes, %ld needed", workspace_bytes, need);
+  const BldBuffer b[] = {{s, 4 * n}, {workspace, need}, {hz_n, 4 * n * K}, {hz_h, 4 * n * K}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 4), "solar_horizon: s, hz_n, hz_h and the workspace must not overlap");
+  return launch_solar_horizon(W, H, K, s, workspace, hz_n, hz_h, stats, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_solar_svf(int W, int H, int K, const int* s, const int* hz_n, const int* hz_h, const double* weight, double q, double* svf,
+                                void* stream) {
+  if (int rc = solar_check_size(W, H, K, "solar_svf")) return rc;
+  ADAMVS_CHECK_ARG(s && hz_n && hz_h && weight && svf, "solar_svf: null pointer");
+  ADAMVS_CHECK_ARG(std::isfinite(q) && q > 0.0, "solar_svf: q=%g must be finite and > 0", q);
+  for (int k = 0; k < K; ++k) ADAMVS_CHECK_ARG(std::isfinite(weight[k]) && weight[k] > 0.0, "solar_svf: weight[%d]=%g must be finite and > 0", k, weight[k]);
+  const long n = (long)W * H;
+  const BldBuffer b[] = {{s, 4 * n}, {hz_n, 4 * n * K}, {hz_h, 4 * n * K}, {svf, 8 * n}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, 4), "solar_svf: s, hz_n, hz_h and svf must not overlap");
+  return launch_solar_svf(W, H, K, s, hz_n, hz_h, weight, q, svf, (hipStream_t)stream);
+}
+
+extern "C" int adamvs_solar_expose(int W, int H, int K, const int* s, const int* hz_n, const int* hz_h, int T, const int* sector, const double* thr,
+                                   const int* minutes_w, const int* energy_w, const int* sun, const int* label, long P, const int* normal,
+                                   void* workspace, long workspace_bytes, int* minutes, int* direct, void* stream) {
+  if (int rc = solar_check_size(W, H, K, "solar_expose")) return rc;
+  const long n = (long)W * H;
+  ADAMVS_CHECK_ARG(T >= 0 && T <= ADAMVS_SOLAR_MAX_SAMPLES, "solar_expose: T=%d samples (0 .. %d)", T, ADAMVS_SOLAR_MAX_SAMPLES);
+  ADAMVS_CHECK_ARG(s && hz_n && hz_h && workspace && minutes && direct, "solar_expose: null pointer");
+  ADAMVS_CHECK_ARG(T == 0 || (sector && thr && minutes_w && energy_w && sun), "solar_expose: null pointer");
+  ADAMVS_CHECK_ARG(P >= 0 && P <= ADAMVS_DSM_MAX_CELLS, "solar_expose: P=%ld planes (0 .. %d)", P, ADAMVS_DSM_MAX_CELLS);
+  ADAMVS_CHECK_ARG((label == nullptr) == (normal == nullptr), "solar_expose: label and normal go together");
+  long sum_m = 0, sum_e = 0;
+  for (int t = 0; t < T; ++t) {
+    ADAMVS_CHECK_ARG(sector[t] >= 0 && sector[t] < K && (t == 0 || sector[t] >= sector[t - 1]), "solar_expose: sector[%d]=%d (0 .. %d, ascending)", t,
+                     sector[t], K - 1);
+    ADAMVS_CHECK_ARG(std::isfinite(thr[t]) && thr[t] >= 0.0, "solar_expose: thr[%d]=%g must be finite and >= 0", t, thr[t]);
+    ADAMVS_CHECK_ARG(minutes_w[t] >= 0 && energy_w[t] >= 0, "solar_expose: the weights of sample %d (%d, %d) must be >= 0", t, minutes_w[t], energy_w[t]);
+    for (int a = 0; a < 3; ++a)
+      ADAMVS_CHECK_ARG(sun[3 * t + a] >= -32768 && sun[3 * t + a] <= 32768, "solar_expose: sun[%d][%d]=%d (|v| <= 32768)", t, a, sun[3 * t + a]);
+    sum_m += minutes_w[t];
+    sum_e += energy_w[t];
+  }
+  ADAMVS_CHECK_ARG(sum_m <= 2147483647L && sum_e <= 2147483647L, "solar_expose: the weights sum to %ld minutes and %ld energy units (at most 2^31 - 1 each)",
+                   sum_m, sum_e);
+  ADAMVS_CHECK_ARG(workspace_bytes >= ADAMVS_SOLAR_HEAD_BYTES, "solar_expose: workspace of %ld bytes, %d needed", workspace_bytes, ADAMVS_SOLAR_HEAD_BYTES);
+  const BldBuffer b[] = {{s, 4 * n}, {hz_n, 4 * n * K}, {hz_h, 4 * n * K}, {workspace, ADAMVS_SOLAR_HEAD_BYTES}, {minutes, 4 * n}, {direct, 4 * n},
+                         {label, 4 * n}, {normal, 12 * (P + 1)}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, label ? 8 : 6), "solar_expose: the inputs, the outputs and the workspace must not overlap");
+  return launch_solar_expose(W, H, K, s, hz_n, hz_h, T, sector, thr, minutes_w, energy_w, sun, label, P, normal, workspace, minutes, direct,
+                             (hipStream_t)stream);
+}
+
+extern "C" int adamvs_solar_plane_sums(int W, int H, const int* s, const int* label, long P, const int* minutes, const int* direct, long long* table,
+                                       void* stream) {
+  if (int rc = solar_check_size(W, H, 8, "solar_plane_sums")) return rc;
+  const long n = (long)W * H;
+  ADAMVS_CHECK_ARG(s && minutes && direct && table, "solar_plane_sums: null pointer");
+  ADAMVS_CHECK_ARG(P >= 0 && P <= ADAMVS_DSM_MAX_CELLS, "solar_plane_sums: P=%ld planes (0 .. %d)", P, ADAMVS_DSM_MAX_CELLS);
+  const BldBuffer b[] = {{s, 4 * n}, {minutes, 4 * n}, {direct, 4 * n}, {table, 24 * (P + 1)}, {label, 4 * n}};
+  ADAMVS_CHECK_ARG(!bld_any_overlap(b, label ? 5 : 4), "solar_plane_sums: s, label, minutes, direct and the table must not overlap");
+  return launch_solar_plane_sums(W, H, s, label, P, minutes, direct, table, (hipStream_t)stream);
+}
+
 // ---- TSDF mesh (mesh.hip): every argument is checked here, before any launch
 static int mesh_check_brick(const adamvs_mesh_brick* b, const char* what) {
   ADAMVS_CHECK_ARG(b, "%s: null brick", what);

@@ -258,6 +258,17 @@ int launch_drain_streams(int W, int H, const uint8_t* dir, const int* acc, int m
 int launch_drain_links(int W, int H, const uint8_t* dir, const uint8_t* nd, const int* link, const int* pos, long L, long P, void* workspace,
                        int* link_first, int* link_head, int* link_end, int* link_to, int* vertex, hipStream_t st);
 
+// dsm_solar.hip: horizon, sky-view factor, exposure, plane sums (include/adamvs_hip.h, "Solar")
+long solar_workspace_bytes(int W, int H, int K);
+int launch_solar_horizon(int W, int H, int K, const int* s, void* workspace, int* hz_n, int* hz_h, adamvs_solar_stats* stats, hipStream_t st);
+int launch_solar_svf(int W, int H, int K, const int* s, const int* hz_n, const int* hz_h, const double* weight, double q, double* svf,
+                     hipStream_t st);
+int launch_solar_expose(int W, int H, int K, const int* s, const int* hz_n, const int* hz_h, int T, const int* sector, const double* thr,
+                        const int* minutes_w, const int* energy_w, const int* sun, const int* label, long P, const int* normal, void* workspace,
+                        int* minutes, int* direct, hipStream_t st);
+int launch_solar_plane_sums(int W, int H, const int* s, const int* label, long P, const int* minutes, const int* direct, long long* table,
+                            hipStream_t st);
+
 // mesh.hip: TSDF integration and marching-tetrahedra extraction per brick (include/adamvs_hip.h, "TSDF mesh")
 constexpr int MESH_TILE = ADAMVS_MESH_TILE;
 int launch_tsdf_integrate(const adamvs_mesh_brick& b, const adamvs_mesh_view* views, int nviews, const int* list, int nlist, float* tsdf,

@@ -1235,6 +1235,93 @@ def drain_links(direction, nd, link, pos, L, P, workspace):
     return link_first, link_head, link_end, link_to, vertex
 
 
+# ---- Solar (csrc/dsm_solar.hip; include/adamvs_hip.h "Solar") ----------------------------------------------------------------
+def _solar_horizons(s, hz_n, hz_h):
+    s = _raster(s, "s", torch.int32)
+    H, W = s.shape
+    hz_n, hz_h = _dev_as(hz_n, "hz_n", torch.int32), _dev_as(hz_h, "hz_h", torch.int32)
+    if hz_n.dim() != 3 or tuple(hz_n.shape[1:]) != (H, W) or hz_h.shape != hz_n.shape:
+        raise _lib.AdaMVSHipError("hz_n and hz_h must be [K, %d, %d], got %s and %s" % (H, W, tuple(hz_n.shape), tuple(hz_h.shape)))
+    return s, hz_n, hz_h, H, W, int(hz_n.shape[0])
+
+
+def solar_horizon(s, K, workspace=None):
+    """adamvs_solar_horizon: s [H, W] int32 (device; contour_surface's with 0 smoothing passes) -> (hz_n int32 [K, H, W], hz_h int32
+    [K, H, W], stats dict(lines, deepest, spills, ms), the workspace).  Blocks until done."""
+    s = _raster(s, "s", torch.int32)
+    H, W = s.shape
+    K = int(K)
+    workspace = _workspace("solar_workspace_bytes", s.device, workspace, W, H, K)
+    hz_n = torch.empty(K, H, W, device=s.device, dtype=torch.int32)
+    hz_h = torch.empty_like(hz_n)
+    st = _lib.SolarStats()
+    check(_lib.load().adamvs_solar_horizon(W, H, K, _p(s), _p(workspace), workspace.numel(), _p(hz_n), _p(hz_h), ctypes.byref(st), _stream()),
+          "solar_horizon")
+    return hz_n, hz_h, dict(lines=int(st.lines), deepest=int(st.deepest), spills=int(st.spills), ms=float(st.ms)), workspace
+
+
+def solar_svf(s, hz_n, hz_h, weight, q):
+    """adamvs_solar_svf: weight: the K sector weights (host floats), q = (256 gsd)^2 -> svf float64 [H, W].  Enqueued on the
+    current stream."""
+    s, hz_n, hz_h, H, W, K = _solar_horizons(s, hz_n, hz_h)
+    weight = [float(v) for v in weight]
+    if len(weight) != K:
+        raise _lib.AdaMVSHipError("solar_svf: %d weights for K=%d directions" % (len(weight), K))
+    svf = torch.empty(H, W, device=s.device, dtype=torch.float64)
+    check(_lib.load().adamvs_solar_svf(W, H, K, _p(s), _p(hz_n), _p(hz_h), (ctypes.c_double * max(K, 1))(*weight), float(q), _p(svf), _stream()),
+          "solar_svf")
+    return svf
+
+
+def solar_expose(s, hz_n, hz_h, table, label=None, normal=None, workspace=None):
+    """adamvs_solar_expose: table = dict(sector int [T], thr float64 [T], minutes int [T], energy int [T], sun int [T, 3]) on the
+    host, sorted by sector; label int32 [H, W] and normal int32 [P + 1, 3] (device) or neither -> (minutes int32 [H, W], direct
+    int32 [H, W], the workspace).  Blocks until done."""
+    import numpy as np
+    s, hz_n, hz_h, H, W, K = _solar_horizons(s, hz_n, hz_h)
+    T = len(table["sector"])
+    cols = [np.ascontiguousarray(table[k], dt).reshape(-1) for k, dt in (("sector", np.int64), ("thr", np.float64), ("minutes", np.int64),
+                                                                          ("energy", np.int64), ("sun", np.int64))]
+    if [c.size for c in cols] != [T, T, T, T, 3 * T]:
+        raise _lib.AdaMVSHipError("solar_expose: the columns of the table must hold T=%d rows" % T)
+    if any(c.size and (c.min() < -2 ** 31 or c.max() >= 2 ** 31) for c in (cols[0], cols[2], cols[3], cols[4])):
+        raise _lib.AdaMVSHipError("solar_expose: the table must hold int32 values")
+    ints = [(ctypes.c_int * max(c.size, 1))(*c.tolist()) for c in (cols[0], cols[2], cols[3], cols[4])]
+    thr = (ctypes.c_double * max(T, 1))(*cols[1].tolist())
+    P = 0
+    if (label is None) != (normal is None):
+        raise _lib.AdaMVSHipError("solar_expose: label and normal go together")
+    if label is not None:
+        label = _raster(label, "label", torch.int32, (H, W))
+        normal = _dev_as(normal, "normal", torch.int32)
+        if normal.dim() != 2 or normal.shape[1] != 3 or normal.shape[0] < 1:
+            raise _lib.AdaMVSHipError("normal must be [P + 1, 3], got %s" % (tuple(normal.shape),))
+        P = int(normal.shape[0]) - 1
+    if workspace is None or workspace.numel() < _lib.SOLAR_HEAD_BYTES:
+        workspace = torch.empty(_lib.SOLAR_HEAD_BYTES, device=s.device, dtype=torch.uint8)
+    minutes = torch.empty(H, W, device=s.device, dtype=torch.int32)
+    direct = torch.empty_like(minutes)
+    check(_lib.load().adamvs_solar_expose(W, H, K, _p(s), _p(hz_n), _p(hz_h), T, ints[0], thr, ints[1], ints[2], ints[3],
+                                          None if label is None else _p(label), P, None if normal is None else _p(normal), _p(workspace),
+                                          workspace.numel(), _p(minutes), _p(direct), _stream()), "solar_expose")
+    return minutes, direct, workspace
+
+
+def solar_plane_sums(s, minutes, direct, label=None, P=0):
+    """adamvs_solar_plane_sums: -> table int64 [3, P + 1] (cells, minutes, direct per label over V; a null label counts every cell
+    under label 0), on the device.  Enqueued on the current stream."""
+    s = _raster(s, "s", torch.int32)
+    H, W = s.shape
+    minutes, direct = _raster(minutes, "minutes", torch.int32, (H, W)), _raster(direct, "direct", torch.int32, (H, W))
+    if label is not None:
+        label = _raster(label, "label", torch.int32, (H, W))
+    P = int(P)
+    table = torch.empty(3, max(P, 0) + 1, device=s.device, dtype=torch.int64)
+    check(_lib.load().adamvs_solar_plane_sums(W, H, _p(s), None if label is None else _p(label), P, _p(minutes), _p(direct), _p(table), _stream()),
+          "solar_plane_sums")
+    return table
+
+
 # ---- TSDF mesh (csrc/mesh.hip; driven brick by brick by ada_mvs_amd/mesh.py) ------------------------------------------------
 # Per-sample state as torch tensors of the signed type of each C type's width: weight int16 = uint16, rgba int32 = uint32
 # (little-endian r g b a), cube_code int32 = uint32, faces int32 = uint32.

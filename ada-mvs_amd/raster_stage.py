@@ -1,4 +1,4 @@
-"""What the raster stages after dsm_whu.py (dtm.py, buildings.py, roofs.py, trees.py, contours.py, drainage.py) share: the grid of
+"""What the raster stages after dsm_whu.py (dtm.py, buildings.py, roofs.py, trees.py, contours.py, drainage.py, solar.py) share: the grid of
 `<prefix>_dsm.json`, the rasters of the earlier stages with their refusals, the default grid of a bare array, the refusal without a
 GPU, the look-up that renumbers the kept labels, the files a stage writes and reads back, and the opening of its main().  Nothing
 here knows one stage from another: a stage passes its name, its hints and its own output_paths().

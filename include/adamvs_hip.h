@@ -1273,6 +1273,97 @@ int adamvs_drain_links(int W, int H, const unsigned char* dir, const unsigned ch
                        void* workspace, long workspace_bytes, int* link_first, int* link_head, int* link_end, int* link_to, int* vertex,
                        void* stream);
 
+/* ---- Solar (after the DSM and the roof planes): the horizon of every cell in K directions, the sky-view factor, the minutes of
+ * sun and the direct-beam energy per cell and per roof plane ------------------------------------------------------------------
+ * ada-mvs_amd/solar.py expose(); solar_whu.py is the CLI.  Input: the surface s of _contour_surface with 0 smoothing passes
+ * (step 1 of Contours: the heights above z_ref in 1 / 256 m, INT32_MIN outside V, refused beyond 8191 m).
+ * W H <= ADAMVS_DSM_MAX_CELLS, W and H <= ADAMVS_SOLAR_MAX_SIDE.  A cell is c = (i, j), its index i W + j, rows running south.
+ * r.horizon's ray march and r.sun's sums, restated without a visiting order.  Every comparison of the horizon is on integers.
+ *
+ * 1. Surface.  s as above: |s| <= 8191 * 256 < 2^21.
+ * 2. Directions.  K is 8, 16 or 32.  The direction set is every (di, dj) with gcd(|di|, |dj|) = 1 and max(|di|, |dj|) <= 1, 2, 3
+ *    respectively, sorted by the azimuth az = atan2(dj, -di) mod 2 pi (clockwise from north), ascending: k = 0 is north, (-1, 0).
+ *    The tables are the literals ADAMVS_SOLAR_DIRS_8, _16, _32 below.  len2_k = di^2 + dj^2.  The sector weight w_k is half the
+ *    angular gap to each cyclic neighbour divided by 2 pi; the weights sum to 1; the host computes them in fp64 and passes them
+ *    (weight[K], a HOST pointer, every one finite and > 0).  The sector of an azimuth is the k at the smallest angular distance,
+ *    a tie going to the smaller k.
+ * 3. Horizon.  hz_n, hz_h int32 [K][H][W].  For a cell c of V and direction k look at the cells c + n (di, dj), n = 1, 2, ..,
+ *    while they stay inside the raster; keep those in V with h_n = s(c + n d) - s(c) > 0; among them maximise h_n / n, comparing
+ *    h_a n_b against h_b n_a in int64, a tie going to the smallest n.  hz_n = n*, hz_h = h_{n*}; both 0 if no cell qualifies
+ *    and 0 outside V.  Cells outside V are transparent: they neither occlude nor get a result.  The ray is bounded by the raster
+ *    only.
+ * 4. Sky-view factor.  svf fp64 [H][W], q = (256 gsd)^2 an fp64 scalar of the host.  acc = 0.0; for k ascending: t = 1.0 if
+ *    hz_h = 0, else L2 = ((double) n * (double) n) * ((double) len2_k * q) and t = L2 / (L2 + (double) h * (double) h);
+ *    acc = acc + w_k * t.  Without fp contraction every operation is one correctly rounded fp64 +, * or /: a loop in the same
+ *    order on the host gives the same bits.  0.0 outside V.  This is 1 - mean(sin^2 horizon), the isotropic sky seen by a
+ *    horizontal surface.
+ * 5. Exposure.  A sample table of 0 <= T <= ADAMVS_SOLAR_MAX_SAMPLES rows, HOST pointers: sector[T] (k_t, ascending), thr[T]
+ *    (fp64, finite, >= 0: tan(elevation) sqrt(len2_k) gsd 256, surface units per step), minutes_w[T] and energy_w[T] (int32,
+ *    >= 0, each summing to at most 2^31 - 1), sun[T][3] (int32, round(32768 v) of the unit vector towards the sun, x east, y
+ *    north, z up, every |component| <= 32768).  Optional: label int32 [H][W] with values 0 .. P and normal int32 [P + 1][3] =
+ *    round(32768 n), every |component| <= 32768 (both device pointers, both or neither); label 0 and a null label pointer
+ *    mean the horizontal normal (0, 0, 32768), whatever row 0 holds.  For c in V: lit_t(c) = !(hz_h > 0 && (double) hz_h >
+ *    thr_t * (double) hz_n) in sector k_t (one multiply, one compare; equality counts as lit); minutes(c) = sum_t lit_t m_t;
+ *    direct(c) = sum_t lit_t (((int64) e_t * min(2^30, max(0, nx sx + ny sy + nz sz))) >> 30), the dot product in int64 (the
+ *    cap is passed only by the rounding of two parallel unit vectors; with it neither sum can overflow).  Both int32
+ *    [H][W], 0 outside V.
+ * 6. Plane table.  table int64 [3][P + 1]: the cells, the sum of minutes and the sum of direct per label over V; a null label
+ *    pointer counts every cell of V under label 0.
+ *
+ * The split into calls (csrc/dsm_solar.hip, whose head gives the reasons).  _solar_horizon: for the look direction d the lattice
+ * lines are walked along w = -d from the cells whose predecessor c - w lies outside the raster; with a = min(|di|, H) and
+ * b = min(|dj|, W) there are a W + (H - a) b of them, numbered in closed form: first the a full rows on the side the lines enter
+ * from (row by row, column ascending), then the first (wj > 0) or last b columns of the remaining rows.  One lane per line, the
+ * lines of all K directions in one grid.  Along a line with the step counter m, cells outside V skipped, the lane keeps the upper
+ * convex hull of the cells passed as a stack of (m, height), nearest on top (Dozier, Bruno and Downey 1981): at a cell of height v,
+ * while the stack holds two entries and the second (m2, v2) is strictly better than the top (m1, v1), (v2 - v)(m - m1) >
+ * (v1 - v)(m - m2) in int64, pop; then the top is the answer, n = m - m1 and h = v1 - v, if v1 > v and there is no occluder
+ * otherwise; push (m, v).  The strict > keeps collinear points, so the nearest of equals is on top.  One refinement that changes no
+ * result: if the last comparison ended in equality, the cell is collinear with the top two entries and takes the top's place
+ * instead of being pushed (the old top lies between its neighbours on the hull; a later cell on their line or below it is
+ * answered by the new top, one above it pops both), so a plane's stack stays at two entries.  The top
+ * ADAMVS_SOLAR_STACK_WINDOW entries live in LDS; deeper ones spill to the workspace, one entry per cell of the line, and come back
+ * one at a time when the window runs below two.  stats: lines, the deepest stack, the entries spilled, the device time.  It
+ * blocks.  _solar_svf, _solar_expose (the table goes to the head of the workspace and is read with wave-uniform addresses; a
+ * label outside 0 .. P is counted and is the error return ADAMVS_SOLAR_BAD_LABEL after one read-back; it blocks) and
+ * _solar_plane_sums (the wave's label runs are summed into their first lane, which issues the integer atomics): one lane per
+ * cell.  Integer atomics only and one owner per stored word: every output is bit-identical from run to run.  No workgroup waits on
+ * another.  Everything is device memory except stats, weight and the sample table; a workspace of at least
+ * _solar_workspace_bytes(W, H, K) for the horizon (about 8 K bytes per cell) and ADAMVS_SOLAR_HEAD_BYTES for the exposure,
+ * 256-byte aligned.  Argument errors (<0, before any launch): a null pointer other than label and normal (and the table's with
+ * T = 0), W or H <= 0 or above ADAMVS_SOLAR_MAX_SIDE or W H > ADAMVS_DSM_MAX_CELLS, K not 8, 16 or 32, T outside
+ * 0 .. ADAMVS_SOLAR_MAX_SAMPLES, a table out of the ranges or the order of step 5, P outside 0 .. ADAMVS_DSM_MAX_CELLS, label without normal or
+ * normal without label, q or a weight not finite or not > 0, workspace_bytes below the need, any two of the device buffers
+ * (workspace included) overlapping.  The query returns < 0 outside the limits. */
+#define ADAMVS_SOLAR_STACK_WINDOW 16     /* stack entries per line kept in LDS */
+#define ADAMVS_SOLAR_MAX_SAMPLES 8192    /* rows of the sample table */
+#define ADAMVS_SOLAR_MAX_SIDE 32768      /* ADAMVS_ROOF_MAX_SIDE */
+#define ADAMVS_SOLAR_HEAD_BYTES 262656   /* 512 + 32 ADAMVS_SOLAR_MAX_SAMPLES: the control block and the sample table */
+#define ADAMVS_SOLAR_BAD_LABEL (-2)
+#define ADAMVS_SOLAR_DIRS_8 {{-1, 0}, {-1, 1}, {0, 1}, {1, 1}, {1, 0}, {1, -1}, {0, -1}, {-1, -1}}
+#define ADAMVS_SOLAR_DIRS_16 {{-1, 0}, {-2, 1}, {-1, 1}, {-1, 2}, {0, 1}, {1, 2}, {1, 1}, {2, 1}, {1, 0}, {2, -1}, {1, -1}, {1, -2}, {0, -1}, {-1, -2}, {-1, -1}, {-2, -1}}
+#define ADAMVS_SOLAR_DIRS_32 {{-1, 0}, {-3, 1}, {-2, 1}, {-3, 2}, {-1, 1}, {-2, 3}, {-1, 2}, {-1, 3}, {0, 1}, {1, 3}, {1, 2}, {2, 3}, {1, 1}, {3, 2}, {2, 1}, {3, 1}, {1, 0}, {3, -1}, {2, -1}, {3, -2}, {1, -1}, {2, -3}, {1, -2}, {1, -3}, {0, -1}, {-1, -3}, {-1, -2}, {-2, -3}, {-1, -1}, {-3, -2}, {-2, -1}, {-3, -1}}
+
+typedef struct {
+  long lines;        /* the lattice lines of all K directions */
+  long spills;       /* stack entries written to the workspace */
+  int deepest;       /* the deepest stack of a line */
+  int reserved;
+  float ms;          /* device time of the call in milliseconds; -1 if the events failed */
+  float reserved2;
+} adamvs_solar_stats;
+
+long adamvs_solar_workspace_bytes(int W, int H, int K);
+int adamvs_solar_horizon(int W, int H, int K, const int* s, void* workspace, long workspace_bytes, int* hz_n, int* hz_h,
+                         adamvs_solar_stats* stats, void* stream);
+int adamvs_solar_svf(int W, int H, int K, const int* s, const int* hz_n, const int* hz_h, const double* weight, double q, double* svf,
+                     void* stream);
+int adamvs_solar_expose(int W, int H, int K, const int* s, const int* hz_n, const int* hz_h, int T, const int* sector, const double* thr,
+                        const int* minutes_w, const int* energy_w, const int* sun, const int* label, long P, const int* normal,
+                        void* workspace, long workspace_bytes, int* minutes, int* direct, void* stream);
+int adamvs_solar_plane_sums(int W, int H, const int* s, const int* label, long P, const int* minutes, const int* direct, long long* table,
+                            void* stream);
+
 /* ---- TSDF mesh (after fuse_whu.py): the depth maps of all views integrated into a truncated signed-distance field on a voxel
  * grid, brick by brick, and its zero level set extracted as a coloured triangle mesh ---------------------------------------
  * ada-mvs_amd/mesh.py drives it per brick; mesh_whu.py is the CLI.  World axes: x east, y north, z up.
